@@ -15,7 +15,10 @@ A "step" is one pass of the hot path over one batch of synthetic input already r
           2 M / 4 M points (weak scaling: 1 M points per rank): local binned voxelization -> RCCL all-gather of the
           per-rank occupied-cell key lists -> global numbering -> RCCL all-reduce of the voxel feature grid
           (d3d_amd.voxel.sharded).
-Rank 0 prints ONE JSON line.  `value` is whole-job Mpoints/s.  At N = 1 the line also carries `roofline` (dominant kernel,
+Rank 0 prints ONE JSON line.  `value` is whole-job Mpoints/s, `ms_per_step` the time of one of the K timed steps.
+`--dump-outputs DIR` writes what the last timed step returned to rank 0's caller as DIR/<name>.npy (float32 / float64, a fixed
+seeded sample of rows when the whole result exceeds 60 MB; see dump_outputs): the inputs are seeded, so two builds compare output
+for output.  At N = 1 the line also carries `roofline` (dominant kernel,
 timed with HIP events on its launch stream in a separate pass of the same K steps), `roofline_large` (the same fill kernel
 on config 5's whole 8 M-point frame on one GPU: 3 GB of output, beyond the 256 MB Infinity Cache, next to the stream
 bandwidth measured on the same box), `cpu_baseline` (the REAL reference voxelizer built from /root/reference into
@@ -58,6 +61,37 @@ def timed(fn, steps, warmup, barrier=None):
         barrier()
     sync()
     return time.perf_counter() - t0
+
+
+def keep_last(fn, box):
+    """fn, with its latest result kept in box[0] (--dump-outputs: what the timed region's last step returned)"""
+    def run():
+        box[0] = fn()
+    return run
+
+
+DUMP_BUDGET = 60_000_000    # bytes of .npy data in all (the limit is 64 MB; headers and rounding fit in the rest)
+
+
+def dump_outputs(path, res, budget=DUMP_BUDGET, seed=0):
+    """every tensor of one step's result as <path>/<name>.npy: float32 stays float32, booleans become float32 and every other
+    dtype float64 (exact for the integer outputs).  When the whole set exceeds the budget, each output keeps the same fraction
+    of its rows, drawn with a fixed seed (outputs of one length share one sample), and the row ids are written beside it as
+    <name>_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for k, v in res.items():
+        if torch.is_tensor(v):
+            a = v.detach().cpu().numpy()
+            arrs[k] = a.astype(np.float32 if a.dtype in (np.float32, np.bool_) else np.float64, copy=False)
+    total = sum(a.nbytes for a in arrs.values())
+    frac = 1.0 if total <= budget else budget / sum(a.nbytes + (8 * a.shape[0] if a.ndim else 0) for a in arrs.values())
+    for k, a in sorted(arrs.items()):
+        if frac < 1.0 and a.ndim:
+            rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], int(a.shape[0] * frac), replace=False))
+            np.save(os.path.join(path, k + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def spread(fn, steps, reps=5):
@@ -724,7 +758,12 @@ def main():
     ap.add_argument("--nms-only", action="store_true", help="run only config 3's box2d_nms and print its leg")
     ap.add_argument("--iou3d-only", action="store_true", help="run only config 4's iou3d (20 k x 5 k fp32) and print its leg")
     ap.add_argument("--master-port", type=int, default=29533, help="rendezvous port when bench.py launches the ranks itself")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (rank 0's) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and (args.iou_only or args.nms_only or args.iou3d_only or args.large_only or args.sparse_only):
+        ap.error("--dump-outputs dumps the headline step: it does not combine with the --*-only legs")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -781,7 +820,11 @@ def main():
         split_bytes, split_skipped = emit_split_bytes(n, P, res.voxel_npoints, plan)
         del res
         step = lambda: gen(cloud)  # noqa: E731
-        dt = timed(step, args.steps, args.warmup)
+        last = [None]
+        dt = timed(keep_last(step, last) if args.dump_outputs else step, args.steps, args.warmup)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last[0])
+        del last[0]
         value = n * args.steps / dt / 1e6
         out["timed_region_repeats"] = spread(step, args.steps)
         workload = "config2: %d %s points, KITTI range, 0.1 m voxels (704x800x40), dense+MEAN, max 32 pts/voxel" % (
@@ -918,7 +961,11 @@ def main():
             note="per rank: all-to-all of the partial voxel records to the cells' owner ranks (a sparse reduce-scatter of the "
                  "feature grid), SUM all-reduce of the one-bit-per-point first-point bitmap (= OR of disjoint sets), all-to-all "
                  "of the voxel ids back; no all-gather of the grid (every rank keeps its owned 1/world of the voxels)")
-        dt_local = timed(step, args.steps, args.warmup, barrier)
+        last = [None]
+        dt_local = timed(keep_last(step, last) if args.dump_outputs else step, args.steps, args.warmup, barrier)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last[0])
+        del last[0]
         # the same with the final all-gather of the finished grid (replicated result, the frame-sized part)
         gen_rep = ShardedVoxelGenerator(synth.WAYMO_BOUNDS, synth.WAYMO_SHAPE, reduction="mean", replicate=True)
         k = max(args.steps // 4, 3)
