@@ -11,10 +11,19 @@ are numpy.  Two associations:
 * `reference_compat=False`: every detection walks its own nearest ground truths -- then ONE association serves all thresholds
   (a box's choice only depends on the boxes of higher score), 40 times less work.  Equal to the first wherever no detection
   has two acceptable ground truths.
+
+SegmentationEvaluator / SegmentationStats are the reference's (benchmarks.pyx:891-1213): the per-point counting of calc_stats
+(collect_labels / collect_labels_pano, :977-1075) is d3d_segeval on the GPU, the bookkeeping over at most 255 classes is host
+arithmetic as the reference does it.
 """
+import ctypes
+import math
+from enum import Enum
+
 import numpy as np
 import torch
 
+from . import _lib
 from .tracking.matcher import DistanceTypes, ReferenceAssociation, prepare_boxes, score_match
 from .utils import Dict
 
@@ -180,4 +189,261 @@ class DetectionEvaluator:
         return out
 
 
-__all__ = ["DetectionEvaluator"]
+_SEG_FIELDS = ("tp", "fp", "fn", "itp", "ifp", "ifn", "cumiou")
+_SEG_MAX_FRAMES = 65535                # frames of one d3d_segeval call (the frame index is 16 bits of the pair key)
+
+
+class SegmentationStats:
+    """Counts of one frame (or of many, summed) per class (benchmarks.pyx:891-929): tp / fp / fn of semantic segmentation
+    (points), itp / ifp / ifn of panoptic segmentation (segments), cumiou = the sum of the IoUs of the matched segments
+    (fp32, as the reference keeps it).  Plain dicts class -> value; pickles (the reference auto-pickles, :891)."""
+
+    def __init__(self):
+        for k in _SEG_FIELDS:
+            setattr(self, k, {})
+
+    def initialize(self, classes):
+        """every counter of every class to 0 (:916-924)"""
+        for k in _SEG_FIELDS:
+            setattr(self, k, {c: (0.0 if k == "cumiou" else 0) for c in classes})
+
+    def as_object(self):
+        return dict(tp=dict(self.tp), fp=dict(self.fp), fn=dict(self.fn),
+                    itp=dict(self.itp), ifp=dict(self.ifp), ifn=dict(self.ifn), cumiou=dict(self.cumiou))
+
+    def __eq__(self, other):
+        return isinstance(other, SegmentationStats) and self.as_object() == other.as_object()
+
+    def __repr__(self):
+        return "SegmentationStats(%r)" % (self.as_object(),)
+
+
+def _f32(x):
+    return float(np.float32(x))
+
+
+def _is_u16(x):
+    return x.dtype == torch.uint16 if torch.is_tensor(x) else np.asarray(x).dtype == np.uint16
+
+
+def _seg_device(*tensors):
+    for t in tensors:
+        if torch.is_tensor(t) and t.device.type == "cuda":
+            return t.device
+    return _lib.require_gpu()
+
+
+def _seg_array(x, dtype, tdtype, dev, what):
+    """a contiguous 1-D device tensor of x (numpy array or torch tensor) without changing its values"""
+    if torch.is_tensor(x):
+        if x.dtype != tdtype:
+            raise ValueError("%s: expected %s, got %s" % (what, tdtype, x.dtype))
+        x = x.reshape(-1)
+        if x.device != dev:
+            x = x.to(dev)
+        return x.contiguous()
+    x = np.asarray(x)
+    if x.dtype != dtype:
+        raise ValueError("%s: expected %s, got %s" % (what, np.dtype(dtype).name, x.dtype))
+    return torch.from_numpy(np.ascontiguousarray(x.reshape(-1))).to(dev)
+
+
+class SegmentationEvaluator:
+    """Benchmark for semantic and panoptic segmentation (benchmarks.pyx:933-1213; cityscapesScripts' panoptic evaluation).
+
+    Extension beyond the reference: calc_stats_batch counts many stacked frames in one device call."""
+
+    def __init__(self, classes, background=0, min_points=0):
+        """
+        :param classes: classes to be considered during evaluation, other classes are all considered as background
+        :param background: class to be considered as background class
+        :param min_points: minimum number of points when calculating segments in panoptic evaluation
+        """
+        if not isinstance(classes, (list, tuple)):                                                   # :950-963
+            classes = [classes]
+        assert len(classes) > 0
+        if isinstance(classes[0], Enum):
+            self._class_type = type(classes[0])
+            values = set(c.value for c in classes)
+        elif isinstance(classes[0], int):
+            self._class_type = None
+            values = set(classes)
+        else:
+            raise ValueError("Classes should be int or Enum")
+        for c in values:                                                                             # (an unordered_set[uint8_t])
+            if not 0 <= c <= 255:
+                raise OverflowError("class %r does not fit in uint8" % (c,))
+        self._classes = sorted(values)
+        if isinstance(background, Enum):                                                             # :965-967
+            background = background.value
+        background = background if background >= 0 else 256 + background
+        if not 0 <= background <= 255:
+            raise OverflowError("background %r does not fit in uint8" % (background,))
+        self._background = int(background)
+        self._min_points = int(min_points)
+        self._stats = SegmentationStats()
+        self._stats.initialize(self._classes)
+        if len(self._classes) > 255:                                                                 # :972-973
+            raise ValueError("Only support up to 255 different categories!")
+        mask = [0] * 8                                                                               # d3d_segeval's 256-bit mask
+        for c in self._classes:
+            mask[c >> 5] |= 1 << (c & 31)
+        self._mask = tuple(mask)
+
+    def reset(self):
+        self._stats.initialize(self._classes)
+
+    def calc_stats(self, gt_labels, pred_labels, gt_ids=None, pred_ids=None):
+        """-> SegmentationStats of one frame (:1077-1095).  Semantic counts only unless both id arrays are given (uint16).
+        numpy arrays (the reference's inputs) or torch tensors; device tensors are read where they are."""
+        n = len(gt_labels)
+        return self._calc(gt_labels, pred_labels, gt_ids, pred_ids, np.array([0, n], np.int64))[0]
+
+    def calc_stats_batch(self, gt_labels, pred_labels, gt_ids=None, pred_ids=None, frame_offsets=None):
+        """Extension (not in the reference): the stats of F frames stacked along the points, frame f = points
+        frame_offsets[f] .. frame_offsets[f + 1] - 1 (F + 1 non-decreasing offsets from 0 to the number of points).  -> list of F
+        SegmentationStats, each equal to calc_stats of its frame; up to 65535 frames go in one device call."""
+        n = len(gt_labels)
+        if frame_offsets is None:
+            raise ValueError("frame_offsets is required")
+        off = frame_offsets.cpu().numpy() if torch.is_tensor(frame_offsets) else np.asarray(frame_offsets)
+        off = off.astype(np.int64).reshape(-1)
+        if len(off) < 1 or off[0] != 0 or off[-1] != n or np.any(np.diff(off) < 0):
+            raise ValueError("frame_offsets must rise from 0 to the number of points")
+        return self._calc(gt_labels, pred_labels, gt_ids, pred_ids, off)
+
+    def _calc(self, gt_labels, pred_labels, gt_ids, pred_ids, off):
+        pano = gt_ids is not None and pred_ids is not None                                           # :1087-1093
+        if pano and not (_is_u16(gt_ids) and _is_u16(pred_ids)):
+            raise ValueError("Please convert ids to uint16!")
+        n, frames = len(gt_labels), len(off) - 1
+        if len(pred_labels) != n or (pano and (len(gt_ids) != n or len(pred_ids) != n)):
+            raise ValueError("labels and ids must have one entry per point")
+        if frames == 0:
+            return []
+        dev = _seg_device(gt_labels, pred_labels, gt_ids, pred_ids)
+        gl = _seg_array(gt_labels, np.uint8, torch.uint8, dev, "gt_labels")
+        pl = _seg_array(pred_labels, np.uint8, torch.uint8, dev, "pred_labels")
+        gi = _seg_array(gt_ids, np.uint16, torch.uint16, dev, "gt_ids") if pano else None
+        pi = _seg_array(pred_ids, np.uint16, torch.uint16, dev, "pred_ids") if pano else None
+        lib = _lib.load()
+        mask = (ctypes.c_uint32 * 8)(*self._mask)
+        out = torch.empty((len(_SEG_FIELDS), frames, 256), dtype=torch.int32, device=dev)
+        for f0 in range(0, frames, _SEG_MAX_FRAMES):
+            f1 = min(frames, f0 + _SEG_MAX_FRAMES)
+            p0, p1 = int(off[f0]), int(off[f1])
+            foff = torch.from_numpy(off[f0:f1 + 1] - p0).to(dev)
+            ws_bytes = lib.d3d_segeval_workspace_bytes(p1 - p0, f1 - f0)
+            ws = _lib.workspace(ws_bytes, dev)
+
+            def at(t):
+                return _lib.ptr(t[p0:p1]) if t is not None and p1 > p0 else None
+            rows = [_lib.ptr(out[k, f0:f1]) for k in range(len(_SEG_FIELDS))]
+            st = lib.d3d_segeval(at(gl), at(pl), at(gi), at(pi),
+                                 _lib.ptr(foff), p1 - p0, f1 - f0, mask, self._background, self._min_points,
+                                 *rows, _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+            _lib.check(st, "d3d_segeval")
+        res = out.cpu().numpy()
+        cum = res[-1].view(np.float32)
+        stats = []
+        for f in range(frames):
+            s = SegmentationStats()
+            for i, k in enumerate(_SEG_FIELDS[:-1]):
+                setattr(s, k, {c: int(res[i, f, c]) for c in self._classes})
+            s.cumiou = {c: float(cum[f, c]) for c in self._classes}
+            stats.append(s)
+        return stats
+
+    def add_stats(self, stats):
+        """:1097-1106 (cumiou summed in fp32 like the reference's float map)"""
+        for k in self._classes:
+            for name in _SEG_FIELDS[:-1]:
+                getattr(self._stats, name)[k] += getattr(stats, name)[k]
+            self._stats.cumiou[k] = _f32(np.float32(self._stats.cumiou[k]) + np.float32(stats.cumiou[k]))
+
+    def get_stats(self):
+        """Summarize current state of the benchmark counters"""
+        return self._stats
+
+    def _typed(self, d):
+        if self._class_type is None:
+            return dict(d)
+        return {self._class_type(k): v for k, v in d.items()}
+
+    def tp(self, instance=False):
+        return self._typed(self._stats.itp if instance else self._stats.tp)
+
+    def fp(self, instance=False):
+        return self._typed(self._stats.ifp if instance else self._stats.fp)
+
+    def fn(self, instance=False):
+        return self._typed(self._stats.ifn if instance else self._stats.fn)
+
+    def _key(self, k):
+        return k if self._class_type is None else self._class_type(k)
+
+    def iou(self, instance=False):
+        """:1144-1160, fp32 arithmetic; NaN without a denominator"""
+        result = {}
+        s = self._stats
+        for k in self._classes:
+            if instance:
+                d = np.float32(s.itp[k])
+                v = _f32(np.float32(s.cumiou[k]) / d) if s.itp[k] > 0 else math.nan
+            else:
+                d = np.float32(s.tp[k] + s.fp[k] + s.fn[k])
+                v = _f32(np.float32(s.tp[k]) / d) if d > 0 else math.nan
+            result[self._key(k)] = v
+        return result
+
+    def sq(self):
+        """Segmentation Quality (SQ) in panoptic segmentation"""
+        return self.iou(instance=True)
+
+    def rq(self):
+        """Recognition Quality (RQ) in panoptic segmentation (:1166-1177: the denominator in double, stored as float)"""
+        result = {}
+        s = self._stats
+        for k in self._classes:
+            d = np.float32(s.itp[k] + s.ifp[k] * 0.5 + s.ifn[k] * 0.5)
+            result[self._key(k)] = _f32(np.float32(s.itp[k]) / d) if d > 0 else math.nan
+        return result
+
+    def pq(self):
+        """Panoptic Quality (PQ) in panoptic segmentation"""
+        sq, rq = self.sq(), self.rq()
+        return {k: sq[k] * rq[k] for k in sq}
+
+    def summary(self):
+        """:1184-1213"""
+        lines = []
+
+        def mean_wo_nan(values):
+            valid = [v for v in values if not math.isnan(v)]
+            if len(valid) == 0:
+                return math.nan
+            return sum(valid) / len(valid)
+
+        lines.append("========== Benchmark Summary ==========")
+        iou = self.iou()
+        sq, rq, pq = self.sq(), self.rq(), self.pq()
+        for k in self._classes:
+            if k == self._background:
+                continue
+            typed_k = self._key(k)
+            name = str(k).rjust(4, " ") if self._class_type is None else typed_k.name.rjust(20, " ")
+            if math.isnan(pq[typed_k]):
+                lines.append("%s: iou=%.3f" % (name, iou[typed_k]))
+            else:
+                lines.append("%s: iou=%.3f, sq=%.3f, rq=%.3f, pq=%.3f" % (name,
+                             iou[typed_k], sq[typed_k], rq[typed_k], pq[typed_k]))
+        lines.append("mean IoU: %.4f" % mean_wo_nan(iou.values()))
+        if not math.isnan(mean_wo_nan(pq.values())):
+            lines.append("mean SQ: %.4f" % mean_wo_nan(sq.values()))
+            lines.append("mean RQ: %.4f" % mean_wo_nan(rq.values()))
+            lines.append("mean PQ: %.4f" % mean_wo_nan(pq.values()))
+        lines.append("========== Summary End ==========")
+        return "\n".join(lines)
+
+
+__all__ = ["DetectionEvaluator", "SegmentationEvaluator", "SegmentationStats"]

@@ -65,3 +65,24 @@ def boxes3d_eval(n_gt=5000, rep=4, seed=2):
     pred[:, 3:6] += 0.1 * rng.standard_normal((len(pred), 3))
     pred[:, 6] += 0.1 * rng.standard_normal(len(pred))
     return pred.astype(np.float32), gt.astype(np.float32)
+
+
+def segmentation_frame(n, num_classes=19, inst_per_class=30, noise=0.05, seed=0):
+    """A panoptic LiDAR frame for SegmentationEvaluator: labels 0 (unlabelled) .. num_classes, each class with inst_per_class
+    instances (ids 1 ..), every instance a contiguous run of points (segments in random order, Dirichlet sizes); the
+    prediction relabels a `noise` fraction of the points and renumbers the ids.  -> gt_labels, pred_labels (u8),
+    gt_ids, pred_ids (u16)."""
+    rng = np.random.default_rng(seed)
+    k = num_classes * inst_per_class
+    seg_label = np.concatenate([1 + np.arange(k) // inst_per_class, [0]]).astype(np.uint8)
+    seg_id = np.concatenate([1 + np.arange(k) % inst_per_class, [0]]).astype(np.uint16)
+    sizes = rng.multinomial(n, rng.dirichlet(np.ones(k + 1)))
+    order = rng.permutation(k + 1)
+    gt_labels = np.repeat(seg_label[order], sizes[order])
+    gt_ids = np.repeat(seg_id[order], sizes[order])
+    pred_labels = gt_labels.copy()
+    pred_ids = ((gt_ids.astype(np.int64) * 7 + 3) % 1000).astype(np.uint16)
+    flip = rng.random(n) < noise
+    pred_labels[flip] = rng.integers(0, num_classes + 1, int(flip.sum()))
+    pred_ids[flip] = rng.integers(0, 1000, int(flip.sum()))
+    return gt_labels, pred_labels, gt_ids, pred_ids

@@ -639,6 +639,29 @@ int d3d_nms2d_notify(const void *boxes, const void *scores, const int64_t *order
 enum { D3D_NMS_STATUS_DENSE_PATH = 1, D3D_NMS_STATUS_SCAN_GAVE_UP = 2 };
 int d3d_nms2d_status(const void *workspace, int32_t suppression_type, void *stream, uint32_t *status);
 
+/* ------------------------------------------------------------------ d3d/benchmarks: segmentation */
+
+/* replaces SegmentationEvaluator.collect_labels / collect_labels_pano (reference d3d/benchmarks.pyx:977-1075, called from
+ * calc_stats, :1077-1095) for `frames` stacked frames in one call:
+ *   gt_labels[n], pred_labels[n] u8; gt_ids[n], pred_ids[n] u16, both NULL for the semantic counts only (collect_labels),
+ *   both set for the panoptic ones as well (collect_labels_pano); frame_off[frames + 1] i64 (device), frame f = points
+ *   frame_off[f] .. frame_off[f + 1] - 1, frame_off[0] = 0, frame_off[frames] = n, non-decreasing;
+ *   class_mask: HOST, 8 words = 256 bits, bit c of word c / 32 set when class c is in `classes`; background 0 .. 255;
+ *   outputs [frames, 256], row f = frame f, column = class: tp, fp, fn, itp, ifp, ifn i32 and cumiou f32 -- every entry
+ *   written (0 for classes outside the mask; itp .. cumiou are 0 without ids).
+ * Counts and match decisions are the reference's, with its "background subtraction" (:1055-1056) read as what it does: it
+ * subtracts the 0 that operator[] has just inserted, so a pair's union is g + p - inter always.  cumiou[f][c] is the exact
+ * sum of the frame's matched fp32 IoUs rounded once to fp32 (the reference adds them in fp32 in hash-map order), the same
+ * bits on every run.  Up to 4 launches (2 without ids), no synchronisation.
+ * D3D_ERR_BAD_ARG: frames > 65535, n >= 2^31, only one of the id arrays, a background outside 0 .. 255.
+ * Workspace: d3d_segeval_workspace_bytes(n, frames). */
+size_t d3d_segeval_workspace_bytes(int64_t n, int64_t frames);
+int d3d_segeval(const uint8_t *gt_labels, const uint8_t *pred_labels, const uint16_t *gt_ids, const uint16_t *pred_ids,
+                const int64_t *frame_off, int64_t n, int64_t frames, const uint32_t *class_mask,
+                int32_t background, int32_t min_points,
+                int32_t *tp, int32_t *fp, int32_t *fn, int32_t *itp, int32_t *ifp, int32_t *ifn, float *cumiou,
+                void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
