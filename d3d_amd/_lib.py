@@ -122,6 +122,9 @@ SIGNATURES = {
     "d3d_segeval_workspace_bytes": (_sz, [_i64, _i64]),
     "d3d_segeval": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.POINTER(ctypes.c_uint32), _i32, _i32,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3d_track_state_bytes": (_sz, [_i64, _i32]),
+    "d3d_track_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
+    "d3d_track_frame": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -15,6 +15,11 @@ are numpy.  Two associations:
 SegmentationEvaluator / SegmentationStats are the reference's (benchmarks.pyx:891-1213): the per-point counting of calc_stats
 (collect_labels / collect_labels_pano, :977-1075) is d3d_segeval on the GPU, the bookkeeping over at most 255 classes is host
 arithmetic as the reference does it.
+
+TrackingEvaluator / TrackingEvalStats are the reference's (benchmarks.pyx:449-890): a frame's carry-over, association and
+id-switch / fragment counting is d3d_match_distance + d3d_track_frame on the GPU with the carried assignments kept on the
+device; the per-frame tid maps and the metrics are host arithmetic.  DetectionEvaluator also has the reference's accumulation
+and metrics (reset, add_stats, get_stats, tp .. ap, acc_*, summary; :146-447).
 """
 import ctypes
 import math
@@ -35,9 +40,11 @@ class DetectionEvaluator:
         self.reference_compat = bool(reference_compat)
         classes = list(classes) if isinstance(classes, (list, tuple)) else [classes]
         assert len(classes) > 0
-        self._classes = [int(getattr(c, "value", c)) for c in classes]
+        self._class_type = type(classes[0]) if isinstance(classes[0], Enum) else None                 # :105-112
+        values = [int(getattr(c, "value", c)) for c in classes]
+        self._classes = list(dict.fromkeys(values))                                                  # (an unordered_set)
         if isinstance(min_overlaps, (list, tuple)):
-            self._max_distance = {c: 1 - v for c, v in zip(self._classes, min_overlaps)}            # :114-115
+            self._max_distance = {c: 1 - v for c, v in zip(values, min_overlaps)}                    # :114-115
         elif isinstance(min_overlaps, (int, float)):
             self._max_distance = {c: 1 - min_overlaps for c in self._classes}
         else:
@@ -54,10 +61,148 @@ class DetectionEvaluator:
         else:
             raise ValueError("Unrecognized PR sample type")
         self._pr_thresholds = np.asarray(thresholds, dtype=np.float32)
+        self._stats = self._new_stats()
+
+    def _new_stats(self):
+        """DetectionEvalStats.initialize (:66-78): counts 0, accuracies NaN"""
+        T = self._pr_nsamples
+        st = Dict(ngt={c: 0 for c in self._classes})
+        for k in ("ndt", "tp", "fp", "fn"):
+            st[k] = {c: [0] * T for c in self._classes}
+        for k in _ACC_FIELDS:
+            st[k] = {c: [math.nan] * T for c in self._classes}
+        return st
 
     @property
     def score_thresholds(self):
         return self._pr_thresholds
+
+    def reset(self):
+        self._stats = self._new_stats()
+
+    def add_stats(self, stats):
+        """Add statistics from calc_stats into database (:300-327): counts summed, the accuracies merged by fp32 wmean
+        (math/__init__.pxd:4-9) weighted by the true positives"""
+        T = self._pr_nsamples
+        for k in self._classes:
+            self._stats.ngt[k] += stats.ngt[k]
+            otp, ntp = np.asarray(self._stats.tp[k], np.int64), np.asarray(stats.tp[k], np.int64)
+            for name in _ACC_FIELDS:
+                mine = getattr(self._stats, name)
+                mine[k] = _wmean(mine[k], otp, getattr(stats, name)[k], ntp)
+            for name in ("ndt", "tp", "fp", "fn"):
+                mine, theirs = getattr(self._stats, name), getattr(stats, name)[k]
+                mine[k] = [int(mine[k][i]) + int(theirs[i]) for i in range(T)]
+
+    def get_stats(self):
+        """Summarize current state of the benchmark counters"""
+        return self._stats
+
+    def _get_score_idx(self, score):
+        """:321-325: NaN -> the middle threshold, otherwise bisect_left over the (fp32) thresholds"""
+        score = np.float32(score)
+        if np.isnan(score):
+            return self._pr_nsamples // 2
+        return int(np.searchsorted(self._pr_thresholds, score, side="left"))
+
+    def _key(self, k):
+        return k if self._class_type is None else self._class_type(k)
+
+    def _name(self, k):
+        return str(k) if self._class_type is None else self._class_type(k).name
+
+    def _at(self, table, score):
+        i = self._get_score_idx(score)
+        return {self._key(k): table[k][i] for k in self._classes}
+
+    def gt_count(self):
+        return {self._key(k): self._stats.ngt[k] for k in self._classes}
+
+    def dt_count(self, score=math.nan):
+        return self._at(self._stats.ndt, score)
+
+    def tp(self, score=math.nan):
+        """Return true positive count. If score is not specified, return the median value"""
+        return self._at(self._stats.tp, score)
+
+    def fp(self, score=math.nan):
+        """Return false positive count. If score is not specified, return the median value"""
+        return self._at(self._stats.fp, score)
+
+    def fn(self, score=math.nan):
+        """Return false negative count. If score is not specified, return the median value"""
+        return self._at(self._stats.fn, score)
+
+    def _per_class(self, fn, score, return_all):
+        """fn(k, i) for every class at one threshold, or (return_all) for every threshold"""
+        if return_all:
+            return {self._key(k): [fn(k, i) for i in range(self._pr_nsamples)] for k in self._classes}
+        i = self._get_score_idx(score)
+        return {self._key(k): fn(k, i) for k in self._classes}
+
+    def precision(self, score=math.nan, return_all=False):
+        s = self._stats
+        return self._per_class(lambda k, i: _calc_precision(s.tp[k][i], s.fp[k][i]), score, return_all)
+
+    def recall(self, score=math.nan, return_all=False):
+        s = self._stats
+        return self._per_class(lambda k, i: _calc_recall(s.tp[k][i], s.fn[k][i]), score, return_all)
+
+    def fscore(self, score=math.nan, beta=1, return_all=False):
+        s, b2 = self._stats, np.float32(beta) * np.float32(beta)
+        return self._per_class(lambda k, i: _calc_fscore(s.tp[k][i], s.fp[k][i], s.fn[k][i], b2), score, return_all)
+
+    def ap(self):
+        """Calculate (mean) average precision (:390-397); the curve runs from bottom right to top left, hence the sign"""
+        p, r = self.precision(return_all=True), self.recall(return_all=True)
+        return {k: float(-np.trapezoid(p[k], r[k])) for k in p}
+
+    def acc_iou(self, score=math.nan):
+        return self._at(self._stats.acc_iou, score)
+
+    def acc_box(self, score=math.nan):
+        return self._at(self._stats.acc_box, score)
+
+    def acc_dist(self, score=math.nan):
+        return self._at(self._stats.acc_dist, score)
+
+    def acc_angular(self, score=math.nan):
+        return self._at(self._stats.acc_angular, score)
+
+    def _summary_accuracy(self, lines, k, score_thres, score_idx):
+        s = self._stats
+        lines.append("\tMean IoU (score > %.2f):\t\t%.3f" % (score_thres, s.acc_iou[k][score_idx]))
+        lines.append("\tMean angular error (score > %.2f):\t%.3f" % (score_thres, s.acc_angular[k][score_idx]))
+        lines.append("\tMean distance (score > %.2f):\t\t%.3f" % (score_thres, s.acc_dist[k][score_idx]))
+        lines.append("\tMean box error (score > %.2f):\t\t%.3f" % (score_thres, s.acc_box[k][score_idx]))
+        if not math.isinf(s.acc_var[k][score_idx]):
+            lines.append("\tMean variance error (score > %.2f):\t%.3f" % (score_thres, s.acc_var[k][score_idx]))
+
+    def summary(self, score_thres=0.8, verbose=False):
+        """Print default summary (into returned string) (:410-447); int classes print as the int"""
+        score_thres = _f32(score_thres)
+        score_idx = self._get_score_idx(score_thres)
+        lines = [""]
+        precision, recall = self.precision(score_thres), self.recall(score_thres)
+        fscore, ap = self.fscore(return_all=True), self.ap()
+        lines.append("========== Benchmark Summary ==========")
+        for k in self._classes:
+            typed_k = self._key(k)
+            if verbose:
+                lines.append("Results for %s:" % self._name(k))
+                lines.append("\tTotal processed targets:\t%d gt boxes, %d dt boxes" % (
+                    self._stats.ngt[k], max(self._stats.ndt[k])))
+                lines.append("\tPrecision (score > %.2f):\t%.3f" % (score_thres, precision[typed_k]))
+                lines.append("\tRecall (score > %.2f):\t\t%.3f" % (score_thres, recall[typed_k]))
+                lines.append("\tMax F1:\t\t\t\t%.3f" % max(fscore[typed_k]))
+                lines.append("\tAP:\t\t\t\t%.3f" % ap[typed_k])
+                lines.append("")
+                self._summary_accuracy(lines, k, score_thres, score_idx)
+            else:
+                lines.append("\tResults for %s: AP=%.3f" % (self._name(k), ap[typed_k]))
+        lines.append("mAP: %.3f" % np.mean(list(ap.values())))
+        lines.append("========== Summary End ==========")
+        return "\n".join(lines)
 
     def calc_stats(self, gt_boxes, dt_boxes):
         """-> Dict(ngt{c}, ndt{c}[T], tp, fp, fn, acc_iou{c}[T], acc_angular, acc_dist, acc_box, acc_var) as
@@ -187,6 +332,31 @@ class DetectionEvaluator:
             # no variances travel in the [n,9] arrays: orientation_var = 0 -> -inf per match (:250-258), NaN without one
             out.acc_var[c] = np.where(tp > 0, -np.inf, np.nan).tolist()
         return out
+
+
+_ACC_FIELDS = ("acc_angular", "acc_box", "acc_iou", "acc_dist", "acc_var")
+
+
+def _wmean(a, wa, b, wb):
+    """math/__init__.pxd:4-9 elementwise, in fp32: a if wb == 0, b if wa == 0, (a * wa + b * wb) / (wa + wb) otherwise"""
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        mixed = (a * wa.astype(np.float32) + b * wb.astype(np.float32)) / (wa + wb).astype(np.float32)
+    return np.where(wa == 0, b, np.where(wb == 0, a, mixed)).astype(np.float32).tolist()
+
+
+def _calc_precision(tp, fp):                    # :32-34 (fp32)
+    return 1.0 if fp == 0 else _f32(np.float32(tp) / np.float32(tp + fp))
+
+
+def _calc_recall(tp, fn):                       # :35-37 (fp32)
+    return 1.0 if fn == 0 else _f32(np.float32(tp) / np.float32(tp + fn))
+
+
+def _calc_fscore(tp, fp, fn, b2):               # :38-39 (fp32; 0 / 0 is NaN under cdivision)
+    one = np.float32(1) + b2
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return _f32(one * np.float32(tp) / (one * np.float32(tp) + b2 * np.float32(fn) + np.float32(fp)))
 
 
 _SEG_FIELDS = ("tp", "fp", "fn", "itp", "ifp", "ifn", "cumiou")
@@ -446,4 +616,429 @@ class SegmentationEvaluator:
         return "\n".join(lines)
 
 
-__all__ = ["DetectionEvaluator", "SegmentationEvaluator", "SegmentationStats"]
+class _TrackFrame(ctypes.Structure):
+    """include/d3d_hip.h: D3DTrackFrame"""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("dt_boxes", "cache", "dt_cls", "gt_cls", "dt_tid", "gt_tid", "dt_stid", "dt_srow",
+                                               "gt_stid", "gt_srow", "dt_perm", "row_off")] + \
+               [(k, ctypes.c_int64) for k in ("n", "m", "n_total", "capacity")]
+
+
+def _tid_counts_merge(a, b):
+    """(tids u64[k], counts[..., k]) + (tids, counts) -> the union, counts added (the reference's `+=` on unordered_maps)"""
+    u = np.union1d(a[0], b[0]).astype(np.uint64)
+    c = np.zeros(a[1].shape[:-1] + (len(u),), np.int64)
+    c[..., np.searchsorted(u, a[0])] += a[1]
+    c[..., np.searchsorted(u, b[0])] += b[1]
+    return u, c
+
+
+class TrackingEvalStats:
+    """Tracking stats summary of an evaluation step (benchmarks.pyx:449-486): the detection counts (ngt, ndt, tp, fp, fn,
+    acc_*) plus id_switches / fragments per class and threshold, and the frame counts of the track ids.  The reference keeps
+    the latter as hash maps tid -> count; here they are sorted arrays: ngt_ids[c] = (tids u64[k], counts i64[k]),
+    ngt_tracked[c] / ndt_ids[c] = (tids u64[k], counts i64[T, k]) -- a tid with count 0 at a threshold is not in that
+    threshold's map.  as_object() builds the reference's layout."""
+
+    def initialize(self, classes, nsamples):
+        T = nsamples
+        self.ngt = {c: 0 for c in classes}
+        for k in ("ndt", "tp", "fp", "fn", "id_switches", "fragments"):
+            setattr(self, k, {c: [0] * T for c in classes})
+        for k in _ACC_FIELDS:
+            setattr(self, k, {c: [math.nan] * T for c in classes})
+        empty = np.zeros((0,), np.uint64)
+        self.ngt_ids = {c: (empty, np.zeros((0,), np.int64)) for c in classes}
+        self.ngt_tracked = {c: (empty, np.zeros((T, 0), np.int64)) for c in classes}
+        self.ndt_ids = {c: (empty, np.zeros((T, 0), np.int64)) for c in classes}
+        return self
+
+    def as_object(self):
+        """:476-486 (whose `ret` is never returned): the tid maps become the lists of their keys, as list() of the
+        converted maps gives them -- ascending here"""
+        def keys(entry):
+            tids, counts = entry
+            if counts.ndim == 1:
+                return [int(x) for x in tids[counts > 0]]
+            return [[int(x) for x in tids[row > 0]] for row in counts]
+        return dict(ngt=dict(self.ngt), tp=dict(self.tp), fp=dict(self.fp), fn=dict(self.fn), ndt=dict(self.ndt),
+                    acc_iou=dict(self.acc_iou), acc_angular=dict(self.acc_angular), acc_dist=dict(self.acc_dist),
+                    acc_box=dict(self.acc_box), acc_var=dict(self.acc_var),
+                    id_switches=dict(self.id_switches), fragments=dict(self.fragments),
+                    ngt_ids={c: keys(v) for c, v in self.ngt_ids.items()},
+                    ngt_tracked={c: keys(v) for c, v in self.ngt_tracked.items()},
+                    ndt_ids={c: keys(v) for c, v in self.ndt_ids.items()})
+
+    def __repr__(self):
+        return "TrackingEvalStats(%r)" % (self.as_object(),)
+
+
+def _host_rows(x, dtype, cols):
+    if torch.is_tensor(x):
+        x = x.detach().cpu().numpy()
+    x = np.asarray(x)
+    return np.ascontiguousarray(x, dtype=dtype).reshape((-1, cols) if cols else (-1,))
+
+
+def _host_tids(x, what):
+    if torch.is_tensor(x):
+        if x.dtype not in (torch.int64, torch.uint64):
+            raise ValueError("%s: expected 64-bit integer track ids, got %s" % (what, x.dtype))
+        x = x.detach().cpu().numpy()
+    x = np.asarray(x)
+    if x.dtype not in (np.uint64, np.int64):
+        raise ValueError("%s: expected uint64 / int64 track ids, got %s" % (what, x.dtype))
+    return np.ascontiguousarray(x.reshape(-1)).view(np.uint64)
+
+
+def _aligned(nbytes):
+    return (nbytes + 255) // 256 * 256
+
+
+class TrackingEvaluator(DetectionEvaluator):
+    """Benchmark for object tracking (benchmarks.pyx:488-890).  Targets association is done by score sorting, with the
+    assignments of the previous frame carried over per score threshold.
+
+    Boxes are [n,9] rows as for DetectionEvaluator; their track ids come as separate arrays (uint64 / int64, numpy or
+    tensors).  The carried state lives on the device: a frame is d3d_match_distance + d3d_track_frame (prepare, the literal
+    association of every threshold, update) without a host round trip, so calc_stats_sequence queues whole sequences and
+    fetches once.  Extension beyond the reference: calc_stats_sequence."""
+
+    def __init__(self, classes, min_overlaps, pr_sample_count=40, min_score=0, pr_sample_scale="log10"):
+        super().__init__(classes, min_overlaps, pr_sample_count=pr_sample_count, min_score=min_score,
+                         pr_sample_scale=pr_sample_scale)
+        self._slot = {c: i for i, c in enumerate(self._classes)}
+        self._dev = None
+        self._state = None              # two device buffers of d3d_track_state_bytes(self._cap, T), self._state[self._cur] current
+        self._cap, self._cur = 0, 0
+        self._host_state = None          # (capacity, bytes) of a state that was pickled, uploaded at the next frame
+
+    def _new_stats(self):
+        return TrackingEvalStats().initialize(self._classes, self._pr_nsamples)
+
+    def reset(self):
+        DetectionEvaluator.reset(self)
+        self._host_state = None
+        if self._state is not None:
+            self._state[self._cur][:4 * self._pr_nsamples].zero_()        # count[T] = 0: no carried pairs
+
+    # ------------------------------------------------------------------ device state
+    def _state_views(self, buf, cap):
+        T = self._pr_nsamples
+        o1 = _aligned(4 * T)
+        o2 = o1 + _aligned(8 * T * cap)
+        o3 = o2 + _aligned(8 * T * cap)
+        o4 = o3 + _aligned(4 * T * cap)
+        return (buf[:4 * T].view(torch.int32), buf[o1:o1 + 8 * T * cap].view(torch.int64).view(T, cap),
+                buf[o2:o2 + 8 * T * cap].view(torch.int64).view(T, cap), buf[o3:o3 + 4 * T * cap].view(torch.int32).view(T, cap),
+                buf[o4:o4 + 4 * T * cap].view(torch.int32).view(T, cap))
+
+    def _ensure_state(self, dev, m):
+        """two state buffers of capacity >= m on `dev` (grown with the pairs copied over: no synchronisation)"""
+        lib = _lib.load()
+        T = self._pr_nsamples
+        if self._state is not None and self._dev != dev:
+            raise ValueError("TrackingEvaluator: frames of one sequence must stay on one device")
+        self._dev = dev
+        if self._host_state is not None:
+            cap, raw = self._host_state
+            self._host_state = None
+            buf = torch.from_numpy(raw.copy()).to(dev)
+            self._state = [buf, torch.zeros_like(buf)]
+            self._cap, self._cur = cap, 0
+        if self._state is not None and m <= self._cap:
+            return
+        cap = max(m, 2 * self._cap, 64)
+        nbytes = lib.d3d_track_state_bytes(cap, T)
+        new = [torch.zeros((nbytes,), dtype=torch.uint8, device=dev) for _ in range(2)]
+        if self._state is not None:
+            old, dst = self._state_views(self._state[self._cur], self._cap), self._state_views(new[0], cap)
+            dst[0].copy_(old[0])
+            for a, b in zip(dst[1:], old[1:]):
+                a[:, :self._cap].copy_(b)
+        self._state, self._cap, self._cur = new, cap, 0
+
+    def __getstate__(self):
+        d = dict(self.__dict__)
+        if self._state is not None:                      # the carried assignments travel with the evaluator
+            d["_host_state"] = (self._cap, self._state[self._cur].cpu().numpy())
+        d["_state"], d["_dev"], d["_cap"], d["_cur"] = None, None, 0, 0
+        return d
+
+    def __setstate__(self, d):
+        self.__dict__.update(d)
+
+    # ------------------------------------------------------------------ calc_stats
+    def calc_stats(self, gt_boxes, dt_boxes, gt_tids, dt_tids):
+        """-> TrackingEvalStats of one frame (:536-723); updates the carried assignments, adds nothing to the totals
+        (add_stats does).  Both box sets must be in the same frame."""
+        gt = _host_rows(gt_boxes, np.float32, 9)
+        dt = _host_rows(dt_boxes, np.float32, 9)
+        h = self._prepare_host(gt, dt, _host_tids(gt_tids, "gt_tids"), _host_tids(dt_tids, "dt_tids"))
+        return self._run([h], _seg_device(gt_boxes, dt_boxes, gt_tids, dt_tids))[0]
+
+    def calc_stats_sequence(self, gt_boxes, dt_boxes, gt_tids, dt_tids, gt_frame_offsets, dt_frame_offsets):
+        """Extension (not in the reference): F frames stacked, frame f = gt rows gt_frame_offsets[f] .. gt_frame_offsets[f + 1]
+        and dt rows dt_frame_offsets[f] .. dt_frame_offsets[f + 1] (F + 1 offsets each, rising from 0 to the number of rows).
+        -> list of F TrackingEvalStats, equal to F successive calc_stats calls; the frames are queued without a host
+        synchronisation between them and the results fetched once."""
+        gt = _host_rows(gt_boxes, np.float32, 9)
+        dt = _host_rows(dt_boxes, np.float32, 9)
+        gtid, dtid = _host_tids(gt_tids, "gt_tids"), _host_tids(dt_tids, "dt_tids")
+        if len(gtid) != len(gt) or len(dtid) != len(dt):
+            raise ValueError("one track id per box is required")
+        go = _host_rows(gt_frame_offsets, np.int64, 0)
+        do = _host_rows(dt_frame_offsets, np.int64, 0)
+        for off, n in ((go, len(gt)), (do, len(dt))):
+            if len(off) < 1 or off[0] != 0 or off[-1] != n or np.any(np.diff(off) < 0):
+                raise ValueError("frame offsets must rise from 0 to the number of boxes")
+        if len(go) != len(do):
+            raise ValueError("gt_frame_offsets and dt_frame_offsets must describe the same frames")
+        hs = [self._prepare_host(gt[go[f]:go[f + 1]], dt[do[f]:do[f + 1]], gtid[go[f]:go[f + 1]], dtid[do[f]:do[f + 1]])
+              for f in range(len(go) - 1)]
+        return self._run(hs, _seg_device(gt_boxes, dt_boxes, gt_tids, dt_tids)) if hs else []
+
+    def _prepare_host(self, gt, dt, gtid, dtid):
+        """what the host knows of a frame before the device runs: the class slots, the selections, the orders, the tid tables"""
+        if len(gtid) != len(gt) or len(dtid) != len(dt):
+            raise ValueError("one track id per box is required")
+        if len(np.unique(gtid)) != len(gtid) or len(np.unique(dtid)) != len(dtid):
+            raise ValueError("track ids must be unique among the boxes of a frame")
+        gslot, dslot = np.full((len(gt),), -1, np.int32), np.full((len(dt),), -1, np.int32)
+        gtag, dtag = gt[:, 0].astype(np.int64), dt[:, 0].astype(np.int64)
+        for c, i in self._slot.items():
+            gslot[gtag == c] = i
+            dslot[dtag == c] = i
+        score = dt[:, 1]
+        sel = (dslot >= 0)[None, :] & ~(score[None, :] < self._pr_thresholds[:, None])          # [T, n]  (:588-593)
+        if np.any(sel.any(0) & (dtid == 0)):
+            raise AssertionError("Tracking id should be greater than 0 for a valid object!")      # :597
+        row_off = np.zeros((self._pr_nsamples + 1,), np.int64)
+        np.cumsum(sel.sum(1), out=row_off[1:])
+        perm = np.flip(np.argsort(score, kind="stable")).astype(np.int32)                        # matcher.pyx:146
+        go, do = np.argsort(gtid, kind="stable"), np.argsort(dtid, kind="stable")
+        return dict(gt=gt, dt=dt, gtid=gtid, dtid=dtid, gslot=gslot, dslot=dslot, sel=sel, row_off=row_off, perm=perm,
+                    gt_stid=gtid[go], gt_srow=go.astype(np.int32), dt_stid=dtid[do], dt_srow=do.astype(np.int32))
+
+    def _run(self, hs, dev):
+        """the device chain of every frame of `hs` (_prepare_host), queued in order; one fetch at the end"""
+        lib = _lib.load()
+        T, C = self._pr_nsamples, len(self._classes)
+        # everything the device reads, in one upload: per frame [dt boxes f32 | row_off i64 | 4 tid arrays u64 | 5 index arrays i32]
+        parts, layout, pos = [], [], 0
+
+        def put(a):
+            nonlocal pos
+            b = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+            at = pos
+            parts.append(b)
+            pad = _aligned(len(b)) - len(b)
+            if pad:
+                parts.append(np.zeros((pad,), np.uint8))
+            pos += len(b) + pad
+            return at
+        consts = (put(self._pr_thresholds), put(np.array([np.float32(self._max_distance[c]) for c in self._classes], np.float32)))
+        for h in hs:
+            layout.append({k: put(h[k]) for k in ("dt", "row_off", "dtid", "gtid", "dt_stid", "gt_stid", "dslot", "gslot",
+                                                  "dt_srow", "gt_srow", "perm")})
+        sizes = [(len(h["dt"]), len(h["gt"])) for h in hs]
+        cache_at, out_at, cpos, opos = [], [], 0, 0
+        for n, m in sizes:                                      # the caches; the outputs assign, iou [T, m] and counts [T, 3, C]
+            cache_at.append(cpos)
+            cpos += n * m
+            out_at.append(opos)
+            opos += 2 * T * m + 3 * T * C
+        with torch.cuda.device(dev):
+            blob = torch.from_numpy(np.concatenate(parts)).to(dev)
+            gts = [torch.from_numpy(h["gt"]) for h in hs]
+            gt_dev = torch.cat(gts).to(dev) if sum(len(g) for g in gts) else None
+            caches = torch.empty((max(cpos, 1),), dtype=torch.float32, device=dev)
+            out = torch.empty((max(opos, 1),), dtype=torch.int32, device=dev)
+            self._ensure_state(dev, max(m for _, m in sizes))
+            ws_bytes = max(max(lib.d3d_track_workspace_bytes(n, m, T, int(h["row_off"][-1])),
+                               lib.d3d_iou3d_workspace_bytes(n, m)) for (n, m), h in zip(sizes, hs))
+            ws = _lib.workspace(ws_bytes, dev)
+            base = blob.data_ptr()
+            stream = _lib.stream_ptr()
+            g0 = 0
+            fr = _TrackFrame()
+            for (n, m), h, lay, ca, oa in zip(sizes, hs, layout, cache_at, out_at):
+                cache_ptr = caches.data_ptr() + 4 * ca
+                if n and m:
+                    rc = lib.d3d_match_distance(ctypes.c_void_p(base + lay["dt"]), n, ctypes.c_void_p(gt_dev.data_ptr() + 36 * g0), m,
+                                                1, ctypes.c_void_p(cache_ptr), _lib.ptr(ws), ws.numel(), stream)
+                    _lib.check(rc, "match_distance")
+                g0 += m
+                for k, f in (("dt", "dt_boxes"), ("dslot", "dt_cls"), ("gslot", "gt_cls"), ("dtid", "dt_tid"), ("gtid", "gt_tid"),
+                             ("dt_stid", "dt_stid"), ("dt_srow", "dt_srow"), ("gt_stid", "gt_stid"), ("gt_srow", "gt_srow"),
+                             ("perm", "dt_perm"), ("row_off", "row_off")):
+                    setattr(fr, f, base + lay[k])
+                fr.cache = cache_ptr if n and m else None
+                fr.n, fr.m, fr.n_total, fr.capacity = n, m, int(h["row_off"][-1]), self._cap
+                optr = out.data_ptr() + 4 * oa
+                rc = lib.d3d_track_frame(ctypes.addressof(fr), ctypes.c_void_p(base + consts[0]), T, ctypes.c_void_p(base + consts[1]),
+                                         C, _lib.ptr(self._state[self._cur]), _lib.ptr(self._state[1 - self._cur]),
+                                         ctypes.c_void_p(optr), ctypes.c_void_p(optr + 4 * T * m),
+                                         ctypes.c_void_p(optr + 8 * T * m), _lib.ptr(ws), ws.numel(), stream)
+                _lib.check(rc, "track_frame")
+                self._cur ^= 1
+            res = out.cpu().numpy()
+        return [self._frame_stats(h, res[oa:oa + 2 * T * len(h["gt"]) + 3 * T * C]) for h, oa in zip(hs, out_at)]
+
+    def _frame_stats(self, h, res):
+        """the TrackingEvalStats of a frame from the device's per-threshold assignment and counters (:617-723)"""
+        T, C, classes = self._pr_nsamples, len(self._classes), self._classes
+        gt, dt, gslot, dslot, sel = h["gt"], h["dt"], h["gslot"], h["dslot"], h["sel"]
+        m = len(gt)
+        assign = res[:T * m].reshape(T, m)
+        iou = res[T * m:2 * T * m].view(np.float32).reshape(T, m)
+        counts = res[2 * T * m:].reshape(T, 3, C)
+        st = TrackingEvalStats()
+        tracked = (assign >= 0) & (gslot >= 0)[None, :]
+        tt, jj = np.nonzero(tracked)
+        terms, gcls = {}, gslot[jj]
+        if len(tt):
+            d_of = assign[tt, jj]
+            ga, da = gt[jj], dt[d_of]
+            dp, db = ga[:, 2:5] - da[:, 2:5], ga[:, 5:8] - da[:, 5:8]
+            dyaw = ga[:, 8] - da[:, 8]
+            terms = dict(acc_iou=iou[tt, jj],
+                         acc_angular=np.abs((dyaw + np.pi) % (2 * np.pi) - np.pi) / np.pi,              # :663-664
+                         acc_dist=np.sqrt((dp[:, 0] * dp[:, 0] + dp[:, 1] * dp[:, 1]) + dp[:, 2] * dp[:, 2]),
+                         acc_box=np.sqrt((db[:, 0] * db[:, 0] + db[:, 1] * db[:, 1]) + db[:, 2] * db[:, 2]))
+        st.ngt, st.ndt, st.tp, st.fp, st.fn, st.id_switches, st.fragments = {}, {}, {}, {}, {}, {}, {}
+        st.ngt_ids, st.ngt_tracked, st.ndt_ids = {}, {}, {}
+        for name in _ACC_FIELDS:
+            setattr(st, name, {})
+        for i, c in enumerate(classes):
+            gi = np.nonzero(gslot == i)[0]
+            gi = gi[np.argsort(h["gtid"][gi], kind="stable")]
+            di = np.nonzero(dslot == i)[0]
+            di = di[np.argsort(h["dtid"][di], kind="stable")]
+            st.ngt[c] = len(gi)
+            st.ngt_ids[c] = (h["gtid"][gi], np.ones((len(gi),), np.int64))
+            st.ngt_tracked[c] = (h["gtid"][gi], tracked[:, gi].astype(np.int64))
+            st.ndt_ids[c] = (h["dtid"][di], sel[:, di].astype(np.int64))
+            st.ndt[c] = sel[:, di].sum(1).tolist()
+            of_c = gcls == i
+            tp = np.bincount(tt[of_c], minlength=T)
+            st.tp[c] = tp.tolist()
+            st.fn[c] = (len(gi) - tp).tolist()
+            st.fp[c] = counts[:, 0, i].tolist()
+            st.id_switches[c] = counts[:, 1, i].tolist()
+            st.fragments[c] = counts[:, 2, i].tolist()
+            for name in ("acc_iou", "acc_angular", "acc_dist", "acc_box"):
+                if name in terms:
+                    ssum = np.bincount(tt[of_c], weights=terms[name][of_c].astype(np.float64), minlength=T)
+                    with np.errstate(invalid="ignore", divide="ignore"):
+                        v = np.where(tp > 0, (ssum / tp).astype(np.float32), np.float32(np.nan))
+                else:
+                    v = np.full((T,), np.nan, np.float32)
+                getattr(st, name)[c] = v.tolist()
+            st.acc_var[c] = np.where(tp > 0, -np.inf, np.nan).tolist()      # orientation_var = 0 (:666-674)
+        return st
+
+    # ------------------------------------------------------------------ accumulation and metrics
+    def add_stats(self, stats):
+        """:725-756"""
+        DetectionEvaluator.add_stats(self, stats)
+        s = self._stats
+        for k in self._classes:
+            s.ngt_ids[k] = _tid_counts_merge(s.ngt_ids[k], stats.ngt_ids[k])
+            s.ngt_tracked[k] = _tid_counts_merge(s.ngt_tracked[k], stats.ngt_tracked[k])
+            s.ndt_ids[k] = _tid_counts_merge(s.ndt_ids[k], stats.ndt_ids[k])
+            s.id_switches[k] = [a + int(b) for a, b in zip(s.id_switches[k], stats.id_switches[k])]
+            s.fragments[k] = [a + int(b) for a, b in zip(s.fragments[k], stats.fragments[k])]
+
+    def id_switches(self, score=math.nan):
+        """Return ID switch count. If score is not specified, return the median value"""
+        return self._at(self._stats.id_switches, score)
+
+    def fragments(self, score=math.nan):
+        """Return fragments count. If score is not specified, return the median value"""
+        return self._at(self._stats.fragments, score)
+
+    def gt_traj_count(self):
+        """Return total ground-truth trajectory count. gt() will return total bounding box count"""
+        return {self._key(k): int(np.count_nonzero(self._stats.ngt_ids[k][1])) for k in self._classes}
+
+    def _calc_frame_ratio(self, score, frame_ratio_threshold, high_pass, return_all):
+        """:790-819: per class, the share of gt trajectories tracked in more (high_pass) / fewer than the threshold's share of
+        their frames (fp32 ratio); divided by the number of gt trajectories (ZeroDivisionError without one, as there)"""
+        thr = np.float32(frame_ratio_threshold)
+        idx = list(range(self._pr_nsamples)) if return_all else [self._get_score_idx(score)]
+        r = {}
+        for k in self._classes:
+            gids, gcnt = self._stats.ngt_ids[k]
+            tids, tcnt = self._stats.ngt_tracked[k]
+            total = gcnt[np.searchsorted(gids, tids)] if len(tids) else np.zeros((0,), np.int64)
+            vals = []
+            for i in idx:
+                on = tcnt[i] > 0
+                ratio = (tcnt[i][on].astype(np.float64) / total[on]).astype(np.float32)
+                hit = ratio > thr if high_pass else ratio < thr
+                vals.append(float(int(hit.sum())) / len(gids))
+            r[self._key(k)] = vals if return_all else vals[0]
+        return r
+
+    def tracked_ratio(self, score=math.nan, frame_ratio_threshold=0.8, return_all=False):
+        """Return the ratio of mostly tracked trajectories (tracked in more than frame_ratio_threshold of their frames)"""
+        return self._calc_frame_ratio(score, frame_ratio_threshold, True, return_all)
+
+    def lost_ratio(self, score=math.nan, frame_ratio_threshold=0.2, return_all=False):
+        """Return the ratio of mostly lost trajectories (tracked in fewer than frame_ratio_threshold of their frames)"""
+        return self._calc_frame_ratio(score, frame_ratio_threshold, False, return_all)
+
+    def mota(self, score=math.nan):
+        """Return the MOTA metric defined by the CLEAR MOT metrics (:835-841). For MOTP equivalents, see acc_* properties"""
+        i, s = self._get_score_idx(score), self._stats
+        r = {}
+        for k in self._classes:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                r[self._key(k)] = float(1 - np.float64(s.fp[k][i] + s.fn[k][i] + s.id_switches[k][i]) / np.float64(s.ngt[k]))
+        return r
+
+    def summary(self, score_thres=0.8, tracked_ratio_thres=0.8, lost_ratio_thres=0.2, note=None, verbose=False):
+        """Print default summary (into returned string) (:843-890); int classes print as the int"""
+        score_thres = _f32(score_thres)
+        tracked_ratio_thres, lost_ratio_thres = _f32(tracked_ratio_thres), _f32(lost_ratio_thres)
+        score_idx = self._get_score_idx(score_thres)
+        s = self._stats
+        lines = [""]
+        precision, recall = self.precision(score_thres), self.recall(score_thres)
+        fscore, ap = self.fscore(return_all=True), self.ap()
+        mlt = self.tracked_ratio(score_thres, tracked_ratio_thres)
+        mll = self.lost_ratio(score_thres, lost_ratio_thres)
+        mota = self.mota(score_thres)
+        if note:
+            lines.append("========== Benchmark Summary (%s) ==========" % note)
+        else:
+            lines.append("========== Benchmark Summary ==========")
+        for k in self._classes:
+            typed_k = self._key(k)
+            if verbose:
+                lines.append("Results for %s:" % self._name(k))
+                lines.append("\tTotal processed targets:\t%d gt boxes, %d dt boxes" % (s.ngt[k], max(s.ndt[k])))
+                lines.append("\tTotal processed trajectories:\t%d gt tracklets, %d dt tracklets" % (
+                    self.gt_traj_count()[typed_k], max(int(np.count_nonzero(row)) for row in s.ndt_ids[k][1])))
+                lines.append("\tPrecision (score > %.2f):\t%.3f" % (score_thres, precision[typed_k]))
+                lines.append("\tRecall (score > %.2f):\t\t%.3f" % (score_thres, recall[typed_k]))
+                lines.append("\tMax F1:\t\t\t\t%.3f" % max(fscore[typed_k]))
+                lines.append("\tAP:\t\t\t\t%.3f" % ap[typed_k])
+                lines.append("")
+                lines.append("\tID switches (score > %.2f):\t\t\t%d" % (score_thres, s.id_switches[k][score_idx]))
+                lines.append("\tFragments (score > %.2f):\t\t\t%d" % (score_thres, s.fragments[k][score_idx]))
+                lines.append("\tMOTA (score > %.2f):\t\t\t\t%.2f" % (score_thres, mota[typed_k]))
+                lines.append("\tMostly tracked (score > %.2f, ratio > %.2f):\t%.3f" % (
+                    score_thres, tracked_ratio_thres, mlt[typed_k]))
+                lines.append("\tMostly lost (score > %.2f, ratio < %.2f):\t%.3f" % (
+                    score_thres, lost_ratio_thres, mll[typed_k]))
+                lines.append("")
+                self._summary_accuracy(lines, k, score_thres, score_idx)
+            else:
+                lines.append("Results for %s: AP=%.3f, MOTA=%.3f" % (self._name(k), ap[typed_k], mota[typed_k]))
+        lines.append("mAP: %.3f" % np.mean(list(ap.values())))
+        lines.append("========== Summary End ==========")
+        return "\n".join(lines)
+
+
+__all__ = ["DetectionEvaluator", "SegmentationEvaluator", "SegmentationStats", "TrackingEvalStats", "TrackingEvaluator"]

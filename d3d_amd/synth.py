@@ -86,3 +86,50 @@ def segmentation_frame(n, num_classes=19, inst_per_class=30, noise=0.05, seed=0)
     pred_labels[flip] = rng.integers(0, num_classes + 1, int(flip.sum()))
     pred_ids[flip] = rng.integers(0, 1000, int(flip.sum()))
     return gt_labels, pred_labels, gt_ids, pred_ids
+
+
+def tracking_sequence(frames=20, n_tracks=30, classes=(1, 2), seed=0, dropout=0.1, swap=0.05, false_tracks=5, jitter=0.3):
+    """A seeded tracking sequence: n_tracks objects moving in straight lines, detected with jitter; a detection drops out with
+    probability `dropout`, two detections of a frame swap their ids with probability `swap`, `false_tracks` spurious tracks
+    per frame.  -> (gt [G,9] f32, dt [D,9] f32, gt_tids u64[G], dt_tids u64[D], gt_offsets [F+1], dt_offsets [F+1]).
+    Scores are distinct (uniform), tids are unique per frame and > 0."""
+    rng = np.random.default_rng(seed)
+    pos = rng.uniform(-40, 40, (n_tracks, 3)).astype(np.float32)
+    pos[:, 2] = rng.uniform(-1, 1, n_tracks)
+    vel = rng.normal(0, 0.6, (n_tracks, 3)).astype(np.float32)
+    vel[:, 2] = 0
+    dims = rng.uniform(1.5, 4.5, (n_tracks, 3)).astype(np.float32)
+    yaw = rng.uniform(-np.pi, np.pi, n_tracks).astype(np.float32)
+    cls = rng.choice(np.asarray(classes), n_tracks)
+    gts, dts, gtids, dtids, go, do = [], [], [], [], [0], [0]
+    next_false = 100000
+    for f in range(frames):
+        p = pos + f * vel
+        g = np.concatenate([cls[:, None], np.ones((n_tracks, 1)), p, dims, yaw[:, None]], 1).astype(np.float32)
+        keep = rng.random(n_tracks) > dropout * 0.5
+        gts.append(g[keep])
+        gtids.append(np.arange(1, n_tracks + 1, dtype=np.uint64)[keep])
+        det = rng.random(n_tracks) > dropout
+        d = g[det].copy()
+        d[:, 2:5] += rng.normal(0, jitter, (len(d), 3)).astype(np.float32)
+        d[:, 5:8] *= rng.uniform(0.9, 1.1, (len(d), 3)).astype(np.float32)
+        d[:, 8] += rng.normal(0, 0.1, len(d)).astype(np.float32)
+        dtid = np.arange(1001, 1001 + n_tracks, dtype=np.uint64)[det]
+        if len(dtid) >= 2 and rng.random() < swap * len(dtid):
+            i, j = rng.choice(len(dtid), 2, replace=False)
+            dtid[i], dtid[j] = dtid[j], dtid[i]
+        fk = np.concatenate([rng.choice(np.asarray(classes), (false_tracks, 1)), np.zeros((false_tracks, 1)),
+                             rng.uniform(-40, 40, (false_tracks, 3)), rng.uniform(1.5, 4.5, (false_tracks, 3)),
+                             rng.uniform(-np.pi, np.pi, (false_tracks, 1))], 1).astype(np.float32)
+        fk[:, 4] = rng.uniform(-1, 1, false_tracks)
+        d = np.concatenate([d, fk])
+        d[:, 1] = rng.random(len(d)).astype(np.float32)
+        dtid = np.concatenate([dtid, np.arange(next_false, next_false + false_tracks, dtype=np.uint64)])
+        next_false += false_tracks
+        o = rng.permutation(len(d))
+        dts.append(d[o])
+        dtids.append(dtid[o])
+        go.append(go[-1] + len(gts[-1]))
+        do.append(do[-1] + len(d))
+    return (np.concatenate(gts), np.concatenate(dts), np.concatenate(gtids), np.concatenate(dtids),
+            np.asarray(go, np.int64), np.asarray(do, np.int64))

@@ -662,6 +662,49 @@ int d3d_segeval(const uint8_t *gt_labels, const uint8_t *pred_labels, const uint
                 int32_t *tp, int32_t *fp, int32_t *fn, int32_t *itp, int32_t *ifp, int32_t *ifn, float *cumiou,
                 void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ d3d/benchmarks: tracking */
+
+/* One frame of TrackingEvaluator.calc_stats (reference d3d/benchmarks.pyx:536-723), every score threshold at once.  All
+ * pointers are device memory.  Boxes are [n,9] / [m,9] f32 rows (label, score, x, y, z, lx, ly, lz, yaw); cache[n,m] f32 =
+ * d3d_match_distance(dt, gt, rotated = 1).  Classes are slots 0 .. C-1 of the evaluator's classes, -1 = outside them.
+ *   dt_cls[n], gt_cls[m] i32 slots; dt_tid[n], gt_tid[m] u64 track ids, unique within the frame;
+ *   dt_stid[n] / dt_srow[n], gt_stid[m] / gt_srow[m]: the tids sorted ascending and the row of each;
+ *   dt_perm[n] i32: the detections in the reference's score order, np.flip(np.argsort(scores, kind="stable"));
+ *   row_off[T + 1] i64: problem t of the association owns rows row_off[t] .. row_off[t + 1], as many as detections are
+ *   selected at threshold t (slot class >= 0 and !(score < threshold)); n_total = row_off[T];
+ *   capacity: pairs per threshold of the two state buffers, >= m. */
+typedef struct D3DTrackFrame {
+    const float *dt_boxes;
+    const float *cache;
+    const int32_t *dt_cls;
+    const int32_t *gt_cls;
+    const uint64_t *dt_tid;
+    const uint64_t *gt_tid;
+    const uint64_t *dt_stid;
+    const int32_t *dt_srow;
+    const uint64_t *gt_stid;
+    const int32_t *gt_srow;
+    const int32_t *dt_perm;
+    const int64_t *row_off;
+    int64_t n;
+    int64_t m;
+    int64_t n_total;
+    int64_t capacity;
+} D3DTrackFrame;
+
+/* Bytes of one state buffer: count i32[T], then gt_tid u64[T, capacity], dt_tid u64[T, capacity], gt_cls i32[T, capacity],
+ * dt_cls i32[T, capacity], each piece starting at a 256-byte boundary.  An all-zero buffer is the empty state. */
+size_t d3d_track_state_bytes(int64_t capacity, int32_t thresholds);
+size_t d3d_track_workspace_bytes(int64_t n, int64_t m, int32_t thresholds, int64_t n_total);
+/* thresholds[T] f32, max_dist[C] f32 (= 1 - min overlap of the class); state_in -> state_out (distinct buffers of
+ * d3d_track_state_bytes(capacity, T)); outputs: assign[T, m] i32 = the detection assigned to ground truth j at threshold t
+ * (fresh match or kept carry-over) or -1, iou[T, m] f32 = 1 - cache of that pair, counts[T, 3, C] i32 = fp, id switches,
+ * fragments.  Three launches (prepare, d3d_score_match_batched, update), no synchronisation.
+ * D3D_ERR_BAD_ARG: T outside 1 .. 65535, C outside 1 .. 4096, capacity < m, state_in == state_out, a missing pointer. */
+int d3d_track_frame(const D3DTrackFrame *frame, const float *thresholds, int32_t T, const float *max_dist, int32_t C,
+                    const void *state_in, void *state_out, int32_t *assign, float *iou, int32_t *counts,
+                    void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
