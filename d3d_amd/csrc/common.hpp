@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 #include "d3d_hip.h"
 
 extern int g_d3d_last_hip_error;
@@ -28,6 +29,11 @@ void d3d_prof_post(const char *name, hipStream_t st);
         if (g_d3d_prof_on) d3d_prof_post(NAME, st);                           \
         D3D_LAUNCH_CHECK();                                                   \
     } while (0)
+
+// a runtime flag -> a template argument: f(std::true_type{}) or f(std::false_type{}), f a generic lambda around ONE launch
+// site (`k<.., flag, ..>` inside it); returns what f returns (D3D_OK, or the error code of a failed launch)
+template <class F>
+static inline int dispatch(bool flag, F &&f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
 
 static inline size_t d3d_align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 static inline int64_t d3d_divup(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -1191,13 +1191,6 @@ constexpr uint32_t kXcdBucketsMin = 2048;     // k_bucket_index: XCD-aware bucke
 //                     kInf                        not a first point.
 // One dependent random gather less per multi-point voxel in k_emit, no record stores in the index, and the points kept
 // (min(count, max_points)) are known to k_emit as soon as its first load returns.  Positions stay below 2^24 - 1 (host-checked).
-// experiment knobs of the diagnostic build (make TUNE=1 -> libd3d_hip_tune.so; tools/tune_ab.py): the product build compiles the defaults in
-#ifdef D3D_TUNE
-int g_d3d_tune[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
-#define D3D_TUNE_VAL(K, DEF) (g_d3d_tune[K] >= 0 ? g_d3d_tune[K] : (DEF))
-#else
-#define D3D_TUNE_VAL(K, DEF) (DEF)
-#endif
 constexpr uint32_t kFmShift = 24, kFmMask = 0xffffffu, kFmRecord = 255u;
 constexpr int64_t kFmMaxPoints = (1 << 24) - 2;
 constexpr uint32_t kDenseMin = 32;            // V2: cells with more points are ranked by ONE wavefront (select + all-pairs on the kept ones);
@@ -1212,6 +1205,8 @@ constexpr uint32_t kDenseMin = 32;            // V2: cells with more points are 
 // behind the buckets (the CUs are full: they only run in the launch's tail): profiles/r06_ab_prefill.txt.  The range is fixed by
 // the host before the first launch, from the frame's size alone (no state from earlier calls): rows past the final V are never
 // returned (the tensor has min(n, max_voxels) rows), so an overshoot only wastes stores.
+// pieces of 1024 x 16 B each filler workgroup of k_tile_sort / k_first_count writes (profiles/r06_ab_prefill.txt)
+constexpr int kFillSortPieces = 36, kFillCountPieces = 12;
 struct ZeroFill {
     float4 *dst = nullptr;
     int64_t n16 = 0;
@@ -2899,8 +2894,7 @@ __global__ __launch_bounds__(WG) void k_emit_split(Key kf, int64_t npad, const u
                                                     const float4 *__restrict__ staged, uint32_t P, int pshift /* log2 P or -1 */,
                                                     int reduction, int64_t *coords, int32_t *npoints, unsigned char *pmask /* or NULL */,
                                                     float4 *agg, float4 *voxels, int64_t *counts, int64_t *host_counts,
-                                                    uint32_t prefilled, int64_t aux_value,
-                                                    uint32_t dbg /* TUNE build: timing experiments with WRONG outputs; else 0 */)
+                                                    uint32_t prefilled, int64_t aux_value)
 {
     typedef float vec4 __attribute__((ext_vector_type(4)));
     typedef uint32_t uvec4 __attribute__((ext_vector_type(4)));
@@ -2952,9 +2946,8 @@ __global__ __launch_bounds__(WG) void k_emit_split(Key kf, int64_t npad, const u
     vec4 *out = reinterpret_cast<vec4 *>(voxels) + (int64_t)vid0 * P;
     const vec4 zero = {0.f, 0.f, 0.f, 0.f};
     if (zrole) {
-        if (dbg & 8u) return;                               // no second role at all
         float4 p0 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (mine && !isrec && !(dbg & 2u)) p0 = points4[il];               // (ascending indices inside the wavefront's 1 KiB window)
+        if (mine && !isrec) p0 = points4[il];               // (ascending indices inside the wavefront's 1 KiB window)
         {
             const uint32_t kept_e = c8 < P ? c8 : P, l8 = (kept_e + 7u) & ~7u;
             sh_lim[lane] = (uint16_t)(!mine ? 0u : (isrec || l8 > P) ? P : l8);
@@ -2964,7 +2957,7 @@ __global__ __launch_bounds__(WG) void k_emit_split(Key kf, int64_t npad, const u
         // store (behind the store loop the compiler can only wait for everything in flight; zeros first: 62 -> 56 us with the
         // filled range below, profiles/r06_ab_split.txt).  Cell: the same arithmetic on the same floats as k_tile_sort.
         long long *cbuf = WG == 512 ? zbuf_all[w & 3] : reinterpret_cast<long long *>(rowbuf);       // 64 * 3 * 8 B = 1.5 KiB
-        if (mine && !isrec && !(dbg & 2u)) {
+        if (mine && !isrec) {
             const float v3[3] = {p0.x, p0.y, p0.z};
             u64 key = 0;
             uint32_t st = 0;
@@ -2976,9 +2969,9 @@ __global__ __launch_bounds__(WG) void k_emit_split(Key kf, int64_t npad, const u
         }
         wave_lds_fence();
         long long *cdst = reinterpret_cast<long long *>(coords) + (int64_t)vid0 * 3;
-        for (uint32_t t = lane; t < ((dbg & 2u) ? 0u : nv * 3); t += kWave)
+        for (uint32_t t = lane; t < nv * 3; t += kWave)
             if (!((recmask >> (t / 3u)) & 1ull)) __builtin_nontemporal_store(cbuf[t], &cdst[t]);
-        if (pmask && !(dbg & 2u)) {                                         // P % 16 == 0, 16-byte aligned (host-checked): 16-byte pieces
+        if (pmask) {                                         // P % 16 == 0, 16-byte aligned (host-checked): 16-byte pieces
             const uint32_t per = P >> 4, total = nv * per;
             uvec4 *pdst = reinterpret_cast<uvec4 *>(pmask + (int64_t)vid0 * P);
             for (uint32_t t = lane; t < total; t += kWave) {
@@ -2997,7 +2990,7 @@ __global__ __launch_bounds__(WG) void k_emit_split(Key kf, int64_t npad, const u
         }
         // rows [lim, P) of the voxels past the range filled under the index launches
         const uint32_t npre = prefilled <= vid0 ? 0u : (prefilled - vid0 < nv ? prefilled - vid0 : nv);
-        const uint32_t qa = (dbg & 1u) ? 0u : nv * P;
+        const uint32_t qa = nv * P;
         for (uint32_t q0 = npre * P; q0 < qa; q0 += 4 * kWave) {
 #pragma unroll
             for (int u = 0; u < 4; u++) {
@@ -3010,7 +3003,6 @@ __global__ __launch_bounds__(WG) void k_emit_split(Key kf, int64_t npad, const u
         }
         return;
     }
-    if (dbg & 4u) return;                                   // no chain role at all
     // the chain
     uint32_t cnt = mine ? c8 : 0u, base = seg;
     u64 key = 0;
@@ -3049,13 +3041,12 @@ __global__ __launch_bounds__(WG) void k_emit_split(Key kf, int64_t npad, const u
                     if (sh_off[mid] - oa <= t) lo = mid; else hi = mid;
                 }
                 const uint32_t k = t - (sh_off[lo] - oa);
-                if (dbg & 16u) continue;                    // no row gather
                 const uint32_t idx = k == 0 ? sh_first[lo] : ranked[sh_base[lo] + k];
                 rowbuf[t] = *reinterpret_cast<const vec4 *>(&points4[idx]);
             }
         }
         wave_lds_fence();
-        if (AGG4 && !(dbg & 32u) && (uint32_t)lane >= ja && (uint32_t)lane < jb && cnt <= P) {     // reductions in point order, one lane per voxel
+        if (AGG4 && (uint32_t)lane >= ja && (uint32_t)lane < jb && cnt <= P) {     // reductions in point order, one lane per voxel
             const vec4 *rw = rowbuf + (off - oa);
             for (uint32_t k = 0; k < kept; k++) {
                 const vec4 x = rw[k];
@@ -3070,7 +3061,7 @@ __global__ __launch_bounds__(WG) void k_emit_split(Key kf, int64_t npad, const u
         // rows [0, lim) of the batch's voxels, flat: eight lanes per 128-byte line
         const uint32_t l0 = (uint32_t)__shfl((int)loff, (int)ja, kWave);
         const uint32_t l1 = (uint32_t)__shfl((int)lincl, (int)jb - 1, kWave);
-        for (uint32_t t0 = l0; t0 < ((dbg & 64u) ? l0 : l1); t0 += kWave) {     // (64: no row lines)
+        for (uint32_t t0 = l0; t0 < l1; t0 += kWave) {
             const uint32_t t = t0 + lane;
             if (t < l1) {
                 uint32_t lo = ja, hi = jb;                  // largest j in [ja, jb) with loff[j] <= t
@@ -3087,7 +3078,7 @@ __global__ __launch_bounds__(WG) void k_emit_split(Key kf, int64_t npad, const u
         wave_lds_fence();                                   // the next batch overwrites the buffer
         ja = jb;
     }
-    if (AGG4 && mine && !(dbg & 128u)) {
+    if (AGG4 && mine) {
         vec4 res;
         if (cnt > P) res = *reinterpret_cast<const vec4 *>(&staged[base + P]);   // fp64 reduction of k_bucket_index (voxelize.cpp:137-157)
         else {
@@ -4295,6 +4286,29 @@ static bool dense_cells_fit_u32(const DenseKey &kf)     // 32-bit cell keys in L
     return (double)kf.shape[0] * (double)kf.shape[1] * (double)kf.shape[2] < 4294967295.0;
 }
 
+// k_tile_sort over tiles of 2^tshift points: 4096, 8192 or 16384 on the float4 rows of the callers that stage rows (ROWS),
+// 8192 for everything else -- only those instantiations are compiled
+template <class Key, bool V4, bool ROWS, class... Args>
+static int launch_tile_sort(int tshift, size_t lds, dim3 grid, hipStream_t st, const Args &...args)
+{
+    auto launch = [&](auto items) {
+        if (lds + 1024 > 65536)
+            D3D_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_sort<Key, V4, ROWS, items>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        D3D_LAUNCH("k_tile_sort", (k_tile_sort<Key, V4, ROWS, items>), grid, dim3(kSortThreads), lds, st, args...);
+        return D3D_OK;
+    };
+    if constexpr (V4 && ROWS) {
+        if (tshift == 14) return launch(std::integral_constant<int, 16>{});
+        if (tshift == 12) return launch(std::integral_constant<int, 4>{});
+    }
+    return launch(std::integral_constant<int, 8>{});
+}
+
+// binned_index's output stage: k_meta_first_lb (fused sparse + filter), nothing (staged call, stage 1), k_emit_split of 256 or
+// 512 lanes, k_emit<.., RESIDENT>, k_emit, k_emit_c (dense contract, C != 4), k_meta_first
+enum class Emit { meta_first_lb, none, split256, split512, resident, emit, emit_c, meta_first };
+
 // ROWS: dense contract on C == 4 rows (ranked rows staged, reductions); !ROWS: keys only (sparse contract, any C)
 template <class Key, bool ROWS>
 static int binned_index(const Key &kf, const float *points, int64_t n, int c, const VoxelWs &w, uint32_t nbins, int hshift,
@@ -4349,19 +4363,16 @@ static int binned_index(const Key &kf, const float *points, int64_t n, int c, co
     x.fm_packed = fm_packed;
     // round 6: the dense contract itself (nothing for the sharded operator, no resident rows, no staged call) leaves through
     // k_emit_split, and part of its zero padding under the index launches (ZeroFill)
-    const bool split = fm_packed && o.emit_voxels && !x.row_state && o.stage == 0 && !x.keys_out && !x.first_out && !x.voff && !want_map &&
-                       D3D_TUNE_VAL(3, 1) != 0;
-    const int fill_sort_k = split ? D3D_TUNE_VAL(6, 36) : 0, fill_count_k = split ? D3D_TUNE_VAL(11, 12) : 0;    // 1024 x 16 B per filler
+    const bool split = fm_packed && o.emit_voxels && !x.row_state && o.stage == 0 && !x.keys_out && !x.first_out && !x.voff && !want_map;
     // (frames of 0.72 .. 1.3 M points: below, k_emit_split is not store-bound and the fillers only lengthen the partition -- 0.5 M
     // points 71 -> 78 us, 0.1 M 57 -> 64 --, above, every CU has a tile: profiles/r06_ab_sizes.txt)
-    const bool fill_tiles = fill_sort_k > 0 && !big_tiles && vec4 && tile_sort && (w.npad >> 13) >= 88 && (w.npad >> 13) <= 160;
+    const bool fill_tiles = split && !big_tiles && vec4 && tile_sort && (w.npad >> 13) >= 88 && (w.npad >> 13) <= 160;
     // tiles of 4096 points while tiles of 8192 would leave a third of the CUs without a workgroup (one workgroup per tile):
     // 1 M points 16.2 -> 13.7 us with the bucket kernel unchanged; at 2 M points (245 tiles of 8192) +4 us, at 4 M +6; tiles of
     // 2048 points: +2 us in the bucket kernel (runs of two entries) -- profiles/r05_b_tune.txt.  Round 6: where fillers take the
     // CUs without a tile, tiles of 8192 it is (those CUs then write 76 MB of zeros in the 16 us).
-    const int tune_tile = !big_tiles && vec4 && ROWS ? D3D_TUNE_VAL(2, (w.npad >> 13) <= 160 && !fill_tiles ? 12 : 0) : 0;
-    const bool small_tiles = tune_tile == 12, tiny_tiles = tune_tile == 11;
-    const int tshift = big_tiles ? 14 : small_tiles ? 12 : tiny_tiles ? 11 : 13;
+    const bool small_tiles = ROWS && !big_tiles && (w.npad >> 13) <= 160 && !fill_tiles;
+    const int tshift = big_tiles ? 14 : small_tiles ? 12 : 13;
     const uint32_t stiles = (uint32_t)(w.npad >> tshift);
     uint32_t *table = nullptr, *tileinfo = nullptr, *gpos = reinterpret_cast<uint32_t *>(w.vinfo) + w.npad;
     if (tile_sort && n <= (ROWS ? kTileSortMaxPoints : kTileSortMaxPointsSparse) && nbins <= 8192u && stiles <= (uint32_t)kRunCap &&
@@ -4370,8 +4381,17 @@ static int binned_index(const Key &kf, const float *points, int64_t n, int c, co
         tileinfo = tilecnt + (size_t)nbins * stiles;
     }
     // (early zero lines: -6 us at 1 M points, -7 at 2 M, -3 at 4 M, nothing at 8 M, where the launch is in its steady state)
-    x.early_zero = fm_packed && D3D_TUNE_VAL(4, n < kBigTileMinPoints ? 1 : 0) != 0;
+    x.early_zero = fm_packed && n < kBigTileMinPoints;
     const bool do_index = o.stage != 2;                        // (stage 2: this frame's index was launched by an earlier call)
+    // the output stage.  k_emit_split with both roles in ONE workgroup of 512 lanes from 3 M points on (less LDS per wavefront,
+    // 32 instead of 28 per CU): 4 M points 384 -> 358 us, 8 M 704 -> 664, a uniform cloud of 1 M 99 -> 93; 2 M and below: the
+    // same or worse (config 2 with its fillers 61 -> 65) -- profiles/r06_ab_sizes.txt
+    const Emit out = !ROWS && o.map_later ? Emit::meta_first_lb
+                     : o.stage == 1 ? Emit::none
+                     : !ROWS && std::is_same<Key, DenseKey>::value && o.emit_generic ? Emit::emit_c
+                     : !ROWS || !(o.emit_voxels || o.emit_reduce) ? Emit::meta_first
+                     : split ? (n >= (3ll << 20) ? Emit::split512 : Emit::split256)
+                     : x.row_state && o.emit_voxels ? Emit::resident : Emit::emit;
     // voxels[0 .. prefilled): as much as the idle CUs of the two launches write in passing, at most the voxels a LiDAR frame of
     // this size has (9 n / 16; config 2: 0.585 n) and never more than the tensor's rows
     ZeroFill zf_sort, zf_count;
@@ -4385,23 +4405,23 @@ static int binned_index(const Key &kf, const float *points, int64_t n, int c, co
             zf_sort.nblk = (uint32_t)kNumCUs - sort_wgs;
             zf_sort.first = sort_wgs;
             zf_sort.dst = o.emit_voxels;
-            zf_sort.n16 = (int64_t)zf_sort.nblk * fill_sort_k * 1024;
+            zf_sort.n16 = (int64_t)zf_sort.nblk * kFillSortPieces * 1024;
             if (zf_sort.n16 > kFillSortMax16) zf_sort.n16 = kFillSortMax16;      // (what leaves in the launch's 16 us, however many fillers)
             if (zf_sort.n16 > all16) zf_sort.n16 = all16;
             at = zf_sort.n16;
         }
-        if (fill_count_k > 0 && fill_tiles && count_wgs + 64u <= (uint32_t)kNumCUs && at < all16) {
+        if (fill_tiles && count_wgs + 64u <= (uint32_t)kNumCUs && at < all16) {
             zf_count.nblk = (uint32_t)kNumCUs - count_wgs;
             zf_count.first = count_wgs;
             zf_count.dst = o.emit_voxels + at;
-            zf_count.n16 = (int64_t)zf_count.nblk * fill_count_k * 1024;
+            zf_count.n16 = (int64_t)zf_count.nblk * kFillCountPieces * 1024;
             if (zf_count.n16 > all16 - at) zf_count.n16 = all16 - at;
             at += zf_count.n16;
         }
         prefilled = (uint32_t)(at / (int64_t)o.P);
     }
     if (o.emit_voxels && o.stage == 0) {
-        g_last_plan[0] = split ? 1 : 0;
+        g_last_plan[0] = out == Emit::split256 || out == Emit::split512;
         g_last_plan[1] = prefilled;
         g_last_plan[2] = zf_sort.n16 * 16;
         g_last_plan[3] = zf_count.n16 * 16;
@@ -4409,35 +4429,29 @@ static int binned_index(const Key &kf, const float *points, int64_t n, int c, co
     if (do_index && table) {
         const size_t lds = ((size_t)1 << tshift) * (sizeof(typename Key::bin_key_t) + 2) + bin_lds;
         uint32_t *ppos = o.map_later ? pbin : nullptr;      // (pfirst: by point, the first point of its voxel when it is kept)
-#define D3D_TILE_SORT(V4, IT)                                                                                                   \
-    do {                                                                                                                        \
-        if (lds + 1024 > 65536)                                                                                                 \
-            D3D_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_sort<Key, V4, ROWS, IT>),                  \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                           \
-        D3D_LAUNCH("k_tile_sort", (k_tile_sort<Key, V4, ROWS, IT>), dim3((((stiles + 7u) >> 3) << 3) + zf_sort.nblk), dim3(kSortThreads), lds, st, kf, points, n, c, \
-                   nbins, stiles, bent, table, tileinfo, ppos, firstmap, counts, o.mapping, o.trimmed, o.keepid, zero_words,    \
-                   nzero, zero_ticket, true, zf_sort);                                                                          \
-    } while (0)
-        if (big_tiles) D3D_TILE_SORT(true, 16);
-        else if (small_tiles) D3D_TILE_SORT(true, 4);
-        else if (tiny_tiles) D3D_TILE_SORT(true, 2);
-        else if (vec4) D3D_TILE_SORT(true, 8);
-        else D3D_TILE_SORT(false, 8);
-#undef D3D_TILE_SORT
+        auto sort = [&](auto v4) {
+            return launch_tile_sort<Key, v4, ROWS>(tshift, lds, dim3((((stiles + 7u) >> 3) << 3) + zf_sort.nblk), st, kf, points, n, c,
+                                                   nbins, stiles, bent, table, tileinfo, ppos, firstmap, counts, o.mapping, o.trimmed,
+                                                   o.keepid, zero_words, nzero, zero_ticket, true, zf_sort);
+        };
+        if constexpr (ROWS) {
+            if (const int rc = sort(std::true_type{})) return rc;        // (vec4 whenever ROWS)
+        } else if (const int rc = dispatch(vec4, sort)) return rc;
     } else if (do_index) {
-    if (bin_lds + 256 > 65536) {
-        D3D_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bin_scatter<ROWS>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds));
-    }
-    if (vec4)
-        D3D_LAUNCH("k_bin_count", (k_bin_count<Key, true, ROWS>), dim3(ntiles), dim3(kBinThreads), bin_lds, st, kf, points, n, c, nbins,
-                   passes, pbin, pkey, tilecnt, firstmap, counts, o.mapping, o.trimmed, o.keepid, zero_words, nzero, zero_ticket);
-    else
-        D3D_LAUNCH("k_bin_count", (k_bin_count<Key, false, ROWS>), dim3(ntiles), dim3(kBinThreads), bin_lds, st, kf, points, n, c, nbins,
-                   passes, pbin, pkey, tilecnt, firstmap, counts, o.mapping, o.trimmed, o.keepid, zero_words, nzero, zero_ticket);
-    D3D_LAUNCH("k_bin_scan", k_bin_scan, dim3((nbins + kWave - 1) / kWave), dim3(1024), 0, st, tilecnt, nbins, ntiles, totals);
-    D3D_LAUNCH("k_bin_scatter", k_bin_scatter<ROWS>, dim3(ntiles), dim3(kBinThreads), bin_lds, st, pkey, n, nbins, pbin, tilecnt, totals,
-               bucket_base, bent, counts, o.map_later, passes);
+        if (bin_lds + 256 > 65536) {
+            D3D_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bin_scatter<ROWS>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds));
+        }
+        if (const int rc = dispatch(vec4, [&](auto v4) {
+                D3D_LAUNCH("k_bin_count", (k_bin_count<Key, v4, ROWS>), dim3(ntiles), dim3(kBinThreads), bin_lds, st, kf, points, n, c,
+                           nbins, passes, pbin, pkey, tilecnt, firstmap, counts, o.mapping, o.trimmed, o.keepid, zero_words, nzero,
+                           zero_ticket);
+                return D3D_OK;
+            }))
+            return rc;
+        D3D_LAUNCH("k_bin_scan", k_bin_scan, dim3((nbins + kWave - 1) / kWave), dim3(1024), 0, st, tilecnt, nbins, ntiles, totals);
+        D3D_LAUNCH("k_bin_scatter", k_bin_scatter<ROWS>, dim3(ntiles), dim3(kBinThreads), bin_lds, st, pkey, n, nbins, pbin, tilecnt, totals,
+                   bucket_base, bent, counts, o.map_later, passes);
     }
     if (!do_index) { }
     else if (!ROWS && o.lists)
@@ -4452,7 +4466,7 @@ static int binned_index(const Key &kf, const float *points, int64_t n, int c, co
                        bent, p4, bucket_base, hshift, o.P, o.agg4 ? o.reduction : (int)D3D_REDUCE_NONE, w.staged, vrec, firstmap,
                        counts, (uint32_t *)nullptr, w.parr, reinterpret_cast<uint32_t *>(w.vinfo), (unsigned char *)nullptr, w.big_list,
                        (uint32_t *)nullptr, table, stiles, tshift, tileinfo, gpos, (uint32_t *)nullptr, (u64 *)nullptr, 0u, 0u,
-                       bits_for((u64)(n > 1 ? n - 1 : 1)), (uint32_t)D3D_TUNE_VAL(0, (int)kDenseMin));
+                       bits_for((u64)(n > 1 ? n - 1 : 1)));
     } else if (ROWS && (o.emit_voxels || o.emit_reduce))
         D3D_LAUNCH("k_bucket_index", (k_bucket_index<Key, ROWS, true, false>), dim3(nbins), dim3(kBucketThreads), 0, st, kf, o.pass,
                    bent, p4, bucket_base, hshift, o.P, o.agg4 ? o.reduction : (int)D3D_REDUCE_NONE, w.staged, vrec, firstmap,
@@ -4465,7 +4479,7 @@ static int binned_index(const Key &kf, const float *points, int64_t n, int c, co
                    precpos, w.parr, reinterpret_cast<uint32_t *>(w.vinfo), o.trimmed, (uint32_t *)nullptr, (uint32_t *)nullptr,
                    table, stiles, tshift, tileinfo, gpos, o.map_later ? pbin : (uint32_t *)nullptr, early_tot, x.npoints_clamp, early_pairs ? early_pairs - 1u : 0u);
     if constexpr (!ROWS) {
-        if (meta_lb) {
+        if (out == Emit::meta_first_lb) {
             D3D_LAUNCH("k_meta_first_lb", k_meta_first_lb<Key>, dim3(mtiles), dim3(kMetaLbThreads), 0, st, kf, w.npad, firstmap, vrec,
                        o.max_voxels, o.coords, o.npoints, counts, x, mlb, points, c);
             return D3D_OK;
@@ -4473,10 +4487,10 @@ static int binned_index(const Key &kf, const float *points, int64_t n, int c, co
     }
     const unsigned nbF = (unsigned)(w.npad / kFlagTile);            // <= 1024 (n <= 16 M)
     if (do_index) D3D_LAUNCH("k_first_count", k_first_count, dim3(nbF + zf_count.nblk), dim3(1024), 0, st, firstmap, w.fwpre, w.bsumF, w.big_count, zf_count);
-    if (o.stage == 1) return D3D_OK;
+    if (out == Emit::none) return D3D_OK;
     const dim3 grid((unsigned)(w.npad / 256));
     if constexpr (!ROWS && std::is_same<Key, DenseKey>::value) {
-        if (o.emit_generic) {
+        if (out == Emit::emit_c) {
             const int pshift = (o.P & (o.P - 1)) == 0 ? __builtin_ctz(o.P) : -1;
 #define D3D_EMIT_C(CC)                                                                                                          \
     D3D_LAUNCH("k_emit_c", (k_emit_c<Key, CC>), grid, dim3(256), 0, st, kf, w.npad, firstmap, w.fwpre, w.bsumF, vrec, o.max_voxels,  \
@@ -4493,69 +4507,36 @@ static int binned_index(const Key &kf, const float *points, int64_t n, int c, co
             return D3D_OK;
         }
     }
-    if constexpr (ROWS) {
-        if (o.emit_voxels || o.emit_reduce) {
-            const int pshift = (o.P & (o.P - 1)) == 0 ? __builtin_ctz(o.P) : -1;
-            // both roles in ONE workgroup of 512 lanes from 3 M points on (less LDS per wavefront, 32 instead of 28 per CU): 4 M
-            // points 384 -> 358 us, 8 M 704 -> 664, a uniform cloud of 1 M 99 -> 93; 2 M and below: the same or worse (config 2
-            // with its fillers 61 -> 65) -- profiles/r06_ab_sizes.txt
-            if (split && D3D_TUNE_VAL(1, n >= (3ll << 20) ? 1 : 0) == 1) {
-                if (o.agg4)
-                    D3D_LAUNCH("k_emit_split", (k_emit_split<Key, true, 512>), dim3(grid.x), dim3(512), 0, st, kf, w.npad, firstmap, w.fwpre,
-                               w.bsumF, vrec, o.max_voxels, p4, w.big_list, w.staged, o.P, pshift, o.reduction, o.coords, o.npoints,
-                               o.fuse_pmask ? o.pmask : nullptr, reinterpret_cast<float4 *>(o.aggregates), o.emit_voxels, counts,
-                               x.host_counts, prefilled, x.aux_value, (uint32_t)D3D_TUNE_VAL(15, 0));
-                else
-                    D3D_LAUNCH("k_emit_split", (k_emit_split<Key, false, 512>), dim3(grid.x), dim3(512), 0, st, kf, w.npad, firstmap, w.fwpre,
-                               w.bsumF, vrec, o.max_voxels, p4, w.big_list, w.staged, o.P, pshift, o.reduction, o.coords, o.npoints,
-                               o.fuse_pmask ? o.pmask : nullptr, (float4 *)nullptr, o.emit_voxels, counts, x.host_counts, prefilled,
-                               x.aux_value, (uint32_t)D3D_TUNE_VAL(15, 0));
-            } else if (split) {
-                if (o.agg4)
-                    D3D_LAUNCH("k_emit_split", (k_emit_split<Key, true>), dim3(2u * grid.x), dim3(256), 0, st, kf, w.npad, firstmap, w.fwpre,
-                               w.bsumF, vrec, o.max_voxels, p4, w.big_list, w.staged, o.P, pshift, o.reduction, o.coords, o.npoints,
-                               o.fuse_pmask ? o.pmask : nullptr, reinterpret_cast<float4 *>(o.aggregates), o.emit_voxels, counts,
-                               x.host_counts, prefilled, x.aux_value, (uint32_t)D3D_TUNE_VAL(15, 0));
-                else
-                    D3D_LAUNCH("k_emit_split", (k_emit_split<Key, false>), dim3(2u * grid.x), dim3(256), 0, st, kf, w.npad, firstmap, w.fwpre,
-                               w.bsumF, vrec, o.max_voxels, p4, w.big_list, w.staged, o.P, pshift, o.reduction, o.coords, o.npoints,
-                               o.fuse_pmask ? o.pmask : nullptr, (float4 *)nullptr, o.emit_voxels, counts, x.host_counts, prefilled,
-                               x.aux_value, (uint32_t)D3D_TUNE_VAL(15, 0));
-            } else
-            if (x.row_state && o.emit_voxels) {
-                if (o.agg4)
-                    D3D_LAUNCH("k_emit_resident", (k_emit<Key, true, true>), grid, dim3(256), 0, st, kf, w.npad, firstmap, w.fwpre, w.bsumF, vrec,
-                               o.max_voxels, p4, w.big_list, w.staged, o.P, pshift, o.reduction, o.coords, o.npoints,
-                               o.fuse_pmask ? o.pmask : nullptr, reinterpret_cast<float4 *>(o.aggregates), o.emit_voxels, counts,
-                               x.host_counts, x);
-                else
-                    D3D_LAUNCH("k_emit_resident", (k_emit<Key, false, true>), grid, dim3(256), 0, st, kf, w.npad, firstmap, w.fwpre, w.bsumF, vrec,
-                               o.max_voxels, p4, w.big_list, w.staged, o.P, pshift, o.reduction, o.coords, o.npoints,
-                               o.fuse_pmask ? o.pmask : nullptr, (float4 *)nullptr, o.emit_voxels, counts, x.host_counts, x);
-            } else if (o.agg4)
-                D3D_LAUNCH("k_emit", (k_emit<Key, true>), grid, dim3(256), 0, st, kf, w.npad, firstmap, w.fwpre, w.bsumF, vrec,
-                           o.max_voxels, p4, w.big_list, w.staged, o.P, pshift, o.reduction, o.coords, o.npoints,
-                           o.fuse_pmask ? o.pmask : nullptr, reinterpret_cast<float4 *>(o.aggregates), o.emit_voxels, counts,
-                           x.host_counts, x);
-            else
-                D3D_LAUNCH("k_emit", (k_emit<Key, false>), grid, dim3(256), 0, st, kf, w.npad, firstmap, w.fwpre, w.bsumF, vrec,
-                           o.max_voxels, p4, w.big_list, w.staged, o.P, pshift, o.reduction, o.coords, o.npoints,
-                           o.fuse_pmask ? o.pmask : nullptr, (float4 *)nullptr, o.emit_voxels, counts, x.host_counts, x);
-            if (want_map && !o.map_later)
-                D3D_LAUNCH("k_map_binned", k_map_binned, dim3(grid_for(n, 256)), dim3(256), 0, st, bucket_base, nbins, precpos,
-                           reinterpret_cast<const uint32_t *>(bent), E::kIdxStride, E::kIdxOff, x.vidof, o.mapping, o.keepid,
-                           (const unsigned char *)o.trimmed, (const uint32_t *)tileinfo, stiles, tshift);
+    float4 *agg = o.agg4 ? reinterpret_cast<float4 *>(o.aggregates) : nullptr;
+    int rc = D3D_OK;
+    if (out == Emit::meta_first)
+        rc = dispatch(o.agg4, [&](auto agg4) {
+            D3D_LAUNCH("k_meta_first", (k_meta_first<Key, agg4>), grid, dim3(256), 0, st, kf, w.npad, firstmap, w.fwpre, w.bsumF, vrec,
+                       o.max_voxels, agg4 || ROWS || o.lists ? w.vinfo : (uint4 *)nullptr, w.staged, o.P, o.reduction, o.coords,
+                       o.npoints, o.fuse_pmask ? o.pmask : nullptr, agg, counts, x, points, c);
             return D3D_OK;
-        }
+        });
+    else if constexpr (ROWS) {
+        const int pshift = (o.P & (o.P - 1)) == 0 ? __builtin_ctz(o.P) : -1;
+        rc = dispatch(o.agg4, [&](auto agg4) {
+            if (out == Emit::split256 || out == Emit::split512)
+                return dispatch(out == Emit::split512, [&](auto wide) {
+                    constexpr int wg = wide ? 512 : 256;             // 256: two workgroups per 256 points, one per role
+                    D3D_LAUNCH("k_emit_split", (k_emit_split<Key, agg4, wg>), dim3(wide ? grid.x : 2u * grid.x), dim3(wg), 0, st, kf,
+                               w.npad, firstmap, w.fwpre, w.bsumF, vrec, o.max_voxels, p4, w.big_list, w.staged, o.P, pshift,
+                               o.reduction, o.coords, o.npoints, o.fuse_pmask ? o.pmask : nullptr, agg, o.emit_voxels, counts,
+                               x.host_counts, prefilled, x.aux_value);
+                    return D3D_OK;
+                });
+            return dispatch(out == Emit::resident, [&](auto resident) {
+                D3D_LAUNCH(resident ? "k_emit_resident" : "k_emit", (k_emit<Key, agg4, resident>), grid, dim3(256), 0, st, kf, w.npad,
+                           firstmap, w.fwpre, w.bsumF, vrec, o.max_voxels, p4, w.big_list, w.staged, o.P, pshift, o.reduction,
+                           o.coords, o.npoints, o.fuse_pmask ? o.pmask : nullptr, agg, o.emit_voxels, counts, x.host_counts, x);
+                return D3D_OK;
+            });
+        });
     }
-    if (o.agg4)
-        D3D_LAUNCH("k_meta_first", (k_meta_first<Key, true>), grid, dim3(256), 0, st, kf, w.npad, firstmap, w.fwpre, w.bsumF, vrec,
-                   o.max_voxels, w.vinfo, w.staged, o.P, o.reduction, o.coords, o.npoints, o.fuse_pmask ? o.pmask : nullptr,
-                   reinterpret_cast<float4 *>(o.aggregates), counts, x, points, c);
-    else
-        D3D_LAUNCH("k_meta_first", (k_meta_first<Key, false>), grid, dim3(256), 0, st, kf, w.npad, firstmap, w.fwpre, w.bsumF, vrec,
-                   o.max_voxels, ROWS || o.lists ? w.vinfo : (uint4 *)nullptr, w.staged, o.P, o.reduction, o.coords, o.npoints,
-                   o.fuse_pmask ? o.pmask : nullptr, (float4 *)nullptr, counts, x, points, c);
+    if (rc) return rc;
     if (want_map && !o.map_later)
         D3D_LAUNCH("k_map_binned", k_map_binned, dim3(grid_for(n, 256)), dim3(256), 0, st, bucket_base, nbins, precpos,
                    reinterpret_cast<const uint32_t *>(bent), E::kIdxStride, E::kIdxOff, x.vidof, o.mapping, o.keepid,
@@ -4577,8 +4558,7 @@ static int sparse_fused_index(const BoundKey &kf, const float *points, int64_t n
     if (n > kFmMaxPoints || nbins > 8192u) return D3D_ERR_UNSUPPORTED;
     const bool vec4 = c == 4 && ((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(out_feats)) & 15) == 0;
     const bool big_tiles = vec4 && n >= kBigTileMinPoints;
-    const int tune_tile = !big_tiles && vec4 ? D3D_TUNE_VAL(2, (w.npad >> 13) <= 160 ? 12 : 0) : 0;
-    const int tshift = big_tiles ? 14 : tune_tile == 12 ? 12 : 13;
+    const int tshift = big_tiles ? 14 : vec4 && (w.npad >> 13) <= 160 ? 12 : 13;    // (binned_index's tile sizes, without fillers)
     const uint32_t stiles = (uint32_t)(w.npad >> tshift);
     if (n > kTileSortMaxPoints || stiles > (uint32_t)kRunCap || ((uint64_t)nbins + 1) * stiles * 4 > w.cap * 8) return D3D_ERR_UNSUPPORTED;
     E::type *bent = reinterpret_cast<E::type *>(w.tabA);
@@ -4595,35 +4575,26 @@ static int sparse_fused_index(const BoundKey &kf, const float *points, int64_t n
     u64 *early_tot = early_pairs ? w.fwords + early_at : nullptr;
     unsigned int *ticket = w.big_count + 40;
     const size_t lds = ((size_t)1 << tshift) * (sizeof(uint32_t) + 2) + (size_t)nbins * 4;
-#define D3D_TILE_SORT_B(V4, IT)                                                                                                  \
-    do {                                                                                                                        \
-        if (lds + 1024 > 65536)                                                                                                 \
-            D3D_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_sort<BoundKey, V4, true, IT>),             \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                           \
-        D3D_LAUNCH("k_tile_sort", (k_tile_sort<BoundKey, V4, true, IT>), dim3(((stiles + 7u) >> 3) << 3), dim3(kSortThreads), lds, st, kf, points, \
-                   n, c, nbins, stiles, bent, table, tileinfo, phandle, firstmap, sparse_counts, (int64_t *)nullptr,           \
-                   (unsigned char *)nullptr, (int32_t *)nullptr, w.fwords, early_at + 16u * early_pairs, ticket, false); \
-    } while (0)
-    if (big_tiles) D3D_TILE_SORT_B(true, 16);
-    else if (tshift == 12) D3D_TILE_SORT_B(true, 4);
-    else if (vec4) D3D_TILE_SORT_B(true, 8);
-    else D3D_TILE_SORT_B(false, 8);
-#undef D3D_TILE_SORT_B
+    if (const int rc = dispatch(vec4, [&](auto v4) {
+            return launch_tile_sort<BoundKey, v4, true>(tshift, lds, dim3(((stiles + 7u) >> 3) << 3), st, kf, points, n, c, nbins, stiles,
+                                                        bent, table, tileinfo, phandle, firstmap, sparse_counts, (int64_t *)nullptr,
+                                                        (unsigned char *)nullptr, (int32_t *)nullptr, w.fwords,
+                                                        early_at + 16u * early_pairs, ticket, false);
+        }))
+        return rc;
     D3D_LAUNCH("k_bucket_index", (k_bucket_index<BoundKey, true, true, false, true>), dim3(nbins), dim3(kBucketThreads), 0, st, kf, pass, bent,
                (const float4 *)nullptr, (const uint32_t *)nullptr, hshift, P, (int)D3D_REDUCE_NONE, (float4 *)nullptr, vrec, firstmap,
                sparse_counts, (uint32_t *)nullptr, w.parr, reinterpret_cast<uint32_t *>(w.vinfo), (unsigned char *)nullptr, w.big_list,
                (uint32_t *)nullptr, table, stiles, tshift, tileinfo, gpos, phandle, early_tot, npoints_clamp,
-               early_pairs ? early_pairs - 1u : 0u, bits_for((u64)(n > 1 ? n - 1 : 1)), (uint32_t)D3D_TUNE_VAL(0, (int)kDenseMin));
+               early_pairs ? early_pairs - 1u : 0u, bits_for((u64)(n > 1 ? n - 1 : 1)));
     SparseFin lb{w.fwords, w.fwords + ftiles, ticket, host, early_tot, early_pairs, {0, 0, 0}};
     if (coord_offset)
         for (int k = 0; k < 3; k++) lb.coord_sub[k] = (long long)coord_offset[k];
-    if (vec4)
-        D3D_LAUNCH("k_sparse_finish", k_sparse_finish<true>, dim3(ftiles), dim3(kFinThreads), 0, st, kf, n, firstmap, phandle, vrec,
+    return dispatch(vec4, [&](auto v4) {
+        D3D_LAUNCH("k_sparse_finish", k_sparse_finish<v4>, dim3(ftiles), dim3(kFinThreads), 0, st, kf, n, firstmap, phandle, vrec,
                    points, c, max_voxels, npoints_clamp, out_coords, out_npoints, out_feats, out_mask, out_mapping, sparse_counts, counts, lb);
-    else
-        D3D_LAUNCH("k_sparse_finish", k_sparse_finish<false>, dim3(ftiles), dim3(kFinThreads), 0, st, kf, n, firstmap, phandle, vrec,
-                   points, c, max_voxels, npoints_clamp, out_coords, out_npoints, out_feats, out_mask, out_mapping, sparse_counts, counts, lb);
-    return D3D_OK;
+        return D3D_OK;
+    });
 }
 
 static int make_dense_key(const int32_t *shape, const float *bound, DenseKey &kf)
@@ -4783,14 +4754,13 @@ static int voxelize_dense_core(const float *points, int64_t n, int32_t c, const 
         if (host_counts) D3D_LAUNCH("k_notify_host", k_notify_host, dim3(1), dim3(64), 0, st, counts, host_counts);
         if (n == 0 || max_voxels == 0) return D3D_OK;
         const dim3 mgrid(grid_for(cap, 256));
-        if (agg4)
-            D3D_LAUNCH("k_meta", (k_meta<DenseKey, true>), mgrid, dim3(256), 0, st, kf, p4, counts, w.vinfo, w.staged, w.unsorted,
+        rc = dispatch(agg4, [&](auto a) {
+            D3D_LAUNCH("k_meta", (k_meta<DenseKey, a>), mgrid, dim3(256), 0, st, kf, p4, counts, w.vinfo, w.staged, w.unsorted,
                        P, reduction, coords, npoints, w.voff, fuse_pmask ? pmask : nullptr,
-                       reinterpret_cast<float4 *>(aggregates), w.big_list, w.big_count);
-        else
-            D3D_LAUNCH("k_meta", (k_meta<DenseKey, false>), mgrid, dim3(256), 0, st, kf, p4, counts, w.vinfo, w.staged, w.unsorted,
-                       P, reduction, coords, npoints, w.voff, fuse_pmask ? pmask : nullptr, (float4 *)nullptr, w.big_list,
-                       w.big_count);
+                       a ? reinterpret_cast<float4 *>(aggregates) : nullptr, w.big_list, w.big_count);
+            return D3D_OK;
+        });
+        if (rc) return rc;
         if (agg4)
             D3D_LAUNCH("k_overflow_reduce", k_overflow_reduce, dim3(512), dim3(256), 0, st, p4, w.vinfo, w.unsorted, w.big_list,
                        w.big_count, reduction, reinterpret_cast<float4 *>(aggregates));
@@ -4957,19 +4927,19 @@ extern "C" int d3d_voxelize_3d_reduce(const float *points, int64_t n, int32_t c,
     rc = dense_index(kf, points, n, c, w, counts, o, flags, st);
     if (rc) return rc;
     if (n == 0) return D3D_OK;
-    if (agg4) {
-        D3D_LAUNCH("k_meta", (k_meta<DenseKey, true>), dim3(grid_for(n, 256)), dim3(256), 0, st, kf, p4, counts, w.vinfo,
-                   w.staged, w.unsorted, P, reduction, coords, npoints, seg_base ? seg_base : w.voff, (unsigned char *)nullptr,
-                   reinterpret_cast<float4 *>(aggregates), w.big_list, w.big_count, keys, n);
+    rc = dispatch(agg4, [&](auto a) {
+        D3D_LAUNCH("k_meta", (k_meta<DenseKey, a>), dim3(grid_for(n, 256)), dim3(256), 0, st, kf, p4, counts, w.vinfo,
+                   w.staged, w.unsorted, P, reduction, coords, npoints, a && seg_base ? seg_base : w.voff, (unsigned char *)nullptr,
+                   a ? reinterpret_cast<float4 *>(aggregates) : nullptr, w.big_list, w.big_count, keys, n);
+        return D3D_OK;
+    });
+    if (rc) return rc;
+    if (agg4)
         D3D_LAUNCH("k_overflow_reduce", k_overflow_reduce, dim3(512), dim3(256), 0, st, p4, w.vinfo, w.unsorted, w.big_list,
                    w.big_count, reduction, reinterpret_cast<float4 *>(aggregates));
-    } else {
-        D3D_LAUNCH("k_meta", (k_meta<DenseKey, false>), dim3(grid_for(n, 256)), dim3(256), 0, st, kf, p4, counts, w.vinfo,
-                   w.staged, w.unsorted, P, reduction, coords, npoints, w.voff, (unsigned char *)nullptr, (float4 *)nullptr,
-                   w.big_list, w.big_count, keys, n);
+    else
         D3D_LAUNCH("k_aggregate", k_aggregate, dim3(grid_for(n * c, 256)), dim3(256), 0, st, points, c, counts, npoints,
                    w.voff, w.list, w.unsorted, P, reduction, aggregates);
-    }
     // (rows were STAGED on this path: counts[D3D_COUNT_AUX] -- the hash path's list-cell count until here -- must not read 1)
     if (rows) D3D_HIP_CHECK(hipMemsetAsync(counts + D3D_COUNT_AUX, 0, sizeof(int64_t), st));
     return D3D_OK;
@@ -5337,9 +5307,6 @@ extern "C" int d3d_voxelize_3d_sparse_filter_call(const D3DSparseFilterCall *a)
                                          a->has_coord_offset ? a->coord_offset : nullptr);
 }
 
-#ifdef D3D_TUNE
-extern "C" void d3d_debug_set_tune(int k, int v) { if (k >= 0 && k < 16) g_d3d_tune[k] = v; }
-#endif
 #ifdef D3D_PHASE_CLOCKS
 // diagnostic build: read (and clear) the phase clocks -- out[4][16] u64 host array
 extern "C" int d3d_debug_phase_clocks(unsigned long long *out)

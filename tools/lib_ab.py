@@ -1,5 +1,5 @@
 """one build of the library against another on ONE box: each (library, frame size) in a process of its own, alternating.
-usage (GPU box): python tools/lib_ab.py libd3d_hip.so libd3d_hip_tune.so [n ...]   (files in d3d_amd/)"""
+usage (GPU box): python tools/lib_ab.py libd3d_hip_base.so libd3d_hip.so [n ...]   (files in d3d_amd/)"""
 import os
 import subprocess
 import sys
@@ -28,4 +28,4 @@ sizes = [int(x) for x in sys.argv[3:]] or [1000000]
 for n in sizes:
     for rep in range(3):
         for lib in libs:
-            subprocess.run([sys.executable, "-c", CHILD, lib, str(n)], env=dict(os.environ), check=False)
+            subprocess.run([sys.executable, "-c", CHILD, lib, str(n)], env=dict(os.environ), check=True)   # (a failed child ends the run)
