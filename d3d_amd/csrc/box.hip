@@ -816,11 +816,6 @@ __global__ __launch_bounds__(256) void k_geom3d2(const float *__restrict__ b1, i
 //   dense    only if a list overflowed or a dependency chain is very long: all-pairs bit matrix (the reference's
 //            nms_cuda.cu layout) + one workgroup sweeping it (diagonal block resolved by a wavefront with lane
 //            broadcasts, rows OR-ed into LDS)
-extern "C" int d3d_internal_argsort_desc_i32(const int32_t *keys, int64_t n, int32_t *order, void *ws, size_t ws_bytes,
-                                             hipStream_t st);      // sort.hip
-extern "C" size_t d3d_internal_argsort_i32_bytes(int64_t n);
-extern "C" int d3d_internal_crop2dr_grid_f32(const float *points, int64_t n, const float *boxes, int64_t m, uint8_t *out,
-                                             hipStream_t st);      // crop.hip
 
 enum { kUndecided = 0, kKept = 1, kSuppressed = 2 };
 constexpr int kIncTile = 1024;      // boxes per workgroup of k_nms_incscan
@@ -2240,6 +2235,22 @@ int nms_typed(const B *boxes, const B *scores, const int64_t *order, int64_t n, 
     uint8_t *regopen = w.take<uint8_t>((size_t)cap_e);
     if (!ws || !w.ok()) return D3D_ERR_WORKSPACE;
     const bool rot = iou_type == D3D_IOU_RBOX;
+    // the narrow phase and the dense fallback's pair matrix, on both paths
+    const unsigned hits_blocks = (unsigned)std::min<unsigned long long>(d3d_divup((int64_t)cap, 256), 4096);
+    const auto hits = [&](const uint32_t *rank) {
+        return dispatch(rot, [&](auto r) {
+            D3D_LAUNCH("k_nms_hits", (k_nms_hits<T, r>), dim3(hits_blocks), dim3(256), 0, st, geom, rank, cand, cap, cand_hdr, (T)iou_thr,
+                       inc_cnt, arrival);
+            return D3D_OK;
+        });
+    };
+    const auto pairs = [&]() {
+        const unsigned pair_blocks = (unsigned)std::min<int64_t>(d3d_divup(nb, kColsPerBlock) * d3d_divup(nb, 4), 8192);
+        return dispatch(rot, [&](auto r) {
+            D3D_LAUNCH("k_nms_pairs", (k_nms_pairs<T, r>), dim3(pair_blocks), dim3(256), 0, st, geom, fbox, n, nb, (T)iou_thr, mask, flags);
+            return D3D_OK;
+        });
+    };
     if (nms_small_eligible(n, opts)) {
         typedef typename KeyBits<T>::U U;
         uint32_t npad = kWave;
@@ -2253,13 +2264,7 @@ int nms_typed(const B *boxes, const B *scores, const int64_t *order, int64_t n, 
                    order_ws, geom, fbox, farea, state, inc_cnt, flags, cand_hdr, remv);
         D3D_LAUNCH("k_nms_cand_all", k_nms_cand_all, dim3((unsigned)d3d_divup(n, 256), (unsigned)nb), dim3(256), 0, st,
                    (const float4 *)fbox, (const float *)farea, (uint32_t)n, rot ? iou_thr : -1.f, cand, cap, cand_hdr, flags);
-        const unsigned hb = (unsigned)std::min<unsigned long long>(d3d_divup((int64_t)cap, 256), 4096);
-        if (rot)
-            D3D_LAUNCH("k_nms_hits", (k_nms_hits<T, true>), dim3(hb), dim3(256), 0, st, geom, (const uint32_t *)nullptr, cand, cap, cand_hdr,
-                       (T)iou_thr, inc_cnt, arrival);
-        else
-            D3D_LAUNCH("k_nms_hits", (k_nms_hits<T, false>), dim3(hb), dim3(256), 0, st, geom, (const uint32_t *)nullptr, cand, cap, cand_hdr,
-                       (T)iou_thr, inc_cnt, arrival);
+        if (const int rc = hits(nullptr)) return rc;
         D3D_LAUNCH("k_nms_fill_small", k_nms_fill_small, dim3(64), dim3(1024), 0, st, (const unsigned long long *)cand, cap,
                    (const NmsCand *)cand_hdr, (const uint32_t *)inc_cnt, (uint32_t)n, inc_off, (const uint32_t *)arrival, inc);
         if (n <= kNmsSmallResolveMax) {
@@ -2270,11 +2275,7 @@ int nms_typed(const B *boxes, const B *scores, const int64_t *order, int64_t n, 
         // 1 k - 4 k boxes: the general fixed point (+ its dense fallback for dependency chains beyond the poll limit)
         D3D_LAUNCH("k_nms_resolve", k_nms_resolve, dim3((unsigned)d3d_divup(n, 256)), dim3(256), 0, st, n, state,
                    (const uint32_t *)inc_cnt, (const uint32_t *)inc_off, inc, flags, ord, suppressed, inv);
-        const unsigned pb = (unsigned)std::min<int64_t>(d3d_divup(nb, kColsPerBlock) * d3d_divup(nb, 4), 8192);
-        if (rot)
-            D3D_LAUNCH("k_nms_pairs", (k_nms_pairs<T, true>), dim3(pb), dim3(256), 0, st, geom, fbox, n, nb, (T)iou_thr, mask, flags);
-        else
-            D3D_LAUNCH("k_nms_pairs", (k_nms_pairs<T, false>), dim3(pb), dim3(256), 0, st, geom, fbox, n, nb, (T)iou_thr, mask, flags);
+        if (const int rc = pairs()) return rc;
         D3D_LAUNCH("k_nms_sweep", k_nms_sweep, dim3(1), dim3(kSweepThreads), (size_t)nb * 8, st, mask, n, nb, remv, ord, state, flags,
                    suppressed, inv);
         return D3D_OK;
@@ -2321,12 +2322,13 @@ int nms_typed(const B *boxes, const B *scores, const int64_t *order, int64_t n, 
                        (const uint32_t *)cellstart, (const NmsGrid *)grid, cand_hdr, (const float *)carea, bthr,
                        (const uint32_t *)cellbox, (const uint8_t *)blocked, (const uint8_t *)state, level, cand, cap, flags);
             const unsigned kb = (unsigned)std::min<int64_t>(d3d_divup(n, 256) * 2, 4096);
-            if (rot)
-                D3D_LAUNCH("k_nms_level_kill", (k_nms_level_kill<T, true>), dim3(kb), dim3(256), 0, st, (const BoxCore<T> *)geom,
-                           (const unsigned long long *)cand, cap, (const NmsGrid *)grid, (const NmsCand *)cand_hdr, level, (T)iou_thr, state);
-            else
-                D3D_LAUNCH("k_nms_level_kill", (k_nms_level_kill<T, false>), dim3(kb), dim3(256), 0, st, (const BoxCore<T> *)geom,
-                           (const unsigned long long *)cand, cap, (const NmsGrid *)grid, (const NmsCand *)cand_hdr, level, (T)iou_thr, state);
+            if (const int rc = dispatch(rot, [&](auto r) {
+                    D3D_LAUNCH("k_nms_level_kill", (k_nms_level_kill<T, r>), dim3(kb), dim3(256), 0, st, (const BoxCore<T> *)geom,
+                               (const unsigned long long *)cand, cap, (const NmsGrid *)grid, (const NmsCand *)cand_hdr, level, (T)iou_thr,
+                               state);
+                    return D3D_OK;
+                }))
+                return rc;
         }
         if (levels > 0) {
             // the boxes the levels left open are registered again, alone: the candidate walk is quadratic in the list lengths
@@ -2357,13 +2359,7 @@ int nms_typed(const B *boxes, const B *scores, const int64_t *order, int64_t n, 
         D3D_LAUNCH("k_nms_cand", k_nms_cand, dim3((unsigned)d3d_divup(nb * nsplit, 4)), dim3(256), 0, st, (const float4 *)fbx,
                    (uint32_t)nb, nsplit, cand, cap, cand_hdr, flags);
     }
-    const unsigned hits_blocks = (unsigned)std::min<unsigned long long>(d3d_divup((int64_t)cap, 256), 4096);
-    if (rot)
-        D3D_LAUNCH("k_nms_hits", (k_nms_hits<T, true>), dim3(hits_blocks), dim3(256), 0, st, geom, rankx, cand, cap, cand_hdr,
-                   (T)iou_thr, inc_cnt, arrival);
-    else
-        D3D_LAUNCH("k_nms_hits", (k_nms_hits<T, false>), dim3(hits_blocks), dim3(256), 0, st, geom, rankx, cand, cap, cand_hdr,
-                   (T)iou_thr, inc_cnt, arrival);
+    if (const int rc = hits(rankx)) return rc;
     D3D_LAUNCH("k_nms_incscan", k_nms_incscan, dim3((unsigned)d3d_divup(n, kIncTile)), dim3(256), 0, st, (const uint32_t *)inc_cnt, n,
                inc_off, tile_tot, tickets, flags, (opts & D3D_NMS_TEST_WITHHOLD) != 0 && (opts & D3D_NMS_BROAD_SWEEP) != 0);
     D3D_LAUNCH("k_nms_fill", k_nms_fill, dim3(hits_blocks), dim3(256), 0, st, (const unsigned long long *)cand, cap,
@@ -2371,13 +2367,7 @@ int nms_typed(const B *boxes, const B *scores, const int64_t *order, int64_t n, 
     D3D_LAUNCH("k_nms_resolve", k_nms_resolve, dim3((unsigned)d3d_divup(n, 256)), dim3(256), 0, st, n, state,
                (const uint32_t *)inc_cnt, (const uint32_t *)inc_off, inc, flags, order, suppressed, inv);
     // dense path, gated on need_sweep inside the kernels
-    const unsigned pair_blocks = (unsigned)std::min<int64_t>(d3d_divup(nb, kColsPerBlock) * d3d_divup(nb, 4), 8192);
-    if (rot)
-        D3D_LAUNCH("k_nms_pairs", (k_nms_pairs<T, true>), dim3(pair_blocks), dim3(256), 0, st, geom, fbox, n, nb, (T)iou_thr,
-                   mask, flags);
-    else
-        D3D_LAUNCH("k_nms_pairs", (k_nms_pairs<T, false>), dim3(pair_blocks), dim3(256), 0, st, geom, fbox, n, nb, (T)iou_thr,
-                   mask, flags);
+    if (const int rc = pairs()) return rc;
     size_t lds = nb <= kSweepLdsWords ? (size_t)nb * 8 : 0;
     D3D_LAUNCH("k_nms_sweep", k_nms_sweep, dim3(1), dim3(kSweepThreads), lds, st, mask, n, nb, remv, order, state, flags,
                suppressed, inv);
@@ -2573,12 +2563,6 @@ static unsigned long long iou_list_capacity(int64_t n, int64_t m)
     return pairs < (1ull << 27) ? pairs : (1ull << 27);
 }
 
-// boxloss.hip
-int d3d_internal_loss_iou_forward(const void *b1, int64_t n, const void *b2, int64_t m, int kind, int dtype, void *out, void *ws,
-                                  size_t ws_bytes, unsigned long long list_cap, hipStream_t st);
-int d3d_internal_loss_iou_backward(const void *b1, int64_t n, const void *b2, int64_t m, const void *grad, int kind, int dtype,
-                                   void *g1, void *g2, void *ws, size_t ws_bytes, hipStream_t st);
-
 extern "C" size_t d3d_iou2d_workspace_bytes(int64_t n, int64_t m, int32_t dtype)
 {
     if (n < 1) n = 1;
@@ -2617,18 +2601,25 @@ static int iou2d_two_phase(const B *b1, int64_t n, const B *b2, int64_t m, S *io
     return D3D_OK;
 }
 
+// the checks d3d_iou2d_forward and d3d_iou2d_backward share, in their order
+static int iou2d_check(int32_t iou_type, int32_t dtype)
+{
+    if (dtype != D3D_F32 && dtype != D3D_F64 && dtype != D3D_F64_M32 && dtype != D3D_F32_WIDE) return D3D_ERR_BAD_ARG;
+    const bool loss_kind = iou_type == D3D_IOU_GRBOX || iou_type == D3D_IOU_DRBOX;
+    if (iou_type != D3D_IOU_BOX && iou_type != D3D_IOU_RBOX && !loss_kind) return D3D_ERR_UNSUPPORTED;
+    if (loss_kind && (dtype == D3D_F64_M32 || dtype == D3D_F32_WIDE)) return D3D_ERR_UNSUPPORTED;
+    return D3D_OK;
+}
+
 extern "C" int d3d_iou2d_forward(const void *boxes1, int64_t n, const void *boxes2, int64_t m, int32_t iou_type,
                                  int32_t dtype, void *ious, void *workspace, size_t workspace_bytes, void *stream, uint32_t flags)
 {
     hipStream_t st = (hipStream_t)stream;
     if (n < 0 || m < 0 || (flags & 0xffu)) return D3D_ERR_BAD_ARG;
-    if (dtype != D3D_F32 && dtype != D3D_F64 && dtype != D3D_F64_M32 && dtype != D3D_F32_WIDE) return D3D_ERR_BAD_ARG;
-    const bool loss_kind = iou_type == D3D_IOU_GRBOX || iou_type == D3D_IOU_DRBOX;
-    if (iou_type != D3D_IOU_BOX && iou_type != D3D_IOU_RBOX && !loss_kind) return D3D_ERR_UNSUPPORTED;
-    if (loss_kind && (dtype == D3D_F64_M32 || dtype == D3D_F32_WIDE)) return D3D_ERR_UNSUPPORTED;
+    if (const int rc = iou2d_check(iou_type, dtype)) return rc;
     if (n == 0 || m == 0) return D3D_OK;
     if (!boxes1 || !boxes2 || !ious) return D3D_ERR_BAD_ARG;
-    if (loss_kind) {        // GIoU / DIoU: every pair has a value (boxloss.hip); GIoU lists the pairs that need the clip
+    if (iou_type == D3D_IOU_GRBOX || iou_type == D3D_IOU_DRBOX) {        // GIoU / DIoU: every pair has a value (boxloss.hip); GIoU lists the pairs that need the clip
         const bool use_ws = workspace && workspace_bytes >= d3d_iou2d_workspace_bytes(n, m, dtype) && n < (1ll << 32) && m < (1ll << 32);
         unsigned long long cap = iou_list_capacity(n, m);
         if ((flags >> 8) != 0 && (unsigned long long)(flags >> 8) < cap) cap = flags >> 8;        // D3D_IOU_LIST_CAP
@@ -2637,56 +2628,34 @@ extern "C" int d3d_iou2d_forward(const void *boxes1, int64_t n, const void *boxe
     }
     const int64_t gy = d3d_divup(n, kTileRows);
     if (gy > 65535 || n >= (1ll << 32) || m >= (1ll << 32)) return D3D_ERR_BAD_ARG;   // callers tile above that
-    const bool rot = iou_type == D3D_IOU_RBOX;
-    if ((unsigned long long)n * (unsigned long long)m <= kIouSmallPairs && (flags >> 8) == 0) {      // (a list-cap flag asks for the list path)
-        const dim3 sgrid((unsigned)d3d_divup(n * m, 256));
-        if (dtype == D3D_F32_WIDE) {
-            if (rot) D3D_LAUNCH("k_iou_small", (k_iou_small<double, true, float, float>), sgrid, dim3(256), 0, st, (const float *)boxes1, n, (const float *)boxes2, m, (float *)ious);
-            else D3D_LAUNCH("k_iou_small", (k_iou_small<double, false, float, float>), sgrid, dim3(256), 0, st, (const float *)boxes1, n, (const float *)boxes2, m, (float *)ious);
-        } else if (dtype == D3D_F64_M32) {
-            if (rot) D3D_LAUNCH("k_iou_small", (k_iou_small<double, true, float>), sgrid, dim3(256), 0, st, (const double *)boxes1, n, (const double *)boxes2, m, (float *)ious);
-            else D3D_LAUNCH("k_iou_small", (k_iou_small<double, false, float>), sgrid, dim3(256), 0, st, (const double *)boxes1, n, (const double *)boxes2, m, (float *)ious);
-        } else if (dtype == D3D_F64) {
-            if (rot) D3D_LAUNCH("k_iou_small", (k_iou_small<double, true>), sgrid, dim3(256), 0, st, (const double *)boxes1, n, (const double *)boxes2, m, (double *)ious);
-            else D3D_LAUNCH("k_iou_small", (k_iou_small<double, false>), sgrid, dim3(256), 0, st, (const double *)boxes1, n, (const double *)boxes2, m, (double *)ious);
-        } else {
-            if (rot) D3D_LAUNCH("k_iou_small", (k_iou_small<float, true>), sgrid, dim3(256), 0, st, (const float *)boxes1, n, (const float *)boxes2, m, (float *)ious);
-            else D3D_LAUNCH("k_iou_small", (k_iou_small<float, false>), sgrid, dim3(256), 0, st, (const float *)boxes1, n, (const float *)boxes2, m, (float *)ious);
-        }
-        return D3D_OK;
-    }
-    if (workspace && workspace_bytes >= d3d_iou2d_workspace_bytes(n, m, dtype)) {
-        // zero fill + candidate list + one candidate per lane (BOX too: its IoU is non-zero only where the AABBs overlap)
-#define D3D_TWO_PHASE(T, R) iou2d_two_phase<T, R>((const T *)boxes1, n, (const T *)boxes2, m, (T *)ious, workspace, workspace_bytes, st, flags)
-        if (dtype == D3D_F32_WIDE) {
-            if (rot) return iou2d_two_phase<double, true, float, float>((const float *)boxes1, n, (const float *)boxes2, m, (float *)ious, workspace, workspace_bytes, st, flags);
-            return iou2d_two_phase<double, false, float, float>((const float *)boxes1, n, (const float *)boxes2, m, (float *)ious, workspace, workspace_bytes, st, flags);
-        }
-        if (dtype == D3D_F64_M32) {
-            if (rot) return iou2d_two_phase<double, true, float>((const double *)boxes1, n, (const double *)boxes2, m, (float *)ious, workspace, workspace_bytes, st, flags);
-            return iou2d_two_phase<double, false, float>((const double *)boxes1, n, (const double *)boxes2, m, (float *)ious, workspace, workspace_bytes, st, flags);
-        }
-        if (dtype == D3D_F64) return rot ? D3D_TWO_PHASE(double, true) : D3D_TWO_PHASE(double, false);
-        return rot ? D3D_TWO_PHASE(float, true) : D3D_TWO_PHASE(float, false);
-#undef D3D_TWO_PHASE
-    }
-    if (dtype == D3D_F64_M32 || dtype == D3D_F32_WIDE) return D3D_ERR_WORKSPACE;       // (the mixed forms have no workspace-free kernel)
-    // single-kernel path: no workspace
+    const bool small = (unsigned long long)n * (unsigned long long)m <= kIouSmallPairs && (flags >> 8) == 0;   // (a list-cap flag asks for the list path)
+    const bool use_ws = workspace && workspace_bytes >= d3d_iou2d_workspace_bytes(n, m, dtype);
     const bool al16 = (reinterpret_cast<uintptr_t>(ious) & 15) == 0;
-#define D3D_IOU2D(T, R, K)                                                                                          \
-    D3D_LAUNCH("k_iou2d", (k_iou2d<T, R, K>), dim3((unsigned)d3d_divup(m, (int64_t)kTileCols * K), (unsigned)gy),   \
-               dim3(kTileCols), 0, st, (const T *)boxes1, n, (const T *)boxes2, m, (T *)ious, (const unsigned int *)nullptr)
-    if (dtype == D3D_F64) {
-        const bool vec = al16 && (m % 2 == 0);
-        if (rot) { if (vec) D3D_IOU2D(double, true, 2); else D3D_IOU2D(double, true, 1); }
-        else     { if (vec) D3D_IOU2D(double, false, 2); else D3D_IOU2D(double, false, 1); }
-    } else {
-        const bool vec = al16 && (m % 4 == 0);
-        if (rot) { if (vec) D3D_IOU2D(float, true, 4); else D3D_IOU2D(float, true, 1); }
-        else     { if (vec) D3D_IOU2D(float, false, 4); else D3D_IOU2D(float, false, 1); }
-    }
-#undef D3D_IOU2D
-    return D3D_OK;
+    return dispatch_dtype<D3D_F32, D3D_F64, D3D_F64_M32, D3D_F32_WIDE>(dtype, [&](auto p) {
+        typedef typename decltype(p)::T T;
+        typedef typename decltype(p)::B B;
+        typedef typename decltype(p)::S S;
+        return dispatch(iou_type == D3D_IOU_RBOX, [&](auto r) -> int {
+            if (small) {
+                D3D_LAUNCH("k_iou_small", (k_iou_small<T, r, S, B>), dim3((unsigned)d3d_divup(n * m, 256)), dim3(256), 0, st,
+                           (const B *)boxes1, n, (const B *)boxes2, m, (S *)ious);
+                return D3D_OK;
+            }
+            // zero fill + candidate list + one candidate per lane (BOX too: its IoU is non-zero only where the AABBs overlap)
+            if (use_ws) return iou2d_two_phase<T, r, S>((const B *)boxes1, n, (const B *)boxes2, m, (S *)ious, workspace, workspace_bytes, st, flags);
+            if constexpr (!std::is_same<T, B>::value || !std::is_same<T, S>::value) {
+                return D3D_ERR_WORKSPACE;         // (the mixed forms have no workspace-free kernel)
+            } else {                              // one kernel: K boxes of a row per lane where the output allows 16-byte stores
+                constexpr int kVec = 16 / sizeof(T);
+                return dispatch(al16 && m % kVec == 0, [&](auto vec) {
+                    constexpr int K = vec ? kVec : 1;
+                    D3D_LAUNCH("k_iou2d", (k_iou2d<T, r, K>), dim3((unsigned)d3d_divup(m, (int64_t)kTileCols * K), (unsigned)gy),
+                               dim3(kTileCols), 0, st, (const T *)boxes1, n, (const T *)boxes2, m, (T *)ious, (const unsigned int *)nullptr);
+                    return D3D_OK;
+                });
+            }
+        });
+    });
 }
 
 extern "C" size_t d3d_iou3d_workspace_bytes(int64_t n, int64_t m)
@@ -2704,52 +2673,49 @@ static int iou3d_impl(const float *boxes1, int64_t n, const float *boxes2, int64
     if (n == 0 || m == 0) return D3D_OK;
     if (!boxes1 || !boxes2 || !out) return D3D_ERR_BAD_ARG;
     if (d3d_divup(n, kTileRows) > 65535 || n >= (1ll << 32) || m >= (1ll << 32)) return D3D_ERR_BAD_ARG;
-    if ((unsigned long long)n * (unsigned long long)m <= kIouSmallPairs) {
-        const dim3 sgrid((unsigned)d3d_divup(n * m, 256));
-        if (rotated) D3D_LAUNCH("k_iou3d_small", k_iou3d_small<true>, sgrid, dim3(256), 0, st, boxes1, n, boxes2, m, out, stride, complement);
-        else D3D_LAUNCH("k_iou3d_small", k_iou3d_small<false>, sgrid, dim3(256), 0, st, boxes1, n, boxes2, m, out, stride, complement);
-        return D3D_OK;
-    }
     const unsigned gy = (unsigned)d3d_divup(n, kTileRows);
     const bool al16 = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-    const bool vec = al16 && (m % 4 == 0);
-#define D3D_IOU3D(R, K, FLAG)                                                                                      \
-    D3D_LAUNCH("k_iou3d", (k_iou3d<R, K>), dim3((unsigned)d3d_divup(m, (int64_t)kTileCols * K), gy), dim3(kTileCols), \
-               0, st, boxes1, n, boxes2, m, out, FLAG, stride, complement)
-    if (workspace && workspace_bytes >= d3d_iou3d_workspace_bytes(n, m) && (al16 || !complement)) {
-        // background fill + candidate list + dense clipping (see "rotated IoU, two-phase")
-        WsCarver w(workspace, workspace_bytes);
-        BoxGeom<float> *ga = w.take<BoxGeom<float>>(n);
-        BoxGeom<float> *gb = w.take<BoxGeom<float>>(m);
-        float2 *za = w.take<float2>(n);
-        float2 *zb = w.take<float2>(m);
-        float4 *ra = w.take<float4>(n);
-        float4 *cb = w.take<float4>(m);
-        IouList *hdr = w.take<IouList>(1);
-        const unsigned long long cap = iou_list_capacity(n, m);
-        unsigned long long *list = w.take<unsigned long long>(cap);
-        if (!w.ok()) return D3D_ERR_WORKSPACE;
-        D3D_LAUNCH("k_geom3d2", k_geom3d2, dim3((unsigned)d3d_divup(n + m, 256)), dim3(256), 0, st, boxes1, n, ga, ra, za, boxes2, m,
-                   gb, cb, zb, hdr, list_segments(cap), rotated != 0, stride, complement);
-        float *fill = out;
-        if (!al16) {
-            D3D_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)n * (size_t)m * sizeof(float), st));
-            fill = nullptr;
+    return dispatch(rotated != 0, [&](auto r) -> int {
+        if ((unsigned long long)n * (unsigned long long)m <= kIouSmallPairs) {
+            D3D_LAUNCH("k_iou3d_small", k_iou3d_small<r>, dim3((unsigned)d3d_divup(n * m, 256)), dim3(256), 0, st, boxes1, n, boxes2, m,
+                       out, stride, complement);
+            return D3D_OK;
         }
-        const int prows = pre_tile_rows(n, m);
-        D3D_LAUNCH("k_iou_pre", k_iou_pre<float>, dim3((unsigned)d3d_divup(m, (int64_t)kPreCols), (unsigned)d3d_divup(n, (int64_t)prows)),
-                   dim3(kTileCols), 0, st, (const float4 *)ra, n, (const float4 *)cb, m, fill, hdr, list, cap, complement ? 1.f : 0.f,
-                   prows);
-        if (rotated)
-            D3D_LAUNCH("k_iou3d_clip", k_iou3d_clip<true>, dim3(256 * 16), dim3(256), 0, st, ga, za, gb, zb, n, m, out, hdr, list, cap, complement);
-        else
-            D3D_LAUNCH("k_iou3d_clip", k_iou3d_clip<false>, dim3(256 * 16), dim3(256), 0, st, ga, za, gb, zb, n, m, out, hdr, list, cap, complement);
-        return D3D_OK;
-    }
-    if (rotated) D3D_IOU3D(true, 1, (const unsigned int *)nullptr);
-    else { if (vec) D3D_IOU3D(false, 4, (const unsigned int *)nullptr); else D3D_IOU3D(false, 1, (const unsigned int *)nullptr); }
-#undef D3D_IOU3D
-    return D3D_OK;
+        if (workspace && workspace_bytes >= d3d_iou3d_workspace_bytes(n, m) && (al16 || !complement)) {
+            // background fill + candidate list + dense clipping (see "rotated IoU, two-phase")
+            WsCarver w(workspace, workspace_bytes);
+            BoxGeom<float> *ga = w.take<BoxGeom<float>>(n);
+            BoxGeom<float> *gb = w.take<BoxGeom<float>>(m);
+            float2 *za = w.take<float2>(n);
+            float2 *zb = w.take<float2>(m);
+            float4 *ra = w.take<float4>(n);
+            float4 *cb = w.take<float4>(m);
+            IouList *hdr = w.take<IouList>(1);
+            const unsigned long long cap = iou_list_capacity(n, m);
+            unsigned long long *list = w.take<unsigned long long>(cap);
+            if (!w.ok()) return D3D_ERR_WORKSPACE;
+            D3D_LAUNCH("k_geom3d2", k_geom3d2, dim3((unsigned)d3d_divup(n + m, 256)), dim3(256), 0, st, boxes1, n, ga, ra, za, boxes2, m,
+                       gb, cb, zb, hdr, list_segments(cap), (bool)r, stride, complement);
+            float *fill = out;
+            if (!al16) {
+                D3D_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)n * (size_t)m * sizeof(float), st));
+                fill = nullptr;
+            }
+            const int prows = pre_tile_rows(n, m);
+            D3D_LAUNCH("k_iou_pre", k_iou_pre<float>, dim3((unsigned)d3d_divup(m, (int64_t)kPreCols), (unsigned)d3d_divup(n, (int64_t)prows)),
+                       dim3(kTileCols), 0, st, (const float4 *)ra, n, (const float4 *)cb, m, fill, hdr, list, cap, complement ? 1.f : 0.f,
+                       prows);
+            D3D_LAUNCH("k_iou3d_clip", k_iou3d_clip<r>, dim3(256 * 16), dim3(256), 0, st, ga, za, gb, zb, n, m, out, hdr, list, cap, complement);
+            return D3D_OK;
+        }
+        // the rotated kernel is scalar; the axis-aligned one stores 4 boxes of a row per lane where the output allows it
+        return dispatch(al16 && m % 4 == 0, [&](auto vec) {
+            constexpr int K = vec && !r ? 4 : 1;
+            D3D_LAUNCH("k_iou3d", (k_iou3d<r, K>), dim3((unsigned)d3d_divup(m, (int64_t)kTileCols * K), gy), dim3(kTileCols), 0, st, boxes1,
+                       n, boxes2, m, out, (const unsigned int *)nullptr, stride, complement);
+            return D3D_OK;
+        });
+    });
 }
 
 extern "C" int d3d_iou3d_forward(const float *boxes1, int64_t n, const float *boxes2, int64_t m, int32_t rotated,
@@ -2840,43 +2806,23 @@ static int nms2d_impl(const void *boxes, const void *scores, const int64_t *orde
         if (rc) return rc;
         order = order_ws;
     }
-    if (suppression_type != D3D_SUPPRESS_HARD) {
-        // one workgroup, one round per box that is still alive when its turn comes, each round a sweep over the boxes behind
+    const bool hard = suppression_type == D3D_SUPPRESS_HARD;
+    if (hard ? d3d_divup(n, 64) > 65535 : n >= (1ll << 31) - 64) return D3D_ERR_BAD_ARG;
+    return dispatch_dtype<D3D_F32, D3D_F64, D3D_F32_WIDE>(dtype, [&](auto p) {
+        typedef typename decltype(p)::T T;
+        typedef typename decltype(p)::B B;
+        if (hard)
+            return nms_typed<T, B>((const B *)boxes, (const B *)scores, order, n, iou_type, iou_threshold, score_threshold, suppressed,
+                                   workspace, nms_bytes, st, flags, order_ws, host_word);
+        // soft: one workgroup, one round per box that is still alive when its turn comes, each round a sweep over the boxes behind
         // it (16-byte AABB reads; position-indexed state in global scratch above kSoftLds boxes): ~n rounds of ~n / 50 us --
         // 100 k boxes with most of them alive take seconds (the reference's loop, nms.cpp:60-94: n^2 / 2 clips and an
         // insertion pass that is itself quadratic per round).  No size limit of its own (nms.cpp has none)
-        if (n >= (1ll << 31) - 64) return D3D_ERR_BAD_ARG;
-        const bool rot = iou_type == D3D_IOU_RBOX;
-        if (dtype == D3D_F32_WIDE)
-            return rot ? softnms_typed<double, true, float>((const float *)boxes, (const float *)scores, order, n, suppression_type,
-                                                            iou_threshold, score_threshold, suppression_param, suppressed, workspace,
-                                                            workspace_bytes, st, flags)
-                       : softnms_typed<double, false, float>((const float *)boxes, (const float *)scores, order, n, suppression_type,
-                                                             iou_threshold, score_threshold, suppression_param, suppressed, workspace,
-                                                             workspace_bytes, st, flags);
-        if (dtype == D3D_F64)
-            return rot ? softnms_typed<double, true>((const double *)boxes, (const double *)scores, order, n, suppression_type,
-                                                     iou_threshold, score_threshold, suppression_param, suppressed, workspace,
-                                                     workspace_bytes, st, flags)
-                       : softnms_typed<double, false>((const double *)boxes, (const double *)scores, order, n, suppression_type,
-                                                      iou_threshold, score_threshold, suppression_param, suppressed, workspace,
-                                                      workspace_bytes, st, flags);
-        return rot ? softnms_typed<float, true>((const float *)boxes, (const float *)scores, order, n, suppression_type,
-                                                iou_threshold, score_threshold, suppression_param, suppressed, workspace,
-                                                workspace_bytes, st, flags)
-                   : softnms_typed<float, false>((const float *)boxes, (const float *)scores, order, n, suppression_type,
-                                                 iou_threshold, score_threshold, suppression_param, suppressed, workspace,
-                                                 workspace_bytes, st, flags);
-    }
-    if (d3d_divup(n, 64) > 65535) return D3D_ERR_BAD_ARG;
-    if (dtype == D3D_F32_WIDE)
-        return nms_typed<double, float>((const float *)boxes, (const float *)scores, order, n, iou_type, iou_threshold,
-                                        score_threshold, suppressed, workspace, nms_bytes, st, flags, order_ws, host_word);
-    if (dtype == D3D_F64)
-        return nms_typed<double>((const double *)boxes, (const double *)scores, order, n, iou_type, iou_threshold,
-                                 score_threshold, suppressed, workspace, nms_bytes, st, flags, order_ws, host_word);
-    return nms_typed<float>((const float *)boxes, (const float *)scores, order, n, iou_type, iou_threshold,
-                            score_threshold, suppressed, workspace, nms_bytes, st, flags, order_ws, host_word);
+        return dispatch(iou_type == D3D_IOU_RBOX, [&](auto r) {
+            return softnms_typed<T, r, B>((const B *)boxes, (const B *)scores, order, n, suppression_type, iou_threshold, score_threshold,
+                                          suppression_param, suppressed, workspace, workspace_bytes, st, flags);
+        });
+    });
 }
 
 extern "C" int d3d_nms2d(const void *boxes, const void *scores, const int64_t *order, int64_t n, int32_t iou_type,
@@ -2924,17 +2870,17 @@ extern "C" int d3d_crop_2dr(const void *points, int64_t n, const void *boxes, in
         const int rc = d3d_internal_crop2dr_grid_f32((const float *)points, n, (const float *)boxes, m, out, st);
         if (rc != D3D_ERR_UNSUPPORTED) return rc;
     }
-    dim3 grid((unsigned)d3d_divup(n, 256 * 4), (unsigned)d3d_divup(m, kTileRows));
-    if (dtype == D3D_F64)
-        D3D_LAUNCH("k_crop2dr", k_crop2dr<double>, grid, dim3(256), 0, st, (const double *)points, n, (const double *)boxes, m, out);
-    else
-        D3D_LAUNCH("k_crop2dr", k_crop2dr<float>, grid, dim3(256), 0, st, (const float *)points, n, (const float *)boxes, m, out);
-    return D3D_OK;
+    return dispatch_dtype<D3D_F32, D3D_F64>(dtype, [&](auto p) {
+        typedef typename decltype(p)::T T;
+        D3D_LAUNCH("k_crop2dr", k_crop2dr<T>, dim3((unsigned)d3d_divup(n, 256 * 4), (unsigned)d3d_divup(m, kTileRows)), dim3(256), 0, st,
+                   (const T *)points, n, (const T *)boxes, m, out);
+        return D3D_OK;
+    });
 }
 
-template <typename T, typename G = T, typename B = T>
-static int iou2d_backward_typed(const B *b1, int64_t n, const B *b2, int64_t m, const G *grad, bool rot, T *g1, T *g2, void *ws,
-                                size_t ws_bytes, hipStream_t st)
+template <typename T, bool ROTATED, typename G, typename B>
+static int iou2d_backward_typed(const B *b1, int64_t n, const B *b2, int64_t m, const G *grad, T *g1, T *g2, void *ws, size_t ws_bytes,
+                                hipStream_t st)
 {
     WsCarver w(ws, ws_bytes);
     BoxGeom<T> *ga = w.take<BoxGeom<T>>(n);
@@ -2961,12 +2907,12 @@ static int iou2d_backward_typed(const B *b1, int64_t n, const B *b2, int64_t m, 
         D3D_HIP_CHECK(hipMemsetAsync(g2, 0, sizeof(T) * 5 * (size_t)m, st));
     }
     if ((unsigned long long)n * (unsigned long long)m <= kIouSmallPairs) {
-        if (rot) D3D_LAUNCH("k_iou_grad_small", (k_iou_grad_small<T, true, G, B>), dim3((unsigned)d3d_divup(n * m, 256)), dim3(256), 0, st, b1, n, b2, m, grad, g1, g2);
-        else D3D_LAUNCH("k_iou_grad_small", (k_iou_grad_small<T, false, G, B>), dim3((unsigned)d3d_divup(n * m, 256)), dim3(256), 0, st, b1, n, b2, m, grad, g1, g2);
+        D3D_LAUNCH("k_iou_grad_small", (k_iou_grad_small<T, ROTATED, G, B>), dim3((unsigned)d3d_divup(n * m, 256)), dim3(256), 0, st, b1, n, b2, m,
+                   grad, g1, g2);
         return D3D_OK;
     }
     D3D_LAUNCH("k_geom", (k_geom2<T, false, B>), dim3((unsigned)d3d_divup(n + m, 256)), dim3(256), 0, st, b1, n, ga, ra, b2, m, gb, cb,
-               (IouList *)nullptr, 1u, rot);           // (both operands in one launch, as the forward does)
+               (IouList *)nullptr, 1u, ROTATED);       // (both operands in one launch, as the forward does)
     {                                                  // marks, then tiles with LDS accumulators (k_iou_grad_mark, k_iou_grad_tiles)
         int tr = kTileRows;                            // fewer rows per workgroup while the launch is short of 2048 workgroups
         while (tr > 8 && d3d_divup(m, kGradCols) * d3d_divup(n, tr) < 2048) tr >>= 1;
@@ -2976,21 +2922,18 @@ static int iou2d_backward_typed(const B *b1, int64_t n, const B *b2, int64_t m, 
         const int64_t rows_max = (int64_t)65535 * tr < rows_bm ? (int64_t)65535 * tr : rows_bm;
         for (int64_t r0 = 0; r0 < n; r0 += rows_max) {
             const int64_t nr = (n - r0) < rows_max ? (n - r0) : rows_max;
-#define D3D_GRAD_TILES(R)                                                                                                                   \
-    D3D_HIP_CHECK(hipMemsetAsync(nmarks, 0, 8 * kMarkStripes, st));                                                                                         \
-    D3D_LAUNCH("k_iou_grad_mark", (k_iou_grad_mark<T, R, G>), dim3((unsigned)d3d_divup(m, 2 * kGradCols), (unsigned)d3d_divup(nr, tr)),            \
-               dim3(kGradCols), 0, st, (const BoxGeom<T> *)ga + r0, (const float4 *)ra + r0, nr, (const BoxGeom<T> *)gb, (const float4 *)cb, \
-               m, grad + r0 * m, bitmap, wpr, tr, nmarks);                                                                                  \
-    D3D_LAUNCH("k_iou_grad_decide", k_iou_grad_decide, dim3(1), dim3(kMarkStripes), 0, st, nmarks, nr, m);                                    \
-    D3D_LAUNCH("k_iou_grad_tiles", (k_iou_grad_tiles<T, R, G, B>), dim3((unsigned)d3d_divup(m, kGradCols), (unsigned)d3d_divup(nr, tr)),               \
-               dim3(kGradCols), 0, st, (const BoxGeom<T> *)ga + r0, (const float4 *)ra + r0, b1 + r0 * 5, nr, (const BoxGeom<T> *)gb,        \
-               (const float4 *)cb, b2, m, grad + r0 * m, g1 + r0 * 5, g2, tr, (const unsigned long long *)bitmap, wpr,                      \
-               (const unsigned long long *)nmarks);                                                                                         \
-    D3D_LAUNCH("k_iou_grad_sparse", (k_iou_grad_sparse<T, R, G, B>), dim3((unsigned)d3d_divup(nr * wpr, (int64_t)kSparseWords)), dim3(256), 0, st,   \
-               (const BoxGeom<T> *)ga + r0, b1 + r0 * 5, nr, (const BoxGeom<T> *)gb, b2, m, grad + r0 * m, g1 + r0 * 5, g2,                  \
-               (const unsigned long long *)bitmap, wpr, (const unsigned long long *)nmarks)
-            if (rot) { D3D_GRAD_TILES(true); } else { D3D_GRAD_TILES(false); }
-#undef D3D_GRAD_TILES
+            D3D_HIP_CHECK(hipMemsetAsync(nmarks, 0, 8 * kMarkStripes, st));
+            D3D_LAUNCH("k_iou_grad_mark", (k_iou_grad_mark<T, ROTATED, G>), dim3((unsigned)d3d_divup(m, 2 * kGradCols), (unsigned)d3d_divup(nr, tr)),
+                       dim3(kGradCols), 0, st, (const BoxGeom<T> *)ga + r0, (const float4 *)ra + r0, nr, (const BoxGeom<T> *)gb, (const float4 *)cb,
+                       m, grad + r0 * m, bitmap, wpr, tr, nmarks);
+            D3D_LAUNCH("k_iou_grad_decide", k_iou_grad_decide, dim3(1), dim3(kMarkStripes), 0, st, nmarks, nr, m);
+            D3D_LAUNCH("k_iou_grad_tiles", (k_iou_grad_tiles<T, ROTATED, G, B>), dim3((unsigned)d3d_divup(m, kGradCols), (unsigned)d3d_divup(nr, tr)),
+                       dim3(kGradCols), 0, st, (const BoxGeom<T> *)ga + r0, (const float4 *)ra + r0, b1 + r0 * 5, nr, (const BoxGeom<T> *)gb,
+                       (const float4 *)cb, b2, m, grad + r0 * m, g1 + r0 * 5, g2, tr, (const unsigned long long *)bitmap, wpr,
+                       (const unsigned long long *)nmarks);
+            D3D_LAUNCH("k_iou_grad_sparse", (k_iou_grad_sparse<T, ROTATED, G, B>), dim3((unsigned)d3d_divup(nr * wpr, (int64_t)kSparseWords)), dim3(256),
+                       0, st, (const BoxGeom<T> *)ga + r0, b1 + r0 * 5, nr, (const BoxGeom<T> *)gb, b2, m, grad + r0 * m, g1 + r0 * 5, g2,
+                       (const unsigned long long *)bitmap, wpr, (const unsigned long long *)nmarks);
         }
     }
     return D3D_OK;
@@ -3002,10 +2945,7 @@ extern "C" int d3d_iou2d_backward(const void *boxes1, int64_t n, const void *box
 {
     hipStream_t st = (hipStream_t)stream;
     if (n < 0 || m < 0) return D3D_ERR_BAD_ARG;
-    if (dtype != D3D_F32 && dtype != D3D_F64 && dtype != D3D_F64_M32 && dtype != D3D_F32_WIDE) return D3D_ERR_BAD_ARG;
-    const bool loss_kind = iou_type == D3D_IOU_GRBOX || iou_type == D3D_IOU_DRBOX;
-    if (iou_type != D3D_IOU_BOX && iou_type != D3D_IOU_RBOX && !loss_kind) return D3D_ERR_UNSUPPORTED;
-    if (loss_kind && (dtype == D3D_F64_M32 || dtype == D3D_F32_WIDE)) return D3D_ERR_UNSUPPORTED;
+    if (const int rc = iou2d_check(iou_type, dtype)) return rc;
     if (n > 0 && (!boxes1 || !grad_boxes1)) return D3D_ERR_BAD_ARG;
     if (m > 0 && (!boxes2 || !grad_boxes2)) return D3D_ERR_BAD_ARG;
     const size_t esz = dtype != D3D_F32 ? 8 : 4;
@@ -3015,20 +2955,17 @@ extern "C" int d3d_iou2d_backward(const void *boxes1, int64_t n, const void *box
         return D3D_OK;
     }
     if (!grad || n >= (1ll << 32) || m >= (1ll << 32)) return D3D_ERR_BAD_ARG;
-    if (loss_kind)
+    if (iou_type == D3D_IOU_GRBOX || iou_type == D3D_IOU_DRBOX)
         return d3d_internal_loss_iou_backward(boxes1, n, boxes2, m, grad, iou_type == D3D_IOU_GRBOX ? 0 : 1, dtype, grad_boxes1,
                                               grad_boxes2, workspace, workspace ? workspace_bytes : 0, st);
     if (workspace_bytes < d3d_iou2d_workspace_bytes(n, m, dtype)) return D3D_ERR_WORKSPACE;
-    const bool rot = iou_type == D3D_IOU_RBOX;
-    if (dtype == D3D_F32_WIDE)
-        return iou2d_backward_typed<double, float, float>((const float *)boxes1, n, (const float *)boxes2, m, (const float *)grad, rot,
-                                                          (double *)grad_boxes1, (double *)grad_boxes2, workspace, workspace_bytes, st);
-    if (dtype == D3D_F64_M32)
-        return iou2d_backward_typed<double, float>((const double *)boxes1, n, (const double *)boxes2, m, (const float *)grad, rot,
-                                                   (double *)grad_boxes1, (double *)grad_boxes2, workspace, workspace_bytes, st);
-    if (dtype == D3D_F64)
-        return iou2d_backward_typed<double>((const double *)boxes1, n, (const double *)boxes2, m, (const double *)grad, rot,
-                                            (double *)grad_boxes1, (double *)grad_boxes2, workspace, workspace_bytes, st);
-    return iou2d_backward_typed<float>((const float *)boxes1, n, (const float *)boxes2, m, (const float *)grad, rot,
-                                       (float *)grad_boxes1, (float *)grad_boxes2, workspace, workspace_bytes, st);
+    return dispatch_dtype<D3D_F32, D3D_F64, D3D_F64_M32, D3D_F32_WIDE>(dtype, [&](auto p) {
+        typedef typename decltype(p)::T T;          // (the box gradients: fp64 for D3D_F32_WIDE too)
+        typedef typename decltype(p)::B B;
+        typedef typename decltype(p)::S G;
+        return dispatch(iou_type == D3D_IOU_RBOX, [&](auto r) {
+            return iou2d_backward_typed<T, r>((const B *)boxes1, n, (const B *)boxes2, m, (const G *)grad, (T *)grad_boxes1,
+                                              (T *)grad_boxes2, workspace, workspace_bytes, st);
+        });
+    });
 }

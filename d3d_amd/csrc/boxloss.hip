@@ -579,8 +579,8 @@ __global__ __launch_bounds__(kCols) void k_pdist_grad(const T *__restrict__ poin
     }
 }
 
-template <typename T>
-int loss_forward(const T *b1, int64_t n, const T *b2, int64_t m, int kind, T *out, void *ws, size_t ws_bytes, unsigned long long list_cap,
+template <typename T, int KIND>
+int loss_forward(const T *b1, int64_t n, const T *b2, int64_t m, T *out, void *ws, size_t ws_bytes, unsigned long long list_cap,
                  hipStream_t st)
 {
     const dim3 grid((unsigned)d3d_divup(m, kCols), (unsigned)d3d_divup(n, kRows));
@@ -596,23 +596,20 @@ int loss_forward(const T *b1, int64_t n, const T *b2, int64_t m, int kind, T *ou
         if (w.ok() && list_cap > 0) {
             const unsigned int *redo = &hdr->overflow;
             D3D_LAUNCH("k_giou_geom", k_giou_geom<T>, dim3((unsigned)d3d_divup(n + m, 256)), dim3(256), 0, st, b1, n, b2, m, ga, ha, gb, hb, hdr);
-#define D3D_LOSS_TWO(K, NAME)                                                                                                            \
-    D3D_LAUNCH(NAME "_main", (k_giou_main<T, K>), grid, dim3(kCols), 0, st, (const BoxGeom<T> *)ga, (const HullPre<T> *)ha, n,             \
-               (const BoxGeom<T> *)gb, (const HullPre<T> *)hb, m, out, hdr, list, list_cap);                                              \
-    D3D_LAUNCH(NAME "_fix", (k_giou_fix<T, K>), dim3(256 * 8), dim3(256), 0, st, ga, gb, m, out, hdr, list, list_cap);                      \
-    D3D_LAUNCH("k_loss_iou<redo>", (k_loss_iou<T, K>), grid, dim3(kCols), 0, st, b1, n, b2, m, out, redo)
-            if (kind == 0) { D3D_LOSS_TWO(0, "k_giou"); } else { D3D_LOSS_TWO(1, "k_diou"); }
-#undef D3D_LOSS_TWO
+            D3D_LAUNCH(KIND ? "k_diou_main" : "k_giou_main", (k_giou_main<T, KIND>), grid, dim3(kCols), 0, st, (const BoxGeom<T> *)ga,
+                       (const HullPre<T> *)ha, n, (const BoxGeom<T> *)gb, (const HullPre<T> *)hb, m, out, hdr, list, list_cap);
+            D3D_LAUNCH(KIND ? "k_diou_fix" : "k_giou_fix", (k_giou_fix<T, KIND>), dim3(256 * 8), dim3(256), 0, st, ga, gb, m, out, hdr, list,
+                       list_cap);
+            D3D_LAUNCH("k_loss_iou<redo>", (k_loss_iou<T, KIND>), grid, dim3(kCols), 0, st, b1, n, b2, m, out, redo);
             return D3D_OK;
         }
     }
-    if (kind == 0) D3D_LAUNCH("k_loss_iou<giou>", (k_loss_iou<T, 0>), grid, dim3(kCols), 0, st, b1, n, b2, m, out, no_gate);
-    else D3D_LAUNCH("k_loss_iou<diou>", (k_loss_iou<T, 1>), grid, dim3(kCols), 0, st, b1, n, b2, m, out, no_gate);
+    D3D_LAUNCH(KIND ? "k_loss_iou<diou>" : "k_loss_iou<giou>", (k_loss_iou<T, KIND>), grid, dim3(kCols), 0, st, b1, n, b2, m, out, no_gate);
     return D3D_OK;
 }
 
-template <typename T>
-int loss_backward(const T *b1, int64_t n, const T *b2, int64_t m, const T *grad, int kind, T *g1, T *g2, void *ws, size_t ws_bytes, hipStream_t st)
+template <typename T, int KIND>
+int loss_backward(const T *b1, int64_t n, const T *b2, int64_t m, const T *grad, T *g1, T *g2, void *ws, size_t ws_bytes, hipStream_t st)
 {
     D3D_HIP_CHECK(hipMemsetAsync(g1, 0, (size_t)n * 5 * sizeof(T), st));
     D3D_HIP_CHECK(hipMemsetAsync(g2, 0, (size_t)m * 5 * sizeof(T), st));
@@ -634,18 +631,16 @@ int loss_backward(const T *b1, int64_t n, const T *b2, int64_t m, const T *grad,
         unsigned long long *bitmap = w.take<unsigned long long>((size_t)n * (size_t)wpr);
         if (w.ok()) {
             D3D_LAUNCH("k_giou_geom", k_giou_geom<T>, dim3((unsigned)d3d_divup(n + m, 256)), dim3(256), 0, st, b1, n, b2, m, ga, ha, gb, hb, hdr);
-#define D3D_GRAD_TWO(K, NAME)                                                                                                            \
-    D3D_LAUNCH(NAME "_grad_main", (k_giou_grad_main<T, K>), tgrid, dim3(kCols), 0, st, (const BoxGeom<T> *)ga, (const HullPre<T> *)ha, b1, n, \
-               (const BoxGeom<T> *)gb, (const HullPre<T> *)hb, b2, m, grad, g1, g2, bitmap, wpr, tr);                                     \
-    D3D_LAUNCH("k_loss_grad_rest", (k_loss_grad_rest<T, K>), tgrid, dim3(kCols), 0, st, b1, n, b2, m, grad, g1, g2,                       \
-               (const unsigned long long *)bitmap, wpr, tr)
-            if (kind == 0) { D3D_GRAD_TWO(0, "k_giou"); } else { D3D_GRAD_TWO(1, "k_diou"); }
-#undef D3D_GRAD_TWO
+            D3D_LAUNCH(KIND ? "k_diou_grad_main" : "k_giou_grad_main", (k_giou_grad_main<T, KIND>), tgrid, dim3(kCols), 0, st,
+                       (const BoxGeom<T> *)ga, (const HullPre<T> *)ha, b1, n, (const BoxGeom<T> *)gb, (const HullPre<T> *)hb, b2, m, grad, g1,
+                       g2, bitmap, wpr, tr);
+            D3D_LAUNCH("k_loss_grad_rest", (k_loss_grad_rest<T, KIND>), tgrid, dim3(kCols), 0, st, b1, n, b2, m, grad, g1, g2,
+                       (const unsigned long long *)bitmap, wpr, tr);
             return D3D_OK;
         }
     }
-    if (kind == 0) D3D_LAUNCH("k_loss_iou_grad<giou>", (k_loss_iou_grad<T, 0>), grid, dim3(kCols), 0, st, b1, n, b2, m, grad, g1, g2, all, (int64_t)0, (int)kRows);
-    else D3D_LAUNCH("k_loss_iou_grad<diou>", (k_loss_iou_grad<T, 1>), grid, dim3(kCols), 0, st, b1, n, b2, m, grad, g1, g2, all, (int64_t)0, (int)kRows);
+    D3D_LAUNCH(KIND ? "k_loss_iou_grad<diou>" : "k_loss_iou_grad<giou>", (k_loss_iou_grad<T, KIND>), grid, dim3(kCols), 0, st, b1, n, b2, m,
+               grad, g1, g2, all, (int64_t)0, (int)kRows);
     return D3D_OK;
 }
 
@@ -658,19 +653,24 @@ int d3d_internal_loss_iou_forward(const void *b1, int64_t n, const void *b2, int
                                   size_t ws_bytes, unsigned long long list_cap, hipStream_t st)
 {
     if (d3d_divup(n, kRows) > 65535) return D3D_ERR_BAD_ARG;
-    if (dtype == D3D_F64)
-        return loss_forward<double>((const double *)b1, n, (const double *)b2, m, kind, (double *)out, ws, ws_bytes, list_cap, st);
-    return loss_forward<float>((const float *)b1, n, (const float *)b2, m, kind, (float *)out, ws, ws_bytes, list_cap, st);
+    return dispatch_dtype<D3D_F32, D3D_F64>(dtype, [&](auto p) {
+        typedef typename decltype(p)::T T;
+        return dispatch(kind != 0, [&](auto diou) {
+            return loss_forward<T, diou ? 1 : 0>((const T *)b1, n, (const T *)b2, m, (T *)out, ws, ws_bytes, list_cap, st);
+        });
+    });
 }
 
 int d3d_internal_loss_iou_backward(const void *b1, int64_t n, const void *b2, int64_t m, const void *grad, int kind, int dtype,
                                    void *g1, void *g2, void *ws, size_t ws_bytes, hipStream_t st)
 {
     if (d3d_divup(n, kRows) > 65535) return D3D_ERR_BAD_ARG;
-    if (dtype == D3D_F64)
-        return loss_backward<double>((const double *)b1, n, (const double *)b2, m, (const double *)grad, kind, (double *)g1, (double *)g2, ws,
-                                     ws_bytes, st);
-    return loss_backward<float>((const float *)b1, n, (const float *)b2, m, (const float *)grad, kind, (float *)g1, (float *)g2, ws, ws_bytes, st);
+    return dispatch_dtype<D3D_F32, D3D_F64>(dtype, [&](auto p) {
+        typedef typename decltype(p)::T T;
+        return dispatch(kind != 0, [&](auto diou) {
+            return loss_backward<T, diou ? 1 : 0>((const T *)b1, n, (const T *)b2, m, (const T *)grad, (T *)g1, (T *)g2, ws, ws_bytes, st);
+        });
+    });
 }
 
 extern "C" int d3d_iou2dr_flags(const void *boxes1, int64_t n, const void *boxes2, int64_t m, int32_t dtype, uint8_t *nx,
@@ -682,13 +682,12 @@ extern "C" int d3d_iou2dr_flags(const void *boxes1, int64_t n, const void *boxes
     if (!boxes1 || !boxes2) return D3D_ERR_BAD_ARG;
     if (((reinterpret_cast<uintptr_t>(xflags) | reinterpret_cast<uintptr_t>(mflags)) & 7)) return D3D_ERR_BAD_ARG;
     const unsigned grid = (unsigned)(d3d_divup(n * m, 256) < 65536 ? d3d_divup(n * m, 256) : 65536);
-    if (dtype == D3D_F64)
-        D3D_LAUNCH("k_pair_flags", k_pair_flags<double>, dim3(grid), dim3(256), 0, st, (const double *)boxes1, n, (const double *)boxes2, m,
-                   nx, xflags, nm, mflags, far);
-    else
-        D3D_LAUNCH("k_pair_flags", k_pair_flags<float>, dim3(grid), dim3(256), 0, st, (const float *)boxes1, n, (const float *)boxes2, m,
-                   nx, xflags, nm, mflags, far);
-    return D3D_OK;
+    return dispatch_dtype<D3D_F32, D3D_F64>(dtype, [&](auto p) {
+        typedef typename decltype(p)::T T;
+        D3D_LAUNCH("k_pair_flags", k_pair_flags<T>, dim3(grid), dim3(256), 0, st, (const T *)boxes1, n, (const T *)boxes2, m, nx, xflags, nm,
+                   mflags, far);
+        return D3D_OK;
+    });
 }
 
 extern "C" int d3d_pdist2dr_forward(const void *points, int64_t n, const void *boxes, int64_t m, int32_t dtype, void *dist,
@@ -700,11 +699,14 @@ extern "C" int d3d_pdist2dr_forward(const void *points, int64_t n, const void *b
     if (!points || !boxes || !dist || d3d_divup(m, kRows) > 65535) return D3D_ERR_BAD_ARG;
     const bool k4 = n % 4 == 0 && (reinterpret_cast<uintptr_t>(dist) & 31) == 0 && (reinterpret_cast<uintptr_t>(iedge) & 3) == 0;
     const dim3 grid((unsigned)d3d_divup(n, (int64_t)kCols * (k4 ? 4 : 1)), (unsigned)d3d_divup(m, kRows));
-#define D3D_PDIST(T, K) D3D_LAUNCH("k_pdist", (k_pdist<T, K>), grid, dim3(kCols), 0, st, (const T *)points, n, (const T *)boxes, m, (T *)dist, iedge)
-    if (dtype == D3D_F64) { if (k4) D3D_PDIST(double, 4); else D3D_PDIST(double, 1); }
-    else { if (k4) D3D_PDIST(float, 4); else D3D_PDIST(float, 1); }
-#undef D3D_PDIST
-    return D3D_OK;
+    return dispatch_dtype<D3D_F32, D3D_F64>(dtype, [&](auto p) {
+        typedef typename decltype(p)::T T;
+        return dispatch(k4, [&](auto vec) {
+            D3D_LAUNCH("k_pdist", (k_pdist<T, vec ? 4 : 1>), grid, dim3(kCols), 0, st, (const T *)points, n, (const T *)boxes, m, (T *)dist,
+                       iedge);
+            return D3D_OK;
+        });
+    });
 }
 
 extern "C" int d3d_pdist2dr_backward(const void *points, int64_t n, const void *boxes, int64_t m, const void *grad, int32_t dtype,
@@ -718,11 +720,10 @@ extern "C" int d3d_pdist2dr_backward(const void *points, int64_t n, const void *
     if (n == 0 || m == 0) return D3D_OK;
     if (!points || !boxes || !grad || d3d_divup(m, kRows) > 65535) return D3D_ERR_BAD_ARG;
     const dim3 grid((unsigned)d3d_divup(n, kCols), (unsigned)d3d_divup(m, kRows));
-    if (dtype == D3D_F64)
-        D3D_LAUNCH("k_pdist_grad", k_pdist_grad<double>, grid, dim3(kCols), 0, st, (const double *)points, n, (const double *)boxes, m,
-                   (const double *)grad, (double *)grad_boxes, (double *)grad_points);
-    else
-        D3D_LAUNCH("k_pdist_grad", k_pdist_grad<float>, grid, dim3(kCols), 0, st, (const float *)points, n, (const float *)boxes, m,
-                   (const float *)grad, (float *)grad_boxes, (float *)grad_points);
-    return D3D_OK;
+    return dispatch_dtype<D3D_F32, D3D_F64>(dtype, [&](auto p) {
+        typedef typename decltype(p)::T T;
+        D3D_LAUNCH("k_pdist_grad", k_pdist_grad<T>, grid, dim3(kCols), 0, st, (const T *)points, n, (const T *)boxes, m, (const T *)grad,
+                   (T *)grad_boxes, (T *)grad_points);
+        return D3D_OK;
+    });
 }

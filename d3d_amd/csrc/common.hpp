@@ -35,6 +35,36 @@ void d3d_prof_post(const char *name, hipStream_t st);
 template <class F>
 static inline int dispatch(bool flag, F &&f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
 
+// a dtype code -> its element types: T the arithmetic, B the boxes (and scores) in memory, S the matrix / incoming gradient
+template <class T_, class B_ = T_, class S_ = T_> struct Prec { typedef T_ T; typedef B_ B; typedef S_ S; };
+template <int DTYPE> struct PrecOf;
+template <> struct PrecOf<D3D_F32> { typedef Prec<float> type; };
+template <> struct PrecOf<D3D_F64> { typedef Prec<double> type; };
+template <> struct PrecOf<D3D_F64_M32> { typedef Prec<double, double, float> type; };      // fp64 boxes, fp32 matrix
+template <> struct PrecOf<D3D_F32_WIDE> { typedef Prec<double, float, float> type; };      // fp32 in memory, fp64 arithmetic
+// dtype -> f(PrecOf<dtype>::type{}) for the codes a site handles (only those are instantiated), D3D_ERR_BAD_ARG for any other
+template <int... CODES, class F>
+static inline int dispatch_dtype(int dtype, F &&f)
+{
+    int rc = D3D_ERR_BAD_ARG;
+    (void)((dtype == CODES && (rc = f(typename PrecOf<CODES>::type{}), true)) || ...);
+    return rc;
+}
+
+// entry points one .hip file offers the others
+extern "C" size_t d3d_internal_argsort_i32_bytes(int64_t n);                                               // sort.hip
+extern "C" int d3d_internal_argsort_desc_i32(const int32_t *keys, int64_t n, int32_t *order, void *ws, size_t ws_bytes,
+                                             hipStream_t st);
+extern "C" size_t d3d_internal_argsort_counts_bytes(int64_t n);
+extern "C" int d3d_internal_argsort_desc_counts_dev(const int32_t *keys, int64_t n, const int64_t *n_dev, int64_t max_key_sum, int32_t *order,
+                                                    void *ws, size_t ws_bytes, hipStream_t st);
+extern "C" int d3d_internal_crop2dr_grid_f32(const float *points, int64_t n, const float *boxes, int64_t m, uint8_t *out,
+                                             hipStream_t st);                                                // crop.hip
+int d3d_internal_loss_iou_forward(const void *b1, int64_t n, const void *b2, int64_t m, int kind, int dtype, void *out, void *ws,
+                                  size_t ws_bytes, unsigned long long list_cap, hipStream_t st);            // boxloss.hip
+int d3d_internal_loss_iou_backward(const void *b1, int64_t n, const void *b2, int64_t m, const void *grad, int kind, int dtype,
+                                   void *g1, void *g2, void *ws, size_t ws_bytes, hipStream_t st);
+
 static inline size_t d3d_align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 static inline int64_t d3d_divup(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

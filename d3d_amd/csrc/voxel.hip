@@ -4622,13 +4622,6 @@ extern "C" size_t d3d_voxelize_workspace_bytes(int64_t n_points, int64_t n_voxel
     return carve(nullptr, 0, n_points, n_voxels).bytes + 256;
 }
 
-extern "C" int d3d_internal_argsort_desc_i32(const int32_t *keys, int64_t n, int32_t *order, void *ws, size_t ws_bytes,
-                                             hipStream_t st);
-extern "C" size_t d3d_internal_argsort_i32_bytes(int64_t n);
-extern "C" size_t d3d_internal_argsort_counts_bytes(int64_t n);
-extern "C" int d3d_internal_argsort_desc_counts_dev(const int32_t *keys, int64_t n, const int64_t *n_dev, int64_t max_key_sum, int32_t *order,
-                                                    void *ws, size_t ws_bytes, hipStream_t st);
-
 // D3D_VOXEL_EXACT_MEAN (kernels above): everything it needs is in the operator's outputs; scratch = the index's, which is done
 static int exact_mean_pass(const DenseKey &kf, const float *points, int64_t n, int32_t c, uint32_t P, const int64_t *coords,
                            const int32_t *npoints, float *aggregates, const int64_t *counts, const VoxelWs &w, hipStream_t st)
@@ -5019,10 +5012,6 @@ extern "C" int d3d_voxelize_3d_sparse(const float *points, int64_t n, int32_t c,
     return voxelize_sparse_impl(points, n, c, voxel_size, points_mapping, coords, npoints, counts, workspace, workspace_bytes, 0,
                                 stream, flags, false);
 }
-
-extern "C" int d3d_internal_argsort_desc_i32(const int32_t *keys, int64_t n, int32_t *order, void *ws, size_t ws_bytes,
-                                             hipStream_t st);
-extern "C" size_t d3d_internal_argsort_i32_bytes(int64_t n);
 
 // nvox_device != NULL: `nvox` is only an upper bound (buffer rows), the number of voxels is read on the device
 static int filter_impl(const float *feats, int64_t n, int32_t c, const int64_t *points_mapping, const int64_t *coords,

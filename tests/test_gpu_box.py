@@ -653,6 +653,12 @@ def test_c_abi_error_codes():
                          z, 0) == _lib.ERR_UNSUPPORTED                                                          # suppression enum
     assert lib.d3d_nms2d(p(b), p(b[:, 0].contiguous()), p(order), 4, 2, 0, _lib.F64, 0.5, 0.0, 0.0, p(sup), p(ws), 16,
                          z, 0) == _lib.ERR_WORKSPACE                                                            # workspace too small
+    assert lib.d3d_nms2d(p(b), p(b[:, 0].contiguous()), p(order), 4, 2, 0, _lib.F64_M32, 0.5, 0.0, 0.0, p(sup), p(ws), ws.numel(),
+                         z, 0) == _lib.ERR_BAD_ARG                                                              # no mixed matrix in NMS
+    u8 = torch.zeros((16,), dtype=torch.uint8, device="cuda")
+    assert lib.d3d_crop_2dr(p(b), 4, p(b), 4, _lib.F64_M32, p(u8), z) == _lib.ERR_BAD_ARG                       # crop: F32 / F64 only
+    assert lib.d3d_pdist2dr_forward(p(b), 4, p(b), 4, _lib.F32_WIDE, p(out), z, z) == _lib.ERR_BAD_ARG           # pdist: F32 / F64 only
+    assert lib.d3d_iou2dr_flags(p(b), 4, p(b), 4, _lib.F64_M32, z, z, z, z, z, z) == _lib.ERR_BAD_ARG            # flags: F32 / F64 only
     assert lib.d3d_iou3d_forward(z, 4, z, 4, 1, z, z, 0, z) == _lib.ERR_BAD_ARG                                     # null boxes
     assert lib.d3d_status_string(_lib.ERR_WORKSPACE) == b"workspace too small"
     torch.cuda.synchronize()
