@@ -292,3 +292,294 @@ class ScoreMatcher:
 
     def num_of_matches(self):
         return len(self._src_assignment)
+
+
+# ------------------------------------------------------------------------------------------ LSAP, Hungarian, nearest neighbour
+LSAP_INVALID, LSAP_INFEASIBLE, LSAP_TOO_BIG = 1, 2, 4          # status bits of d3d_lsap_batched (include/d3d_hip.h)
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def _lsap_launch(cost, ld, row_idx, col_idx, row_off, col_off, max_rows, max_cols, dev):
+    """one d3d_lsap_batched call; row_idx / col_idx / row_off / col_off int64 numpy arrays, shipped in ONE copy.
+    -> (row_match, col_match, status) device tensors (nothing is read back)"""
+    lib = _lib.load()
+    B = row_off.size - 1
+    nrt, nct = int(row_off[-1]), int(col_off[-1])
+    with torch.cuda.device(dev):
+        d = torch.from_numpy(np.concatenate([row_idx, col_idx, row_off, col_off]).astype(np.int64)).to(dev)
+        ri, ci = d[:nrt], d[nrt:nrt + nct]
+        ro, co = d[nrt + nct:nrt + nct + B + 1], d[nrt + nct + B + 1:]
+        row_match = torch.empty((nrt,), dtype=torch.int32, device=dev)
+        col_match = torch.empty((nct,), dtype=torch.int32, device=dev)
+        status = torch.zeros((1,), dtype=torch.int32, device=dev)
+        ws = _lib.workspace(lib.d3d_lsap_batched_workspace_bytes(B, nrt, nct), dev)
+        rc = lib.d3d_lsap_batched(_lib.ptr(cost), _lib.F64 if cost.dtype == torch.float64 else _lib.F32, int(ld), _lib.ptr(ri),
+                                  _lib.ptr(ci), _lib.ptr(ro), _lib.ptr(co), B, int(max_rows), int(max_cols), _lib.ptr(row_match),
+                                  _lib.ptr(col_match), _lib.ptr(status), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+        _lib.check(rc, "lsap_batched")
+    return row_match, col_match, status
+
+
+def _lsap_raise(status):
+    s = int(status)
+    if s & LSAP_INVALID:
+        raise ValueError("matrix contains invalid numeric entries")
+    if s & LSAP_INFEASIBLE:
+        raise ValueError("cost matrix is infeasible")
+    if s & LSAP_TOO_BIG:
+        raise RuntimeError("lsap_batched: a problem beyond the stated sizes or the workspace")
+
+
+def linear_sum_assignment(cost):
+    """scipy.optimize.linear_sum_assignment(cost) on the GPU, the same result bit for bit (ties included): the solver is scipy's
+    (Crouse's shortest augmenting path, fp64) step for step.  `cost` is a 2-D matrix -> (row_ind, col_ind), or a [B, n, m] batch
+    solved in ONE launch -> (row_ind[B, k], col_ind[B, k]), k = min(n, m).  Accepts numpy arrays (-> int64 numpy arrays, as
+    scipy), host tensors (-> int64 host tensors) and device tensors (-> int64 device tensors).  fp32 and fp64 are read as they
+    are, other dtypes are widened to fp64 first (as scipy does).  NaN or -inf entries, or a matrix without a full assignment of
+    finite cost, raise ValueError (scipy's messages); the call reads its status word back for that."""
+    as_numpy = not isinstance(cost, torch.Tensor)
+    t = torch.from_numpy(np.asarray(cost)) if as_numpy else cost.detach()
+    if t.dim() not in (2, 3):
+        raise ValueError("expected a matrix (2-D array) or a batch of matrices (3-D array), got shape %r" % (tuple(t.shape),))
+    if t.dtype not in (torch.float32, torch.float64):
+        t = t.to(torch.float64)
+    odev = t.device
+    batched = t.dim() == 3
+    if not batched:
+        t = t[None]
+    B, n, m = t.shape
+    k = min(n, m)
+    if B == 0 or k == 0:
+        empty = torch.zeros((B, 0) if batched else (0,), dtype=torch.int64)
+        return (empty.numpy(), empty.numpy()) if as_numpy else (empty.to(odev), empty.to(odev))
+    dev = odev if t.is_cuda else _lib.require_gpu()
+    c = t.to(dev).contiguous().view(B * n, m)
+    row_idx = np.arange(B * n, dtype=np.int64)
+    col_idx = np.tile(np.arange(m, dtype=np.int64), B)
+    row_match, col_match, status = _lsap_launch(c, m, row_idx, col_idx, np.arange(B + 1, dtype=np.int64) * n,
+                                                np.arange(B + 1, dtype=np.int64) * m, n, m, dev)
+    with torch.cuda.device(dev):
+        if n <= m:              # every row is assigned: scipy returns rows 0 .. n-1 in order
+            rows = torch.arange(n, dtype=torch.int64, device=dev).expand(B, n)
+            cols = row_match.view(B, n).to(torch.int64)
+        else:                   # every column is assigned: scipy orders the pairs by row
+            cm = col_match.view(B, m).to(torch.int64)
+            order = torch.argsort(cm, dim=1)
+            rows, cols = torch.gather(cm, 1, order), order
+        st = status.cpu()
+    _lsap_raise(st[0])
+    if not batched:
+        rows, cols = rows[0], cols[0]
+    if as_numpy:
+        return rows.cpu().numpy(), cols.cpu().numpy()
+    return _lib.to_caller((rows.contiguous(), cols.contiguous()), odev, dev)
+
+
+def _matrix_on_device(distance):
+    t = torch.from_numpy(np.ascontiguousarray(distance, dtype=np.float32)) if not isinstance(distance, torch.Tensor) else distance
+    if t.dim() != 2:
+        raise ValueError("distance should be a [n, m] matrix")
+    if t.dtype != torch.float32:
+        t = t.to(torch.float32)
+    dev = t.device if t.is_cuda else _lib.require_gpu()
+    return t.to(dev).contiguous(), dev
+
+
+def _tags(tags, count, what):
+    t = _host(tags).reshape(-1)
+    if t.size != count:
+        raise ValueError("%s should hold one tag per box (%d), got %d" % (what, count, t.size))
+    return t.astype(np.int64)
+
+
+def _subset(subset, count, what):
+    s = np.arange(count, dtype=np.int64) if subset is None else _index_array(_host(subset) if isinstance(subset, torch.Tensor) else subset)
+    if s.size and (s.min() < 0 or s.max() >= count):
+        raise ValueError("%s holds an index outside 0 .. %d" % (what, count - 1))
+    return s
+
+
+def _threshold_of(distance_threshold, tags):
+    """unordered_map<int, float>::operator[] (matcher.pyx:115, :227): a tag missing from the map reads as 0.0"""
+    thr = np.zeros((tags.size,), np.float32)
+    for tag in np.unique(tags):
+        thr[tags == tag] = np.float32(float(distance_threshold.get(int(tag), 0.0)))
+    return thr
+
+
+def _hungarian_problems(stags, dtags, ssub, dsub):
+    """HungarianMatcher.match's split (matcher.pyx:194-220): the subsets by class, subset order kept inside each class, the
+    classes in first-appearance order among the sources, those without destinations skipped.  -> (row lists, column lists)"""
+    rows, cols = {}, {}
+    for s in ssub.tolist():
+        rows.setdefault(int(stags[s]), []).append(s)
+    for d in dsub.tolist():
+        cols.setdefault(int(dtags[d]), []).append(d)
+    keep = [c for c in rows if c in cols]
+    return [rows[c] for c in keep], [cols[c] for c in keep], keep
+
+
+def hungarian_match(distance, src_tags, dst_tags, distance_threshold, src_subset=None, dst_subset=None):
+    """HungarianMatcher.match (matcher.pyx:188-230) on arrays: per class, the optimal assignment of
+    distance[src of the class, dst of the class] (scipy's linear_sum_assignment, reproduced bit for bit, ties included), then
+    the pairs with distance <= distance_threshold[class] (0.0 for a class missing from the map) are kept -- the assignment is not
+    solved again without the others.  All classes in ONE launch.  `distance` f32 [n, m] (a device tensor, or moved there),
+    tags one per box, subsets default to every box.  -> (src_match[n], dst_match[m]) int32 device tensors, -1 = unmatched.
+    A NaN or -inf distance inside a class's block raises ValueError, as scipy does (the call reads its status word back)."""
+    dist, dev = _matrix_on_device(distance)
+    n, m = dist.shape
+    stags, dtags = _tags(src_tags, n, "src_tags"), _tags(dst_tags, m, "dst_tags")
+    ssub, dsub = _subset(src_subset, n, "src_subset"), _subset(dst_subset, m, "dst_subset")
+    with torch.cuda.device(dev):
+        src_match = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        dst_match = torch.full((m,), -1, dtype=torch.int32, device=dev)
+    rows, cols, classes = _hungarian_problems(stags, dtags, ssub, dsub)
+    if not rows:
+        return src_match, dst_match
+    nr = np.array([len(r) for r in rows], np.int64)
+    nc = np.array([len(c) for c in cols], np.int64)
+    row_off, col_off = np.zeros((len(rows) + 1,), np.int64), np.zeros((len(rows) + 1,), np.int64)
+    row_off[1:], col_off[1:] = np.cumsum(nr), np.cumsum(nc)
+    row_idx, col_idx = np.concatenate([np.asarray(r, np.int64) for r in rows]), np.concatenate([np.asarray(c, np.int64) for c in cols])
+    thr = np.repeat(np.array([np.float32(float(distance_threshold.get(int(c), 0.0))) for c in classes], np.float32), nr)
+    row_match, _, status = _lsap_launch(dist, m, row_idx, col_idx, row_off, col_off, int(nr.max()), int(nc.max()), dev)
+    with torch.cuda.device(dev):
+        aux = torch.from_numpy(np.concatenate([row_idx, np.repeat(col_off[:-1], nr), thr.view(np.int32).astype(np.int64)])).to(dev)
+        R = row_idx.size
+        ri, cbase, thr_t = aux[:R], aux[R:2 * R], aux[2 * R:].to(torch.int32).view(torch.float32)
+        ci_all = torch.from_numpy(col_idx).to(dev)
+        has = row_match >= 0
+        cj = ci_all[(cbase + row_match.clamp_min(0).to(torch.int64))]
+        ok = has & (dist[ri, cj] <= thr_t)
+        src_match[ri[ok]] = cj[ok].to(torch.int32)
+        dst_match[cj[ok]] = ri[ok].to(torch.int32)
+        st = status.cpu()
+    _lsap_raise(st[0])
+    return src_match, dst_match
+
+
+def nearest_neighbor_match(distance, src_tags, dst_tags, distance_threshold, src_subset=None, dst_subset=None, src_free=None,
+                           dst_free=None):
+    """NearestNeighborMatcher.match (matcher.pyx:164-186 + match_by_order :90-121) on arrays: the (src, dst) pairs of the two
+    subsets from the least distance up; a pair is taken when neither side is taken yet, the tags agree and
+    distance <= distance_threshold[dst tag] (0.0 for a tag missing from the map).  Equal distances: row-major order of the
+    subset positions (what a stable sort gives; the reference's unstable argsort leaves it open).  src_free[n] / dst_free[m]
+    (bool, optional): False = the box was matched by an earlier call and takes no part.  -> (src_match[n], dst_match[m]) int32
+    device tensors, -1 = unmatched.  Nothing is read back."""
+    dist, dev = _matrix_on_device(distance)
+    n, m = dist.shape
+    stags, dtags = _tags(src_tags, n, "src_tags"), _tags(dst_tags, m, "dst_tags")
+    ssub, dsub = _subset(src_subset, n, "src_subset"), _subset(dst_subset, m, "dst_subset")
+    with torch.cuda.device(dev):
+        src_match = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        dst_match = torch.full((m,), -1, dtype=torch.int32, device=dev)
+    ns, nd = ssub.size, dsub.size
+    if ns == 0 or nd == 0:
+        return src_match, dst_match
+    lib = _lib.load()
+    st, dt = stags[ssub].astype(np.int32), dtags[dsub].astype(np.int32)
+    thr = _threshold_of(distance_threshold, dt)
+    sf = np.ones((ns,), np.uint8) if src_free is None else _host(src_free).reshape(-1).astype(bool)[ssub].astype(np.uint8)
+    df = np.ones((nd,), np.uint8) if dst_free is None else _host(dst_free).reshape(-1).astype(bool)[dsub].astype(np.uint8)
+    # one buffer: [src subset i64 | dst subset i64 | src tags i32 | dst tags i32 | thresholds f32 | src free u8 | dst free u8]
+    packed = np.concatenate([ssub.view(np.uint8), dsub.view(np.uint8), st.view(np.uint8), dt.view(np.uint8), thr.view(np.uint8),
+                             sf, df])
+    with torch.cuda.device(dev):
+        d = torch.from_numpy(packed).to(dev)
+        o = 0
+        def take(nbytes, dtype):
+            nonlocal o
+            t = d[o:o + nbytes].view(dtype)
+            o += nbytes
+            return t
+        si, di = take(8 * ns, torch.int64), take(8 * nd, torch.int64)
+        st_t, dt_t, thr_t = take(4 * ns, torch.int32), take(4 * nd, torch.int32), take(4 * nd, torch.float32)
+        sf_t, df_t = take(ns, torch.uint8), take(nd, torch.uint8)
+        sm = torch.empty((ns,), dtype=torch.int32, device=dev)
+        dm = torch.empty((nd,), dtype=torch.int32, device=dev)
+        ws = _lib.workspace(lib.d3d_nn_match_workspace_bytes(ns, nd), dev)
+        rc = lib.d3d_nn_match(_lib.ptr(dist), m, _lib.ptr(si), ns, _lib.ptr(di), nd, _lib.ptr(st_t), _lib.ptr(dt_t), _lib.ptr(thr_t),
+                              _lib.ptr(sf_t), _lib.ptr(df_t), _lib.ptr(sm), _lib.ptr(dm), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+        _lib.check(rc, "nn_match")
+        hs, hd = sm >= 0, dm >= 0
+        src_match[si[hs]] = di[sm[hs].to(torch.int64)].to(torch.int32)
+        dst_match[di[hd]] = si[dm[hd].to(torch.int64)].to(torch.int32)
+    return src_match, dst_match
+
+
+class _AssignmentMatcher:
+    """BaseMatcher's array-level state (matcher.pyx:12-136) for the two matchers below.  Unlike ScoreMatcher here, `match`
+    does not clear the assignment first -- as in the reference, a second `match` without clear_match / prepare_boxes adds to
+    it."""
+
+    def __init__(self):
+        self._cache = None
+        self._src = self._dst = None
+        self._src_assignment, self._dst_assignment = {}, {}
+
+    def clear_match(self):
+        self._src_assignment, self._dst_assignment = {}, {}
+
+    def prepare_boxes(self, src_arr, dst_arr, distance_metric):
+        self.clear_match()
+        self._src, self._dst = _boxes(src_arr, "src_boxes"), _boxes(dst_arr, "dst_boxes")
+        if len(self._src) == 0 or len(self._dst) == 0:
+            self._cache = torch.zeros((len(self._src), len(self._dst)), dtype=torch.float32)      # matcher.pyx:41-43
+            return
+        self._cache = prepare_boxes(self._src, self._dst, distance_metric)
+
+    @property
+    def distance_cache(self):
+        return self._cache
+
+    def _tags(self):
+        return self._src[:, 0].cpu().numpy().astype(np.int64), self._dst[:, 0].cpu().numpy().astype(np.int64)
+
+    def query_src_match(self, src_idx):
+        return self._src_assignment.get(int(src_idx), -1)
+
+    def query_dst_match(self, dst_idx):
+        return self._dst_assignment.get(int(dst_idx), -1)
+
+    def num_of_matches(self):
+        assert len(self._src_assignment) == len(self._dst_assignment)
+        return len(self._src_assignment)
+
+
+class NearestNeighborMatcher(_AssignmentMatcher):
+    """NearestNeighborMatcher (matcher.pyx:164-186): the pairs from the closest up (nearest_neighbor_match); boxes that an
+    earlier `match` assigned take no part."""
+
+    def match(self, src_subset, dst_subset, distance_threshold):
+        src_subset, dst_subset = list(src_subset), list(dst_subset)
+        if not src_subset or not dst_subset or self._cache is None or self._cache.numel() == 0:
+            return
+        n, m = self._cache.shape
+        stags, dtags = self._tags()
+        sf, df = np.ones((n,), bool), np.ones((m,), bool)
+        sf[list(self._src_assignment)] = False
+        df[list(self._dst_assignment)] = False
+        sm, dm = nearest_neighbor_match(self._cache, stags, dtags, distance_threshold, src_subset, dst_subset, sf, df)
+        sm = sm.cpu().numpy()
+        for i in np.nonzero(sm >= 0)[0].tolist():
+            self._src_assignment[i] = int(sm[i])
+            self._dst_assignment[int(sm[i])] = i
+
+
+class HungarianMatcher(_AssignmentMatcher):
+    """HungarianMatcher (matcher.pyx:188-230): the optimal assignment per class (hungarian_match, every class in one launch);
+    a second `match` overwrites the assignment key by key, as the reference's maps do."""
+
+    def match(self, src_subset, dst_subset, distance_threshold):
+        src_subset, dst_subset = list(src_subset), list(dst_subset)
+        if not src_subset or not dst_subset or self._cache is None or self._cache.numel() == 0:
+            return
+        stags, dtags = self._tags()
+        sm, _ = hungarian_match(self._cache, stags, dtags, distance_threshold, src_subset, dst_subset)
+        sm = sm.cpu().numpy()
+        for i in np.nonzero(sm >= 0)[0].tolist():
+            self._src_assignment[i] = int(sm[i])
+            self._dst_assignment[int(sm[i])] = i

@@ -561,6 +561,34 @@ int d3d_score_match_batched(const float *dist, const int64_t *row_src, const uin
                             int32_t *src_match, int32_t *dst_match, int32_t *status, void *workspace, size_t workspace_bytes,
                             void *stream);
 
+/* replaces scipy.optimize.linear_sum_assignment as HungarianMatcher.match calls it once per class (reference
+ * d3d/tracking/matcher.pyx:188-230): `batches` independent problems in one launch, one workgroup each.  Problem b is the
+ * matrix cost[row_idx[r] * ld + col_idx[c]] for r in row_off[b] .. row_off[b + 1], c in col_off[b] .. col_off[b + 1]
+ * (row_off, col_off i64[batches + 1], row_idx, col_idx i64, all on the device): gathered by index, no stacked matrix.  cost is
+ * D3D_F32 or D3D_F64 (`dtype`); the solver computes in fp64 and reproduces scipy's algorithm step for step (Crouse 2016,
+ * scipy's rectangular_lsap), ties included.  row_match[row_off[b] + r] i32 = the column (local to the problem) assigned to
+ * row r or -1, col_match[col_off[b] + c] = the row assigned to column c or -1.  max_rows / max_cols bound every problem's
+ * sizes (host values: they size the launch).  status (device i32, zeroed here): bit 0 = a NaN or -inf entry, bit 1 = a row
+ * without a finite path (scipy raises ValueError for both; the problem's matches stay -1), bit 2 = a problem beyond max_rows /
+ * max_cols or the workspace.  Workspace: d3d_lsap_batched_workspace_bytes(batches, sum of rows, sum of columns). */
+size_t d3d_lsap_batched_workspace_bytes(int64_t batches, int64_t total_rows, int64_t total_cols);
+int d3d_lsap_batched(const void *cost, int32_t dtype, int64_t ld, const int64_t *row_idx, const int64_t *col_idx,
+                     const int64_t *row_off, const int64_t *col_off, int64_t batches, int64_t max_rows, int64_t max_cols,
+                     int32_t *row_match, int32_t *col_match, int32_t *status, void *workspace, size_t workspace_bytes,
+                     void *stream);
+
+/* replaces NearestNeighborMatcher.match + BaseMatcher.match_by_order (reference d3d/tracking/matcher.pyx:164-186, :90-121):
+ * the pairs (r, c) of the subsets src_idx[ns], dst_idx[nd] (i64 rows / columns of dist, leading dimension ld) taken from the
+ * least distance up; a pair is accepted when neither side is matched yet, src_tag[r] == dst_tag[c] and
+ * dist <= dst_threshold[c] (i32 / i32 / f32 per subset position).  src_free[ns] / dst_free[nd] u8 (NULL = all free): 0 = the box
+ * was matched by an earlier call and takes no part.  Equal distances: row-major order of (src position, dst position).
+ * src_match[ns], dst_match[nd] i32 = the partner's subset position or -1.  Three launches, no synchronisation. */
+size_t d3d_nn_match_workspace_bytes(int64_t ns, int64_t nd);
+int d3d_nn_match(const float *dist, int64_t ld, const int64_t *src_idx, int64_t ns, const int64_t *dst_idx, int64_t nd,
+                 const int32_t *src_tag, const int32_t *dst_tag, const float *dst_threshold, const uint8_t *src_free,
+                 const uint8_t *dst_free, int32_t *src_match, int32_t *dst_match, void *workspace, size_t workspace_bytes,
+                 void *stream);
+
 /* replaces crop_2dr (reference d3d/box/utils.cpp:9-47, bound at box/impl.cpp as crop_2dr; Python box2dr_crop /
  * box3dp_crop, box/__init__.py:278-315): points[n,2], boxes[m,5] in `dtype`; out[m,n] u8 (0/1),
  * out[i,j] = point j lies in rotated box i (boundary inclusive). */
