@@ -133,6 +133,41 @@ def nearest_neighbor_match(distance, src_tags, dst_tags, src_subset, dst_subset,
     return src_assignment, dst_assignment
 
 
+def nearest_neighbor_match_fast(distance, src_tags, dst_tags, src_subset, dst_subset, distance_threshold,
+                                src_assignment=None, dst_assignment=None):
+    """nearest_neighbor_match for large frames: match_by_order over the ACCEPTABLE free pairs only (tags agree, distance <=
+    the threshold of the dst tag, neither side assigned before the call), stably sorted by (distance, src position, dst
+    position).  The pairs left out never change match_by_order's state, so the result is the same -- except where
+    match_by_order's early exit (an assignment map exactly as long as the whole pair list) can fire; such a small call is
+    handed to the literal version."""
+    src_assignment = {} if src_assignment is None else src_assignment
+    dst_assignment = {} if dst_assignment is None else dst_assignment
+    ssub, dsub = np.asarray(src_subset, np.int64).reshape(-1), np.asarray(dst_subset, np.int64).reshape(-1)
+    if ssub.size == 0 or dsub.size == 0:
+        return src_assignment, dst_assignment
+    total = ssub.size * dsub.size
+    if max(len(src_assignment), len(dst_assignment)) + min(ssub.size, dsub.size) >= total:
+        return nearest_neighbor_match(distance, src_tags, dst_tags, ssub, dsub, distance_threshold, src_assignment, dst_assignment)
+    st, dt = np.asarray(src_tags, np.int64)[ssub], np.asarray(dst_tags, np.int64)[dsub]
+    thr = np.array([_thr(distance_threshold, t) for t in dt], np.float64)
+    sfree = np.array([int(s) not in src_assignment for s in ssub])
+    dfree = np.array([int(d) not in dst_assignment for d in dsub])
+    sub = np.asarray(distance)[np.ix_(ssub, dsub)]
+    ok = (st[:, None] == dt[None, :]) & (sub.astype(np.float64) <= thr[None, :]) & sfree[:, None] & dfree[None, :]
+    si, di = np.nonzero(ok)                                  # row-major: (src position, dst position) ascending
+    order = np.argsort(sub[si, di], kind="stable")           # (-0.0 and +0.0 compare equal, as in the literal sort)
+    left_s, left_d = int(sfree.sum()), int(dfree.sum())
+    for s, d in zip(ssub[si[order]].tolist(), dsub[di[order]].tolist()):
+        if s in src_assignment or d in dst_assignment:
+            continue
+        src_assignment[s] = d
+        dst_assignment[d] = s
+        left_s, left_d = left_s - 1, left_d - 1
+        if left_s == 0 or left_d == 0:                       # nothing later can match
+            break
+    return src_assignment, dst_assignment
+
+
 def hungarian_match(distance, src_tags, dst_tags, src_subset, dst_subset, distance_threshold, src_assignment=None,
                     dst_assignment=None, solver=lsap):
     """HungarianMatcher.match, statement for statement (`solver` = scipy's linear_sum_assignment where it is wanted)"""

@@ -95,3 +95,86 @@ def test_argument_validation_without_gpu():
         mt.prepare_boxes(np.zeros((0, 9), np.float32), np.zeros((2, 9), np.float32), 3)     # empty: matcher.pyx:41-43
         mt.match([], [0, 1], {0: 1.0})
         assert mt.num_of_matches() == 0 and mt.query_src_match(0) == -1 and mt.query_dst_match(1) == -1
+
+
+# --------------------------------------------------------------- tests/golden/lsap_route_cases.npz: the large launch routes
+def test_route_goldens_regenerate_and_name_their_routes():
+    g = assign_cases.route_generator()
+    assert os.path.getsize(assign_cases.ROUTE_GOLDEN) < 500 * 1024
+    z = np.load(assign_cases.ROUTE_GOLDEN)
+    meta = __import__("json").loads(bytes(z["__meta__"]).decode())
+    assert meta["scipy_version"]
+    routes = set()
+    for name, c, rows, cols, m in assign_cases.route_cases():
+        assert tuple(m["route"]) == g.route(*c.shape), name
+        k = min(c.shape)
+        assert rows.shape == (k,) and cols.shape == (k,), name
+        routes.add(tuple(m["route"]))
+    assert routes == {(256, "lds"), (256, "workspace"), (1024, "workspace")}
+    dist, stags, dtags, ssub, dsub, thr, large, rows, cols, r, k = assign_cases.route_frame()
+    assert g.route(len(rows), len(cols)) == (256, "workspace") and r.shape == (min(len(rows), len(cols)),)
+    for cls in (3, 12):     # the small classes take smaller routes on their own
+        rr, cc, _ = g.class_block(dist, stags, dtags, ssub, dsub, cls)
+        assert g.route(len(rr), len(cc)) == ((256, "lds") if cls == 3 else (64, "lds"))
+
+
+def test_route_goldens_are_scipys_results():
+    sp = pytest.importorskip("scipy.optimize")
+    for name, c, rows, cols, m in assign_cases.route_cases():
+        a, b = sp.linear_sum_assignment(c)
+        assert np.array_equal(a, rows) and np.array_equal(b, cols), name
+    dist, stags, dtags, ssub, dsub, thr, large, rr, cc, r, k = assign_cases.route_frame()
+    a, b = sp.linear_sum_assignment(dist[np.ix_(rr, cc)])
+    assert np.array_equal(a, r) and np.array_equal(b, k)
+
+
+def test_restatement_equals_the_route_goldens():
+    """every recorded case but the two uniform fp64 squares of 1500+ columns (minutes of pure Python): about 3 s"""
+    seen = 0
+    for name, c, rows, cols, m in assign_cases.route_cases():
+        if m["kind"] == "uniform" and min(c.shape) > 1:
+            continue
+        a, b = ar.lsap(c)
+        assert np.array_equal(a, rows) and np.array_equal(b, cols), name
+        seen += 1
+    assert seen == 9
+
+
+def test_near_tie_golden_changes_when_read_as_fp32():
+    """the near-tie case is only a test of the fp64 cost read if narrowing the matrix to fp32 changes scipy's answer"""
+    sp = pytest.importorskip("scipy.optimize")
+    for name, c, rows, cols, m in assign_cases.route_cases():
+        if m["kind"] == "neartie":
+            a, b = sp.linear_sum_assignment(c.astype(np.float32))
+            assert not np.array_equal(b, cols), name
+
+
+def _free_as_assigned(free, subset):
+    """a box that is not free: a key of the assignment map (what an earlier call leaves), partner -2"""
+    return {int(i): -2 for i in np.nonzero(~np.asarray(free, bool))[0]}
+
+
+def test_fast_nn_restatement_equals_the_literal_one():
+    rng = np.random.default_rng(41)
+    for t in range(40):
+        n, m = (int(x) for x in rng.integers(1, 70, 2))
+        d, stags, dtags, thr, ssub, dsub, sfree, dfree = assign_cases.nn_edge_frame(rng, n, m)
+        if t % 4 == 0:
+            sfree[:], dfree[:] = True, True
+        if t % 5 == 1:
+            ssub, dsub = ssub[: 1 + t % 3], dsub[: 2]           # tiny calls: the literal's early exit applies
+        sa0, da0 = _free_as_assigned(sfree, ssub), _free_as_assigned(dfree, dsub)
+        lit = ar.nearest_neighbor_match(d, stags, dtags, ssub, dsub, thr, dict(sa0), dict(da0))
+        fast = ar.nearest_neighbor_match_fast(d, stags, dtags, ssub, dsub, thr, dict(sa0), dict(da0))
+        assert lit == fast, t
+    # a chain of decreasing pairs (r0 c0 r1 c1 ...): the greedy takes the diagonal from the far end
+    n = 50
+    d = np.full((n, n), 1e6, np.float32)
+    for k in range(n):
+        d[k, k] = 2.0 * n - 2 * k
+        if k + 1 < n:
+            d[k + 1, k] = 2.0 * n - 2 * k - 1
+    z = np.zeros(n, np.int64)
+    lit = ar.nearest_neighbor_match(d, z, z, range(n), range(n), {0: 4.0 * n})
+    fast = ar.nearest_neighbor_match_fast(d, z, z, range(n), range(n), {0: 4.0 * n})
+    assert lit == fast and lit[0] == {k: k for k in range(n)}
