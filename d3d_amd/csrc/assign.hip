@@ -395,16 +395,11 @@ extern "C" int d3d_lsap_batched(const void *cost, int32_t dtype, int64_t ld, con
     auto go = [&](auto prec) {
         typedef typename decltype(prec)::T T;
         const T *c = (const T *)cost;
-        if (kc <= kWave)
-            D3D_LAUNCH("k_lsap", (k_lsap<T, kWave>), dim3(grid), dim3(kWave), lds, st, c, ld, row_idx, col_idx, row_off, col_off,
+        return dispatch_int<kWave, 256, 1024>(kc <= kWave ? kWave : kc <= 2048 ? 256 : 1024, [&](auto block) {
+            D3D_LAUNCH("k_lsap", (k_lsap<T, block>), dim3(grid), dim3(block), lds, st, c, ld, row_idx, col_idx, row_off, col_off,
                        max_rows, max_cols, row_match, col_match, status, (char *)workspace, workspace_bytes, (int)use_lds);
-        else if (kc <= 2048)
-            D3D_LAUNCH("k_lsap", (k_lsap<T, 256>), dim3(grid), dim3(256), lds, st, c, ld, row_idx, col_idx, row_off, col_off,
-                       max_rows, max_cols, row_match, col_match, status, (char *)workspace, workspace_bytes, (int)use_lds);
-        else
-            D3D_LAUNCH("k_lsap", (k_lsap<T, 1024>), dim3(grid), dim3(1024), lds, st, c, ld, row_idx, col_idx, row_off, col_off,
-                       max_rows, max_cols, row_match, col_match, status, (char *)workspace, workspace_bytes, (int)use_lds);
-        return D3D_OK;
+            return D3D_OK;
+        });
     };
     return dispatch_dtype<D3D_F32, D3D_F64>(dtype, go);
 }

@@ -50,6 +50,15 @@ static inline int dispatch_dtype(int dtype, F &&f)
     (void)((dtype == CODES && (rc = f(typename PrecOf<CODES>::type{}), true)) || ...);
     return rc;
 }
+// an int -> f(std::integral_constant<int, V>{}) for the values V a site lists (only those are instantiated), D3D_ERR_BAD_ARG
+// for any other
+template <int... VALUES, class F>
+static inline int dispatch_int(int v, F &&f)
+{
+    int rc = D3D_ERR_BAD_ARG;
+    (void)((v == VALUES && (rc = f(std::integral_constant<int, VALUES>{}), true)) || ...);
+    return rc;
+}
 
 // entry points one .hip file offers the others
 extern "C" size_t d3d_internal_argsort_i32_bytes(int64_t n);                                               // sort.hip

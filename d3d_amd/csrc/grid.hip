@@ -395,8 +395,8 @@ extern "C" int d3d_grid_compact_index(const int64_t *keys, int64_t m, int64_t nc
     uint32_t *prefix = w.take<uint32_t>(nw);
     unsigned long long *bsum = w.take<unsigned long long>(d3d_divup(nw, kScanTile) + 1);
     if (!workspace || !w.ok()) return D3D_ERR_WORKSPACE;
-    D3D_HIP_CHECK(hipMemsetAsync(bitmap, 0, (size_t)nw * 8, st));
-    if (m > 0) D3D_LAUNCH("k_grid_mark", k_grid_mark, dim3((unsigned)d3d_divup(m, 256)), dim3(256), 0, st, keys, m, ncells, bitmap);
+    const int rc = d3d_grid_bitmap_mark(keys, m, ncells, bitmap, stream);
+    if (rc) return rc;
     PopcountWords f{bitmap, prefix};
     return d3d_run_scan(f, nw, bsum, counts, -1, 0, ~0ull, st);
 }
@@ -513,6 +513,14 @@ extern "C" int d3d_sharded_scatter(const int64_t *keys_all, int64_t m, int64_t b
     return D3D_OK;
 }
 
+// the tail of a PACKED finalize (either kind): the parked {cell key, count} slots -> coordinates and counts, in place
+static int sharded_unpack(int64_t nvox, const int32_t *shape, int64_t *coords, int32_t *cnt_out, hipStream_t st)
+{
+    D3D_LAUNCH("k_sharded_unpack", k_sharded_unpack, dim3((unsigned)d3d_divup(nvox, 256)), dim3(256), 0, st, nvox, (int64_t)shape[1],
+               (int64_t)shape[2], coords, cnt_out);
+    return D3D_OK;
+}
+
 extern "C" int d3d_sharded_finalize(int64_t nvox, int32_t c, const int64_t *first, int64_t n_total, int64_t *counts,
                                     void *compact_ws, size_t compact_ws_bytes, const int64_t *key_of_slot,
                                     const float *table, int32_t table_stride, int32_t mean, const int32_t *cnt_in,
@@ -531,19 +539,13 @@ extern "C" int d3d_sharded_finalize(int64_t nvox, int32_t c, const int64_t *firs
     unsigned long long *bitmap = w.take<unsigned long long>(nw);
     uint32_t *prefix = w.take<uint32_t>(nw);
     const bool al16 = ((reinterpret_cast<uintptr_t>(feats) | reinterpret_cast<uintptr_t>(coords)) & 15) == 0;
-    if (c == 4 && al16) {
-        D3D_LAUNCH("k_sharded_finalize", k_sharded_finalize<true>, dim3((unsigned)d3d_divup(nvox, 256)), dim3(256), 0, st, nvox, c, first,
-                   n_total > 0 ? n_total : (int64_t)1, bitmap, prefix, key_of_slot, table, table_stride, mean, cnt_in,
-                   (int64_t)shape[1], (int64_t)shape[2], vid_of_slot, coords, cnt_out, feats, true);
-        D3D_LAUNCH("k_sharded_unpack", k_sharded_unpack, dim3((unsigned)d3d_divup(nvox, 256)), dim3(256), 0, st, nvox,
-                   (int64_t)shape[1], (int64_t)shape[2], coords, cnt_out);
-        return D3D_OK;
-    }
-    D3D_LAUNCH("k_sharded_finalize", k_sharded_finalize<false>, dim3((unsigned)d3d_divup(nvox, 256)), dim3(256), 0, st, nvox, c, first,
-               n_total > 0 ? n_total : (int64_t)1, bitmap, prefix, key_of_slot, table, table_stride, mean, cnt_in,
-               (int64_t)shape[1], (int64_t)shape[2], vid_of_slot, coords, cnt_out, feats,
-               (reinterpret_cast<uintptr_t>(feats) & 15) == 0);
-    return D3D_OK;
+    return dispatch(c == 4 && al16, [&](auto packed) -> int {
+        D3D_LAUNCH("k_sharded_finalize", k_sharded_finalize<packed>, dim3((unsigned)d3d_divup(nvox, 256)), dim3(256), 0, st, nvox, c,
+                   first, n_total > 0 ? n_total : (int64_t)1, bitmap, prefix, key_of_slot, table, table_stride, mean, cnt_in,
+                   (int64_t)shape[1], (int64_t)shape[2], vid_of_slot, coords, cnt_out, feats,
+                   (reinterpret_cast<uintptr_t>(feats) & 15) == 0);
+        return packed ? sharded_unpack(nvox, shape, coords, cnt_out, st) : D3D_OK;
+    });
 }
 
 extern "C" int d3d_sharded_scatter_owned(const int64_t *keys_local, int64_t n_local, int64_t ncells, const void *compact_ws,
@@ -592,18 +594,12 @@ extern "C" int d3d_sharded_finalize_owned(int64_t nvox, int32_t c, const int64_t
     if (nvox == 0) return D3D_OK;
     if (!key_of_slot || !table || !vid_of_slot || !coords || !cnt_out || !feats || (!mean && !cnt_in)) return D3D_ERR_BAD_ARG;
     const bool al16 = ((reinterpret_cast<uintptr_t>(feats) | reinterpret_cast<uintptr_t>(coords)) & 15) == 0;
-    if (c == 4 && al16) {
-        D3D_LAUNCH("k_sharded_finalize_owned", k_sharded_finalize_owned<true>, dim3((unsigned)d3d_divup(nvox, 256)), dim3(256), 0, st,
-                   nvox, c, key_of_slot, table, table_stride, mean, cnt_in, (int64_t)shape[1], (int64_t)shape[2], vid_of_slot,
-                   coords, cnt_out, feats, true);
-        D3D_LAUNCH("k_sharded_unpack", k_sharded_unpack, dim3((unsigned)d3d_divup(nvox, 256)), dim3(256), 0, st, nvox,
-                   (int64_t)shape[1], (int64_t)shape[2], coords, cnt_out);
-        return D3D_OK;
-    }
-    D3D_LAUNCH("k_sharded_finalize_owned", k_sharded_finalize_owned<false>, dim3((unsigned)d3d_divup(nvox, 256)), dim3(256), 0, st,
-               nvox, c, key_of_slot, table, table_stride, mean, cnt_in, (int64_t)shape[1], (int64_t)shape[2], vid_of_slot, coords,
-               cnt_out, feats, al16);
-    return D3D_OK;
+    return dispatch(c == 4 && al16, [&](auto packed) -> int {
+        D3D_LAUNCH("k_sharded_finalize_owned", k_sharded_finalize_owned<packed>, dim3((unsigned)d3d_divup(nvox, 256)), dim3(256), 0, st,
+                   nvox, c, key_of_slot, table, table_stride, mean, cnt_in, (int64_t)shape[1], (int64_t)shape[2], vid_of_slot, coords,
+                   cnt_out, feats, al16);
+        return packed ? sharded_unpack(nvox, shape, coords, cnt_out, st) : D3D_OK;
+    });
 }
 
 extern "C" int d3d_sharded_map(int64_t n, const int64_t *local_map, const int64_t *slot_of_local, int64_t nvox,

@@ -322,6 +322,39 @@ __global__ __launch_bounds__(kStableThreads) void k_match_stable(const int64_t *
 
 }  // namespace
 
+// the work of d3d_score_match (batches = 1, no row_off / row_src / mask / row_mask) and d3d_score_match_batched, after their
+// argument checks.  For one batch the carve takes d3d_score_match_workspace_bytes(n, m) less 512 bytes.
+static int score_match_run(const float *dist, const int64_t *row_src, const uint8_t *mask, const int64_t *row_mask, const int64_t *row_off,
+                           int64_t batches, int64_t n_total, int64_t m, const int32_t *src_tag, const int32_t *dst_tag,
+                           const float *dst_threshold, const int64_t *order, int32_t *src_match, int32_t *dst_match, int32_t *status,
+                           void *workspace, size_t workspace_bytes, hipStream_t st)
+{
+    const size_t words = ((size_t)m + 31) / 32;
+    WsCarver w(workspace, workspace_bytes);
+    int32_t *cand_dst = w.take<int32_t>((size_t)n_total * kMaxCand);
+    float *cand_dist = w.take<float>((size_t)n_total * kMaxCand);
+    int32_t *cand_cnt = w.take<int32_t>((size_t)n_total);
+    unsigned int *taken = w.take<unsigned int>((size_t)batches * words);
+    int32_t *rank = w.take<int32_t>((size_t)n_total), *ptr = w.take<int32_t>((size_t)n_total), *q0 = w.take<int32_t>((size_t)n_total),
+            *q1 = w.take<int32_t>((size_t)n_total);
+    int32_t *hold = w.take<int32_t>((size_t)batches * (size_t)m), *need_walk = w.take<int32_t>((size_t)batches);
+    if (!workspace || !w.ok()) return D3D_ERR_WORKSPACE;
+    D3D_HIP_CHECK(hipMemsetAsync(taken, 0, (size_t)batches * words * 4, st));
+    D3D_LAUNCH("k_match_candidates", k_match_candidates, dim3((unsigned)d3d_divup(n_total, 256 / kWave)), dim3(256), 0, st, dist, n_total, m,
+               src_tag, dst_tag, dst_threshold, cand_dst, cand_dist, cand_cnt, status, row_src, mask, row_mask);
+    const int64_t n = row_off ? 0 : n_total;          // the kernels take a problem's rows from row_off when it is given
+    D3D_LAUNCH("k_match_stable", k_match_stable, dim3((unsigned)batches), dim3(kStableThreads), 0, st, order, n, m, (const int32_t *)cand_dst,
+               (const int32_t *)cand_cnt, src_match, dst_match, rank, ptr, hold, q0, q1, need_walk, row_off);
+    const size_t map_bytes = words * 4;
+    // (+ 16 KB of staging: inside the 64 KB a workgroup gets without opting in)
+    return dispatch(map_bytes <= 32 * 1024, [&](auto lds_map) {
+        D3D_LAUNCH("k_match_greedy", k_match_greedy<lds_map>, dim3((unsigned)batches), dim3(64), lds_map ? map_bytes : 0, st, order, n, m,
+                   (const int32_t *)cand_dst, (const int32_t *)cand_cnt, src_match, dst_match, taken, dist, src_tag, dst_tag, dst_threshold,
+                   (const int32_t *)need_walk, row_off, row_src, mask, row_mask);
+        return D3D_OK;
+    });
+}
+
 // B problems at once (the evaluator's score thresholds on a frame: 40 small associations, each a chain of short launches when
 // issued one by one): the rows of all problems stacked in dist[N, m] (problem b = rows [row_off[b], row_off[b + 1])), the
 // destinations -- dst_tag, dst_threshold, m -- common to all; order / src_match in the same stacked layout with indices LOCAL
@@ -355,31 +388,8 @@ extern "C" int d3d_score_match_batched(const float *dist, const int64_t *row_src
     if (!src_match || !src_tag || !order) return D3D_ERR_BAD_ARG;
     if (m == 0) { D3D_HIP_CHECK(hipMemsetAsync(src_match, 0xff, (size_t)n_total * 4, st)); return D3D_OK; }
     if (!dist || !dst_tag || !dst_threshold || m >= (1ll << 31) || n_total >= (1ll << 31) || batches > 65535) return D3D_ERR_BAD_ARG;
-    const size_t words = ((size_t)m + 31) / 32;
-    WsCarver w(workspace, workspace_bytes);
-    int32_t *cand_dst = w.take<int32_t>((size_t)n_total * kMaxCand);
-    float *cand_dist = w.take<float>((size_t)n_total * kMaxCand);
-    int32_t *cand_cnt = w.take<int32_t>((size_t)n_total);
-    unsigned int *taken = w.take<unsigned int>((size_t)batches * words);
-    int32_t *rank = w.take<int32_t>((size_t)n_total), *ptr = w.take<int32_t>((size_t)n_total), *q0 = w.take<int32_t>((size_t)n_total),
-            *q1 = w.take<int32_t>((size_t)n_total);
-    int32_t *hold = w.take<int32_t>((size_t)batches * (size_t)m), *need_walk = w.take<int32_t>((size_t)batches);
-    if (!workspace || !w.ok()) return D3D_ERR_WORKSPACE;
-    D3D_HIP_CHECK(hipMemsetAsync(taken, 0, (size_t)batches * words * 4, st));
-    D3D_LAUNCH("k_match_candidates", k_match_candidates, dim3((unsigned)d3d_divup(n_total, 256 / kWave)), dim3(256), 0, st, dist, n_total, m,
-               src_tag, dst_tag, dst_threshold, cand_dst, cand_dist, cand_cnt, status, row_src, mask, row_mask);
-    D3D_LAUNCH("k_match_stable", k_match_stable, dim3((unsigned)batches), dim3(kStableThreads), 0, st, order, (int64_t)0, m,
-               (const int32_t *)cand_dst, (const int32_t *)cand_cnt, src_match, dst_match, rank, ptr, hold, q0, q1, need_walk, row_off);
-    const size_t map_bytes = words * 4;
-    if (map_bytes <= 32 * 1024)
-        D3D_LAUNCH("k_match_greedy", k_match_greedy<true>, dim3((unsigned)batches), dim3(64), map_bytes, st, order, (int64_t)0, m,
-                   (const int32_t *)cand_dst, (const int32_t *)cand_cnt, src_match, dst_match, taken, dist, src_tag, dst_tag, dst_threshold,
-                   (const int32_t *)need_walk, row_off, row_src, mask, row_mask);
-    else
-        D3D_LAUNCH("k_match_greedy", k_match_greedy<false>, dim3((unsigned)batches), dim3(64), 0, st, order, (int64_t)0, m,
-                   (const int32_t *)cand_dst, (const int32_t *)cand_cnt, src_match, dst_match, taken, dist, src_tag, dst_tag, dst_threshold,
-                   (const int32_t *)need_walk, row_off, row_src, mask, row_mask);
-    return D3D_OK;
+    return score_match_run(dist, row_src, mask, row_mask, row_off, batches, n_total, m, src_tag, dst_tag, dst_threshold, order, src_match,
+                           dst_match, status, workspace, workspace_bytes, st);
 }
 
 extern "C" size_t d3d_score_match_workspace_bytes(int64_t n, int64_t m)
@@ -404,25 +414,6 @@ extern "C" int d3d_score_match(const float *dist, int64_t n, int64_t m, const in
     if (!src_match || !src_tag || !order) return D3D_ERR_BAD_ARG;
     if (m == 0) { D3D_HIP_CHECK(hipMemsetAsync(src_match, 0xff, (size_t)n * 4, st)); return D3D_OK; }
     if (!dist || !dst_tag || !dst_threshold || m >= (1ll << 31) || n >= (1ll << 31)) return D3D_ERR_BAD_ARG;
-    WsCarver w(workspace, workspace_bytes);
-    int32_t *cand_dst = w.take<int32_t>((size_t)n * kMaxCand);
-    float *cand_dist = w.take<float>((size_t)n * kMaxCand);
-    int32_t *cand_cnt = w.take<int32_t>((size_t)n);
-    unsigned int *taken = w.take<unsigned int>(((size_t)m + 31) / 32);
-    int32_t *rank = w.take<int32_t>((size_t)n), *ptr = w.take<int32_t>((size_t)n), *q0 = w.take<int32_t>((size_t)n), *q1 = w.take<int32_t>((size_t)n);
-    int32_t *hold = w.take<int32_t>((size_t)m), *need_walk = w.take<int32_t>(1);
-    if (!workspace || !w.ok()) return D3D_ERR_WORKSPACE;
-    D3D_HIP_CHECK(hipMemsetAsync(taken, 0, ((size_t)m + 31) / 32 * 4, st));
-    D3D_LAUNCH("k_match_candidates", k_match_candidates, dim3((unsigned)d3d_divup(n, 256 / kWave)), dim3(256), 0, st, dist, n, m,
-               src_tag, dst_tag, dst_threshold, cand_dst, cand_dist, cand_cnt, status);
-    D3D_LAUNCH("k_match_stable", k_match_stable, dim3(1), dim3(kStableThreads), 0, st, order, n, m, (const int32_t *)cand_dst,
-               (const int32_t *)cand_cnt, src_match, dst_match, rank, ptr, hold, q0, q1, need_walk);
-    const size_t map_bytes = ((size_t)m + 31) / 32 * 4;
-    if (map_bytes <= 32 * 1024)          // (+ 16 KB of staging: inside the 64 KB a workgroup gets without opting in)
-        D3D_LAUNCH("k_match_greedy", k_match_greedy<true>, dim3(1), dim3(64), map_bytes, st, order, n, m, (const int32_t *)cand_dst,
-                   (const int32_t *)cand_cnt, src_match, dst_match, taken, dist, src_tag, dst_tag, dst_threshold, (const int32_t *)need_walk);
-    else
-        D3D_LAUNCH("k_match_greedy", k_match_greedy<false>, dim3(1), dim3(64), 0, st, order, n, m, (const int32_t *)cand_dst,
-                   (const int32_t *)cand_cnt, src_match, dst_match, taken, dist, src_tag, dst_tag, dst_threshold, (const int32_t *)need_walk);
-    return D3D_OK;
+    return score_match_run(dist, nullptr, nullptr, nullptr, nullptr, 1, n, m, src_tag, dst_tag, dst_threshold, order, src_match, dst_match,
+                           status, workspace, workspace_bytes, st);
 }

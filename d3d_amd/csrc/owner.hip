@@ -1408,8 +1408,11 @@ extern "C" int d3d_owner_pack(const int64_t *keys, const int32_t *cnt, const flo
     PackDense pd{(uint32_t)max_points, seg_base, reinterpret_cast<const float4 *>(rows_local), reinterpret_cast<const float4 *>(points),
                  index_offset, reinterpret_cast<float4 *>(send_rows), tilerows, dest_rowbase};
     if (n > 0) {
-        if (dense) D3D_LAUNCH("k_owner_count", k_owner_count<true>, dim3(ntiles), dim3(1024), 0, st, keys, cnt, counts, (uint32_t)world, tilecnt, pd);
-        else D3D_LAUNCH("k_owner_count", k_owner_count<false>, dim3(ntiles), dim3(1024), 0, st, keys, cnt, counts, (uint32_t)world, tilecnt, pd);
+        const int rc = dispatch(dense, [&](auto DENSE) {
+            D3D_LAUNCH("k_owner_count", k_owner_count<DENSE>, dim3(ntiles), dim3(1024), 0, st, keys, cnt, counts, (uint32_t)world, tilecnt, pd);
+            return D3D_OK;
+        });
+        if (rc) return rc;
     } else {
         D3D_HIP_CHECK(hipMemsetAsync(tilecnt, 0, (size_t)ntiles * world * 4, st));
         D3D_HIP_CHECK(hipMemsetAsync(tilerows, 0, (size_t)ntiles * world * 4, st));
@@ -1420,15 +1423,12 @@ extern "C" int d3d_owner_pack(const int64_t *keys, const int32_t *cnt, const flo
     if (!fused)
         D3D_LAUNCH("k_owner_offsets", k_owner_offsets, dim3(1), dim3(1024), 0, st, tilecnt, dense ? tilerows : (uint32_t *)nullptr, ntiles,
                    (uint32_t)world, send_counts, dest_base, dest_rowbase, status_key);
-    if (n > 0) {
-        if (dense)
-            D3D_LAUNCH("k_owner_scatter", k_owner_scatter<true>, dim3(ntiles), dim3(1024), 0, st, keys, cnt, agg, first, counts, (int)c,
-                       (uint32_t)world, tilecnt, dest_base, send, perm, pos_of_local, pd, fused ? ntiles : 0u, send_counts, status_key);
-        else
-            D3D_LAUNCH("k_owner_scatter", k_owner_scatter<false>, dim3(ntiles), dim3(1024), 0, st, keys, cnt, agg, first, counts, (int)c,
-                       (uint32_t)world, tilecnt, dest_base, send, perm, pos_of_local, pd, fused ? ntiles : 0u, send_counts, status_key);
-    }
-    return D3D_OK;
+    if (n == 0) return D3D_OK;
+    return dispatch(dense, [&](auto DENSE) {
+        D3D_LAUNCH("k_owner_scatter", k_owner_scatter<DENSE>, dim3(ntiles), dim3(1024), 0, st, keys, cnt, agg, first, counts, (int)c,
+                   (uint32_t)world, tilecnt, dest_base, send, perm, pos_of_local, pd, fused ? ntiles : 0u, send_counts, status_key);
+        return D3D_OK;
+    });
 }
 
 static bool merge_on_chains(int64_t R, uint32_t flags) { return (flags & D3D_OWNER_MERGE_CHAINS) || R > kRecMaxRecords; }
@@ -1560,35 +1560,27 @@ extern "C" int d3d_owner_dense(const int32_t *recv, int64_t R, const float *recv
     if (!merge_workspace || merge_workspace_bytes < d3d_owner_merge_workspace_bytes(R, world)) return D3D_ERR_WORKSPACE;
     const uint32_t P = (uint32_t)max_points;
     const int pshift = (P & (P - 1)) == 0 ? __builtin_ctz(P) : -1;
-    if (!merge_on_chains(R, flags)) {
+    // the record lists of the bucketed merge, else the chains of the hash merge
+    const bool buckets = !merge_on_chains(R, flags);
+    const uint32_t *rec_slot = nullptr, *next = nullptr, *rinfo = nullptr, *cellrecs = nullptr;
+    const MergeSlot *slot = nullptr;
+    const int64_t *src_off;
+    if (buckets) {
         RecWs m = carve_rec(const_cast<void *>(merge_workspace), merge_workspace_bytes, R, world);
-        if (row_state)
-            D3D_LAUNCH("k_owner_dense_resident", (k_owner_dense<true, true>), dim3(blocks_for(cap_o, 256)), dim3(256), 0, st, counts_o, lead_rec,
-                       npoints, (const uint32_t *)nullptr, (const MergeSlot *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)m.rinfo,
-                       (const uint32_t *)m.cellrecs, (const int64_t *)m.src_off, (int)world, recv, rec_stride(4),
-                       reinterpret_cast<const float4 *>(recv_rows), rows_src_off, P, pshift, reinterpret_cast<float4 *>(voxels), pmask,
-                       row_state);
-        else
-            D3D_LAUNCH("k_owner_dense", k_owner_dense<true>, dim3(blocks_for(cap_o, 256)), dim3(256), 0, st, counts_o, lead_rec, npoints,
-                       (const uint32_t *)nullptr, (const MergeSlot *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)m.rinfo,
-                       (const uint32_t *)m.cellrecs, (const int64_t *)m.src_off, (int)world, recv, rec_stride(4),
-                       reinterpret_cast<const float4 *>(recv_rows), rows_src_off, P, pshift, reinterpret_cast<float4 *>(voxels), pmask,
-                       (uint16_t *)nullptr);
-        return D3D_OK;
+        rinfo = m.rinfo; cellrecs = m.cellrecs; src_off = m.src_off;
+    } else {
+        MergeWs m = carve_merge(const_cast<void *>(merge_workspace), merge_workspace_bytes, R, world);
+        rec_slot = m.rec_slot; slot = m.slot; next = m.next; src_off = m.src_off;
     }
-    MergeWs m = carve_merge(const_cast<void *>(merge_workspace), merge_workspace_bytes, R, world);
-    if (row_state)
-        D3D_LAUNCH("k_owner_dense_resident", (k_owner_dense<false, true>), dim3(blocks_for(cap_o, 256)), dim3(256), 0, st, counts_o, lead_rec,
-                   npoints, (const uint32_t *)m.rec_slot, (const MergeSlot *)m.slot, (const uint32_t *)m.next, (const uint32_t *)nullptr,
-                   (const uint32_t *)nullptr, (const int64_t *)m.src_off, (int)world, recv, rec_stride(4),
-                   reinterpret_cast<const float4 *>(recv_rows), rows_src_off, P, pshift, reinterpret_cast<float4 *>(voxels), pmask, row_state);
-    else
-        D3D_LAUNCH("k_owner_dense", k_owner_dense<false>, dim3(blocks_for(cap_o, 256)), dim3(256), 0, st, counts_o, lead_rec, npoints,
-                   (const uint32_t *)m.rec_slot, (const MergeSlot *)m.slot, (const uint32_t *)m.next, (const uint32_t *)nullptr,
-                   (const uint32_t *)nullptr, (const int64_t *)m.src_off, (int)world, recv, rec_stride(4),
-                   reinterpret_cast<const float4 *>(recv_rows), rows_src_off, P, pshift, reinterpret_cast<float4 *>(voxels), pmask,
-                   (uint16_t *)nullptr);
-    return D3D_OK;
+    return dispatch(buckets, [&](auto BUCKETS) {
+        return dispatch(row_state != nullptr, [&](auto RESIDENT) {
+            D3D_LAUNCH(RESIDENT ? "k_owner_dense_resident" : "k_owner_dense", (k_owner_dense<BUCKETS, RESIDENT>), dim3(blocks_for(cap_o, 256)),
+                       dim3(256), 0, st, counts_o, lead_rec, npoints, rec_slot, slot, next, rinfo, cellrecs, src_off, (int)world, recv,
+                       rec_stride(4), reinterpret_cast<const float4 *>(recv_rows), rows_src_off, P, pshift, reinterpret_cast<float4 *>(voxels),
+                       pmask, row_state);
+            return D3D_OK;
+        });
+    });
 }
 
 // reply[i] = global voxel id of received record i (sent back to the record's source rank)
@@ -1625,12 +1617,11 @@ extern "C" int d3d_owner_replicate(int64_t V, const int64_t *vids, const int64_t
         int64_t *bounds = static_cast<int64_t *>(workspace);
         D3D_LAUNCH("k_owner_replicate_bounds", k_owner_replicate_bounds, dim3(blocks_for((ntiles + 1) * world)), dim3(256), 0, st, V, vids,
                    src_off, (int)world, ntiles, bounds);
-        if (c <= 4)
-            D3D_LAUNCH("k_owner_replicate_merge", k_owner_replicate_merge<4>, dim3((unsigned)ntiles), dim3(256), 0, st, V, vids, coords_in,
+        return dispatch_int<4, kRepMaxC>(c <= 4 ? 4 : kRepMaxC, [&](auto MAXC) {
+            D3D_LAUNCH("k_owner_replicate_merge", k_owner_replicate_merge<MAXC>, dim3((unsigned)ntiles), dim3(256), 0, st, V, vids, coords_in,
                        cnt_in, feats_in, (int)c, coords, cnt, feats, (const int64_t *)bounds, (int)world);
-        else
-            D3D_LAUNCH("k_owner_replicate_merge", k_owner_replicate_merge<kRepMaxC>, dim3((unsigned)ntiles), dim3(256), 0, st, V, vids,
-                       coords_in, cnt_in, feats_in, (int)c, coords, cnt, feats, (const int64_t *)bounds, (int)world);
+            return D3D_OK;
+        });
     } else
         D3D_LAUNCH("k_owner_replicate", k_owner_replicate, dim3(blocks_for(V)), dim3(256), 0, st, V, vids, coords_in, cnt_in, feats_in,
                    (int)c, coords, cnt, feats);

@@ -118,27 +118,19 @@ int scatter_dispatch(bool backward, const T *coord, long long n, const T *a, Map
     const bool cl = ws && batch > 0 && md.C >= 8 && ws_bytes >= map_bytes && md.vol < (1ll << 31) && batch < 65536;
     const dim3 tgrid((unsigned)d3d_divup(md.vol, 32), (unsigned)d3d_divup(md.C, 32), (unsigned)(cl ? batch : 1));
     T *stage = reinterpret_cast<T *>(ws);
-    if (!backward) {
-        if (cl) {
-            D3D_LAUNCH("k_channels_last", (k_channels_last<T, false>), tgrid, dim3(256), 0, st, a, stage, md.C, md.vol);
-            if (lin) D3D_LAUNCH("k_scatter_fwd", (k_scatter_fwd<T, true, true>), grid, dim3(256), 0, st, coord, n, (const T *)stage, md, b);
-            else D3D_LAUNCH("k_scatter_fwd", (k_scatter_fwd<T, false, true>), grid, dim3(256), 0, st, coord, n, (const T *)stage, md, b);
-        } else {
-            if (lin) D3D_LAUNCH("k_scatter_fwd", (k_scatter_fwd<T, true, false>), grid, dim3(256), 0, st, coord, n, a, md, b);
-            else D3D_LAUNCH("k_scatter_fwd", (k_scatter_fwd<T, false, false>), grid, dim3(256), 0, st, coord, n, a, md, b);
-        }
-    } else {
-        if (cl) {
-            D3D_HIP_CHECK(hipMemsetAsync(stage, 0, map_bytes, st));
-            if (lin) D3D_LAUNCH("k_scatter_bwd", (k_scatter_bwd<T, true, true>), grid, dim3(256), 0, st, coord, n, a, md, stage);
-            else D3D_LAUNCH("k_scatter_bwd", (k_scatter_bwd<T, false, true>), grid, dim3(256), 0, st, coord, n, a, md, stage);
-            D3D_LAUNCH("k_channels_last", (k_channels_last<T, true>), tgrid, dim3(256), 0, st, (const T *)stage, b, md.C, md.vol);
-        } else {
-            if (lin) D3D_LAUNCH("k_scatter_bwd", (k_scatter_bwd<T, true, false>), grid, dim3(256), 0, st, coord, n, a, md, b);
-            else D3D_LAUNCH("k_scatter_bwd", (k_scatter_bwd<T, false, false>), grid, dim3(256), 0, st, coord, n, a, md, b);
-        }
-    }
-    return D3D_OK;
+    return dispatch(lin, [&](auto LIN) {
+        return dispatch(cl, [&](auto CL) {
+            if (!backward) {
+                if (CL) D3D_LAUNCH("k_channels_last", (k_channels_last<T, false>), tgrid, dim3(256), 0, st, a, stage, md.C, md.vol);
+                D3D_LAUNCH("k_scatter_fwd", (k_scatter_fwd<T, LIN, CL>), grid, dim3(256), 0, st, coord, n, CL ? (const T *)stage : a, md, b);
+            } else {
+                if (CL) D3D_HIP_CHECK(hipMemsetAsync(stage, 0, map_bytes, st));
+                D3D_LAUNCH("k_scatter_bwd", (k_scatter_bwd<T, LIN, CL>), grid, dim3(256), 0, st, coord, n, a, md, CL ? stage : b);
+                if (CL) D3D_LAUNCH("k_channels_last", (k_channels_last<T, true>), tgrid, dim3(256), 0, st, (const T *)stage, b, md.C, md.vol);
+            }
+            return D3D_OK;
+        });
+    });
 }
 
 int scatter_common(bool backward, const void *coord, int64_t n, int32_t dim, const void *a, int64_t C, const int64_t *dims,

@@ -4177,21 +4177,19 @@ static int build_index(const Key &kf, const Tab &tab, const float *points, int64
                w.big_count, box, warm ? reinterpret_cast<const float4 *>(points) : nullptr, warm ? n * c / 4 : (int64_t)0);
     if (n > 0) {
         const bool vec4 = (c == 4) && ((reinterpret_cast<uintptr_t>(points) & 15) == 0);
-        if constexpr (Key::kBox) {
-            const unsigned nb = (unsigned)std::min<int64_t>(d3d_divup(n, 256 * 4), 512);
-            int *partial = reinterpret_cast<int *>(w.big_list);          // nb x 6 ints (the sparse contract has no work list)
-            unsigned int *ticket = w.big_count + 32;                      // zeroed by k_init
-            if (vec4) D3D_LAUNCH("k_bbox", k_bbox<true>, dim3(nb), dim3(256), 0, st, kf, points, n, c, counts, partial, ticket);
-            else D3D_LAUNCH("k_bbox", k_bbox<false>, dim3(nb), dim3(256), 0, st, kf, points, n, c, counts, partial, ticket);
-        }
-        dim3 grid((unsigned)d3d_divup(n, 256));
-        uint32_t *parr = o.max_points ? w.parr : nullptr;
-        if (vec4)
-            D3D_LAUNCH("k_insert", (k_insert<Key, Tab, true>), grid, dim3(256), 0, st, kf, tab, points, n, c, w.cap - 1,
-                       w.pslot, parr, counts);
-        else
-            D3D_LAUNCH("k_insert", (k_insert<Key, Tab, false>), grid, dim3(256), 0, st, kf, tab, points, n, c, w.cap - 1,
-                       w.pslot, parr, counts);
+        const int rc = dispatch(vec4, [&](auto v4) {
+            if constexpr (Key::kBox) {
+                const unsigned nb = (unsigned)std::min<int64_t>(d3d_divup(n, 256 * 4), 512);
+                int *partial = reinterpret_cast<int *>(w.big_list);          // nb x 6 ints (the sparse contract has no work list)
+                unsigned int *ticket = w.big_count + 32;                      // zeroed by k_init
+                D3D_LAUNCH("k_bbox", k_bbox<v4>, dim3(nb), dim3(256), 0, st, kf, points, n, c, counts, partial, ticket);
+            }
+            dim3 grid((unsigned)d3d_divup(n, 256));
+            uint32_t *parr = o.max_points ? w.parr : nullptr;
+            D3D_LAUNCH("k_insert", (k_insert<Key, Tab, v4>), grid, dim3(256), 0, st, kf, tab, points, n, c, w.cap - 1, w.pslot, parr, counts);
+            return D3D_OK;
+        });
+        if (rc) return rc;
     }
     const unsigned nbA = (unsigned)(cap / kSweepTile), nbF = (unsigned)(w.npad / kFlagTile);
     D3D_LAUNCH("k_sweep1", k_sweep1<Tab>, dim3(nbA), dim3(256), 0, st, tab, cap, w.flags, w.bsumA);
@@ -4453,31 +4451,32 @@ static int binned_index(const Key &kf, const float *points, int64_t n, int c, co
         D3D_LAUNCH("k_bin_scatter", k_bin_scatter<ROWS>, dim3(ntiles), dim3(kBinThreads), bin_lds, st, pkey, n, nbins, pbin, tilecnt, totals,
                    bucket_base, bent, counts, o.map_later, passes);
     }
-    if (!do_index) { }
-    else if (!ROWS && o.lists)
-        D3D_LAUNCH("k_bucket_index", (k_bucket_index<Key, false, true>), dim3(nbins), dim3(kBucketThreads), 0, st, kf, o.pass,
-                   reinterpret_cast<const typename BinEntry<false>::type *>(bent), p4, bucket_base, hshift, o.P, (int)D3D_REDUCE_NONE,
-                   w.staged, vrec, firstmap, counts, precpos, w.parr, reinterpret_cast<uint32_t *>(w.vinfo), o.trimmed, w.big_list,
-                   o.reduction != D3D_REDUCE_NONE ? w.unsorted : (uint32_t *)nullptr, table, stiles, tshift, tileinfo, gpos, o.map_later ? pbin : (uint32_t *)nullptr,
-                   early_tot, x.npoints_clamp, early_pairs ? early_pairs - 1u : 0u);
-    else if (fm_packed) {
-        if constexpr (ROWS)
-            D3D_LAUNCH("k_bucket_index", (k_bucket_index<Key, true, true, false, true>), dim3(nbins), dim3(kBucketThreads), 0, st, kf, o.pass,
-                       bent, p4, bucket_base, hshift, o.P, o.agg4 ? o.reduction : (int)D3D_REDUCE_NONE, w.staged, vrec, firstmap,
-                       counts, (uint32_t *)nullptr, w.parr, reinterpret_cast<uint32_t *>(w.vinfo), (unsigned char *)nullptr, w.big_list,
-                       (uint32_t *)nullptr, table, stiles, tshift, tileinfo, gpos, (uint32_t *)nullptr, (u64 *)nullptr, 0u, 0u,
-                       bits_for((u64)(n > 1 ? n - 1 : 1)));
-    } else if (ROWS && (o.emit_voxels || o.emit_reduce))
-        D3D_LAUNCH("k_bucket_index", (k_bucket_index<Key, ROWS, true, false>), dim3(nbins), dim3(kBucketThreads), 0, st, kf, o.pass,
-                   bent, p4, bucket_base, hshift, o.P, o.agg4 ? o.reduction : (int)D3D_REDUCE_NONE, w.staged, vrec, firstmap,
-                   counts, precpos, w.parr, reinterpret_cast<uint32_t *>(w.vinfo), o.trimmed, w.big_list /* the per-point keys are
-                   done with it; w.unsorted may be precpos */, (uint32_t *)nullptr, table, stiles, tshift, tileinfo, gpos, o.map_later ? pbin : (uint32_t *)nullptr,
-                   early_tot, x.npoints_clamp, early_pairs ? early_pairs - 1u : 0u);
-    else
-        D3D_LAUNCH("k_bucket_index", (k_bucket_index<Key, ROWS, false>), dim3(nbins), dim3(kBucketThreads), 0, st, kf, o.pass,
-                   bent, p4, bucket_base, hshift, o.P, o.agg4 ? o.reduction : (int)D3D_REDUCE_NONE, w.staged, vrec, firstmap, counts,
-                   precpos, w.parr, reinterpret_cast<uint32_t *>(w.vinfo), o.trimmed, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                   table, stiles, tshift, tileinfo, gpos, o.map_later ? pbin : (uint32_t *)nullptr, early_tot, x.npoints_clamp, early_pairs ? early_pairs - 1u : 0u);
+    if (do_index) {
+        // k_bucket_index<Key, ROWS', LISTS, STAGE, V2> by route: the sparse contract's index lists <false, true, false, false>, the
+        // packed first-point entries <true, true, false, true> (fm_packed: no precpos, trimmed, pfirst or early totals), rows with
+        // lists <ROWS, true, false, false>, plain rows <ROWS, false, ROWS, false>
+        enum { kLists, kPacked, kRowLists, kPlain };
+        const int route = !ROWS && o.lists ? kLists : fm_packed ? kPacked : ROWS && (o.emit_voxels || o.emit_reduce) ? kRowLists : kPlain;
+        const int reduction = route != kLists && o.agg4 ? o.reduction : (int)D3D_REDUCE_NONE;
+        // (the per-point keys are done with w.big_list; w.unsorted may be precpos)
+        uint32_t *sorted_out = route != kPlain ? w.big_list : nullptr;
+        uint32_t *unsorted_out = route == kLists && o.reduction != D3D_REDUCE_NONE ? w.unsorted : nullptr;
+        const uint32_t early_clamp = route == kPacked ? 0u : x.npoints_clamp;
+        const int idx_bits = route == kPacked ? bits_for((u64)(n > 1 ? n - 1 : 1)) : 24;      // (24: the kernel's default)
+        auto bucket_index = [&](auto r) {
+            constexpr bool rows = r == kPacked || (r != kLists && ROWS);
+            D3D_LAUNCH("k_bucket_index", (k_bucket_index<Key, rows, r != kPlain, r == kPlain && ROWS, r == kPacked>), dim3(nbins),
+                       dim3(kBucketThreads), 0, st, kf, o.pass, reinterpret_cast<const typename BinEntry<rows>::type *>(bent), p4,
+                       bucket_base, hshift, o.P, reduction, w.staged, vrec, firstmap, counts, precpos, w.parr,
+                       reinterpret_cast<uint32_t *>(w.vinfo), o.trimmed, sorted_out, unsorted_out, table, stiles, tshift, tileinfo, gpos,
+                       o.map_later ? pbin : (uint32_t *)nullptr, early_tot, early_clamp, early_pairs ? early_pairs - 1u : 0u, idx_bits);
+            return D3D_OK;
+        };
+        int rc;
+        if constexpr (ROWS) rc = dispatch_int<kLists, kPacked, kRowLists, kPlain>(route, bucket_index);
+        else rc = dispatch_int<kLists, kPlain>(route, bucket_index);          // (the other two need ROWS)
+        if (rc) return rc;
+    }
     if constexpr (!ROWS) {
         if (out == Emit::meta_first_lb) {
             D3D_LAUNCH("k_meta_first_lb", k_meta_first_lb<Key>, dim3(mtiles), dim3(kMetaLbThreads), 0, st, kf, w.npad, firstmap, vrec,
@@ -4492,19 +4491,12 @@ static int binned_index(const Key &kf, const float *points, int64_t n, int c, co
     if constexpr (!ROWS && std::is_same<Key, DenseKey>::value) {
         if (out == Emit::emit_c) {
             const int pshift = (o.P & (o.P - 1)) == 0 ? __builtin_ctz(o.P) : -1;
-#define D3D_EMIT_C(CC)                                                                                                          \
-    D3D_LAUNCH("k_emit_c", (k_emit_c<Key, CC>), grid, dim3(256), 0, st, kf, w.npad, firstmap, w.fwpre, w.bsumF, vrec, o.max_voxels,  \
-               points, w.big_list, o.P, pshift, o.reduction, o.coords, o.npoints, o.fuse_pmask ? o.pmask : nullptr, o.aggregates,   \
-               w.voff, o.emit_generic, counts, x.host_counts, reinterpret_cast<uint32_t *>(w.vinfo), w.big_count, x.row_state)
-            switch (c) {
-            case 3: D3D_EMIT_C(3); break;
-            case 5: D3D_EMIT_C(5); break;
-            case 6: D3D_EMIT_C(6); break;
-            case 7: D3D_EMIT_C(7); break;
-            default: D3D_EMIT_C(8); break;
-            }
-#undef D3D_EMIT_C
-            return D3D_OK;
+            return dispatch_int<3, 5, 6, 7, 8>(c, [&](auto cc) {        // (voxelize_dense_core sends no other C here)
+                D3D_LAUNCH("k_emit_c", (k_emit_c<Key, cc>), grid, dim3(256), 0, st, kf, w.npad, firstmap, w.fwpre, w.bsumF, vrec, o.max_voxels,
+                           points, w.big_list, o.P, pshift, o.reduction, o.coords, o.npoints, o.fuse_pmask ? o.pmask : nullptr, o.aggregates,
+                           w.voff, o.emit_generic, counts, x.host_counts, reinterpret_cast<uint32_t *>(w.vinfo), w.big_count, x.row_state);
+                return D3D_OK;
+            });
         }
     }
     float4 *agg = o.agg4 ? reinterpret_cast<float4 *>(o.aggregates) : nullptr;
@@ -4639,19 +4631,39 @@ static int exact_mean_pass(const DenseKey &kf, const float *points, int64_t n, i
                tiles, ticket);
     D3D_LAUNCH("k_exact_table", k_exact_table, dim3((unsigned)d3d_divup(n, 256)), dim3(256), 0, st, kf, coords, npoints, counts, P, tkeys,
                tvals, cap2 - 1);
-    const bool v4 = c == 4 && (reinterpret_cast<uintptr_t>(points) & 15) == 0;
-    if (v4)
-        D3D_LAUNCH("k_exact_collect", k_exact_collect<true>, dim3(tiles), dim3(kExactThreads), 0, st, kf, points, n, (int)c, (const u64 *)tkeys,
-                   (const uint32_t *)tvals, cap2 - 1, sortkey, oidx, w.bsum, ticket);
-    else
-        D3D_LAUNCH("k_exact_collect", k_exact_collect<false>, dim3(tiles), dim3(kExactThreads), 0, st, kf, points, n, (int)c, (const u64 *)tkeys,
-                   (const uint32_t *)tvals, cap2 - 1, sortkey, oidx, w.bsum, ticket);
+    const bool vec4 = c == 4 && (reinterpret_cast<uintptr_t>(points) & 15) == 0;
+    if (const int rc = dispatch(vec4, [&](auto v4) {
+            D3D_LAUNCH("k_exact_collect", k_exact_collect<v4>, dim3(tiles), dim3(kExactThreads), 0, st, kf, points, n, (int)c, (const u64 *)tkeys,
+                       (const uint32_t *)tvals, cap2 - 1, sortkey, oidx, w.bsum, ticket);
+            return D3D_OK;
+        }))
+        return rc;
     // stable sort of the hits by voxel (the table is done with: its region is the sort's scratch)
     const size_t sort_bytes = d3d_internal_argsort_i32_bytes(n);
     if (sort_bytes > w.tab_bytes) return D3D_ERR_WORKSPACE;
     if (int rc = d3d_internal_argsort_desc_i32(sortkey, n, order, w.tabA, w.tab_bytes, st)) return rc;
     D3D_LAUNCH("k_exact_sum", k_exact_sum, dim3((unsigned)d3d_divup(n, 256)), dim3(256), 0, st, points, (int)c, (const int32_t *)sortkey,
                (const int32_t *)order, (const uint32_t *)oidx, n, npoints, aggregates);
+    return D3D_OK;
+}
+
+// the dense contract's hash path after its index: per-voxel outputs (k_meta) and, on C == 4 rows, the reduction of the voxels
+// with more than P points (k_overflow_reduce)
+static int dense_meta(const DenseKey &kf, const float *points, const VoxelWs &w, int64_t *counts, dim3 grid, uint32_t P, int reduction,
+                      bool agg4, int64_t *coords, int32_t *npoints, uint32_t *voff, uint8_t *pmask, float *aggregates, int64_t *keys,
+                      int64_t status_row, hipStream_t st)
+{
+    const float4 *p4 = reinterpret_cast<const float4 *>(points);
+    if (const int rc = dispatch(agg4, [&](auto a) {
+            D3D_LAUNCH("k_meta", (k_meta<DenseKey, a>), grid, dim3(256), 0, st, kf, p4, counts, w.vinfo, w.staged, w.unsorted, P, reduction,
+                       coords, npoints, voff, pmask, a ? reinterpret_cast<float4 *>(aggregates) : nullptr, w.big_list, w.big_count, keys,
+                       status_row);
+            return D3D_OK;
+        }))
+        return rc;
+    if (agg4)
+        D3D_LAUNCH("k_overflow_reduce", k_overflow_reduce, dim3(512), dim3(256), 0, st, p4, w.vinfo, w.unsorted, w.big_list, w.big_count,
+                   reduction, reinterpret_cast<float4 *>(aggregates));
     return D3D_OK;
 }
 
@@ -4705,7 +4717,6 @@ static int voxelize_dense_core(const float *points, int64_t n, int32_t c, const 
     const uint32_t P = (uint32_t)max_points;
     const bool fuse_pmask = P > 0 && (P % 16 == 0) && ((reinterpret_cast<uintptr_t>(pmask) & 15) == 0);
     const bool agg4 = vec4 && reduction != D3D_REDUCE_NONE && P > 0;
-    const float4 *p4 = reinterpret_cast<const float4 *>(points);
     uint32_t nbins = 0;
     int hshift = 0;
     bool lists_ready = false;           // C != 4 on the binned index: w.big_list / w.unsorted / w.voff hold the lists
@@ -4746,29 +4757,14 @@ static int voxelize_dense_core(const float *points, int64_t n, int32_t c, const 
         if (rc) return rc;
         if (host_counts) D3D_LAUNCH("k_notify_host", k_notify_host, dim3(1), dim3(64), 0, st, counts, host_counts);
         if (n == 0 || max_voxels == 0) return D3D_OK;
-        const dim3 mgrid(grid_for(cap, 256));
-        rc = dispatch(agg4, [&](auto a) {
-            D3D_LAUNCH("k_meta", (k_meta<DenseKey, a>), mgrid, dim3(256), 0, st, kf, p4, counts, w.vinfo, w.staged, w.unsorted,
-                       P, reduction, coords, npoints, w.voff, fuse_pmask ? pmask : nullptr,
-                       a ? reinterpret_cast<float4 *>(aggregates) : nullptr, w.big_list, w.big_count);
-            return D3D_OK;
-        });
+        rc = dense_meta(kf, points, w, counts, dim3(grid_for(cap, 256)), P, reduction, agg4, coords, npoints, w.voff,
+                        fuse_pmask ? pmask : nullptr, aggregates, nullptr, -1, st);
         if (rc) return rc;
-        if (agg4)
-            D3D_LAUNCH("k_overflow_reduce", k_overflow_reduce, dim3(512), dim3(256), 0, st, p4, w.vinfo, w.unsorted, w.big_list,
-                       w.big_count, reduction, reinterpret_cast<float4 *>(aggregates));
     }
     if (P == 0) return D3D_OK;
-    if (emitted || emitted_generic) {
-        if (!fuse_pmask)
-            D3D_LAUNCH("k_pmask", k_pmask, dim3(grid_for(d3d_divup(cap * P, 16), 256)), dim3(256), 0, st, counts, npoints, P, pmask);
-        if (emitted_generic && reduction != D3D_REDUCE_NONE)          // voxels with more than P points: all their points count
-            D3D_LAUNCH("k_aggregate_overflow", k_aggregate_overflow, dim3(1024), dim3(256), 0, st, points, c,
-                       (const uint32_t *)reinterpret_cast<uint32_t *>(w.vinfo), (const uint32_t *)w.big_count, (const int32_t *)npoints,
-                       (const uint32_t *)w.voff, (const uint32_t *)w.unsorted, reduction, aggregates);
-        return D3D_OK;
-    }
-    if (vec4 && n <= kFillRowsMaxPoints) {
+    const bool fill = !emitted && !emitted_generic;          // (else the output launch of the index wrote voxels[] already)
+    if (!fill) {
+    } else if (vec4 && n <= kFillRowsMaxPoints) {
         D3D_LAUNCH("k_fill_c4", k_fill_c4_rows, dim3(grid_for(cap * P, 256, 256 * 32)), dim3(256), 0, st, w.staged, counts, w.vinfo,
                    P, reinterpret_cast<float4 *>(voxels));
     } else if (vec4) {
@@ -4786,7 +4782,11 @@ static int voxelize_dense_core(const float *points, int64_t n, int32_t c, const 
                    counts, w.vinfo, lists_ready ? w.big_list : w.list, P, voxels);
     if (!fuse_pmask)
         D3D_LAUNCH("k_pmask", k_pmask, dim3(grid_for(d3d_divup(cap * P, 16), 256)), dim3(256), 0, st, counts, npoints, P, pmask);
-    if (reduction != D3D_REDUCE_NONE && !agg4)
+    if (emitted_generic && reduction != D3D_REDUCE_NONE)          // voxels with more than P points: all their points count
+        D3D_LAUNCH("k_aggregate_overflow", k_aggregate_overflow, dim3(1024), dim3(256), 0, st, points, c,
+                   (const uint32_t *)reinterpret_cast<uint32_t *>(w.vinfo), (const uint32_t *)w.big_count, (const int32_t *)npoints,
+                   (const uint32_t *)w.voff, (const uint32_t *)w.unsorted, reduction, aggregates);
+    if (fill && reduction != D3D_REDUCE_NONE && !agg4)
         D3D_LAUNCH("k_aggregate", k_aggregate, dim3(grid_for(cap * c, 256)), dim3(256), 0, st, points, c, counts, npoints,
                    w.voff, lists_ready ? w.big_list : w.list, w.unsorted, P, reduction, aggregates);
     return D3D_OK;
@@ -4897,7 +4897,6 @@ extern "C" int d3d_voxelize_3d_reduce(const float *points, int64_t n, int32_t c,
     const bool agg4 = (c == 4) && ((reinterpret_cast<uintptr_t>(points) & 15) == 0) &&
                       ((reinterpret_cast<uintptr_t>(aggregates) & 15) == 0);
     if (rows && (!agg4 || (reinterpret_cast<uintptr_t>(rows) & 15))) return D3D_ERR_UNSUPPORTED;    // staged rows are float4
-    const float4 *p4 = reinterpret_cast<const float4 *>(points);
     uint32_t nbins = 0;
     int hshift = 0;
     if (agg4 && dense_cells_fit_u32(kf) && binned_eligible(n, w, flags, &nbins, &hshift)) {
@@ -4920,17 +4919,10 @@ extern "C" int d3d_voxelize_3d_reduce(const float *points, int64_t n, int32_t c,
     rc = dense_index(kf, points, n, c, w, counts, o, flags, st);
     if (rc) return rc;
     if (n == 0) return D3D_OK;
-    rc = dispatch(agg4, [&](auto a) {
-        D3D_LAUNCH("k_meta", (k_meta<DenseKey, a>), dim3(grid_for(n, 256)), dim3(256), 0, st, kf, p4, counts, w.vinfo,
-                   w.staged, w.unsorted, P, reduction, coords, npoints, a && seg_base ? seg_base : w.voff, (unsigned char *)nullptr,
-                   a ? reinterpret_cast<float4 *>(aggregates) : nullptr, w.big_list, w.big_count, keys, n);
-        return D3D_OK;
-    });
+    rc = dense_meta(kf, points, w, counts, dim3(grid_for(n, 256)), P, reduction, agg4, coords, npoints, agg4 && seg_base ? seg_base : w.voff,
+                    nullptr, aggregates, keys, n, st);
     if (rc) return rc;
-    if (agg4)
-        D3D_LAUNCH("k_overflow_reduce", k_overflow_reduce, dim3(512), dim3(256), 0, st, p4, w.vinfo, w.unsorted, w.big_list,
-                   w.big_count, reduction, reinterpret_cast<float4 *>(aggregates));
-    else
+    if (!agg4)
         D3D_LAUNCH("k_aggregate", k_aggregate, dim3(grid_for(n * c, 256)), dim3(256), 0, st, points, c, counts, npoints,
                    w.voff, w.list, w.unsorted, P, reduction, aggregates);
     // (rows were STAGED on this path: counts[D3D_COUNT_AUX] -- the hash path's list-cell count until here -- must not read 1)
@@ -4975,6 +4967,15 @@ static int voxelize_sparse_impl(const float *points, int64_t n, int32_t c, const
         return binned_index<SparseKey, false>(kf, points, n, c, w, nbins, hshift, counts, d, st, !(flags & D3D_VOXEL_PARTITION_3PASS));
     }
     IndexOpts o{0u, 0xffffffffu, nullptr, 0, points_mapping, false};
+    auto hash_index = [&](const auto &kf, const auto &tab) -> int {
+        typedef typename std::decay<decltype(kf)>::type Key;
+        int rc = build_index(kf, tab, points, n, c, w, counts, o, st);
+        if (rc || n == 0) return rc;
+        D3D_LAUNCH("k_meta", (k_meta<Key, false>), dim3(grid_for(n, 256)), dim3(256), 0, st, kf, (const float4 *)nullptr, counts, w.vinfo,
+                   w.staged, w.unsorted, 0u, 0, coords, npoints, (uint32_t *)nullptr, (unsigned char *)nullptr, (float4 *)nullptr,
+                   w.big_list, w.big_count);
+        return D3D_OK;
+    };
     const int ib = bits_for((u64)(n > 1 ? n - 1 : 1));
     if (!(flags & D3D_VOXEL_PLAIN_SLOTS) && ib <= 40) {
         // one-word slots keyed inside the frame's bounding box; PACK_OVERFLOW (box too large for the word, or a
@@ -4984,24 +4985,12 @@ static int voxelize_sparse_impl(const float *points, int64_t n, int32_t c, const
         kf.tolerant = tolerant;
         kf.prm = reinterpret_cast<BoxParams *>(w.big_count + 16);
         kf.kb_max = 56 - ib;
-        TabPacked tab{w.tabA, ib, 0, reinterpret_cast<uint32_t *>(w.tabB), kf.prm};
-        int rc = build_index(kf, tab, points, n, c, w, counts, o, st);
-        if (rc || n == 0) return rc;
-        D3D_LAUNCH("k_meta", (k_meta<BoxKey, false>), dim3(grid_for(n, 256)), dim3(256), 0, st, kf, (const float4 *)nullptr,
-                   counts, w.vinfo, w.staged, w.unsorted, 0u, 0, coords, npoints, (uint32_t *)nullptr,
-                   (unsigned char *)nullptr, (float4 *)nullptr, w.big_list, w.big_count);
-        return D3D_OK;
+        return hash_index(kf, TabPacked{w.tabA, ib, 0, reinterpret_cast<uint32_t *>(w.tabB), kf.prm});
     }
     SparseKey kf;
     for (int d = 0; d < 3; d++) kf.size[d] = voxel_size[d];
     kf.tolerant = tolerant;
-    TabPlain tab{w.tabA, w.tabB};
-    int rc = build_index(kf, tab, points, n, c, w, counts, o, st);
-    if (rc || n == 0) return rc;
-    D3D_LAUNCH("k_meta", (k_meta<SparseKey, false>), dim3(grid_for(n, 256)), dim3(256), 0, st, kf, (const float4 *)nullptr,
-               counts, w.vinfo, w.staged, w.unsorted, 0u, 0, coords, npoints, (uint32_t *)nullptr, (unsigned char *)nullptr,
-               (float4 *)nullptr, w.big_list, w.big_count);
-    return D3D_OK;
+    return hash_index(kf, TabPlain{w.tabA, w.tabB});
 }
 
 // order (descending stable argsort of voxel_npoints) for MAXVOX_DESCENDING, implemented in sort.hip
@@ -5223,15 +5212,12 @@ extern "C" int d3d_voxelize_3d_sparse_filter(const float *points, int64_t n, int
                 int64_t *late_host = desc ? host_counts : nullptr;
                 const bool v4 = c == 4 && ((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(out_feats)) & 15) == 0;
                 unsigned int *cticket = w.big_count + 41;
-                if (v4)
-                    D3D_LAUNCH("k_compact_kept", k_compact_kept<true>, dim3(d.compact_tiles), dim3(kCompactThreads), 0, st, points, (int)c, n,
-                               w.npad, (const uint32_t *)w.pslot, (const uint32_t *)w.voff, out_feats, out_mask, out_mapping, w.bsum, cticket,
-                               counts, (const int64_t *)sparse_counts, late_host, vix);
-                else
-                    D3D_LAUNCH("k_compact_kept", k_compact_kept<false>, dim3(d.compact_tiles), dim3(kCompactThreads), 0, st, points, (int)c, n,
-                               w.npad, (const uint32_t *)w.pslot, (const uint32_t *)w.voff, out_feats, out_mask, out_mapping, w.bsum, cticket,
-                               counts, (const int64_t *)sparse_counts, late_host, vix);
-                return D3D_OK;
+                return dispatch(v4, [&](auto vec4) {
+                    D3D_LAUNCH("k_compact_kept", k_compact_kept<vec4>, dim3(d.compact_tiles), dim3(kCompactThreads), 0, st, points, (int)c,
+                               n, w.npad, (const uint32_t *)w.pslot, (const uint32_t *)w.voff, out_feats, out_mask, out_mapping, w.bsum,
+                               cticket, counts, (const int64_t *)sparse_counts, late_host, vix);
+                    return D3D_OK;
+                });
             }
         }
     }
