@@ -22,6 +22,7 @@ VOXEL_PATH_HASH, VOXEL_PARTITION_3PASS, VOXEL_PLAIN_SLOTS, VOXEL_SPLIT_FILL, VOX
 OWNER_MERGE_CHAINS, OWNER_MERGE_TEST_TINY = 1, 2
 NMS_BROAD_SWEEP, NMS_FORCE_DENSE, NMS_SOFT_NO_LDS, NMS_GENERAL, NMS_TEST_WITHHOLD, NMS_FORCE_LEVELS, NMS_ONE_LEVEL = 1, 2, 4, 8, 16, 32, 64
 NMS_KEEP_MASK = 128
+PROJECT_ALL_UV, PROJECT_DMASK = 1, 2
 
 
 def nms_cand_cap(k):
@@ -117,6 +118,9 @@ SIGNATURES = {
     "d3d_crop_3dp": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _vp]),
     "d3d_crop_3dr": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _vp]),
     "d3d_paint_label": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "d3d_project_points_workspace_bytes": (_sz, [_i64, _i32]),
+    "d3d_project_points": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3d_transform_points": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "d3d_argsort_desc_workspace_bytes": (_sz, [_i64, _i32]),
     "d3d_argsort_desc": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _sz, _vp]),
     "d3d_nms2d_workspace_bytes": (_sz, [_i64]),

@@ -425,6 +425,46 @@ int d3d_crop_3dr(const float *points, int64_t n, int32_t point_stride, const flo
 int d3d_paint_label(const float *points, int64_t n, int32_t point_stride, const uint8_t *semantics, const float *boxes,
                     int64_t m, int32_t box_stride, int32_t box_offset, const uint8_t *labels, uint16_t *idarr, void *stream);
 
+/* ---- points to cameras: TransformSet.transform_points / project_points_to_camera (reference d3d/abstraction.pyx:971-977,
+ * 979-1035).  points[n, stride >= 3] in `dtype` (D3D_F32 or D3D_F64; x, y, z first), read in place; all arithmetic fp64, no
+ * contraction.  One camera record, HOST memory (the entry point copies the records into the kernel arguments):
+ *   rt: rows 0..2 of the 4x4 extrinsic frame_from -> frame_to, row-major 3x4;  P: the camera's stored 3x3 intrinsic (the axis
+ *   rotation of set_intrinsic_camera(rotate=True) already folded in);  fx, fy, cx, cy: intri_matrix[0,0], [1,1], [0,2], [1,2]
+ *   and dist = (k1, k2, p1, p2, k3), read only where has_dist != 0;  width, height: the image size in pixels. */
+typedef struct D3DCamera {
+    double rt[12];
+    double P[9];
+    double fx, fy, cx, cy;
+    double dist[5];
+    int32_t width;
+    int32_t height;
+    int32_t has_dist;
+    int32_t reserved;           /* pads the record to 256 bytes */
+} D3DCamera;
+
+enum { D3D_PROJECT_ALL_UV = 1,      /* uv row i = point i (remove_outlier=False); without it uv row j = the j-th point in view */
+       D3D_PROJECT_DMASK = 2 };     /* also list the points in front of the camera (return_dmask=True) */
+
+size_t d3d_project_points_workspace_bytes(int64_t n, int32_t ncam);
+/* abstraction.pyx:979-1035 for ncam >= 1 cameras over one cloud, which is read once per 8 cameras.  Per point and camera
+ *   cam = rt . (x, y, z, 1);  h = P . cam;  d = h[2];  u = h[0] / d;  v = h[1] / d        (:991-996, IEEE divisions)
+ *   dmask = d > 0;  mask = 0 < u < width and 0 < v < height and dmask                      (:999-1000)
+ * and with has_dist the +-20 px mask on the undistorted (u, v), the distortion and the second mask of :1006-1024.
+ * Camera c writes its own section of each output (device memory, upper-bound sized):
+ *   uv[ncam, n, 2] f64: rows 0 .. K-1 = (u, v) of the points in view in point order, or with D3D_PROJECT_ALL_UV every point's;
+ *   mask[ncam, n] i64: entries 0 .. K-1 = the ascending indices of the points in view (np.where, :1029);
+ *   dmask[ncam, n] i64 (D3D_PROJECT_DMASK; else may be NULL): entries 0 .. Kd-1 = those of the points with d > 0 (:1030);
+ *   counts[ncam, 2] i64 = (K, Kd), final once the call's second launch has run.
+ * Three launches per 8 cameras (count, a scan of the workgroups' counts, emit); no launch waits on another workgroup, nothing
+ * synchronises.  n <= 2^31 - 1.  Results per camera do not depend on the other records of the call. */
+int d3d_project_points(const void *points, int64_t n, int32_t stride, int32_t dtype, const D3DCamera *cameras /* host */,
+                       int32_t ncam, uint32_t flags, double *uv, int64_t *mask, int64_t *dmask, int64_t *counts,
+                       void *workspace, size_t workspace_bytes, void *stream);
+/* abstraction.pyx:971-977: out[n, stride] f64, columns 0..2 = rt[0:3, 0:3] . p + rt[0:3, 3] (rt: host, row-major 3x4 f64), the
+ * other columns widened to f64 as numpy's concatenate promotes them. */
+int d3d_transform_points(const void *points, int64_t n, int32_t stride, int32_t dtype, const double *rt /* host */, double *out,
+                         void *stream);
+
 /* ------------------------------------------------------------------ d3d/point ("next" row) */
 
 /* replaces aligned_scatter_forward[_cuda] / aligned_scatter_backward[_cuda] (reference d3d/point/scatter.h:39-56,
