@@ -6,6 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np, torch
 import oracle
+import point_reference
 import test_gpu_voxel as tv
 from d3d_amd.box import box2d_iou, box2d_nms, iou2dr_flags, pdist2dr_forward
 from d3d_amd.tracking import DistanceTypes, prepare_boxes, score_match
@@ -188,7 +189,7 @@ for seed in range(first, first + count):
     if not np.array_equal(gp.astype(np.int64), oracle.paint_label(b7, p4, sem, lab).astype(np.int64)):
         bad += 1; print("PAINT seed", seed, npt, nbx, "FAILED")
     # aligned_scatter (d3d.point): 2-D / 3-D maps, all align types, coordinates partly outside the map; forward bit-exact
-    # (same accumulation order), backward against the oracle's adjoint within the atomics' reordering
+    # (same accumulation order), backward against the fp64 model's adjoint within its count of roundings
     from d3d_amd.point import AlignType, aligned_scatter_backward, aligned_scatter_forward
     nd_ = int(rng.choice([2, 3]))
     dims = [int(rng.integers(2, 24)) for _ in range(nd_)]
@@ -208,10 +209,11 @@ for seed in range(first, first + count):
         gr = rng.standard_normal(want.shape).astype(dtp)
         ig = torch.zeros(img_.shape, dtype=torch.from_numpy(img_).dtype, device="cuda")
         aligned_scatter_backward(torch.from_numpy(crd).cuda(), torch.from_numpy(gr).cuda(), atype, ig)
-        wb = oracle.aligned_scatter_backward(crd, gr, at, img_.shape)
-        tolb = 1e-4 if dtp == np.float32 else 1e-11
-        if not np.allclose(ig.cpu().numpy(), wb, rtol=tolb, atol=tolb * max(1.0, float(np.abs(wb).max()))):
-            bad += 1; print("SCATTER-BWD seed", seed, at, dims, ch, npts_, "FAILED", float(np.abs(ig.cpu().numpy() - wb).max()))
+        # every element against the fp64 model within its rounding count (tests/point_reference.py), not a relative tolerance
+        wb, kb, ab, eb = point_reference.backward_terms(crd, gr, int(atype), img_.shape, None, point_reference.unit(dtp))
+        errb = np.abs(ig.cpu().numpy() - wb)
+        if not np.all(errb <= point_reference.backward_bound(kb, ab, nd_, point_reference.unit(dtp), eb)):
+            bad += 1; print("SCATTER-BWD seed", seed, at, dims, ch, npts_, "FAILED", float(errb.max()))
     # matcher: [n,9] boxes with classes, scores (ties every 5th seed), thresholds per class
     nd, ng = int(rng.integers(1, 400)), int(rng.integers(1, 150))
     gt7 = np.stack([rng.random(ng) * 40, rng.random(ng) * 40, rng.random(ng) * 2 - 2, rng.random(ng) * 1.5 + 3.5, rng.random(ng) * .5 + 1.6,
