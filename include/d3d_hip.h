@@ -1,6 +1,6 @@
 /*
  * d3d_hip.h -- C ABI of libd3d_hip.so: the MI355X (gfx950) implementation of the
- * data-parallel hot path of cmpute/d3d (d3d/voxel + d3d/box).
+ * data-parallel hot path of cmpute/d3d (d3d/voxel + d3d/box, and the operator packages around them: d3d/point, d3d/math).
  *
  * This is the drop-in boundary.  Every entry point replaces one function that the
  * reference binds through pybind11 in d3d/voxel/impl.cpp:3-21 and d3d/box/impl.cpp:8-54
@@ -772,6 +772,23 @@ size_t d3d_track_workspace_bytes(int64_t n, int64_t m, int32_t thresholds, int64
 int d3d_track_frame(const D3DTrackFrame *frame, const float *thresholds, int32_t T, const float *max_dist, int32_t C,
                     const void *state_in, void *state_out, int32_t *assign, float *iou, int32_t *counts,
                     void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------ d3d/math */
+
+/* replaces i0e / i1e / i0e_cuda / i1e_cuda (reference d3d/math/impl.cpp:16-46, math.h:6-11, over the templates of
+ * math/bessel.h:16-35, 121-132, 223-238): out[i] = exp(-|x[i]|) I_order(x[i]) for the n elements of a flat fp32 (D3D_F32) or
+ * fp64 (D3D_F64) array, order 0 or 1 -- the reference's bits in both dtypes (where it rounds: bessel.hip's header; for fp64
+ * these are scipy.special.i0e / i1e's bits).  x and out need the alignment of their element only and may be the same buffer;
+ * n is not bounded by 2^31 (the reference's loop index is an int).  One launch, no workspace, no synchronisation; n == 0
+ * launches nothing.
+ * D3D_ERR_BAD_ARG: order outside {0, 1}, n < 0, a null or misaligned pointer with n > 0; D3D_ERR_UNSUPPORTED: any other dtype
+ * (AT_DISPATCH_FLOATING_TYPES in the reference). */
+int d3d_bessel_e(int32_t order, const void *x, int64_t n, int32_t dtype, void *out, void *stream);
+/* the derivative of i0e, which the reference's I0Exp.backward (d3d/math/__init__.py:19-24) does not compute -- it returns
+ * i1e(grad) -- in one pass over x and grad: grad_x[i] = grad[i] * (i1e(x[i]) - sign(x[i]) * i0e(x[i])), sign(0) = 0, both
+ * Bessel values with d3d_bessel_e's bits, the multiply, the subtract and the multiply rounded in the dtype, uncontracted.
+ * Arguments and errors as d3d_bessel_e; grad_x may be x or grad. */
+int d3d_i0e_backward(const void *x, const void *grad, int64_t n, int32_t dtype, void *grad_x, void *stream);
 
 #ifdef __cplusplus
 }
