@@ -4253,12 +4253,10 @@ struct DenseOut {
     u64 *compact_stat = nullptr;        // ... look-back words of k_compact_kept (cleared by k_meta_first)
     uint32_t compact_tiles = 0;
     uint32_t npoints_clamp = 0xffffffffu;   // ... and voxel_npoints = min(count, max_points) (voxelize.cpp:403)
-    bool lists = false;                 // dense contract with C != 4: ranked index lists + voff instead of staged rows
     uint32_t *seg_out = nullptr;        // reduce contract: segment base of every voxel's staged rows (for the caller)
     float4 *emit_voxels = nullptr;      // dense contract on C == 4 rows: k_emit writes voxels[V,P,4] too (no staging, no fill)
     float *emit_generic = nullptr;      // dense contract, C = 3, 5 .. 8: k_emit_c writes voxels[V,P,C] and the per-voxel outputs
     bool emit_reduce = false;           // reduce contract without rows: k_emit without the stretch (nothing staged by the index)
-    int stage = 0;                      // d3d_voxelize_3d_dense_staged: 1 = index launches only, 2 = the output launch only
 };
 
 // n points -> which index path: bucket count / hash shift of the binned index, or false for the hash table
@@ -4303,29 +4301,142 @@ static int launch_tile_sort(int tshift, size_t lds, dim3 grid, hipStream_t st, c
     return launch(std::integral_constant<int, 8>{});
 }
 
-// binned_index's output stage: k_meta_first_lb (fused sparse + filter), nothing (staged call, stage 1), k_emit_split of 256 or
-// 512 lanes, k_emit<.., RESIDENT>, k_emit, k_emit_c (dense contract, C != 4), k_meta_first
-enum class Emit { meta_first_lb, none, split256, split512, resident, emit, emit_c, meta_first };
+// k_bucket_index<Key, ROWS', LISTS, STAGE, V2> by route: the sparse contract's index lists <false, true, false, false>, the
+// packed first-point entries <true, true, false, true> (fm_packed: no precpos, trimmed, pfirst or early totals), rows with
+// lists <ROWS, true, false, false>, plain rows <ROWS, false, ROWS, false>
+enum BucketRoute { kLists, kPacked, kRowLists, kPlain };
 
-// ROWS: dense contract on C == 4 rows (ranked rows staged, reductions); !ROWS: keys only (sparse contract, any C)
-template <class Key, bool ROWS>
-static int binned_index(const Key &kf, const float *points, int64_t n, int c, const VoxelWs &w, uint32_t nbins, int hshift,
-                        int64_t *counts, const DenseOut &o, hipStream_t st, bool tile_sort)
+// the output stage: k_meta_first_lb (fused sparse + filter), k_emit_split of 256 or 512 lanes, k_emit<.., RESIDENT>, k_emit,
+// k_emit_c (dense contract, C != 4), k_meta_first
+enum class Emit { meta_first_lb, split256, split512, resident, emit, emit_c, meta_first };
+
+// Everything the host decides about one call of the binned index, before the first launch (plan_binned: no HIP call in it).
+// launch_index and launch_output only launch from it.
+struct BinnedPlan {
+    uint32_t nbins;
+    int hshift;
+    bool vec4;                          // float4 point rows
+    // partition.  One launch (k_tile_sort) on tiles of 2^tshift points when `table` is set, else the three passes
+    int tshift;
+    uint32_t stiles;
+    uint32_t *table, *tileinfo;         // bucket-major {offset : 16 | entries : 16} per (bucket, tile); per-tile totals
+    uint32_t passes, ntiles;            // three passes: passes per workgroup, workgroups
+    void *pkey;                         // ... per-point keys until the scatter (BinEntry<ROWS>::key_store_t)
+    uint32_t *tilecnt, *totals, *pbin;
+    void *bent;                         // the entries in bucket order (BinEntry<ROWS>::type)
+    uint32_t *bucket_base;
+    uint32_t *firstmap;
+    uint32_t *ppos;                     // fused sparse + filter: by point, the first point of its voxel when it is kept (pfirst)
+    u64 *zero_words;                    // look-back words + early totals the partition clears, with the ticket
+    uint32_t nzero;
+    unsigned int *zero_ticket;
+    ZeroFill zf_sort, zf_count;         // zero padding under k_tile_sort / k_first_count
+    uint32_t prefilled;                 // voxels[0 .. prefilled) are zero when the output stage starts
+    // k_bucket_index
+    int route;                          // BucketRoute
+    int reduction;
+    uint32_t *sorted_out, *unsorted_out;
+    uint32_t early_clamp;
+    int idx_bits;
+    float4 *staged;
+    uint4 *vrec;
+    uint32_t *precpos, *parr, *vinfo32, *gpos;
+    u64 *early_tot;                     // early totals: early_pairs pairs at 16 words each behind the look-back words (0: off)
+    uint32_t early_pairs;
+    // k_first_count
+    uint32_t *fwpre, *bsumF, *big_count;
+    // output stage
+    Emit out;
+    int64_t npad;
+    uint32_t mtiles;                    // k_meta_first_lb: tiles
+    MetaLb mlb;
+    BinnedExtras x;
+    uint4 *meta_vinfo;                  // k_meta_first: records by voxel id, where a later launch reads them
+    uint32_t *big_list, *voff;
+};
+
+
+// tiles of 8192 points (4096: profiles/r04_bucket_target.txt); large frames of the dense contract on C == 4 rows: 16384 -- half
+// the tiles, so half the table, and k_bucket_index finds a bucket's entries in half as many runs of twice the length
+static bool wants_big_tiles(bool rows, bool vec4, int key_bytes, int64_t n)
 {
-    const uint32_t passes = (uint32_t)bin_passes(n), ntiles = (uint32_t)d3d_divup((int64_t)(w.npad / kBinTile), (int64_t)passes);
-    const float4 *p4 = reinterpret_cast<const float4 *>(points);
-    typedef BinEntry<ROWS> E;
-    typename E::type *bent = reinterpret_cast<typename E::type *>(w.tabA);      // cap * 8 bytes >= 16 n
+    return rows && vec4 && key_bytes == 4 && n >= kBigTileMinPoints;
+}
+
+// tiles of 4096 points while tiles of 8192 would leave a third of the CUs without a workgroup (one workgroup per tile):
+// 1 M points 16.2 -> 13.7 us with the bucket kernel unchanged; at 2 M points (245 tiles of 8192) +4 us, at 4 M +6; tiles of
+// 2048 points: +2 us in the bucket kernel (runs of two entries) -- profiles/r05_b_tune.txt.  Round 6: where fillers take the
+// CUs without a tile, tiles of 8192 it is (those CUs then write 76 MB of zeros in the 16 us).
+// (launch_tile_sort has the tile sizes other than 8192 on float4 rows only)
+static bool wants_small_tiles(bool rows, bool vec4, bool big_tiles, int64_t npad, bool fill_tiles)
+{
+    return rows && vec4 && !big_tiles && (npad >> 13) <= 160 && !fill_tiles;
+}
+
+struct TilePlan {
+    int tshift;
+    uint32_t stiles;
+    uint32_t *table, *tileinfo;     // null: the frame or the table does not fit the one-launch partition
+};
+// one-launch partition (k_tile_sort) whenever the frame and the table fit; else, or on request, the three-pass one
+static TilePlan plan_tiles(bool big_tiles, bool small_tiles, bool rows, bool tile_sort, int64_t n, uint32_t nbins, const VoxelWs &w)
+{
+    TilePlan t{big_tiles ? 14 : small_tiles ? 12 : 13, 0, nullptr, nullptr};
+    t.stiles = (uint32_t)(w.npad >> t.tshift);
+    if (tile_sort && n <= (rows ? kTileSortMaxPoints : kTileSortMaxPointsSparse) && nbins <= 8192u && t.stiles <= (uint32_t)kRunCap &&
+        ((uint64_t)nbins + 1) * t.stiles * 4 <= w.cap * 8) {
+        t.table = reinterpret_cast<uint32_t *>(w.tabB);
+        t.tileinfo = t.table + (size_t)nbins * t.stiles;
+    }
+    return t;
+}
+
+// (w.fwords: npad / 64 words of the hash path; here two look-back words per tile of the launch behind the index, then, from the
+// next multiple of 16 words on, up to 64 pairs of early totals at 16 words each -- as many as fit, a power of two)
+struct EarlyLayout { uint32_t at, pairs; };
+static EarlyLayout early_layout(uint32_t lb_tiles, int64_t npad, bool on)
+{
+    EarlyLayout e{(2 * lb_tiles + 15u) & ~15u, 0};
+    if (!on) return e;
+    for (e.pairs = 64; e.pairs > 1 && (uint64_t)e.at + 16ull * e.pairs > (uint64_t)(npad / 64); e.pairs >>= 1) { }
+    if ((uint64_t)e.at + 16ull * e.pairs > (uint64_t)(npad / 64)) e.pairs = 0;
+    return e;
+}
+
+// rows: dense contract on C == 4 rows, else keys only; key_bytes: sizeof(Key::bin_key_t); stage: 0, or 1 / 2 of the staged call
+static BinnedPlan plan_binned(bool rows, int key_bytes, const float *points, int64_t n, int c, const VoxelWs &w, uint32_t nbins, int hshift,
+                              const DenseOut &o, bool tile_sort, int stage)
+{
+    BinnedPlan p;
+    p.nbins = nbins;
+    p.hshift = hshift;
+    p.npad = w.npad;
+    p.passes = (uint32_t)bin_passes(n);
+    p.ntiles = (uint32_t)d3d_divup((int64_t)(w.npad / kBinTile), (int64_t)p.passes);
+    p.bent = w.tabA;                                            // cap * 8 bytes >= 16 n
     // per-point keys until the scatter: dense u32 (an index array of the hash path), sparse u64 (`staged` is not used there)
-    typename E::key_store_t *pkey = ROWS ? reinterpret_cast<typename E::key_store_t *>(w.big_list)
-                                         : reinterpret_cast<typename E::key_store_t *>(w.staged);
-    uint32_t *tilecnt = reinterpret_cast<uint32_t *>(w.tabB);
-    uint4 *vrec = reinterpret_cast<uint4 *>(w.aux);
-    uint32_t *bucket_base = w.vidarr, *totals = w.vidarr + nbins + 2;
-    uint32_t *pbin = w.pslot, *firstmap = w.list;
+    p.pkey = rows ? static_cast<void *>(w.big_list) : static_cast<void *>(w.staged);
+    p.tilecnt = reinterpret_cast<uint32_t *>(w.tabB);
+    p.vrec = reinterpret_cast<uint4 *>(w.aux);
+    p.bucket_base = w.vidarr;
+    p.totals = w.vidarr + nbins + 2;
+    p.pbin = w.pslot;
+    p.firstmap = w.list;
+    p.staged = w.staged;
+    p.parr = w.parr;
+    p.vinfo32 = reinterpret_cast<uint32_t *>(w.vinfo);
+    p.gpos = reinterpret_cast<uint32_t *>(w.vinfo) + w.npad;
+    p.fwpre = w.fwpre;
+    p.bsumF = w.bsumF;
+    p.big_count = w.big_count;
+    p.big_list = w.big_list;
+    p.voff = w.voff;
+    const bool lists = !rows && key_bytes == 4;                 // dense contract with C != 4 (DenseKey without rows): ranked index
+                                                                // lists + voff instead of staged rows
     const bool want_map = o.mapping || o.keepid || o.map_later;
-    uint32_t *precpos = want_map && !o.map_later ? w.unsorted : nullptr;        // the hash path's lists are not used here
-    BinnedExtras x = o.x;
+    p.precpos = want_map && !o.map_later ? w.unsorted : nullptr;        // the hash path's lists are not used here
+    BinnedExtras &x = p.x;
+    x = o.x;
     x.vidof = want_map ? w.voff : nullptr;
     x.npoints_clamp = o.npoints_clamp;
     if (o.count_out) { x.count_out = o.count_out; x.first_out = o.first_out; x.index_offset = 0; }
@@ -4335,71 +4446,55 @@ static int binned_index(const Key &kf, const float *points, int64_t n, int c, co
     }
     // fused sparse + filter: numbering + per-voxel outputs + output sizes in one launch (k_meta_first_lb)
     const bool meta_lb = o.map_later;
-    const uint32_t mtiles = (uint32_t)(w.npad / kMetaLbTile);
-    // (w.fwords: npad / 64 words of the hash path; here 2 * npad / 4096 look-back words, then, from the next multiple of 16
-    // words on, up to 64 pairs of early totals at 16 words each -- as many as fit, a power of two)
-    const uint32_t early_at = (2 * mtiles + 15u) & ~15u;
-    uint32_t early_pairs = 0;
-    if (meta_lb && o.early_host)
-        for (early_pairs = 64; early_pairs > 1 && (uint64_t)early_at + 16ull * early_pairs > (uint64_t)(w.npad / 64); early_pairs >>= 1) { }
-    MetaLb mlb{w.fwords, w.big_count + 40, o.compact_stat, o.compact_tiles, w.big_count + 41, o.early_host, w.fwords + early_at, early_pairs};
-    u64 *zero_words = meta_lb ? mlb.stat : nullptr;
-    const uint32_t nzero = early_at + 16u * early_pairs;
-    u64 *early_tot = early_pairs ? w.fwords + early_at : nullptr;
-    unsigned int *zero_ticket = meta_lb ? mlb.ticket : nullptr;
-    x.voff = o.seg_out ? o.seg_out : (o.lists ? w.voff : nullptr);
-    const bool vec4 = ROWS || (c == 4 && (reinterpret_cast<uintptr_t>(points) & 15) == 0);
-    const size_t bin_lds = (size_t)nbins * 4;                 // (at 16384 buckets the scatter's 64 KB + 128 B exceed the default limit)
-    // one-launch partition (k_tile_sort) whenever the frame and the table fit; else, or on request, the three-pass one
-    // tiles of 8192 points (4096: profiles/r04_bucket_target.txt); large frames of the dense contract on C == 4 rows: 16384 -- half
-    // the tiles, so half the table, and k_bucket_index finds a bucket's entries in half as many runs of twice the length
-    const bool big_tiles = ROWS && vec4 && sizeof(typename Key::bin_key_t) == 4 && n >= kBigTileMinPoints;
+    p.mtiles = (uint32_t)(w.npad / kMetaLbTile);
+    const EarlyLayout early = early_layout(p.mtiles, w.npad, meta_lb && o.early_host);
+    p.early_pairs = early.pairs;
+    p.mlb = MetaLb{w.fwords, w.big_count + 40, o.compact_stat, o.compact_tiles, w.big_count + 41, o.early_host, w.fwords + early.at, early.pairs};
+    p.zero_words = meta_lb ? p.mlb.stat : nullptr;
+    p.nzero = early.at + 16u * early.pairs;
+    p.early_tot = early.pairs ? w.fwords + early.at : nullptr;
+    p.zero_ticket = meta_lb ? p.mlb.ticket : nullptr;
+    p.ppos = o.map_later ? p.pbin : nullptr;                    // (pfirst: by point, the first point of its voxel when it is kept)
+    x.voff = o.seg_out ? o.seg_out : (lists ? w.voff : nullptr);
+    p.vec4 = rows || (c == 4 && (reinterpret_cast<uintptr_t>(points) & 15) == 0);
+    const bool big_tiles = wants_big_tiles(rows, p.vec4, key_bytes, n);
     // round 5: the lean bucket kernel + packed first-point entries, whenever k_emit is the consumer and nothing needs the
     // cells' first indices per point (the point -> voxel map, the sparse contract's filters)
-    const bool fm_packed = ROWS && (o.emit_voxels || o.emit_reduce) && !precpos && !o.map_later && !o.trimmed &&
+    const bool fm_packed = rows && (o.emit_voxels || o.emit_reduce) && !p.precpos && !o.map_later && !o.trimmed &&
                            !o.pass.on && n <= kFmMaxPoints;
     x.fm_packed = fm_packed;
     // round 6: the dense contract itself (nothing for the sharded operator, no resident rows, no staged call) leaves through
     // k_emit_split, and part of its zero padding under the index launches (ZeroFill)
-    const bool split = fm_packed && o.emit_voxels && !x.row_state && o.stage == 0 && !x.keys_out && !x.first_out && !x.voff && !want_map;
+    const bool split = fm_packed && o.emit_voxels && !x.row_state && stage == 0 && !x.keys_out && !x.first_out && !x.voff && !want_map;
     // (frames of 0.72 .. 1.3 M points: below, k_emit_split is not store-bound and the fillers only lengthen the partition -- 0.5 M
     // points 71 -> 78 us, 0.1 M 57 -> 64 --, above, every CU has a tile: profiles/r06_ab_sizes.txt)
-    const bool fill_tiles = split && !big_tiles && vec4 && tile_sort && (w.npad >> 13) >= 88 && (w.npad >> 13) <= 160;
-    // tiles of 4096 points while tiles of 8192 would leave a third of the CUs without a workgroup (one workgroup per tile):
-    // 1 M points 16.2 -> 13.7 us with the bucket kernel unchanged; at 2 M points (245 tiles of 8192) +4 us, at 4 M +6; tiles of
-    // 2048 points: +2 us in the bucket kernel (runs of two entries) -- profiles/r05_b_tune.txt.  Round 6: where fillers take the
-    // CUs without a tile, tiles of 8192 it is (those CUs then write 76 MB of zeros in the 16 us).
-    const bool small_tiles = ROWS && !big_tiles && (w.npad >> 13) <= 160 && !fill_tiles;
-    const int tshift = big_tiles ? 14 : small_tiles ? 12 : 13;
-    const uint32_t stiles = (uint32_t)(w.npad >> tshift);
-    uint32_t *table = nullptr, *tileinfo = nullptr, *gpos = reinterpret_cast<uint32_t *>(w.vinfo) + w.npad;
-    if (tile_sort && n <= (ROWS ? kTileSortMaxPoints : kTileSortMaxPointsSparse) && nbins <= 8192u && stiles <= (uint32_t)kRunCap &&
-        ((uint64_t)nbins + 1) * stiles * 4 <= w.cap * 8) {
-        table = tilecnt;
-        tileinfo = tilecnt + (size_t)nbins * stiles;
-    }
+    const bool fill_tiles = split && !big_tiles && p.vec4 && tile_sort && (w.npad >> 13) >= 88 && (w.npad >> 13) <= 160;
+    const TilePlan t = plan_tiles(big_tiles, wants_small_tiles(rows, p.vec4, big_tiles, w.npad, fill_tiles), rows, tile_sort, n, nbins, w);
+    p.tshift = t.tshift;
+    p.stiles = t.stiles;
+    p.table = t.table;
+    p.tileinfo = t.tileinfo;
     // (early zero lines: -6 us at 1 M points, -7 at 2 M, -3 at 4 M, nothing at 8 M, where the launch is in its steady state)
     x.early_zero = fm_packed && n < kBigTileMinPoints;
-    const bool do_index = o.stage != 2;                        // (stage 2: this frame's index was launched by an earlier call)
     // the output stage.  k_emit_split with both roles in ONE workgroup of 512 lanes from 3 M points on (less LDS per wavefront,
     // 32 instead of 28 per CU): 4 M points 384 -> 358 us, 8 M 704 -> 664, a uniform cloud of 1 M 99 -> 93; 2 M and below: the
     // same or worse (config 2 with its fillers 61 -> 65) -- profiles/r06_ab_sizes.txt
-    const Emit out = !ROWS && o.map_later ? Emit::meta_first_lb
-                     : o.stage == 1 ? Emit::none
-                     : !ROWS && std::is_same<Key, DenseKey>::value && o.emit_generic ? Emit::emit_c
-                     : !ROWS || !(o.emit_voxels || o.emit_reduce) ? Emit::meta_first
-                     : split ? (n >= (3ll << 20) ? Emit::split512 : Emit::split256)
-                     : x.row_state && o.emit_voxels ? Emit::resident : Emit::emit;
+    p.out = !rows && o.map_later ? Emit::meta_first_lb
+            : lists && o.emit_generic ? Emit::emit_c
+            : !rows || !(o.emit_voxels || o.emit_reduce) ? Emit::meta_first
+            : split ? (n >= (3ll << 20) ? Emit::split512 : Emit::split256)
+            : x.row_state && o.emit_voxels ? Emit::resident : Emit::emit;
+    p.meta_vinfo = o.agg4 || rows || lists ? w.vinfo : nullptr;
     // voxels[0 .. prefilled): as much as the idle CUs of the two launches write in passing, at most the voxels a LiDAR frame of
     // this size has (9 n / 16; config 2: 0.585 n) and never more than the tensor's rows
-    ZeroFill zf_sort, zf_count;
-    uint32_t prefilled = 0;
-    if (split && table && do_index) {
+    p.prefilled = 0;
+    if (split && p.table && stage != 2) {                       // (stage 2: this frame's index was launched by an earlier call)
+        ZeroFill &zf_sort = p.zf_sort, &zf_count = p.zf_count;
         const int64_t capv = n < (int64_t)o.max_voxels ? n : (int64_t)o.max_voxels;
         const int64_t all16 = (n * 9 / 16 < capv ? n * 9 / 16 : capv) * (int64_t)o.P;
-        const uint32_t sort_wgs = ((stiles + 7u) >> 3) << 3, count_wgs = (uint32_t)(w.npad / kFlagTile);
+        const uint32_t sort_wgs = ((p.stiles + 7u) >> 3) << 3, count_wgs = (uint32_t)(w.npad / kFlagTile);
         int64_t at = 0;
-        if (fill_tiles && tshift == 13 && sort_wgs + 64u <= (uint32_t)kNumCUs) {
+        if (fill_tiles && p.tshift == 13 && sort_wgs + 64u <= (uint32_t)kNumCUs) {
             zf_sort.nblk = (uint32_t)kNumCUs - sort_wgs;
             zf_sort.first = sort_wgs;
             zf_sort.dst = o.emit_voxels;
@@ -4416,123 +4511,156 @@ static int binned_index(const Key &kf, const float *points, int64_t n, int c, co
             if (zf_count.n16 > all16 - at) zf_count.n16 = all16 - at;
             at += zf_count.n16;
         }
-        prefilled = (uint32_t)(at / (int64_t)o.P);
+        p.prefilled = (uint32_t)(at / (int64_t)o.P);
     }
-    if (o.emit_voxels && o.stage == 0) {
-        g_last_plan[0] = out == Emit::split256 || out == Emit::split512;
-        g_last_plan[1] = prefilled;
-        g_last_plan[2] = zf_sort.n16 * 16;
-        g_last_plan[3] = zf_count.n16 * 16;
-    }
-    if (do_index && table) {
-        const size_t lds = ((size_t)1 << tshift) * (sizeof(typename Key::bin_key_t) + 2) + bin_lds;
-        uint32_t *ppos = o.map_later ? pbin : nullptr;      // (pfirst: by point, the first point of its voxel when it is kept)
+    const bool emits = rows && (o.emit_voxels || o.emit_reduce);
+    p.route = lists ? kLists : fm_packed ? kPacked : emits ? kRowLists : kPlain;
+    p.reduction = p.route != kLists && o.agg4 ? o.reduction : (int)D3D_REDUCE_NONE;
+    // (the per-point keys are done with w.big_list; w.unsorted may be precpos)
+    p.sorted_out = p.route != kPlain ? w.big_list : nullptr;
+    p.unsorted_out = p.route == kLists && o.reduction != D3D_REDUCE_NONE ? w.unsorted : nullptr;
+    p.early_clamp = p.route == kPacked ? 0u : x.npoints_clamp;
+    p.idx_bits = p.route == kPacked ? bits_for((u64)(n > 1 ? n - 1 : 1)) : 24;      // (24: the kernel's default)
+    return p;
+}
+
+
+// job 2 of the binned index: partition -> k_bucket_index -> k_first_count
+template <class Key, bool ROWS>
+static int launch_index(const BinnedPlan &p, const Key &kf, const float *points, int64_t n, int c, int64_t *counts, const DenseOut &o,
+                        hipStream_t st)
+{
+    typedef BinEntry<ROWS> E;
+    typename E::type *bent = static_cast<typename E::type *>(p.bent);
+    const float4 *p4 = reinterpret_cast<const float4 *>(points);
+    const uint32_t nbins = p.nbins;
+    const size_t bin_lds = (size_t)nbins * 4;                 // (at 16384 buckets the scatter's 64 KB + 128 B exceed the default limit)
+    if (p.table) {
+        const size_t lds = ((size_t)1 << p.tshift) * (sizeof(typename Key::bin_key_t) + 2) + bin_lds;
         auto sort = [&](auto v4) {
-            return launch_tile_sort<Key, v4, ROWS>(tshift, lds, dim3((((stiles + 7u) >> 3) << 3) + zf_sort.nblk), st, kf, points, n, c,
-                                                   nbins, stiles, bent, table, tileinfo, ppos, firstmap, counts, o.mapping, o.trimmed,
-                                                   o.keepid, zero_words, nzero, zero_ticket, true, zf_sort);
+            return launch_tile_sort<Key, v4, ROWS>(p.tshift, lds, dim3((((p.stiles + 7u) >> 3) << 3) + p.zf_sort.nblk), st, kf, points, n, c,
+                                                   nbins, p.stiles, bent, p.table, p.tileinfo, p.ppos, p.firstmap, counts, o.mapping,
+                                                   o.trimmed, o.keepid, p.zero_words, p.nzero, p.zero_ticket, true, p.zf_sort);
         };
         if constexpr (ROWS) {
             if (const int rc = sort(std::true_type{})) return rc;        // (vec4 whenever ROWS)
-        } else if (const int rc = dispatch(vec4, sort)) return rc;
-    } else if (do_index) {
+        } else if (const int rc = dispatch(p.vec4, sort)) return rc;
+    } else {
+        typename E::key_store_t *pkey = static_cast<typename E::key_store_t *>(p.pkey);
         if (bin_lds + 256 > 65536) {
             D3D_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bin_scatter<ROWS>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds));
         }
-        if (const int rc = dispatch(vec4, [&](auto v4) {
-                D3D_LAUNCH("k_bin_count", (k_bin_count<Key, v4, ROWS>), dim3(ntiles), dim3(kBinThreads), bin_lds, st, kf, points, n, c,
-                           nbins, passes, pbin, pkey, tilecnt, firstmap, counts, o.mapping, o.trimmed, o.keepid, zero_words, nzero,
-                           zero_ticket);
+        if (const int rc = dispatch(p.vec4, [&](auto v4) {
+                D3D_LAUNCH("k_bin_count", (k_bin_count<Key, v4, ROWS>), dim3(p.ntiles), dim3(kBinThreads), bin_lds, st, kf, points, n, c,
+                           nbins, p.passes, p.pbin, pkey, p.tilecnt, p.firstmap, counts, o.mapping, o.trimmed, o.keepid, p.zero_words,
+                           p.nzero, p.zero_ticket);
                 return D3D_OK;
             }))
             return rc;
-        D3D_LAUNCH("k_bin_scan", k_bin_scan, dim3((nbins + kWave - 1) / kWave), dim3(1024), 0, st, tilecnt, nbins, ntiles, totals);
-        D3D_LAUNCH("k_bin_scatter", k_bin_scatter<ROWS>, dim3(ntiles), dim3(kBinThreads), bin_lds, st, pkey, n, nbins, pbin, tilecnt, totals,
-                   bucket_base, bent, counts, o.map_later, passes);
+        D3D_LAUNCH("k_bin_scan", k_bin_scan, dim3((nbins + kWave - 1) / kWave), dim3(1024), 0, st, p.tilecnt, nbins, p.ntiles, p.totals);
+        D3D_LAUNCH("k_bin_scatter", k_bin_scatter<ROWS>, dim3(p.ntiles), dim3(kBinThreads), bin_lds, st, pkey, n, nbins, p.pbin, p.tilecnt,
+                   p.totals, p.bucket_base, bent, counts, o.map_later, p.passes);
     }
-    if (do_index) {
-        // k_bucket_index<Key, ROWS', LISTS, STAGE, V2> by route: the sparse contract's index lists <false, true, false, false>, the
-        // packed first-point entries <true, true, false, true> (fm_packed: no precpos, trimmed, pfirst or early totals), rows with
-        // lists <ROWS, true, false, false>, plain rows <ROWS, false, ROWS, false>
-        enum { kLists, kPacked, kRowLists, kPlain };
-        const int route = !ROWS && o.lists ? kLists : fm_packed ? kPacked : ROWS && (o.emit_voxels || o.emit_reduce) ? kRowLists : kPlain;
-        const int reduction = route != kLists && o.agg4 ? o.reduction : (int)D3D_REDUCE_NONE;
-        // (the per-point keys are done with w.big_list; w.unsorted may be precpos)
-        uint32_t *sorted_out = route != kPlain ? w.big_list : nullptr;
-        uint32_t *unsorted_out = route == kLists && o.reduction != D3D_REDUCE_NONE ? w.unsorted : nullptr;
-        const uint32_t early_clamp = route == kPacked ? 0u : x.npoints_clamp;
-        const int idx_bits = route == kPacked ? bits_for((u64)(n > 1 ? n - 1 : 1)) : 24;      // (24: the kernel's default)
-        auto bucket_index = [&](auto r) {
-            constexpr bool rows = r == kPacked || (r != kLists && ROWS);
-            D3D_LAUNCH("k_bucket_index", (k_bucket_index<Key, rows, r != kPlain, r == kPlain && ROWS, r == kPacked>), dim3(nbins),
-                       dim3(kBucketThreads), 0, st, kf, o.pass, reinterpret_cast<const typename BinEntry<rows>::type *>(bent), p4,
-                       bucket_base, hshift, o.P, reduction, w.staged, vrec, firstmap, counts, precpos, w.parr,
-                       reinterpret_cast<uint32_t *>(w.vinfo), o.trimmed, sorted_out, unsorted_out, table, stiles, tshift, tileinfo, gpos,
-                       o.map_later ? pbin : (uint32_t *)nullptr, early_tot, early_clamp, early_pairs ? early_pairs - 1u : 0u, idx_bits);
-            return D3D_OK;
-        };
-        int rc;
-        if constexpr (ROWS) rc = dispatch_int<kLists, kPacked, kRowLists, kPlain>(route, bucket_index);
-        else rc = dispatch_int<kLists, kPlain>(route, bucket_index);          // (the other two need ROWS)
-        if (rc) return rc;
-    }
+    auto bucket_index = [&](auto r) {
+        constexpr bool rows = r == kPacked || (r != kLists && ROWS);
+        D3D_LAUNCH("k_bucket_index", (k_bucket_index<Key, rows, r != kPlain, r == kPlain && ROWS, r == kPacked>), dim3(nbins),
+                   dim3(kBucketThreads), 0, st, kf, o.pass, reinterpret_cast<const typename BinEntry<rows>::type *>(bent), p4,
+                   p.bucket_base, p.hshift, o.P, p.reduction, p.staged, p.vrec, p.firstmap, counts, p.precpos, p.parr, p.vinfo32,
+                   o.trimmed, p.sorted_out, p.unsorted_out, p.table, p.stiles, p.tshift, p.tileinfo, p.gpos, p.ppos, p.early_tot,
+                   p.early_clamp, p.early_pairs ? p.early_pairs - 1u : 0u, p.idx_bits);
+        return D3D_OK;
+    };
+    int rc;
+    if constexpr (ROWS) rc = dispatch_int<kLists, kPacked, kRowLists, kPlain>(p.route, bucket_index);
+    else rc = dispatch_int<kLists, kPlain>(p.route, bucket_index);          // (the other two need ROWS)
+    if (rc) return rc;
+    if (p.out == Emit::meta_first_lb) return D3D_OK;                // (k_meta_first_lb numbers the voxels itself)
+    const unsigned nbF = (unsigned)(p.npad / kFlagTile);            // <= 1024 (n <= 16 M)
+    D3D_LAUNCH("k_first_count", k_first_count, dim3(nbF + p.zf_count.nblk), dim3(1024), 0, st, p.firstmap, p.fwpre, p.bsumF, p.big_count, p.zf_count);
+    return D3D_OK;
+}
+
+// job 3: the output stage of the plan (+ k_map_binned)
+template <class Key, bool ROWS>
+static int launch_output(const BinnedPlan &p, const Key &kf, const float *points, int64_t n, int c, int64_t *counts, const DenseOut &o,
+                         hipStream_t st)
+{
+    typedef BinEntry<ROWS> E;
+    const BinnedExtras &x = p.x;
+    const float4 *p4 = reinterpret_cast<const float4 *>(points);
     if constexpr (!ROWS) {
-        if (out == Emit::meta_first_lb) {
-            D3D_LAUNCH("k_meta_first_lb", k_meta_first_lb<Key>, dim3(mtiles), dim3(kMetaLbThreads), 0, st, kf, w.npad, firstmap, vrec,
-                       o.max_voxels, o.coords, o.npoints, counts, x, mlb, points, c);
+        if (p.out == Emit::meta_first_lb) {
+            D3D_LAUNCH("k_meta_first_lb", k_meta_first_lb<Key>, dim3(p.mtiles), dim3(kMetaLbThreads), 0, st, kf, p.npad, p.firstmap, p.vrec,
+                       o.max_voxels, o.coords, o.npoints, counts, x, p.mlb, points, c);
             return D3D_OK;
         }
     }
-    const unsigned nbF = (unsigned)(w.npad / kFlagTile);            // <= 1024 (n <= 16 M)
-    if (do_index) D3D_LAUNCH("k_first_count", k_first_count, dim3(nbF + zf_count.nblk), dim3(1024), 0, st, firstmap, w.fwpre, w.bsumF, w.big_count, zf_count);
-    if (out == Emit::none) return D3D_OK;
-    const dim3 grid((unsigned)(w.npad / 256));
+    const dim3 grid((unsigned)(p.npad / 256));
     if constexpr (!ROWS && std::is_same<Key, DenseKey>::value) {
-        if (out == Emit::emit_c) {
+        if (p.out == Emit::emit_c) {
             const int pshift = (o.P & (o.P - 1)) == 0 ? __builtin_ctz(o.P) : -1;
             return dispatch_int<3, 5, 6, 7, 8>(c, [&](auto cc) {        // (voxelize_dense_core sends no other C here)
-                D3D_LAUNCH("k_emit_c", (k_emit_c<Key, cc>), grid, dim3(256), 0, st, kf, w.npad, firstmap, w.fwpre, w.bsumF, vrec, o.max_voxels,
-                           points, w.big_list, o.P, pshift, o.reduction, o.coords, o.npoints, o.fuse_pmask ? o.pmask : nullptr, o.aggregates,
-                           w.voff, o.emit_generic, counts, x.host_counts, reinterpret_cast<uint32_t *>(w.vinfo), w.big_count, x.row_state);
+                D3D_LAUNCH("k_emit_c", (k_emit_c<Key, cc>), grid, dim3(256), 0, st, kf, p.npad, p.firstmap, p.fwpre, p.bsumF, p.vrec, o.max_voxels,
+                           points, p.big_list, o.P, pshift, o.reduction, o.coords, o.npoints, o.fuse_pmask ? o.pmask : nullptr, o.aggregates,
+                           p.voff, o.emit_generic, counts, x.host_counts, p.vinfo32, p.big_count, x.row_state);
                 return D3D_OK;
             });
         }
     }
     float4 *agg = o.agg4 ? reinterpret_cast<float4 *>(o.aggregates) : nullptr;
     int rc = D3D_OK;
-    if (out == Emit::meta_first)
+    if (p.out == Emit::meta_first)
         rc = dispatch(o.agg4, [&](auto agg4) {
-            D3D_LAUNCH("k_meta_first", (k_meta_first<Key, agg4>), grid, dim3(256), 0, st, kf, w.npad, firstmap, w.fwpre, w.bsumF, vrec,
-                       o.max_voxels, agg4 || ROWS || o.lists ? w.vinfo : (uint4 *)nullptr, w.staged, o.P, o.reduction, o.coords,
-                       o.npoints, o.fuse_pmask ? o.pmask : nullptr, agg, counts, x, points, c);
+            D3D_LAUNCH("k_meta_first", (k_meta_first<Key, agg4>), grid, dim3(256), 0, st, kf, p.npad, p.firstmap, p.fwpre, p.bsumF, p.vrec,
+                       o.max_voxels, p.meta_vinfo, p.staged, o.P, o.reduction, o.coords, o.npoints, o.fuse_pmask ? o.pmask : nullptr, agg,
+                       counts, x, points, c);
             return D3D_OK;
         });
     else if constexpr (ROWS) {
         const int pshift = (o.P & (o.P - 1)) == 0 ? __builtin_ctz(o.P) : -1;
         rc = dispatch(o.agg4, [&](auto agg4) {
-            if (out == Emit::split256 || out == Emit::split512)
-                return dispatch(out == Emit::split512, [&](auto wide) {
+            if (p.out == Emit::split256 || p.out == Emit::split512)
+                return dispatch(p.out == Emit::split512, [&](auto wide) {
                     constexpr int wg = wide ? 512 : 256;             // 256: two workgroups per 256 points, one per role
                     D3D_LAUNCH("k_emit_split", (k_emit_split<Key, agg4, wg>), dim3(wide ? grid.x : 2u * grid.x), dim3(wg), 0, st, kf,
-                               w.npad, firstmap, w.fwpre, w.bsumF, vrec, o.max_voxels, p4, w.big_list, w.staged, o.P, pshift,
+                               p.npad, p.firstmap, p.fwpre, p.bsumF, p.vrec, o.max_voxels, p4, p.big_list, p.staged, o.P, pshift,
                                o.reduction, o.coords, o.npoints, o.fuse_pmask ? o.pmask : nullptr, agg, o.emit_voxels, counts,
-                               x.host_counts, prefilled, x.aux_value);
+                               x.host_counts, p.prefilled, x.aux_value);
                     return D3D_OK;
                 });
-            return dispatch(out == Emit::resident, [&](auto resident) {
-                D3D_LAUNCH(resident ? "k_emit_resident" : "k_emit", (k_emit<Key, agg4, resident>), grid, dim3(256), 0, st, kf, w.npad,
-                           firstmap, w.fwpre, w.bsumF, vrec, o.max_voxels, p4, w.big_list, w.staged, o.P, pshift, o.reduction,
+            return dispatch(p.out == Emit::resident, [&](auto resident) {
+                D3D_LAUNCH(resident ? "k_emit_resident" : "k_emit", (k_emit<Key, agg4, resident>), grid, dim3(256), 0, st, kf, p.npad,
+                           p.firstmap, p.fwpre, p.bsumF, p.vrec, o.max_voxels, p4, p.big_list, p.staged, o.P, pshift, o.reduction,
                            o.coords, o.npoints, o.fuse_pmask ? o.pmask : nullptr, agg, o.emit_voxels, counts, x.host_counts, x);
                 return D3D_OK;
             });
         });
     }
     if (rc) return rc;
-    if (want_map && !o.map_later)
-        D3D_LAUNCH("k_map_binned", k_map_binned, dim3(grid_for(n, 256)), dim3(256), 0, st, bucket_base, nbins, precpos,
-                   reinterpret_cast<const uint32_t *>(bent), E::kIdxStride, E::kIdxOff, x.vidof, o.mapping, o.keepid,
-                   (const unsigned char *)o.trimmed, (const uint32_t *)tileinfo, stiles, tshift);
+    if (p.precpos)                                                  // a point -> voxel map that no later scan of the caller computes
+        D3D_LAUNCH("k_map_binned", k_map_binned, dim3(grid_for(n, 256)), dim3(256), 0, st, p.bucket_base, p.nbins, p.precpos,
+                   static_cast<const uint32_t *>(p.bent), E::kIdxStride, E::kIdxOff, x.vidof, o.mapping, o.keepid,
+                   (const unsigned char *)o.trimmed, (const uint32_t *)p.tileinfo, p.stiles, p.tshift);
+    return D3D_OK;
+}
+
+// The binned index, whole (stage 0) or the half of it a staged call asks for: plan, then the launchers.
+// ROWS: dense contract on C == 4 rows (ranked rows staged, reductions); !ROWS: keys only (sparse contract, any C)
+template <class Key, bool ROWS>
+static int binned_index(const Key &kf, const float *points, int64_t n, int c, const VoxelWs &w, uint32_t nbins, int hshift,
+                        int64_t *counts, const DenseOut &o, hipStream_t st, bool tile_sort, int stage = 0)
+{
+    const BinnedPlan p = plan_binned(ROWS, (int)sizeof(typename Key::bin_key_t), points, n, c, w, nbins, hshift, o, tile_sort, stage);
+    if (o.emit_voxels && stage == 0) {
+        g_last_plan[0] = p.out == Emit::split256 || p.out == Emit::split512;
+        g_last_plan[1] = p.prefilled;
+        g_last_plan[2] = p.zf_sort.n16 * 16;
+        g_last_plan[3] = p.zf_count.n16 * 16;
+    }
+    if (stage != 2)                                            // (stage 2: this frame's index was launched by an earlier call)
+        if (const int rc = launch_index<Key, ROWS>(p, kf, points, n, c, counts, o, st)) return rc;
+    if (stage != 1) return launch_output<Key, ROWS>(p, kf, points, n, c, counts, o, st);
     return D3D_OK;
 }
 
@@ -4547,23 +4675,24 @@ static int sparse_fused_index(const BoundKey &kf, const float *points, int64_t n
                               hipStream_t st)
 {
     typedef BinEntry<true> E;
-    if (n > kFmMaxPoints || nbins > 8192u) return D3D_ERR_UNSUPPORTED;
+    if (n > kFmMaxPoints) return D3D_ERR_UNSUPPORTED;
     const bool vec4 = c == 4 && ((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(out_feats)) & 15) == 0;
-    const bool big_tiles = vec4 && n >= kBigTileMinPoints;
-    const int tshift = big_tiles ? 14 : vec4 && (w.npad >> 13) <= 160 ? 12 : 13;    // (binned_index's tile sizes, without fillers)
-    const uint32_t stiles = (uint32_t)(w.npad >> tshift);
-    if (n > kTileSortMaxPoints || stiles > (uint32_t)kRunCap || ((uint64_t)nbins + 1) * stiles * 4 > w.cap * 8) return D3D_ERR_UNSUPPORTED;
+    // binned_index's tiles on 4-byte keys with rows, without fillers; no three-pass partition behind this call
+    const bool big_tiles = wants_big_tiles(true, vec4, (int)sizeof(BoundKey::bin_key_t), n);
+    const TilePlan t = plan_tiles(big_tiles, wants_small_tiles(true, vec4, big_tiles, w.npad, false), true, true, n, nbins, w);
+    if (!t.table) return D3D_ERR_UNSUPPORTED;
+    const int tshift = t.tshift;
+    const uint32_t stiles = t.stiles;
     E::type *bent = reinterpret_cast<E::type *>(w.tabA);
-    uint32_t *table = reinterpret_cast<uint32_t *>(w.tabB), *tileinfo = table + (size_t)nbins * stiles;
+    uint32_t *table = t.table, *tileinfo = t.tileinfo;
     uint4 *vrec = reinterpret_cast<uint4 *>(w.aux);
     uint32_t *firstmap = w.list, *phandle = w.pslot;
     uint32_t *gpos = reinterpret_cast<uint32_t *>(w.vinfo) + w.npad;
     // look-back words of k_sparse_finish (two per tile of 4096 points) and, behind them, up to 64 pairs of early totals
+    // (also without a host buffer: k_sparse_finish learns from them that max_voxels cannot cut)
     const uint32_t ftiles = (uint32_t)(w.npad / kFinTile);
-    const uint32_t early_at = (2 * ftiles + 15u) & ~15u;
-    uint32_t early_pairs = 64;       // (also without a host buffer: k_sparse_finish learns from them that max_voxels cannot cut)
-    for (; early_pairs > 1 && (uint64_t)early_at + 16ull * early_pairs > (uint64_t)(w.npad / 64); early_pairs >>= 1) { }
-    if ((uint64_t)early_at + 16ull * early_pairs > (uint64_t)(w.npad / 64)) early_pairs = 0;
+    const EarlyLayout early = early_layout(ftiles, w.npad, true);
+    const uint32_t early_at = early.at, early_pairs = early.pairs;
     u64 *early_tot = early_pairs ? w.fwords + early_at : nullptr;
     unsigned int *ticket = w.big_count + 40;
     const size_t lds = ((size_t)1 << tshift) * (sizeof(uint32_t) + 2) + (size_t)nbins * 4;
@@ -4670,30 +4799,6 @@ static int dense_meta(const DenseKey &kf, const float *points, const VoxelWs &w,
 static int voxelize_dense_core(const float *points, int64_t n, int32_t c, const int32_t *shape, const float *bound,
                                int32_t max_points, int32_t max_voxels, int32_t reduction, float *voxels, int64_t *coords,
                                uint8_t *pmask, int32_t *npoints, float *aggregates, int64_t *counts, void *workspace,
-                               size_t workspace_bytes, void *stream, int64_t *host_counts, uint32_t flags, int stage, uint16_t *row_state);
-
-static int voxelize_dense_impl(const float *points, int64_t n, int32_t c, const int32_t *shape, const float *bound,
-                               int32_t max_points, int32_t max_voxels, int32_t reduction, float *voxels, int64_t *coords,
-                               uint8_t *pmask, int32_t *npoints, float *aggregates, int64_t *counts, void *workspace,
-                               size_t workspace_bytes, void *stream, int64_t *host_counts, uint32_t flags, int stage = 0,
-                               uint16_t *row_state = nullptr)
-{
-    int rc = voxelize_dense_core(points, n, c, shape, bound, max_points, max_voxels, reduction, voxels, coords, pmask, npoints,
-                                 aggregates, counts, workspace, workspace_bytes, stream, host_counts, flags, stage, row_state);
-    if (rc == D3D_OK && (flags & D3D_VOXEL_EXACT_MEAN) && reduction == D3D_REDUCE_MEAN && max_points > 0 && max_voxels > 0 && n > 0 &&
-        stage != 1) {
-        DenseKey kf;
-        rc = make_dense_key(shape, bound, kf);
-        if (rc) return rc;
-        const VoxelWs w = carve(workspace, workspace_bytes, n, 0);
-        rc = exact_mean_pass(kf, points, n, c, (uint32_t)max_points, coords, npoints, aggregates, counts, w, (hipStream_t)stream);
-    }
-    return rc;
-}
-
-static int voxelize_dense_core(const float *points, int64_t n, int32_t c, const int32_t *shape, const float *bound,
-                               int32_t max_points, int32_t max_voxels, int32_t reduction, float *voxels, int64_t *coords,
-                               uint8_t *pmask, int32_t *npoints, float *aggregates, int64_t *counts, void *workspace,
                                size_t workspace_bytes, void *stream, int64_t *host_counts, uint32_t flags, int stage, uint16_t *row_state)
 {
     hipStream_t st = (hipStream_t)stream;
@@ -4732,14 +4837,12 @@ static int voxelize_dense_core(const float *points, int64_t n, int32_t c, const 
         // staged calls (d3d_voxelize_3d_dense_staged): only the path whose output is ONE launch
         if (stage != 0 && !(emitted && fuse_pmask)) return D3D_ERR_UNSUPPORTED;
         d.x.row_state = row_state;
-        d.stage = stage;
         if (vec4) {
             if (row_state && !emitted) return D3D_ERR_UNSUPPORTED;       // (resident rows: the one-launch output kernels only)
-            rc = binned_index<DenseKey, true>(kf, points, n, c, w, nbins, hshift, counts, d, st, !(flags & D3D_VOXEL_PARTITION_3PASS));
+            rc = binned_index<DenseKey, true>(kf, points, n, c, w, nbins, hshift, counts, d, st, !(flags & D3D_VOXEL_PARTITION_3PASS), stage);
         } else {
             // any C: the {cell, index} entries travel alone, the bucket kernel leaves per-voxel index lists in point order
             // and the generic output kernels below gather through them
-            d.lists = true;
             lists_ready = true;
             if ((c == 3 || (c >= 5 && c <= 8)) && P > 0 && P <= (uint32_t)kEmitCap && (P * (uint32_t)c) % 4 == 0 &&
                 (reinterpret_cast<uintptr_t>(voxels) & 15) == 0 && !(flags & D3D_VOXEL_SPLIT_FILL)) {
@@ -4747,7 +4850,7 @@ static int voxelize_dense_core(const float *points, int64_t n, int32_t c, const 
                 emitted_generic = true;
             }
             if (row_state && !emitted_generic) return D3D_ERR_UNSUPPORTED;
-            rc = binned_index<DenseKey, false>(kf, points, n, c, w, nbins, hshift, counts, d, st, !(flags & D3D_VOXEL_PARTITION_3PASS));
+            rc = binned_index<DenseKey, false>(kf, points, n, c, w, nbins, hshift, counts, d, st, !(flags & D3D_VOXEL_PARTITION_3PASS), stage);
         }
         if (rc) return rc;
     } else {
@@ -4790,6 +4893,25 @@ static int voxelize_dense_core(const float *points, int64_t n, int32_t c, const 
         D3D_LAUNCH("k_aggregate", k_aggregate, dim3(grid_for(cap * c, 256)), dim3(256), 0, st, points, c, counts, npoints,
                    w.voff, lists_ready ? w.big_list : w.list, w.unsorted, P, reduction, aggregates);
     return D3D_OK;
+}
+
+static int voxelize_dense_impl(const float *points, int64_t n, int32_t c, const int32_t *shape, const float *bound,
+                               int32_t max_points, int32_t max_voxels, int32_t reduction, float *voxels, int64_t *coords,
+                               uint8_t *pmask, int32_t *npoints, float *aggregates, int64_t *counts, void *workspace,
+                               size_t workspace_bytes, void *stream, int64_t *host_counts, uint32_t flags, int stage = 0,
+                               uint16_t *row_state = nullptr)
+{
+    int rc = voxelize_dense_core(points, n, c, shape, bound, max_points, max_voxels, reduction, voxels, coords, pmask, npoints,
+                                 aggregates, counts, workspace, workspace_bytes, stream, host_counts, flags, stage, row_state);
+    if (rc == D3D_OK && (flags & D3D_VOXEL_EXACT_MEAN) && reduction == D3D_REDUCE_MEAN && max_points > 0 && max_voxels > 0 && n > 0 &&
+        stage != 1) {
+        DenseKey kf;
+        rc = make_dense_key(shape, bound, kf);
+        if (rc) return rc;
+        const VoxelWs w = carve(workspace, workspace_bytes, n, 0);
+        rc = exact_mean_pass(kf, points, n, c, (uint32_t)max_points, coords, npoints, aggregates, counts, w, (hipStream_t)stream);
+    }
+    return rc;
 }
 
 // What the calling thread's last d3d_voxelize_3d_dense[_notify] launched (bench.py prices k_emit_split on the bytes IT moves):
