@@ -715,10 +715,12 @@ extern "C" int d3d_pdist2dr_backward(const void *points, int64_t n, const void *
     hipStream_t st = (hipStream_t)stream;
     if (n < 0 || m < 0 || (dtype != D3D_F32 && dtype != D3D_F64)) return D3D_ERR_BAD_ARG;
     const size_t es = dtype == D3D_F64 ? 8 : 4;
-    if (m > 0) { if (!grad_boxes) return D3D_ERR_BAD_ARG; D3D_HIP_CHECK(hipMemsetAsync(grad_boxes, 0, (size_t)m * 5 * es, st)); }
-    if (n > 0) { if (!grad_points) return D3D_ERR_BAD_ARG; D3D_HIP_CHECK(hipMemsetAsync(grad_points, 0, (size_t)n * 2 * es, st)); }
+    // every refusal first: a refused call writes nothing
+    if ((m > 0 && !grad_boxes) || (n > 0 && !grad_points)) return D3D_ERR_BAD_ARG;
+    if (n > 0 && m > 0 && (!points || !boxes || !grad || d3d_divup(m, kRows) > 65535)) return D3D_ERR_BAD_ARG;
+    if (m > 0) D3D_HIP_CHECK(hipMemsetAsync(grad_boxes, 0, (size_t)m * 5 * es, st));
+    if (n > 0) D3D_HIP_CHECK(hipMemsetAsync(grad_points, 0, (size_t)n * 2 * es, st));
     if (n == 0 || m == 0) return D3D_OK;
-    if (!points || !boxes || !grad || d3d_divup(m, kRows) > 65535) return D3D_ERR_BAD_ARG;
     const dim3 grid((unsigned)d3d_divup(n, kCols), (unsigned)d3d_divup(m, kRows));
     return dispatch_dtype<D3D_F32, D3D_F64>(dtype, [&](auto p) {
         typedef typename decltype(p)::T T;

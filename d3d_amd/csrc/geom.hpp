@@ -1201,21 +1201,38 @@ __device__ __forceinline__ T point_box_distance(const BoxGeom<T> &b, T w, T h, T
     const T cx[4] = {-b.ux - b.vx, b.ux - b.vx, b.ux + b.vx, -b.ux + b.vx};
     const T cy[4] = {-b.uy - b.vy, b.uy - b.vy, b.uy + b.vy, -b.uy + b.vy};
     T best = -1, bdx = 0, bdy = 0;
+    T tr[4];                                                      // the edges' own t, before it is clamped (GRAD)
     bool inside = true;
     feat = 0;
 #pragma unroll
     for (int e = 0; e < 4; e++) {
-        const T ex = cx[(e + 1) & 3] - cx[e], ey = cy[(e + 1) & 3] - cy[e], rx = rx0 - cx[e], ry = ry0 - cy[e];
+        // edge e = corner e -> e + 1: 2u, 2v, -2u, -2v -- taken from u and v, not as the difference of two corners, which for a
+        // slender box rounds the short edge to eps * the LONG half-extent (a box 0.1 x 5: 50 eps on the normal's direction)
+        const T ex = (e & 1 ? b.vx : b.ux) * (e & 2 ? (T)-2 : (T)2), ey = (e & 1 ? b.vy : b.uy) * (e & 2 ? (T)-2 : (T)2);
+        const T rx = rx0 - cx[e], ry = ry0 - cy[e];
         if (ex * ry - ey * rx < 0) inside = false;
         const T len2 = ex * ex + ey * ey;
         T t = len2 > 0 ? (rx * ex + ry * ey) / len2 : 0;
         int f = e;
+        tr[e] = t;
         if (t <= 0) { t = 0; f = 4 + e; } else if (t >= 1) { t = 1; f = 4 + ((e + 1) & 3); }
         const T dx = rx - t * ex, dy = ry - t * ey, d2 = dx * dx + dy * dy;
         if (best < 0 || d2 < best) { best = d2; feat = f; bdx = dx; bdy = dy; }
     }
     const T d = sqrt(best);
     if (GRAD) {
+        // A corner is the nearest point only beyond the ends of BOTH its edges.  The squared distances cannot tell: beside an
+        // edge, a fraction sqrt(eps) of the point's distance from its end, the corner's rounds to the same number and the
+        // first minimum keeps the corner -- whose gradient points sqrt(eps) (fp32: 3e-4) away from the edge's normal.
+        if (feat >= 4) {
+            const int k = feat - 4, km = (k + 3) & 3;
+            const T tk = k == 0 ? tr[0] : k == 1 ? tr[1] : k == 2 ? tr[2] : tr[3];
+            const T tm = km == 0 ? tr[0] : km == 1 ? tr[1] : km == 2 ? tr[2] : tr[3];
+            if (!(tk <= 0 && tm >= 1)) {
+                if (tk > 0 && tk < 1) feat = k;
+                else if (tm > 0 && tm < 1) feat = km;
+            }
+        }
 #pragma unroll
         for (int k = 0; k < 5; k++) gb[k] = 0;
         gp[0] = 0; gp[1] = 0;
@@ -1229,7 +1246,8 @@ __device__ __forceinline__ T point_box_distance(const BoxGeom<T> &b, T w, T h, T
         } else {
             // nearest point inside edge k: dist = n . (p - c_k) with n the inward unit normal (left of the edge direction)
             const int k = feat;
-            const T ex = cx[(k + 1) & 3] - cx[k], ey = cy[(k + 1) & 3] - cy[k], len = sqrt(ex * ex + ey * ey);
+            const T ex = (k & 1 ? b.vx : b.ux) * (k & 2 ? (T)-2 : (T)2), ey = (k & 1 ? b.vy : b.uy) * (k & 2 ? (T)-2 : (T)2);
+            const T len = sqrt(ex * ex + ey * ey);
             const T nx = -ey / len, ny = ex / len;
             gp[0] = nx; gp[1] = ny;
             corner_chain<T>(b, (T)1 / w, (T)1 / h, k, -nx, -ny, gb);           // - n . d(c_k)

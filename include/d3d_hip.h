@@ -552,7 +552,8 @@ int d3d_iou2dr_flags(const void *boxes1, int64_t n, const void *boxes2, int64_t 
  * dist_cuda.cu:10-80; Python box2dr_pdist / box3dr_pdist, box/__init__.py:333-381): SIGNED distance from points[n,2] to the
  * boundary of boxes[m,5], positive inside; dist[m,n] (box-major, as dist.cpp:39), iedge[m,n] (may be NULL) = nearest edge k
  * (corner k -> k + 1) or 4 + k when the nearest boundary point is corner k.  backward: grad[m,n] -> grad_boxes[m,5],
- * grad_points[n,2] (both overwritten; the reference's CUDA kernel accumulates them with a data race, dist_cuda.cu:78-79). */
+ * grad_points[n,2] (both overwritten; the reference's CUDA kernel accumulates them with a data race, dist_cuda.cu:78-79).
+ * A call that returns D3D_ERR_BAD_ARG has written nothing. */
 int d3d_pdist2dr_forward(const void *points, int64_t n, const void *boxes, int64_t m, int32_t dtype, void *dist,
                          uint8_t *iedge, void *stream);
 int d3d_pdist2dr_backward(const void *points, int64_t n, const void *boxes, int64_t m, const void *grad, int32_t dtype,
