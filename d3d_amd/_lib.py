@@ -127,6 +127,9 @@ SIGNATURES = {
     "d3d_nms2d": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _sz, _vp, _u32]),
     "d3d_nms2d_notify": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _sz, _vp, _u32, _vp]),
     "d3d_nms2d_status": (ctypes.c_int, [_vp, _i32, _vp, _vp]),
+    "d3d_nms2d_group_max": (_i32, []),
+    "d3d_nms2d_grouped_workspace_bytes": (_sz, [_i64, _i64]),
+    "d3d_nms2d_grouped": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _sz, _vp, _u32]),
     "d3d_segeval_workspace_bytes": (_sz, [_i64, _i64]),
     "d3d_segeval": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.POINTER(ctypes.c_uint32), _i32, _i32,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -390,6 +390,91 @@ def box2d_nms(boxes, scores, iou_method="box", supression_method="hard",
     return _egress(keep, was_numpy)
 
 
+def _group_ids(groups):
+    """groups as an int64 torch tensor whose equal values are the caller's equal values (uint64 is reinterpreted: a bijection)"""
+    if isinstance(groups, np.ndarray):
+        if not np.issubdtype(groups.dtype, np.integer):
+            raise TypeError("groups must be an integer array, got %s" % groups.dtype)
+        groups = np.ascontiguousarray(groups)
+        return torch.from_numpy(groups.view(np.int64) if groups.dtype == np.uint64 else groups.astype(np.int64, copy=False))
+    if not torch.is_tensor(groups):
+        raise TypeError("groups must be a torch tensor or a numpy array of integers")
+    if groups.dtype == torch.bool or groups.is_floating_point() or groups.is_complex():
+        raise TypeError("groups must be an integer tensor, got %s" % groups.dtype)
+    if groups.dtype == getattr(torch, "uint64", None):
+        return groups.contiguous().view(torch.int64)
+    return groups.to(torch.int64)
+
+
+def box2d_nms_batched(boxes, scores, groups, iou_method="box", supression_method="hard",
+                      iou_threshold=0, score_threshold=0, supression_param=0, precise=True):
+    """Hard NMS inside every group of a batch -- the (sample, class) groups of a detector's output -- and never across groups;
+    returns the KEEP mask bool[N].  The reference has no counterpart (its nms2d is one loop over one set).
+
+    boxes [N,5], scores [N] or [N,K] and the keywords are box2d_nms's (torch or numpy, CPU or GPU, any strides; the same fp64
+    promotion for `precise`, class-max of 2-D scores, messages, empty result and egress).  groups [N]: any integer dtype, any
+    values (negative, above 2^31, unsorted, with gaps); rows with equal values form a group.  For every group value g, with
+    idx = (groups == g).nonzero() in ascending row order,
+
+        keep[idx] == box2d_nms(boxes[idx], scores[idx], <same keywords>)      bit for bit
+
+    -- ties in score keep ascending row order, and the score-threshold tail never suppresses the top-ranked box of its own
+    group.  One workgroup per group in one launch (d3d_nms2d_grouped); a group above d3d_nms2d_group_max() boxes (1024) goes
+    through nms2d on its own.  Only supression_method="hard": soft-NMS is sequential per set and stays with box2d_nms.
+    """
+    (boxes, scores), was_numpy = _ingress(boxes, scores)
+    wide32 = precise and boxes.dtype == torch.float32 and scores.dtype == torch.float32
+    if precise and not wide32:
+        boxes, scores = boxes.double(), scores.double()
+    if len(boxes) != len(scores):
+        raise ValueError("Numbers of boxes and scores are inconsistent!")
+    groups = _group_ids(groups)
+    if groups.dim() != 1 or len(groups) != len(boxes):
+        raise ValueError("Numbers of boxes and groups are inconsistent!")
+    if scores.dim() == 2:
+        scores = scores.max(axis=1).values
+    if boxes.numel() == 0:
+        return torch.tensor([], dtype=torch.bool)
+    iou_type = getattr(IouType, iou_method.upper())
+    if getattr(SupressionType, supression_method.upper()) != SupressionType.HARD:
+        raise ValueError("box2d_nms_batched does hard NMS only: soft-NMS is sequential per set, use box2d_nms on each group")
+    if iou_type not in (IouType.BOX, IouType.RBOX):
+        raise ValueError("Unsupported iou type!")                   # common.h:25
+    if boxes.dtype != scores.dtype:
+        raise RuntimeError("boxes and scores must have the same dtype")
+    code = _lib.F32_WIDE if wide32 else _dtype_code(boxes)
+    # everything above is host-side: nothing has touched the library or a device
+    lib = _lib.load()
+    odev = boxes.device
+    (b, s), dev = _to_device(boxes, scores)
+    n = b.shape[0]
+    with torch.cuda.device(dev):
+        # stable: the rows of a segment stay in ascending row order, the order ties in score keep
+        ids, perm = torch.sort(groups.to(dev), stable=True)
+        counts = torch.unique_consecutive(ids, return_counts=True)[1]
+        ngroups = counts.numel()
+        seg = torch.zeros((ngroups + 1,), dtype=torch.int64, device=dev)
+        seg[1:] = counts.cumsum(0)
+        largest = int(counts.max())                                  # (the one host read besides the number of groups)
+        cap = int(lib.d3d_nms2d_group_max())
+        keep = torch.empty((n,), dtype=torch.uint8, device=dev)
+        if largest > cap:
+            # the grouped entry skips these segments (their keep bytes stay untouched): each is one set for nms2d
+            sizes, starts = counts.tolist(), seg.tolist()
+            for g, size in enumerate(sizes):
+                if size > cap:
+                    idx = perm[starts[g]:starts[g + 1]]
+                    keep[idx] = nms2d(b[idx], s[idx], iou_type, SupressionType.HARD, iou_threshold, score_threshold,
+                                      supression_param, keep_mask=True, wide32=wide32).view(torch.uint8)
+            largest = max([size for size in sizes if size <= cap], default=0)
+        ws = _lib.workspace(lib.d3d_nms2d_grouped_workspace_bytes(n, ngroups), dev)
+        rc = lib.d3d_nms2d_grouped(_lib.ptr(b), _lib.ptr(s), _lib.ptr(perm), _lib.ptr(seg), n, ngroups, largest, int(iou_type), code,
+                                   float(iou_threshold), float(score_threshold), _lib.ptr(keep), _lib.ptr(ws), ws.numel(),
+                                   _lib.stream_ptr(), _lib.NMS_KEEP_MASK)
+        _lib.check(rc, "nms2d_grouped")
+    return _egress(_lib.to_caller(keep.view(torch.bool), odev, dev), was_numpy)
+
+
 def iou3d(boxes1, boxes2, method="rbox"):
     """Pairwise "3D IoU" of [N,7] x [M,7] boxes (x,y,z,lx,ly,lz,rz) -> f32[N,M]: BEV IoU (rotated for
     'rbox' = box3dr_iou, AABB for 'box' = box3d_iou) times the 1-D z-interval IoU, all in fp32
@@ -594,5 +679,6 @@ nms = box2d_nms
 __all__ = ["Iou2D", "Iou2DR", "GIou2DR", "DIou2DR", "PDist2DR", "iou2d_backward", "iou2dr_backward", "giou2dr_forward",
            "giou2dr_backward", "diou2dr_forward", "diou2dr_backward", "iou2dr_flags", "pdist2dr_forward", "pdist2dr_backward",
            "box2dr_crop", "box3dp_crop", "box2dr_pdist", "box3dr_pdist", "seg1d_pdist", "seg1d_iou", "crop_2dr", "box2d_iou", "box2d_nms",
+           "box2d_nms_batched",
            "iou2d", "iou3d", "nms", "iou2d_forward", "iou2dr_forward", "nms2d", "nms2d_cuda", "argsort_desc", "IouType",
            "SupressionType", "cuda_available"]

@@ -2374,6 +2374,160 @@ int nms_typed(const B *boxes, const B *scores, const int64_t *order, int64_t n, 
     return D3D_OK;
 }
 
+// ---------------------------------------------------------------- grouped NMS (d3d_nms2d_grouped): one workgroup per group
+// A detector's output is B samples x K classes of a few hundred boxes each, and NMS runs inside every (sample, class) group.
+// One workgroup takes one group -- rows perm[seg_offsets[g] .. seg_offsets[g + 1]) -- from the scores to the keep bytes with
+// everything in LDS and no word exchanged with another workgroup.  THREADS (256 or 1024) is also the most boxes the
+// instantiation holds: rank p of the group's score order belongs to thread p, so the wavefront w owns the ranks of chunk w.
+//   1. sort      KeyBits composites with the LOCAL index (ties: ascending position in the segment, i.e. ascending row for a
+//                stable perm), sort_lds as in k_nms_small_front
+//   2. pre-pass  BoxCore, outward-rounded fp32 AABB and area per rank (what k_nms_small_front leaves in the workspace); the
+//                tail with score <= threshold is suppressed up front, never rank 0 of the group (nms.cpp:23-29)
+//   3. sweep     chunk c = ranks 64 c .. 64 c + 63.  (a) the chunk's own triangle: row r (wavefronts take the rows in turn)
+//                against the 64 columns, one per lane -> a ballot word per row; (b) the greedy pass over the 64 rows -- serial,
+//                64 scalar steps -- which every wavefront repeats for itself on the same words instead of waiting for one
+//                wavefront to publish the result (a barrier less per chunk); (c) every later rank that is still open against
+//                the boxes the chunk KEPT.  A suppressed box never suppresses, so the states a chunk starts from are final.
+//                The pair test is k_nms_cand_all's filter (fp32 AABB gap, IoU upper bound) followed by nms_pair_hits: the
+//                decisions are those of the small-set path, pair for pair.
+//   4. write     keep[row] of every rank
+// LDS per workgroup: THREADS x (sizeof(BoxCore<T>) + 16 + 4) + 64 x 8 + THREADS / 8 bytes -- 21.6 KiB (fp64, 256 threads: seven
+// groups per CU), 53 / 85 KiB (fp32 / fp64, 1024 threads); the sort's buffers (24 bytes per entry) lie under the geometry, which
+// is written after the order has been read into registers.  An n x n / 64 hit matrix (128 KiB at 1024 boxes) is never stored.
+// BoxCore<double> is 64 bytes, so a wavefront's own-rank read in (c) is a 4-way bank conflict per 16-lane group; the record is
+// the one nms_pair_hits takes, and the read sits in front of a polygon clip of a few thousand fp64 operations.
+constexpr int kNmsGroupMax = 1024;
+
+template <typename T> static inline size_t nms_group_lds_bytes(int cap)
+{
+    return (size_t)cap * (sizeof(BoxCore<T>) + sizeof(float4) + sizeof(float)) + (size_t)(kWave + cap / kWave) * 8;
+}
+
+template <typename T, bool ROTATED>
+__device__ __forceinline__ bool nms_group_pair(const BoxCore<T> *geom, const float4 *fbox, const float *farea, uint32_t p,
+                                               uint32_t q, const float4 &fb, float ab, float thr)
+{
+    const float4 fa = fbox[p];
+    const float gap = fminf(fminf(fb.z - fa.x, fa.z - fb.x), fminf(fb.w - fa.y, fa.w - fb.y));
+    if (!(gap > 0.f)) return false;
+    if (ROTATED && thr >= 0.f) {                                   // (k_nms_cand_all: the bound is used for rbox only)
+        const float aa = farea[p];
+        const float ix = fminf(fa.z, fb.z) - fmaxf(fa.x, fb.x), iy = fminf(fa.w, fb.w) - fmaxf(fa.y, fb.y);
+        const float iub = fminf(ix * iy, fminf(aa, ab));
+        if (iub * (1.f + thr) < thr * (1.f - 1e-4f) * (aa + ab)) return false;
+    }
+    return nms_pair_hits<T, ROTATED>(geom, p, q, (T)thr);
+}
+
+__device__ __forceinline__ unsigned long long wave_uniform_u64(unsigned long long v)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+template <typename T, typename B, bool ROTATED, int THREADS>
+__global__ __launch_bounds__(THREADS) void k_nms_group(const B *__restrict__ boxes, const B *__restrict__ scores,
+                                                       const int64_t *__restrict__ perm, const int64_t *__restrict__ seg_offsets,
+                                                       float iou_threshold, float score_threshold, uint8_t *__restrict__ keep)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char group_lds[];
+    typedef typename KeyBits<T>::U U;
+    constexpr int NW = THREADS / kWave;
+    static_assert(THREADS <= kNmsGroupMax && sizeof(BoxCore<T>) >= 2 * sizeof(U) + 8, "the sort buffers lie under the geometry");
+    const int64_t seg0 = seg_offsets[blockIdx.x], len = seg_offsets[blockIdx.x + 1] - seg0;
+    // longer than this instantiation holds (above the cap: the caller routes that group elsewhere): nothing is touched
+    if (len <= 0 || len > THREADS) return;
+    const uint32_t n = (uint32_t)len, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    BoxCore<T> *geom = reinterpret_cast<BoxCore<T> *>(group_lds);
+    float4 *fbox = reinterpret_cast<float4 *>(geom + THREADS);
+    float *farea = reinterpret_cast<float *>(fbox + THREADS);
+    unsigned long long *tri = reinterpret_cast<unsigned long long *>(farea + THREADS);   // the chunk's triangle, a word per row
+    unsigned long long *supw = tri + kWave;                                              // suppressed ranks, a word per chunk
+    // ---- 1. sort
+    uint32_t npad = kWave;
+    while (npad < n) npad <<= 1;
+    U *d0 = reinterpret_cast<U *>(group_lds), *d1 = d0 + npad;
+    uint32_t *i0 = reinterpret_cast<uint32_t *>(d1 + npad), *i1 = i0 + npad, *ii;
+    if (threadIdx.x < npad) {
+        const uint32_t e = threadIdx.x;
+        d0[e] = e < n ? KeyBits<T>::desc((T)scores[perm ? perm[seg0 + e] : seg0 + e]) : ~(U)0;   // padding: last, unique
+        i0[e] = e < n ? e : 0x80000000u + e;
+    }
+    __syncthreads();
+    U *d;
+    sort_lds<1>(d0, i0, d1, i1, (int)npad, &d, &ii);
+    const uint32_t p = threadIdx.x;
+    const bool live = p < n;
+    const uint32_t local = live ? ii[p] : 0u;
+    __syncthreads();                                               // (the geometry goes where the sort was)
+    // ---- 2. geometry and score pre-pass
+    int64_t row = 0;
+    bool sup = true;                                               // (ranks past n count as suppressed: they never hit)
+    float4 fb = make_float4(INFINITY, INFINITY, -INFINITY, -INFINITY);
+    float ab = 0.f;
+    if (live) {
+        row = perm ? perm[seg0 + local] : seg0 + local;
+        const BoxGeom<T> g = Box2D<T>::load(boxes + row * 5);
+        geom[p] = core_of(g);
+        fb = make_float4(round_down(g.xmin), round_down(g.ymin), round_up(g.xmax), round_up(g.ymax));
+        ab = round_down(g.area);
+        fbox[p] = fb;
+        farea[p] = ab;
+        sup = p > 0 && !((T)scores[row] > (T)score_threshold);
+    }
+    {
+        const unsigned long long w = __ballot(sup);
+        if (lane == 0) supw[wave] = w;
+    }
+    // ---- 3. sweep
+    const uint32_t nchunks = (n + 63) >> 6;
+    for (uint32_t c = 0; c < nchunks; c++) {
+        __syncthreads();                                           // supw[c] is final; the previous triangle has been read
+        const unsigned long long pre = wave_uniform_u64(supw[c]);
+        const uint32_t q = c * kWave + lane;
+        {                                                          // (a) the chunk's triangle
+            const bool qopen = !((pre >> lane) & 1ull);
+            const float4 fq = qopen ? fbox[q] : make_float4(INFINITY, INFINITY, -INFINITY, -INFINITY);
+            const float aq = qopen ? farea[q] : 0.f;
+            for (uint32_t r = wave; r < (uint32_t)kWave; r += NW) {
+                unsigned long long w = 0;
+                if (!((pre >> r) & 1ull)) {                        // (wave-uniform: a suppressed row suppresses nothing)
+                    const bool hit = qopen && r < lane && nms_group_pair<T, ROTATED>(geom, fbox, farea, c * kWave + r, q, fq, aq, iou_threshold);
+                    w = __ballot(hit);
+                }
+                if (lane == 0) tri[r] = w;
+            }
+        }
+        __syncthreads();
+        // (b) greedy over the chunk's 64 ranks: rank r, unless suppressed by then, suppresses the columns of its row
+        unsigned long long s = pre;
+        {
+            const unsigned long long mine = tri[lane];
+            const int mlo = (int)(uint32_t)mine, mhi = (int)(uint32_t)(mine >> 32);
+#pragma unroll
+            for (int r = 0; r < kWave; r++) {
+                const unsigned long long wr = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane(mhi, r) << 32) |
+                                              (uint32_t)__builtin_amdgcn_readlane(mlo, r);
+                if (!((s >> r) & 1ull)) s |= wr;
+            }
+        }
+        if (wave == c) sup = (s >> lane) & 1ull;
+        else if (wave > c && wave < nchunks) {
+            // (c) the chunk's kept boxes against the open ranks behind it
+            for (unsigned long long k = ~s; k; k &= k - 1) {
+                if (!__ballot(!sup)) break;
+                const uint32_t r = (uint32_t)__builtin_ctzll(k);
+                if (!sup && nms_group_pair<T, ROTATED>(geom, fbox, farea, c * kWave + r, p, fb, ab, iou_threshold)) sup = true;
+            }
+            const unsigned long long w = __ballot(sup);
+            if (lane == 0) supw[wave] = w;
+        }
+    }
+    // ---- 4. write back
+    if (live) keep[row] = sup ? 0 : 1;
+}
+
 // ---------------------------------------------------------------- soft-NMS (linear / gaussian), nms.cpp:32-95
 // Sequential by construction: every kept box rescales the scores of ALL later boxes it overlaps, and the order of the
 // remaining boxes is re-established after every box (an insertion pass that sinks the suppressed ones).  One workgroup
@@ -2855,6 +3009,45 @@ extern "C" int d3d_nms2d_status(const void *workspace, int32_t suppression_type,
     D3D_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     *status = (h.need_sweep ? D3D_NMS_STATUS_DENSE_PATH : 0u) | (h.scan_gave_up ? D3D_NMS_STATUS_SCAN_GAVE_UP : 0u);
     return D3D_OK;
+}
+
+extern "C" int32_t d3d_nms2d_group_max(void) { return kNmsGroupMax; }
+
+// (k_nms_group keeps a group in LDS from its scores to its keep bytes: nothing of it lives in global memory)
+extern "C" size_t d3d_nms2d_grouped_workspace_bytes(int64_t, int64_t) { return 0; }
+
+extern "C" int d3d_nms2d_grouped(const void *boxes, const void *scores, const int64_t *perm, const int64_t *seg_offsets, int64_t n,
+                                 int64_t ngroups, int32_t max_group, int32_t iou_type, int32_t dtype, float iou_threshold,
+                                 float score_threshold, uint8_t *keep, void *workspace, size_t workspace_bytes, void *stream,
+                                 uint32_t flags)
+{
+    (void)workspace;
+    (void)workspace_bytes;
+    hipStream_t st = (hipStream_t)stream;
+    if (n < 0 || ngroups < 0 || ngroups > 0x7fffffffll || (flags & ~(uint32_t)D3D_NMS_KEEP_MASK)) return D3D_ERR_BAD_ARG;
+    if (dtype != D3D_F32 && dtype != D3D_F64 && dtype != D3D_F32_WIDE) return D3D_ERR_UNSUPPORTED;
+    if (iou_type != D3D_IOU_BOX && iou_type != D3D_IOU_RBOX) return D3D_ERR_UNSUPPORTED;   // common.h:25
+    if (n == 0 || ngroups == 0) return D3D_OK;
+    if (!boxes || !scores || !seg_offsets || !keep) return D3D_ERR_BAD_ARG;
+    // 256 threads when no group needs more (several groups per CU), one box per lane of 1024 otherwise
+    const int threads = max_group > 0 && max_group <= 256 ? 256 : kNmsGroupMax;
+    return dispatch_dtype<D3D_F32, D3D_F64, D3D_F32_WIDE>(dtype, [&](auto p) {
+        typedef typename decltype(p)::T T;
+        typedef typename decltype(p)::B B;
+        return dispatch(iou_type == D3D_IOU_RBOX, [&](auto r) {
+            return dispatch_int<256, kNmsGroupMax>(threads, [&](auto t) {
+                constexpr int THREADS = decltype(t)::value;
+                constexpr bool ROT = decltype(r)::value;
+                const size_t lds = nms_group_lds_bytes<T>(THREADS);
+                if (lds > 65536)
+                    D3D_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_nms_group<T, B, ROT, THREADS>),
+                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                D3D_LAUNCH("k_nms_group", (k_nms_group<T, B, ROT, THREADS>), dim3((unsigned)ngroups), dim3(THREADS), lds, st, (const B *)boxes,
+                           (const B *)scores, perm, seg_offsets, iou_threshold, score_threshold, keep);
+                return D3D_OK;
+            });
+        });
+    });
 }
 
 extern "C" int d3d_crop_2dr(const void *points, int64_t n, const void *boxes, int64_t m, int32_t dtype, uint8_t *out,

@@ -708,6 +708,33 @@ int d3d_nms2d_notify(const void *boxes, const void *scores, const int64_t *order
 enum { D3D_NMS_STATUS_DENSE_PATH = 1, D3D_NMS_STATUS_SCAN_GAVE_UP = 2 };
 int d3d_nms2d_status(const void *workspace, int32_t suppression_type, void *stream, uint32_t *status);
 
+/* Hard NMS inside every group of a batch -- the (sample, class) groups of a detector's output -- in ONE launch: a workgroup
+ * per group, the group's sort, geometry and greedy sweep all in LDS (box.hip, k_nms_group).  The reference has no counterpart:
+ * its nms2d is one loop over one set (nms.cpp:10-119), and a caller loops over the groups or shifts their coordinates apart.
+ *   boxes[n,5], scores[n] in `dtype` (D3D_F32 / D3D_F64 / D3D_F32_WIDE, as d3d_nms2d); iou_type BOX or RBOX; others return
+ *   D3D_ERR_UNSUPPORTED, as does any other dtype.
+ *   seg_offsets[ngroups + 1] i64, ascending, seg_offsets[0] >= 0, seg_offsets[ngroups] <= n: group g owns positions
+ *   seg_offsets[g] .. seg_offsets[g + 1] - 1 of perm[] (i64 row numbers, each row in at most one group), or of the rows
+ *   themselves when perm is NULL (rows already grouped contiguously).  Ties in score keep the order of the positions, so a
+ *   STABLE sort of the group ids gives the order d3d_nms2d has on each group alone.
+ *   keep[n] u8, indexed by ROW: for every group of at most d3d_nms2d_group_max() boxes (1024: one box per lane of the
+ *   largest workgroup) exactly the bytes d3d_nms2d writes for that group's rows alone, given D3D_NMS_KEEP_MASK, the same
+ *   thresholds and order = NULL -- key order, the C `float` thresholds against the working type, and the score-threshold tail
+ *   that never suppresses the top-ranked box of ITS OWN group (nms.cpp:23-29) included.  A longer group is SKIPPED: its
+ *   workgroup returns at once and its keep bytes are not written -- hand it to d3d_nms2d.
+ *   max_group: the length of the longest group that is not to be skipped (a host-side hint that only chooses the workgroup
+ *   size: up to 256 -> 256 threads and several groups per CU; 0 or less = unknown -> 1024).  A group longer than a hint of
+ *   256 or less is skipped like one above the cap.
+ *   flags: 0 or D3D_NMS_KEEP_MASK (implied: the keep mask is what is written).  Status code; no allocation, no
+ *   synchronisation, work on `stream` only, capturable in a graph.  The workspace is the caller's; the query currently
+ *   returns 0 (nothing of a group leaves the LDS) and `workspace` may then be NULL.  n == 0 or ngroups == 0: nothing is done. */
+int32_t d3d_nms2d_group_max(void);
+size_t d3d_nms2d_grouped_workspace_bytes(int64_t n, int64_t ngroups);
+int d3d_nms2d_grouped(const void *boxes, const void *scores, const int64_t *perm, const int64_t *seg_offsets,
+                      int64_t n, int64_t ngroups, int32_t max_group, int32_t iou_type, int32_t dtype,
+                      float iou_threshold, float score_threshold, uint8_t *keep,
+                      void *workspace, size_t workspace_bytes, void *stream, uint32_t flags);
+
 /* ------------------------------------------------------------------ d3d/benchmarks: segmentation */
 
 /* replaces SegmentationEvaluator.collect_labels / collect_labels_pano (reference d3d/benchmarks.pyx:977-1075, called from
