@@ -404,11 +404,22 @@ extern "C" int d3d_lsap_batched(const void *cost, int32_t dtype, int64_t ld, con
     return dispatch_dtype<D3D_F32, D3D_F64>(dtype, go);
 }
 
+// the scratch arrays of NNArgs, from its ns and nd
+static void nn_carve(WsCarver &w, NNArgs &a)
+{
+    a.prop = w.take<int32_t>((size_t)a.ns);
+    a.rescan = w.take<int32_t>((size_t)(a.ns + a.nd));
+    a.colkey = w.take<unsigned long long>((size_t)a.nd);
+}
+
 extern "C" size_t d3d_nn_match_workspace_bytes(int64_t ns, int64_t nd)
 {
-    if (ns < 1) ns = 1;
-    if (nd < 1) nd = 1;
-    return d3d_align_up((size_t)ns * 4) + d3d_align_up((size_t)(ns + nd) * 4) + d3d_align_up((size_t)nd * 8) + 256;
+    NNArgs a;
+    a.ns = ns < 1 ? 1 : ns;
+    a.nd = nd < 1 ? 1 : nd;
+    WsCarver w(nullptr, 0);
+    nn_carve(w, a);
+    return w.off;
 }
 
 extern "C" int d3d_nn_match(const float *dist, int64_t ld, const int64_t *src_idx, int64_t ns, const int64_t *dst_idx, int64_t nd,
@@ -428,9 +439,7 @@ extern "C" int d3d_nn_match(const float *dist, int64_t ld, const int64_t *src_id
     a.dist = dist; a.ld = ld; a.src_idx = src_idx; a.dst_idx = dst_idx; a.src_tag = src_tag; a.dst_tag = dst_tag;
     a.dst_thr = dst_threshold; a.src_free = src_free; a.dst_free = dst_free; a.ns = ns; a.nd = nd;
     a.src_match = src_match; a.dst_match = dst_match;
-    a.prop = w.take<int32_t>((size_t)ns);
-    a.rescan = w.take<int32_t>((size_t)(ns + nd));
-    a.colkey = w.take<unsigned long long>((size_t)nd);
+    nn_carve(w, a);
     if (!workspace || !w.ok()) return D3D_ERR_WORKSPACE;
     D3D_HIP_CHECK(hipMemsetAsync(a.colkey, 0xff, (size_t)nd * 8, st));
     D3D_LAUNCH("k_nn_propose", k_nn_propose, dim3((unsigned)d3d_divup(ns, 256 / kWave)), dim3(256), 0, st, a);

@@ -2184,70 +2184,110 @@ static inline bool nms_small_eligible(int64_t n, uint32_t opts)
     return n <= kNmsSmallMax && !(opts & (D3D_NMS_BROAD_SWEEP | D3D_NMS_FORCE_DENSE | D3D_NMS_GENERAL | D3D_NMS_FORCE_LEVELS)) && (opts >> 8) == 0;
 }
 
+// the score order d3d_nms2d makes itself when the caller passes none (nms.cpp:103): the last takes of either NMS layout
+struct OrderWs {
+    int64_t *order;
+    char *sort_ws;                     // of d3d_argsort_desc, sized for fp64 scores (the largest it takes)
+    size_t sort_bytes;
+};
+static OrderWs order_carve(WsCarver &w, int64_t n)
+{
+    OrderWs o;
+    o.order = w.take<int64_t>(n);
+    o.sort_bytes = d3d_argsort_desc_workspace_bytes(n, D3D_F64);
+    o.sort_ws = w.take<char>(o.sort_bytes);
+    return o;
+}
+
+// hard NMS: every array of nms_typed's kernel chains, on all of its routes
+template <typename T> struct NmsWs {
+    NmsFlags *flags;
+    BoxCore<T> *geom;
+    float4 *fbox, *fbx, *fbc;
+    uint8_t *state, *blocked, *regopen;
+    uint32_t *inc_cnt, *inc_off, *inc, *arrival, *rankx, *cellcur, *cellstart, *cellbox, *cellof;
+    float *farea, *gpartial, *carea;
+    unsigned long long *tile_tot, *chunk_tot, *remv, *cand, *mask;
+    unsigned int *tickets;             // [0] k_nms_incscan, [1] k_nms_gridscan
+    NmsCand *cand_hdr;
+    NmsGrid *grid;
+    int32_t *xkey, *perm;
+    char *sort_ws;                     // of d3d_internal_argsort_desc_i32 (the sweep-and-prune order)
+    size_t sort_bytes;
+    unsigned long long cap_auto, cap_e;
+    OrderWs ord;
+};
+// k_nms_prepare and k_nms_regrid_reset clear k_nms_gridscan's ready words and, in the same pass, the word behind them: the two tickets
+constexpr int kChunkTotWords = kGridScanWgs + 1;
+template <typename T>
+static NmsWs<T> nms_carve(WsCarver &w, int64_t n)
+{
+    const int64_t nb = d3d_divup(n, 64);
+    NmsWs<T> a;
+    a.flags = w.take<NmsFlags>(1);                 // at offset 0: d3d_nms2d_status reads it there
+    a.geom = w.take<BoxCore<T>>(nb * 64);
+    a.fbox = w.take<float4>(nb * 64);
+    a.state = w.take<uint8_t>(nb * 64);
+    a.blocked = w.take<uint8_t>(nb * 64);
+    a.inc_cnt = w.take<uint32_t>(nb * 64);
+    a.inc_off = w.take<uint32_t>(nb * 64);
+    a.farea = w.take<float>(nb * 64);
+    static_assert(kIncTile == kScanTile, "workspace sized with kScanTile");
+    a.tile_tot = w.take<unsigned long long>(d3d_divup(nb * 64, kScanTile));
+    a.chunk_tot = w.take<unsigned long long>(kChunkTotWords);
+    a.tickets = reinterpret_cast<unsigned int *>(a.chunk_tot + kGridScanWgs);
+    a.remv = w.take<unsigned long long>(nb);
+    a.cand_hdr = w.take<NmsCand>(1);
+    // the arrays are carved for the automatic capacity; a per-call override (D3D_NMS_CAND_CAP, tests of the overflow -> dense
+    // path hand-over) can only shrink what is used of them
+    a.cap_auto = nms_cand_capacity(n);
+    a.cand = w.take<unsigned long long>((size_t)a.cap_auto);
+    a.inc = w.take<uint32_t>((size_t)a.cap_auto);                     // hits <= candidates
+    a.arrival = w.take<uint32_t>((size_t)a.cap_auto);
+    a.xkey = w.take<int32_t>(nb * 64);
+    a.perm = w.take<int32_t>(nb * 64);
+    a.fbx = w.take<float4>(nb * 64 + kCandPad);                       // k_nms_xgather's sentinels, read by k_nms_cand
+    a.rankx = w.take<uint32_t>(nb * 64);
+    a.sort_bytes = d3d_internal_argsort_i32_bytes(n);
+    a.sort_ws = w.take<char>(a.sort_bytes);
+    a.mask = w.take<unsigned long long>((size_t)nb * 64 * nb);
+    // uniform-grid broad phase
+    a.cap_e = (unsigned long long)kGridReg * (unsigned long long)(nb * 64);
+    a.cellcur = w.take<uint32_t>((size_t)(kGridCells + 1) * kGridPad);
+    a.cellstart = w.take<uint32_t>(kGridCells + 1);
+    a.gpartial = w.take<float>((size_t)d3d_divup(nb * 64, 256) * 6);
+    a.grid = w.take<NmsGrid>(1);
+    a.cellbox = w.take<uint32_t>((size_t)a.cap_e);
+    a.cellof = w.take<uint32_t>((size_t)a.cap_e);
+    a.fbc = w.take<float4>((size_t)a.cap_e);
+    a.carea = w.take<float>((size_t)a.cap_e);
+    a.regopen = w.take<uint8_t>((size_t)a.cap_e);
+    a.ord = order_carve(w, n);
+    return a;
+}
+
 template <typename T, typename B = T>
 int nms_typed(const B *boxes, const B *scores, const int64_t *order, int64_t n, int iou_type, float iou_thr,
-              float score_thr, uint8_t *suppressed, void *ws, size_t ws_bytes, hipStream_t st, uint32_t opts, int64_t *order_ws,
-              int32_t *host_word)
+              float score_thr, uint8_t *suppressed, const NmsWs<T> &a, hipStream_t st, uint32_t opts, int32_t *host_word)
 {
     const int64_t nb = d3d_divup(n, 64);
     const uint8_t inv = (opts & D3D_NMS_KEEP_MASK) ? 1 : 0;        // the mask comes out inverted: what box2d_nms returns
-    WsCarver w(ws, ws_bytes);
-    NmsFlags *flags = w.take<NmsFlags>(1);                 // at offset 0: d3d_nms2d_status reads it there
-    BoxCore<T> *geom = w.take<BoxCore<T>>(nb * 64);
-    float4 *fbox = w.take<float4>(nb * 64);
-    uint8_t *state = w.take<uint8_t>(nb * 64);
-    uint8_t *blocked = w.take<uint8_t>(nb * 64);
-    uint32_t *inc_cnt = w.take<uint32_t>(nb * 64);
-    uint32_t *inc_off = w.take<uint32_t>(nb * 64);
-    float *farea = w.take<float>(nb * 64);
-    unsigned long long *tile_tot = w.take<unsigned long long>(d3d_divup(nb * 64, kScanTile) + 1 + kGridScanWgs + 1);
-    unsigned long long *chunk_tot = tile_tot + d3d_divup(nb * 64, kScanTile) + 1;
-    unsigned int *tickets = reinterpret_cast<unsigned int *>(chunk_tot + kGridScanWgs);     // [0] k_nms_incscan, [1] k_nms_gridscan
-    (void)w.take<int64_t>(D3D_NUM_COUNTS);
-    static_assert(kIncTile == kScanTile, "workspace sized with kScanTile");
-    unsigned long long *remv = w.take<unsigned long long>(nb);
-    NmsCand *cand_hdr = w.take<NmsCand>(1);
-    // the arrays are carved for the automatic capacity (what the workspace query counts); a per-call override
-    // (D3D_NMS_CAND_CAP, tests of the overflow -> dense path hand-over) can only shrink what is used of them
-    const unsigned long long cap_auto = nms_cand_capacity(n);
-    unsigned long long cap = cap_auto;
+    unsigned long long cap = a.cap_auto;
     if ((opts >> 8) != 0 && (unsigned long long)(opts >> 8) < cap) cap = opts >> 8;
-    unsigned long long *cand = w.take<unsigned long long>((size_t)cap_auto);
-    uint32_t *inc = w.take<uint32_t>((size_t)cap_auto);                     // hits <= candidates
-    uint32_t *arrival = w.take<uint32_t>((size_t)cap_auto);
-    int32_t *xkey = w.take<int32_t>(nb * 64);
-    int32_t *perm = w.take<int32_t>(nb * 64);
-    float4 *fbx = w.take<float4>(nb * 64 + kCandPad);
-    uint32_t *rankx = w.take<uint32_t>(nb * 64);
-    const size_t sort_bytes = d3d_internal_argsort_i32_bytes(n);
-    char *sort_ws = w.take<char>(sort_bytes);
-    unsigned long long *mask = w.take<unsigned long long>((size_t)nb * 64 * nb);
-    // uniform-grid broad phase
-    const unsigned long long cap_e = (unsigned long long)kGridReg * (unsigned long long)(nb * 64);
-    uint32_t *cellcur = w.take<uint32_t>((size_t)(kGridCells + 1) * kGridPad);
-    uint32_t *cellstart = w.take<uint32_t>(kGridCells + 1);
-    float *gpartial = w.take<float>((size_t)d3d_divup(nb * 64, 256) * 6);
-    NmsGrid *grid = w.take<NmsGrid>(1);
-    uint32_t *cellbox = w.take<uint32_t>((size_t)cap_e);
-    uint32_t *cellof = w.take<uint32_t>((size_t)cap_e);
-    float4 *fbc = w.take<float4>((size_t)cap_e);
-    float *carea = w.take<float>((size_t)cap_e);
-    uint8_t *regopen = w.take<uint8_t>((size_t)cap_e);
-    if (!ws || !w.ok()) return D3D_ERR_WORKSPACE;
     const bool rot = iou_type == D3D_IOU_RBOX;
     // the narrow phase and the dense fallback's pair matrix, on both paths
     const unsigned hits_blocks = (unsigned)std::min<unsigned long long>(d3d_divup((int64_t)cap, 256), 4096);
     const auto hits = [&](const uint32_t *rank) {
         return dispatch(rot, [&](auto r) {
-            D3D_LAUNCH("k_nms_hits", (k_nms_hits<T, r>), dim3(hits_blocks), dim3(256), 0, st, geom, rank, cand, cap, cand_hdr, (T)iou_thr,
-                       inc_cnt, arrival);
+            D3D_LAUNCH("k_nms_hits", (k_nms_hits<T, r>), dim3(hits_blocks), dim3(256), 0, st, a.geom, rank, a.cand, cap, a.cand_hdr, (T)iou_thr,
+                       a.inc_cnt, a.arrival);
             return D3D_OK;
         });
     };
     const auto pairs = [&]() {
         const unsigned pair_blocks = (unsigned)std::min<int64_t>(d3d_divup(nb, kColsPerBlock) * d3d_divup(nb, 4), 8192);
         return dispatch(rot, [&](auto r) {
-            D3D_LAUNCH("k_nms_pairs", (k_nms_pairs<T, r>), dim3(pair_blocks), dim3(256), 0, st, geom, fbox, n, nb, (T)iou_thr, mask, flags);
+            D3D_LAUNCH("k_nms_pairs", (k_nms_pairs<T, r>), dim3(pair_blocks), dim3(256), 0, st, a.geom, a.fbox, n, nb, (T)iou_thr, a.mask, a.flags);
             return D3D_OK;
         });
     };
@@ -2259,41 +2299,41 @@ int nms_typed(const B *boxes, const B *scores, const int64_t *order, int64_t n, 
         if (lds > 65536)
             D3D_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_nms_small_front<T, B>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const int64_t *ord = order ? order : order_ws;
+        const int64_t *ord = order ? order : a.ord.order;
         D3D_LAUNCH("k_nms_small_front", (k_nms_small_front<T, B>), dim3(1), dim3(1024), lds, st, boxes, scores, order, (uint32_t)n, score_thr,
-                   order_ws, geom, fbox, farea, state, inc_cnt, flags, cand_hdr, remv);
+                   a.ord.order, a.geom, a.fbox, a.farea, a.state, a.inc_cnt, a.flags, a.cand_hdr, a.remv);
         D3D_LAUNCH("k_nms_cand_all", k_nms_cand_all, dim3((unsigned)d3d_divup(n, 256), (unsigned)nb), dim3(256), 0, st,
-                   (const float4 *)fbox, (const float *)farea, (uint32_t)n, rot ? iou_thr : -1.f, cand, cap, cand_hdr, flags);
+                   (const float4 *)a.fbox, (const float *)a.farea, (uint32_t)n, rot ? iou_thr : -1.f, a.cand, cap, a.cand_hdr, a.flags);
         if (const int rc = hits(nullptr)) return rc;
-        D3D_LAUNCH("k_nms_fill_small", k_nms_fill_small, dim3(64), dim3(1024), 0, st, (const unsigned long long *)cand, cap,
-                   (const NmsCand *)cand_hdr, (const uint32_t *)inc_cnt, (uint32_t)n, inc_off, (const uint32_t *)arrival, inc);
+        D3D_LAUNCH("k_nms_fill_small", k_nms_fill_small, dim3(64), dim3(1024), 0, st, (const unsigned long long *)a.cand, cap,
+                   (const NmsCand *)a.cand_hdr, (const uint32_t *)a.inc_cnt, (uint32_t)n, a.inc_off, (const uint32_t *)a.arrival, a.inc);
         if (n <= kNmsSmallResolveMax) {
-            D3D_LAUNCH("k_nms_resolve_small", k_nms_resolve_small, dim3(1), dim3(1024), 0, st, (uint32_t)n, (const uint8_t *)state,
-                       (const uint32_t *)inc_cnt, (const uint32_t *)inc_off, inc, ord, suppressed, inv);
+            D3D_LAUNCH("k_nms_resolve_small", k_nms_resolve_small, dim3(1), dim3(1024), 0, st, (uint32_t)n, (const uint8_t *)a.state,
+                       (const uint32_t *)a.inc_cnt, (const uint32_t *)a.inc_off, a.inc, ord, suppressed, inv);
             return D3D_OK;
         }
         // 1 k - 4 k boxes: the general fixed point (+ its dense fallback for dependency chains beyond the poll limit)
-        D3D_LAUNCH("k_nms_resolve", k_nms_resolve, dim3((unsigned)d3d_divup(n, 256)), dim3(256), 0, st, n, state,
-                   (const uint32_t *)inc_cnt, (const uint32_t *)inc_off, inc, flags, ord, suppressed, inv);
+        D3D_LAUNCH("k_nms_resolve", k_nms_resolve, dim3((unsigned)d3d_divup(n, 256)), dim3(256), 0, st, n, a.state,
+                   (const uint32_t *)a.inc_cnt, (const uint32_t *)a.inc_off, a.inc, a.flags, ord, suppressed, inv);
         if (const int rc = pairs()) return rc;
-        D3D_LAUNCH("k_nms_sweep", k_nms_sweep, dim3(1), dim3(kSweepThreads), (size_t)nb * 8, st, mask, n, nb, remv, ord, state, flags,
+        D3D_LAUNCH("k_nms_sweep", k_nms_sweep, dim3(1), dim3(kSweepThreads), (size_t)nb * 8, st, a.mask, n, nb, a.remv, ord, a.state, a.flags,
                    suppressed, inv);
         return D3D_OK;
     }
     const bool use_grid = !(opts & D3D_NMS_BROAD_SWEEP);
     const unsigned nbl = (unsigned)d3d_divup(n, 256);
     D3D_LAUNCH("k_nms_prepare", (k_nms_prepare<T, B>), dim3(nbl), dim3(256), 0, st, boxes, scores, order, n, score_thr,
-               geom, fbox, state, inc_cnt, farea, remv, nb, flags, cand_hdr, (opts & D3D_NMS_FORCE_DENSE) ? 1u : 0u, xkey, &grid->ticket, tile_tot, gpartial, cellcur, chunk_tot, blocked,
+               a.geom, a.fbox, a.state, a.inc_cnt, a.farea, a.remv, nb, a.flags, a.cand_hdr, (opts & D3D_NMS_FORCE_DENSE) ? 1u : 0u, a.xkey, &a.grid->ticket, a.tile_tot, a.gpartial, a.cellcur, a.chunk_tot, a.blocked,
                (opts & D3D_NMS_FORCE_LEVELS) ? 1u : 0u);
     if (use_grid) {
         const bool fold_inline = nbl <= (unsigned)kGridFoldMax;
-        if (!fold_inline) D3D_LAUNCH("k_nms_extent", k_nms_extent, dim3(1), dim3(256), 0, st, (const float *)gpartial, nbl, grid);
-        D3D_LAUNCH("k_nms_gridreg<count>", k_nms_gridreg<false>, dim3(nbl), dim3(256), 0, st, (const float4 *)fbox, n, grid,
-                   cellcur, cap_e, cellbox, cellof, fbc, flags, (const float *)farea, carea, (const float *)gpartial, fold_inline ? nbl : 0u,
-                   (const uint32_t *)cellstart, (const uint8_t *)state, regopen);
-        D3D_LAUNCH("k_nms_gridscan", k_nms_gridscan, dim3(kGridScanWgs), dim3(1024), 0, st, cellcur, cellstart, grid, cap_e, flags,
-                   chunk_tot, tickets + 1, (opts & D3D_NMS_TEST_WITHHOLD) != 0 && (opts & D3D_NMS_BROAD_SWEEP) == 0,
-                   &cand_hdr->count[kHdrDensity]);
+        if (!fold_inline) D3D_LAUNCH("k_nms_extent", k_nms_extent, dim3(1), dim3(256), 0, st, (const float *)a.gpartial, nbl, a.grid);
+        D3D_LAUNCH("k_nms_gridreg<count>", k_nms_gridreg<false>, dim3(nbl), dim3(256), 0, st, (const float4 *)a.fbox, n, a.grid,
+                   a.cellcur, a.cap_e, a.cellbox, a.cellof, a.fbc, a.flags, (const float *)a.farea, a.carea, (const float *)a.gpartial, fold_inline ? nbl : 0u,
+                   (const uint32_t *)a.cellstart, (const uint8_t *)a.state, a.regopen);
+        D3D_LAUNCH("k_nms_gridscan", k_nms_gridscan, dim3(kGridScanWgs), dim3(1024), 0, st, a.cellcur, a.cellstart, a.grid, a.cap_e, a.flags,
+                   a.chunk_tot, a.tickets + 1, (opts & D3D_NMS_TEST_WITHHOLD) != 0 && (opts & D3D_NMS_BROAD_SWEEP) == 0,
+                   &a.cand_hdr->count[kHdrDensity]);
         int *host_dense = nullptr;
         if (host_word && !(opts & D3D_NMS_FORCE_LEVELS)) {
             hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -2305,71 +2345,70 @@ int nms_typed(const B *boxes, const B *scores, const int64_t *order, int64_t n, 
             }
         }
         if (host_dense) *reinterpret_cast<volatile int32_t *>(host_word) = 0;
-        D3D_LAUNCH("k_nms_gridreg<place>", k_nms_gridreg<true>, dim3(nbl), dim3(256), 0, st, (const float4 *)fbox, n, grid,
-                   cellcur, cap_e, cellbox, cellof, fbc, flags, (const float *)farea, carea, (const float *)gpartial, 0u,
-                   (const uint32_t *)cellstart, (const uint8_t *)state, regopen, (const NmsCand *)nullptr, (const uint8_t *)nullptr, 0u,
-                   (const NmsCand *)cand_hdr, host_dense);
+        D3D_LAUNCH("k_nms_gridreg<place>", k_nms_gridreg<true>, dim3(nbl), dim3(256), 0, st, (const float4 *)a.fbox, n, a.grid,
+                   a.cellcur, a.cap_e, a.cellbox, a.cellof, a.fbc, a.flags, (const float *)a.farea, a.carea, (const float *)a.gpartial, 0u,
+                   (const uint32_t *)a.cellstart, (const uint8_t *)a.state, a.regopen, (const NmsCand *)nullptr, (const uint8_t *)nullptr, 0u,
+                   (const NmsCand *)a.cand_hdr, host_dense);
         unsigned int levels = (opts & D3D_NMS_ONE_LEVEL) ? 1u : (unsigned int)kNmsLevels;
         if (host_dense && !nms_wait_dense(host_word, st)) levels = 0;
         for (unsigned int level = 1; level <= levels; level++) {
-            const dim3 lg((unsigned)d3d_divup((int64_t)cap_e, 256));
+            const dim3 lg((unsigned)d3d_divup((int64_t)a.cap_e, 256));
             const float bthr = rot ? iou_thr : -1.f;
-            D3D_LAUNCH("k_nms_level_block", k_nms_level_block, lg, dim3(256), 0, st, (const float4 *)fbc, (const uint32_t *)cellof,
-                       (const uint32_t *)cellstart, (const uint32_t *)cellcur, (const NmsGrid *)grid, (const NmsCand *)cand_hdr,
-                       (const float *)carea, bthr, (const uint32_t *)cellbox, blocked, (const uint8_t *)state, level,
-                       (uint32_t)(n >> kEliteShift), level == 1 ? (const uint8_t *)regopen : (const uint8_t *)nullptr);
-            D3D_LAUNCH("k_nms_level_roots", k_nms_level_roots, lg, dim3(256), 0, st, (const float4 *)fbc, (const uint32_t *)cellof,
-                       (const uint32_t *)cellstart, (const NmsGrid *)grid, cand_hdr, (const float *)carea, bthr,
-                       (const uint32_t *)cellbox, (const uint8_t *)blocked, (const uint8_t *)state, level, cand, cap, flags);
+            D3D_LAUNCH("k_nms_level_block", k_nms_level_block, lg, dim3(256), 0, st, (const float4 *)a.fbc, (const uint32_t *)a.cellof,
+                       (const uint32_t *)a.cellstart, (const uint32_t *)a.cellcur, (const NmsGrid *)a.grid, (const NmsCand *)a.cand_hdr,
+                       (const float *)a.carea, bthr, (const uint32_t *)a.cellbox, a.blocked, (const uint8_t *)a.state, level,
+                       (uint32_t)(n >> kEliteShift), level == 1 ? (const uint8_t *)a.regopen : (const uint8_t *)nullptr);
+            D3D_LAUNCH("k_nms_level_roots", k_nms_level_roots, lg, dim3(256), 0, st, (const float4 *)a.fbc, (const uint32_t *)a.cellof,
+                       (const uint32_t *)a.cellstart, (const NmsGrid *)a.grid, a.cand_hdr, (const float *)a.carea, bthr,
+                       (const uint32_t *)a.cellbox, (const uint8_t *)a.blocked, (const uint8_t *)a.state, level, a.cand, cap, a.flags);
             const unsigned kb = (unsigned)std::min<int64_t>(d3d_divup(n, 256) * 2, 4096);
             if (const int rc = dispatch(rot, [&](auto r) {
-                    D3D_LAUNCH("k_nms_level_kill", (k_nms_level_kill<T, r>), dim3(kb), dim3(256), 0, st, (const BoxCore<T> *)geom,
-                               (const unsigned long long *)cand, cap, (const NmsGrid *)grid, (const NmsCand *)cand_hdr, level, (T)iou_thr,
-                               state);
+                    D3D_LAUNCH("k_nms_level_kill", (k_nms_level_kill<T, r>), dim3(kb), dim3(256), 0, st, (const BoxCore<T> *)a.geom,
+                               (const unsigned long long *)a.cand, cap, (const NmsGrid *)a.grid, (const NmsCand *)a.cand_hdr, level, (T)iou_thr,
+                               a.state);
                     return D3D_OK;
                 }))
                 return rc;
         }
         if (levels > 0) {
             // the boxes the levels left open are registered again, alone: the candidate walk is quadratic in the list lengths
-            D3D_LAUNCH("k_nms_regrid_reset", k_nms_regrid_reset, dim3(64), dim3(256), 0, st, cellcur, (const NmsGrid *)grid,
-                       (const NmsCand *)cand_hdr, chunk_tot, tickets + 1);
-            D3D_LAUNCH("k_nms_gridreg<count>", k_nms_gridreg<false>, dim3(nbl), dim3(256), 0, st, (const float4 *)fbox, n, grid,
-                       cellcur, cap_e, cellbox, cellof, fbc, flags, (const float *)farea, carea, (const float *)gpartial, 0u,
-                       (const uint32_t *)cellstart, (const uint8_t *)state, regopen, (const NmsCand *)cand_hdr, (const uint8_t *)blocked,
+            D3D_LAUNCH("k_nms_regrid_reset", k_nms_regrid_reset, dim3(64), dim3(256), 0, st, a.cellcur, (const NmsGrid *)a.grid,
+                       (const NmsCand *)a.cand_hdr, a.chunk_tot, a.tickets + 1);
+            D3D_LAUNCH("k_nms_gridreg<count>", k_nms_gridreg<false>, dim3(nbl), dim3(256), 0, st, (const float4 *)a.fbox, n, a.grid,
+                       a.cellcur, a.cap_e, a.cellbox, a.cellof, a.fbc, a.flags, (const float *)a.farea, a.carea, (const float *)a.gpartial, 0u,
+                       (const uint32_t *)a.cellstart, (const uint8_t *)a.state, a.regopen, (const NmsCand *)a.cand_hdr, (const uint8_t *)a.blocked,
                        levels);
-            D3D_LAUNCH("k_nms_gridscan", k_nms_gridscan, dim3(kGridScanWgs), dim3(1024), 0, st, cellcur, cellstart, grid, cap_e, flags,
-                       chunk_tot, tickets + 1, false, &cand_hdr->count[kHdrDensity], (const NmsCand *)cand_hdr);
-            D3D_LAUNCH("k_nms_gridreg<place>", k_nms_gridreg<true>, dim3(nbl), dim3(256), 0, st, (const float4 *)fbox, n, grid,
-                       cellcur, cap_e, cellbox, cellof, fbc, flags, (const float *)farea, carea, (const float *)gpartial, 0u,
-                       (const uint32_t *)cellstart, (const uint8_t *)state, regopen, (const NmsCand *)cand_hdr, (const uint8_t *)blocked,
+            D3D_LAUNCH("k_nms_gridscan", k_nms_gridscan, dim3(kGridScanWgs), dim3(1024), 0, st, a.cellcur, a.cellstart, a.grid, a.cap_e, a.flags,
+                       a.chunk_tot, a.tickets + 1, false, &a.cand_hdr->count[kHdrDensity], (const NmsCand *)a.cand_hdr);
+            D3D_LAUNCH("k_nms_gridreg<place>", k_nms_gridreg<true>, dim3(nbl), dim3(256), 0, st, (const float4 *)a.fbox, n, a.grid,
+                       a.cellcur, a.cap_e, a.cellbox, a.cellof, a.fbc, a.flags, (const float *)a.farea, a.carea, (const float *)a.gpartial, 0u,
+                       (const uint32_t *)a.cellstart, (const uint8_t *)a.state, a.regopen, (const NmsCand *)a.cand_hdr, (const uint8_t *)a.blocked,
                        levels);
         }
-        D3D_LAUNCH("k_nms_cand_grid", k_nms_cand_grid, dim3((unsigned)d3d_divup((int64_t)cap_e, 256)), dim3(256), 0, st,
-                   (const float4 *)fbc, (const uint32_t *)cellof, (const uint32_t *)cellstart, (const NmsGrid *)grid, cand, cap,
-                   cand_hdr, flags, (const float *)carea, rot ? iou_thr : -1.f, (const uint32_t *)cellbox, (const uint8_t *)blocked,
-                   (const uint8_t *)state, levels);
-        rankx = cellbox;                                   // registration -> score rank, for k_nms_hits
+        D3D_LAUNCH("k_nms_cand_grid", k_nms_cand_grid, dim3((unsigned)d3d_divup((int64_t)a.cap_e, 256)), dim3(256), 0, st,
+                   (const float4 *)a.fbc, (const uint32_t *)a.cellof, (const uint32_t *)a.cellstart, (const NmsGrid *)a.grid, a.cand, cap,
+                   a.cand_hdr, a.flags, (const float *)a.carea, rot ? iou_thr : -1.f, (const uint32_t *)a.cellbox, (const uint8_t *)a.blocked,
+                   (const uint8_t *)a.state, levels);
     } else {
-        if (int rc = d3d_internal_argsort_desc_i32(xkey, n, perm, sort_ws, sort_bytes, st)) return rc;
-        D3D_LAUNCH("k_nms_xgather", k_nms_xgather, dim3((unsigned)d3d_divup(nb * 64 + kCandPad, 256)), dim3(256), 0, st, fbox,
-                   perm, n, nb, fbx, rankx);
+        if (int rc = d3d_internal_argsort_desc_i32(a.xkey, n, a.perm, a.sort_ws, a.sort_bytes, st)) return rc;
+        D3D_LAUNCH("k_nms_xgather", k_nms_xgather, dim3((unsigned)d3d_divup(nb * 64 + kCandPad, 256)), dim3(256), 0, st, a.fbox,
+                   a.perm, n, nb, a.fbx, a.rankx);
         // enough wavefronts to fill the chip even when few row blocks exist: nsplit wavefronts share a row block
         const uint32_t nsplit = (uint32_t)std::min<int64_t>(std::max<int64_t>(8192 / nb, 1), kCandMaxSplit);
-        D3D_LAUNCH("k_nms_cand", k_nms_cand, dim3((unsigned)d3d_divup(nb * nsplit, 4)), dim3(256), 0, st, (const float4 *)fbx,
-                   (uint32_t)nb, nsplit, cand, cap, cand_hdr, flags);
+        D3D_LAUNCH("k_nms_cand", k_nms_cand, dim3((unsigned)d3d_divup(nb * nsplit, 4)), dim3(256), 0, st, (const float4 *)a.fbx,
+                   (uint32_t)nb, nsplit, a.cand, cap, a.cand_hdr, a.flags);
     }
-    if (const int rc = hits(rankx)) return rc;
-    D3D_LAUNCH("k_nms_incscan", k_nms_incscan, dim3((unsigned)d3d_divup(n, kIncTile)), dim3(256), 0, st, (const uint32_t *)inc_cnt, n,
-               inc_off, tile_tot, tickets, flags, (opts & D3D_NMS_TEST_WITHHOLD) != 0 && (opts & D3D_NMS_BROAD_SWEEP) != 0);
-    D3D_LAUNCH("k_nms_fill", k_nms_fill, dim3(hits_blocks), dim3(256), 0, st, (const unsigned long long *)cand, cap,
-               (const NmsCand *)cand_hdr, (const uint32_t *)inc_off, (const uint32_t *)arrival, inc, (const NmsFlags *)flags);
-    D3D_LAUNCH("k_nms_resolve", k_nms_resolve, dim3((unsigned)d3d_divup(n, 256)), dim3(256), 0, st, n, state,
-               (const uint32_t *)inc_cnt, (const uint32_t *)inc_off, inc, flags, order, suppressed, inv);
+    if (const int rc = hits(use_grid ? a.cellbox : a.rankx)) return rc;      // (grid: registration -> score rank)
+    D3D_LAUNCH("k_nms_incscan", k_nms_incscan, dim3((unsigned)d3d_divup(n, kIncTile)), dim3(256), 0, st, (const uint32_t *)a.inc_cnt, n,
+               a.inc_off, a.tile_tot, a.tickets, a.flags, (opts & D3D_NMS_TEST_WITHHOLD) != 0 && (opts & D3D_NMS_BROAD_SWEEP) != 0);
+    D3D_LAUNCH("k_nms_fill", k_nms_fill, dim3(hits_blocks), dim3(256), 0, st, (const unsigned long long *)a.cand, cap,
+               (const NmsCand *)a.cand_hdr, (const uint32_t *)a.inc_off, (const uint32_t *)a.arrival, a.inc, (const NmsFlags *)a.flags);
+    D3D_LAUNCH("k_nms_resolve", k_nms_resolve, dim3((unsigned)d3d_divup(n, 256)), dim3(256), 0, st, n, a.state,
+               (const uint32_t *)a.inc_cnt, (const uint32_t *)a.inc_off, a.inc, a.flags, order, suppressed, inv);
     // dense path, gated on need_sweep inside the kernels
     if (const int rc = pairs()) return rc;
     size_t lds = nb <= kSweepLdsWords ? (size_t)nb * 8 : 0;
-    D3D_LAUNCH("k_nms_sweep", k_nms_sweep, dim3(1), dim3(kSweepThreads), lds, st, mask, n, nb, remv, order, state, flags,
+    D3D_LAUNCH("k_nms_sweep", k_nms_sweep, dim3(1), dim3(kSweepThreads), lds, st, a.mask, n, nb, a.remv, order, a.state, a.flags,
                suppressed, inv);
     return D3D_OK;
 }
@@ -2717,14 +2756,69 @@ static unsigned long long iou_list_capacity(int64_t n, int64_t m)
     return pairs < (1ull << 27) ? pairs : (1ull << 27);
 }
 
+// BOX / RBOX forward on the list path (iou2d_two_phase): geometry and candidate boxes of both sets, the candidate list
+template <typename T> struct IouWs {
+    BoxGeom<T> *ga, *gb;
+    float4 *ra, *cb;
+    IouList *hdr;
+    unsigned long long *list;
+};
+template <typename T>
+static IouWs<T> iou_carve(WsCarver &w, int64_t n, int64_t m)
+{
+    IouWs<T> a;
+    a.ga = w.take<BoxGeom<T>>(n);
+    a.gb = w.take<BoxGeom<T>>(m);
+    a.ra = w.take<float4>(n);
+    a.cb = w.take<float4>(m);
+    a.hdr = w.take<IouList>(1);
+    a.list = w.take<unsigned long long>(iou_list_capacity(n, m));
+    return a;
+}
+
+// BOX / RBOX backward (iou2d_backward_typed): geometry and candidate boxes, one bit per pair for rows_bm rows at a time, the
+// counters of the marks
+template <typename T> struct IouGradWs {
+    BoxGeom<T> *ga, *gb;
+    float4 *ra, *cb;
+    int64_t wpr, rows_bm;              // rows_bm = 0: not even eight rows of marks fit
+    unsigned long long *bitmap, *nmarks;
+};
+template <typename T>
+static IouGradWs<T> iou_grad_carve(WsCarver &w, int64_t n, int64_t m)
+{
+    IouGradWs<T> a;
+    a.ga = w.take<BoxGeom<T>>(n);
+    a.gb = w.take<BoxGeom<T>>(m);
+    a.ra = w.take<float4>(n);
+    a.cb = w.take<float4>(m);
+    a.wpr = d3d_divup(m, 64);
+    // a row chunk's marks at a time, no more words than the forward's candidate list has entries (iou_list_capacity): matrices
+    // beyond 8.6e9 pairs take several chunks (they came back with D3D_ERR_WORKSPACE)
+    a.rows_bm = n < (int64_t)65535 * kTileRows ? n : (int64_t)65535 * kTileRows;
+    const int64_t rows_fit = (int64_t)(iou_list_capacity(n, m) / (unsigned long long)a.wpr);
+    if (a.rows_bm > rows_fit) a.rows_bm = rows_fit < 8 ? 0 : rows_fit & ~(int64_t)7;      // (never below 2^27 pairs: n x ceil(m / 64) words <= n x m)
+    a.bitmap = w.take<unsigned long long>((size_t)a.rows_bm * (size_t)a.wpr);
+    a.nmarks = w.take<unsigned long long>(kMarkStripes + 1);        // 64 counters + the decision
+    return a;
+}
+
+// serves d3d_iou2d_forward and d3d_iou2d_backward: iou_carve and iou_grad_carve (BOX / RBOX) and the two-kernel routes of
+// GRBOX / DRBOX in boxloss.hip, with fp64 geometry for every dtype but D3D_F32.  The loss backward marks its pairs in ONE bitmap
+// of n x ceil(m / 64) words: above 2^33 pairs that outgrows everything else here, and the query does not follow it -- the route
+// falls back to its single kernel there unless the caller passes more.  OPEN: loss_backward itself knows no such limit (it
+// takes the route whenever its carve fits), so the rule below stands here alone until the query may grow or the bitmap is chunked.
 extern "C" size_t d3d_iou2d_workspace_bytes(int64_t n, int64_t m, int32_t dtype)
 {
     if (n < 1) n = 1;
     if (m < 1) m = 1;
-    const size_t g = dtype != D3D_F32 ? sizeof(BoxGeom<double>) : sizeof(BoxGeom<float>);
-    // 64 bytes per box instead of the 16 of the candidate boxes: GRBOX keeps its per-box hull terms there (boxloss.hip, HullPre)
-    return d3d_align_up(g * n) + d3d_align_up(g * m) + d3d_align_up(64 * n) + d3d_align_up(64 * m) + d3d_align_up(sizeof(IouList)) + d3d_align_up(8 * iou_list_capacity(n, m)) +
-           256;
+    WsCarver f(nullptr, 0), b(nullptr, 0);
+    if (dtype != D3D_F32) { iou_carve<double>(f, n, m); iou_grad_carve<double>(b, n, m); }
+    else { iou_carve<float>(f, n, m); iou_grad_carve<float>(b, n, m); }
+    size_t bytes = std::max(std::max(f.off, b.off), d3d_internal_loss_iou_forward_bytes(n, m, dtype, iou_list_capacity(n, m)));
+    if ((unsigned long long)n * (unsigned long long)d3d_divup(m, 64) <= iou_list_capacity(n, m))
+        bytes = std::max(bytes, d3d_internal_loss_iou_backward_bytes(n, m, dtype));
+    return bytes;
 }
 
 template <typename T, bool ROTATED, typename S = T, typename B = T>
@@ -2732,17 +2826,12 @@ static int iou2d_two_phase(const B *b1, int64_t n, const B *b2, int64_t m, S *io
                            uint32_t opts)
 {
     WsCarver w(ws, ws_bytes);
-    BoxGeom<T> *ga = w.take<BoxGeom<T>>(n);
-    BoxGeom<T> *gb = w.take<BoxGeom<T>>(m);
-    float4 *ra = w.take<float4>(n);
-    float4 *cb = w.take<float4>(m);
-    IouList *hdr = w.take<IouList>(1);
+    const IouWs<T> a = iou_carve<T>(w, n, m);
     unsigned long long cap = iou_list_capacity(n, m);
-    unsigned long long *list = w.take<unsigned long long>(cap);
     if (!w.ok()) return D3D_ERR_WORKSPACE;
     if ((opts >> 8) != 0 && (unsigned long long)(opts >> 8) < cap) cap = opts >> 8;     // D3D_IOU_LIST_CAP: use less of it
-    D3D_LAUNCH("k_geom", (k_geom2<T, ROTATED, B>), dim3((unsigned)d3d_divup(n + m, 256)), dim3(256), 0, st, b1, n, ga, ra, b2, m, gb, cb,
-               hdr, list_segments(cap), ROTATED);
+    D3D_LAUNCH("k_geom", (k_geom2<T, ROTATED, B>), dim3((unsigned)d3d_divup(n + m, 256)), dim3(256), 0, st, b1, n, a.ga, a.ra, b2, m, a.gb, a.cb,
+               a.hdr, list_segments(cap), ROTATED);
     S *fill = ious;
     if (reinterpret_cast<uintptr_t>(ious) & 15) {             // unaligned output: plain memset, candidates only
         D3D_HIP_CHECK(hipMemsetAsync(ious, 0, (size_t)n * (size_t)m * sizeof(S), st));
@@ -2750,8 +2839,8 @@ static int iou2d_two_phase(const B *b1, int64_t n, const B *b2, int64_t m, S *io
     }
     const int prows = pre_tile_rows(n, m);
     D3D_LAUNCH("k_iou_pre", k_iou_pre<S>, dim3((unsigned)d3d_divup(m, (int64_t)kPreCols), (unsigned)d3d_divup(n, (int64_t)prows)),
-               dim3(kTileCols), 0, st, (const float4 *)ra, n, (const float4 *)cb, m, fill, hdr, list, cap, 0.f, prows);
-    D3D_LAUNCH("k_iou_clip", (k_iou_clip<T, ROTATED, S>), dim3(256 * 16), dim3(256), 0, st, ga, gb, n, m, ious, hdr, list, cap);
+               dim3(kTileCols), 0, st, (const float4 *)a.ra, n, (const float4 *)a.cb, m, fill, a.hdr, a.list, cap, 0.f, prows);
+    D3D_LAUNCH("k_iou_clip", (k_iou_clip<T, ROTATED, S>), dim3(256 * 16), dim3(256), 0, st, a.ga, a.gb, n, m, ious, a.hdr, a.list, cap);
     return D3D_OK;
 }
 
@@ -2812,12 +2901,33 @@ extern "C" int d3d_iou2d_forward(const void *boxes1, int64_t n, const void *boxe
     });
 }
 
+// 3-D IoU on the list path (iou3d_impl): as iou_carve, with the boxes' z ranges
+struct Iou3dWs {
+    BoxGeom<float> *ga, *gb;
+    float2 *za, *zb;
+    float4 *ra, *cb;
+    IouList *hdr;
+    unsigned long long *list;
+};
+static Iou3dWs iou3d_carve(WsCarver &w, int64_t n, int64_t m)
+{
+    Iou3dWs a;
+    a.ga = w.take<BoxGeom<float>>(n);
+    a.gb = w.take<BoxGeom<float>>(m);
+    a.za = w.take<float2>(n);
+    a.zb = w.take<float2>(m);
+    a.ra = w.take<float4>(n);
+    a.cb = w.take<float4>(m);
+    a.hdr = w.take<IouList>(1);
+    a.list = w.take<unsigned long long>(iou_list_capacity(n, m));
+    return a;
+}
+
 extern "C" size_t d3d_iou3d_workspace_bytes(int64_t n, int64_t m)
 {
-    if (n < 1) n = 1;
-    if (m < 1) m = 1;
-    return d3d_align_up(sizeof(BoxGeom<float>) * n) + d3d_align_up(sizeof(BoxGeom<float>) * m) + d3d_align_up(8 * n) +
-           d3d_align_up(8 * m) + d3d_align_up(16 * n) + d3d_align_up(16 * m) + d3d_align_up(sizeof(IouList)) + d3d_align_up(8 * iou_list_capacity(n, m)) + 256;
+    WsCarver w(nullptr, 0);
+    iou3d_carve(w, n < 1 ? 1 : n, m < 1 ? 1 : m);
+    return w.off;
 }
 
 static int iou3d_impl(const float *boxes1, int64_t n, const float *boxes2, int64_t m, int32_t rotated, float *out,
@@ -2838,18 +2948,11 @@ static int iou3d_impl(const float *boxes1, int64_t n, const float *boxes2, int64
         if (workspace && workspace_bytes >= d3d_iou3d_workspace_bytes(n, m) && (al16 || !complement)) {
             // background fill + candidate list + dense clipping (see "rotated IoU, two-phase")
             WsCarver w(workspace, workspace_bytes);
-            BoxGeom<float> *ga = w.take<BoxGeom<float>>(n);
-            BoxGeom<float> *gb = w.take<BoxGeom<float>>(m);
-            float2 *za = w.take<float2>(n);
-            float2 *zb = w.take<float2>(m);
-            float4 *ra = w.take<float4>(n);
-            float4 *cb = w.take<float4>(m);
-            IouList *hdr = w.take<IouList>(1);
-            const unsigned long long cap = iou_list_capacity(n, m);
-            unsigned long long *list = w.take<unsigned long long>(cap);
+            const Iou3dWs a = iou3d_carve(w, n, m);
             if (!w.ok()) return D3D_ERR_WORKSPACE;
-            D3D_LAUNCH("k_geom3d2", k_geom3d2, dim3((unsigned)d3d_divup(n + m, 256)), dim3(256), 0, st, boxes1, n, ga, ra, za, boxes2, m,
-                       gb, cb, zb, hdr, list_segments(cap), (bool)r, stride, complement);
+            const unsigned long long cap = iou_list_capacity(n, m);
+            D3D_LAUNCH("k_geom3d2", k_geom3d2, dim3((unsigned)d3d_divup(n + m, 256)), dim3(256), 0, st, boxes1, n, a.ga, a.ra, a.za, boxes2, m,
+                       a.gb, a.cb, a.zb, a.hdr, list_segments(cap), (bool)r, stride, complement);
             float *fill = out;
             if (!al16) {
                 D3D_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)n * (size_t)m * sizeof(float), st));
@@ -2857,9 +2960,9 @@ static int iou3d_impl(const float *boxes1, int64_t n, const float *boxes2, int64
             }
             const int prows = pre_tile_rows(n, m);
             D3D_LAUNCH("k_iou_pre", k_iou_pre<float>, dim3((unsigned)d3d_divup(m, (int64_t)kPreCols), (unsigned)d3d_divup(n, (int64_t)prows)),
-                       dim3(kTileCols), 0, st, (const float4 *)ra, n, (const float4 *)cb, m, fill, hdr, list, cap, complement ? 1.f : 0.f,
+                       dim3(kTileCols), 0, st, (const float4 *)a.ra, n, (const float4 *)a.cb, m, fill, a.hdr, a.list, cap, complement ? 1.f : 0.f,
                        prows);
-            D3D_LAUNCH("k_iou3d_clip", k_iou3d_clip<r>, dim3(256 * 16), dim3(256), 0, st, ga, za, gb, zb, n, m, out, hdr, list, cap, complement);
+            D3D_LAUNCH("k_iou3d_clip", k_iou3d_clip<r>, dim3(256 * 16), dim3(256), 0, st, a.ga, a.za, a.gb, a.zb, n, m, out, a.hdr, a.list, cap, complement);
             return D3D_OK;
         }
         // the rotated kernel is scalar; the axis-aligned one stores 4 boxes of a row per lane where the output allows it
@@ -2890,46 +2993,51 @@ extern "C" int d3d_match_distance(const float *src, int64_t n, const float *dst,
 }
 
 constexpr size_t kSoftLdsBytes = 128 * 1024;      // position-indexed state of the soft-NMS kernel stays in LDS below this
+// soft NMS: k_softnms's geometry and, when they do not fit the LDS, its position-indexed scores, order and flags
+template <typename T> struct SoftWs {
+    BoxGeom<T> *geom;
+    float4 *aabb;
+    int *ord;
+    T *sc;
+    uint8_t *sp;
+    OrderWs order;
+};
+template <typename T>
+static SoftWs<T> soft_carve(WsCarver &w, int64_t n)
+{
+    SoftWs<T> a;
+    a.geom = w.take<BoxGeom<T>>(n);
+    a.aabb = w.take<float4>(n);
+    a.ord = w.take<int>(n);
+    a.sc = w.take<T>(n);
+    a.sp = w.take<uint8_t>(n);
+    a.order = order_carve(w, n);
+    return a;
+}
+
 template <typename T, bool ROTATED, typename B = T>
 static int softnms_typed(const B *boxes, const B *scores, const int64_t *order, int64_t n, int sup, float iou_thr,
-                         float score_thr, float param, uint8_t *suppressed, void *ws, size_t ws_bytes, hipStream_t st, uint32_t opts)
+                         float score_thr, float param, uint8_t *suppressed, const SoftWs<T> &a, hipStream_t st, uint32_t opts)
 {
-    WsCarver w(ws, ws_bytes);
-    BoxGeom<T> *geom = w.take<BoxGeom<T>>(n);
-    float4 *aabb = w.take<float4>(n);
-    int *ord = w.take<int>(n);
-    T *sc = w.take<T>(n);
-    uint8_t *sp = w.take<uint8_t>(n);
-    if (!ws || !w.ok()) return D3D_ERR_WORKSPACE;
     const size_t lds = (size_t)n * (sizeof(T) + 4 + 1);
     const bool in_lds = lds <= kSoftLdsBytes && !(opts & D3D_NMS_SOFT_NO_LDS);    // (flag: the global-scratch variant)
     if (in_lds)
         D3D_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_softnms<T, ROTATED, B>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSoftLdsBytes));
     D3D_LAUNCH("k_softnms", (k_softnms<T, ROTATED, B>), dim3(1), dim3(kSoftThreads), in_lds ? lds : 0, st, boxes, scores, order, (int)n,
-               sup, iou_thr, score_thr, param, geom, aabb, ord, sc, sp, in_lds ? 1 : 0, suppressed, (uint8_t)((opts & D3D_NMS_KEEP_MASK) ? 1 : 0));
+               sup, iou_thr, score_thr, param, a.geom, a.aabb, a.ord, a.sc, a.sp, in_lds ? 1 : 0, suppressed, (uint8_t)((opts & D3D_NMS_KEEP_MASK) ? 1 : 0));
     return D3D_OK;
 }
 
-static size_t nms_core_workspace_bytes(int64_t n)
-{
-    if (n < 1) n = 1;
-    const size_t nb = (size_t)d3d_divup(n, 64);
-    return d3d_align_up(nb * 64 * sizeof(BoxGeom<double>)) + d3d_align_up(nb * 64 * 16) + 2 * d3d_align_up(nb * 64) +
-           d3d_align_up(nb * 64 * 4) * 3 + d3d_align_up((nb * 64 / kScanTile + 2 + 80) * 8) + 256 + 2 * d3d_align_up((size_t)nms_cand_capacity(n) * 4) +
-           256 + d3d_align_up(nb * 8) +
-           d3d_align_up(sizeof(NmsCand)) +
-           d3d_align_up((size_t)nms_cand_capacity(n) * 8) + 2 * d3d_align_up(nb * 64 * 4) + d3d_align_up((nb * 64 + kCandPad) * 16) +
-           d3d_align_up(nb * 64 * 4) + d3d_align_up(d3d_internal_argsort_i32_bytes(n)) + d3d_align_up(nb * 64 * nb * 8) + 256 +
-           d3d_align_up((size_t)(kGridCells + 1) * kGridPad * 4) + d3d_align_up((kGridCells + 1) * 4) + d3d_align_up((nb * 64 / 256 + 1) * 6 * 4) + d3d_align_up(sizeof(NmsGrid)) +
-           d3d_align_up(kGridReg * nb * 64 * 4) * 3 + d3d_align_up(kGridReg * nb * 64 * 16) + d3d_align_up(kGridReg * nb * 64);
-}
-
+// serves d3d_nms2d / d3d_nms2d_notify: hard NMS (nms_carve) and soft NMS (soft_carve), each with fp64 geometry -- the largest
+// of the element types the entries accept -- and with the score order behind it
 extern "C" size_t d3d_nms2d_workspace_bytes(int64_t n)
 {
     if (n < 1) n = 1;
-    // [NMS arrays][order, when the caller passes none][workspace of d3d_argsort_desc]
-    return nms_core_workspace_bytes(n) + d3d_align_up((size_t)n * 8) + d3d_align_up(d3d_argsort_desc_workspace_bytes(n, D3D_F64)) + 256;
+    WsCarver hard(nullptr, 0), soft(nullptr, 0);
+    nms_carve<double>(hard, n);
+    soft_carve<double>(soft, n);
+    return std::max(hard.off, soft.off);
 }
 
 static int nms2d_impl(const void *boxes, const void *scores, const int64_t *order, int64_t n, int32_t iou_type,
@@ -2946,35 +3054,40 @@ static int nms2d_impl(const void *boxes, const void *scores, const int64_t *orde
         return D3D_ERR_UNSUPPORTED;                                                          // common.h:40
     if (n == 0) return D3D_OK;
     if (!boxes || !scores || !suppressed) return D3D_ERR_BAD_ARG;
-    // order == NULL: the descending argsort of the scores happens here (nms.cpp:103 does it inside nms2d too) -- inside the
-    // first kernel of the small-set path, by d3d_argsort_desc otherwise; both live behind the NMS part of the workspace
-    const size_t nms_bytes = nms_core_workspace_bytes(n);
     if (!workspace || workspace_bytes < d3d_nms2d_workspace_bytes(n)) return D3D_ERR_WORKSPACE;
-    int64_t *order_ws = reinterpret_cast<int64_t *>(static_cast<char *>(workspace) + nms_bytes);
-    const bool small = suppression_type == D3D_SUPPRESS_HARD && nms_small_eligible(n, flags);
-    if (!order && !small) {
-        char *sort_ws = reinterpret_cast<char *>(order_ws) + d3d_align_up((size_t)n * 8);
-        // (D3D_F32_WIDE: the order of the fp32 scores is the order of their widened values)
-        const int sdt = dtype == D3D_F32_WIDE ? D3D_F32 : dtype;
-        const int rc = d3d_argsort_desc(scores, n, sdt, order_ws, sort_ws, d3d_argsort_desc_workspace_bytes(n, sdt), stream);
-        if (rc) return rc;
-        order = order_ws;
-    }
     const bool hard = suppression_type == D3D_SUPPRESS_HARD;
-    if (hard ? d3d_divup(n, 64) > 65535 : n >= (1ll << 31) - 64) return D3D_ERR_BAD_ARG;
-    return dispatch_dtype<D3D_F32, D3D_F64, D3D_F32_WIDE>(dtype, [&](auto p) {
+    // order == NULL: the descending argsort of the scores happens here (nms.cpp:103 does it inside nms2d too) -- inside the
+    // first kernel of the small-set path, by d3d_argsort_desc otherwise; then the sizes either kind refuses
+    const auto own_order = [&](const OrderWs &o) -> int {
+        if (!order && !(hard && nms_small_eligible(n, flags))) {
+            // (D3D_F32_WIDE: the order of the fp32 scores is the order of their widened values)
+            const int rc = d3d_argsort_desc(scores, n, dtype == D3D_F32_WIDE ? D3D_F32 : dtype, o.order, o.sort_ws, o.sort_bytes, stream);
+            if (rc) return rc;
+            order = o.order;
+        }
+        return (hard ? d3d_divup(n, 64) > 65535 : n >= (1ll << 31) - 64) ? D3D_ERR_BAD_ARG : D3D_OK;
+    };
+    return dispatch_dtype<D3D_F32, D3D_F64, D3D_F32_WIDE>(dtype, [&](auto p) -> int {
         typedef typename decltype(p)::T T;
         typedef typename decltype(p)::B B;
-        if (hard)
-            return nms_typed<T, B>((const B *)boxes, (const B *)scores, order, n, iou_type, iou_threshold, score_threshold, suppressed,
-                                   workspace, nms_bytes, st, flags, order_ws, host_word);
+        WsCarver w(workspace, workspace_bytes);
+        if (hard) {
+            const NmsWs<T> a = nms_carve<T>(w, n);
+            if (!w.ok()) return D3D_ERR_WORKSPACE;
+            if (const int rc = own_order(a.ord)) return rc;
+            return nms_typed<T, B>((const B *)boxes, (const B *)scores, order, n, iou_type, iou_threshold, score_threshold, suppressed, a, st,
+                                   flags, host_word);
+        }
         // soft: one workgroup, one round per box that is still alive when its turn comes, each round a sweep over the boxes behind
         // it (16-byte AABB reads; position-indexed state in global scratch above kSoftLds boxes): ~n rounds of ~n / 50 us --
         // 100 k boxes with most of them alive take seconds (the reference's loop, nms.cpp:60-94: n^2 / 2 clips and an
         // insertion pass that is itself quadratic per round).  No size limit of its own (nms.cpp has none)
+        const SoftWs<T> a = soft_carve<T>(w, n);
+        if (!w.ok()) return D3D_ERR_WORKSPACE;
+        if (const int rc = own_order(a.order)) return rc;
         return dispatch(iou_type == D3D_IOU_RBOX, [&](auto r) {
             return softnms_typed<T, r, B>((const B *)boxes, (const B *)scores, order, n, suppression_type, iou_threshold, score_threshold,
-                                          suppression_param, suppressed, workspace, workspace_bytes, st, flags);
+                                          suppression_param, suppressed, a, st, flags);
         });
     });
 }
@@ -3076,24 +3189,9 @@ static int iou2d_backward_typed(const B *b1, int64_t n, const B *b2, int64_t m, 
                                 hipStream_t st)
 {
     WsCarver w(ws, ws_bytes);
-    BoxGeom<T> *ga = w.take<BoxGeom<T>>(n);
-    BoxGeom<T> *gb = w.take<BoxGeom<T>>(m);
-    float4 *ra = w.take<float4>(n);
-    float4 *cb = w.take<float4>(m);
-    const int64_t wpr = d3d_divup(m, 64);
-    // a row chunk's marks at a time, one bit per pair, inside what the forward's workspace holds for its candidate list (8 bytes x
-    // iou_list_capacity): matrices beyond 8.6e9 pairs take several chunks (they came back with D3D_ERR_WORKSPACE)
-    int64_t rows_bm = n < (int64_t)65535 * kTileRows ? n : (int64_t)65535 * kTileRows;
-    {
-        const int64_t rows_fit = (int64_t)(iou_list_capacity(n, m) / (unsigned long long)wpr);
-        if (rows_bm > rows_fit) {                      // (never below 2^27 pairs: n x ceil(m / 64) words <= n x m)
-            if (rows_fit < 8) return D3D_ERR_WORKSPACE;
-            rows_bm = rows_fit & ~(int64_t)7;
-        }
-    }
-    unsigned long long *bitmap = w.take<unsigned long long>((size_t)rows_bm * (size_t)wpr);
-    unsigned long long *nmarks = w.take<unsigned long long>(kMarkStripes + 1);        // 64 counters + the decision
-    if (!ws || !w.ok()) return D3D_ERR_WORKSPACE;      // (geometry and candidate boxes of both sets + one bit per pair: inside the forward's workspace)
+    const IouGradWs<T> a = iou_grad_carve<T>(w, n, m);
+    if (a.rows_bm == 0) return D3D_ERR_WORKSPACE;
+    if (!ws || !w.ok()) return D3D_ERR_WORKSPACE;
     if (g2 == g1 + 5 * (size_t)n) D3D_HIP_CHECK(hipMemsetAsync(g1, 0, sizeof(T) * 5 * (size_t)(n + m), st));   // one buffer: one launch
     else {
         D3D_HIP_CHECK(hipMemsetAsync(g1, 0, sizeof(T) * 5 * (size_t)n, st));
@@ -3104,29 +3202,29 @@ static int iou2d_backward_typed(const B *b1, int64_t n, const B *b2, int64_t m, 
                    grad, g1, g2);
         return D3D_OK;
     }
-    D3D_LAUNCH("k_geom", (k_geom2<T, false, B>), dim3((unsigned)d3d_divup(n + m, 256)), dim3(256), 0, st, b1, n, ga, ra, b2, m, gb, cb,
+    D3D_LAUNCH("k_geom", (k_geom2<T, false, B>), dim3((unsigned)d3d_divup(n + m, 256)), dim3(256), 0, st, b1, n, a.ga, a.ra, b2, m, a.gb, a.cb,
                (IouList *)nullptr, 1u, ROTATED);       // (both operands in one launch, as the forward does)
     {                                                  // marks, then tiles with LDS accumulators (k_iou_grad_mark, k_iou_grad_tiles)
         int tr = kTileRows;                            // fewer rows per workgroup while the launch is short of 2048 workgroups
         while (tr > 8 && d3d_divup(m, kGradCols) * d3d_divup(n, tr) < 2048) tr >>= 1;
-        while (tr > 8 && tr > rows_bm) tr >>= 1;
+        while (tr > 8 && tr > a.rows_bm) tr >>= 1;
         // rows per pass: what the bitmap holds and one launch's grid.y covers (a pass may end on a partial tile -- rounding this down
         // to whole tiles gave 5000 rows a second pass of 8 rows with its four launches)
-        const int64_t rows_max = (int64_t)65535 * tr < rows_bm ? (int64_t)65535 * tr : rows_bm;
+        const int64_t rows_max = (int64_t)65535 * tr < a.rows_bm ? (int64_t)65535 * tr : a.rows_bm;
         for (int64_t r0 = 0; r0 < n; r0 += rows_max) {
             const int64_t nr = (n - r0) < rows_max ? (n - r0) : rows_max;
-            D3D_HIP_CHECK(hipMemsetAsync(nmarks, 0, 8 * kMarkStripes, st));
+            D3D_HIP_CHECK(hipMemsetAsync(a.nmarks, 0, 8 * kMarkStripes, st));
             D3D_LAUNCH("k_iou_grad_mark", (k_iou_grad_mark<T, ROTATED, G>), dim3((unsigned)d3d_divup(m, 2 * kGradCols), (unsigned)d3d_divup(nr, tr)),
-                       dim3(kGradCols), 0, st, (const BoxGeom<T> *)ga + r0, (const float4 *)ra + r0, nr, (const BoxGeom<T> *)gb, (const float4 *)cb,
-                       m, grad + r0 * m, bitmap, wpr, tr, nmarks);
-            D3D_LAUNCH("k_iou_grad_decide", k_iou_grad_decide, dim3(1), dim3(kMarkStripes), 0, st, nmarks, nr, m);
+                       dim3(kGradCols), 0, st, (const BoxGeom<T> *)a.ga + r0, (const float4 *)a.ra + r0, nr, (const BoxGeom<T> *)a.gb, (const float4 *)a.cb,
+                       m, grad + r0 * m, a.bitmap, a.wpr, tr, a.nmarks);
+            D3D_LAUNCH("k_iou_grad_decide", k_iou_grad_decide, dim3(1), dim3(kMarkStripes), 0, st, a.nmarks, nr, m);
             D3D_LAUNCH("k_iou_grad_tiles", (k_iou_grad_tiles<T, ROTATED, G, B>), dim3((unsigned)d3d_divup(m, kGradCols), (unsigned)d3d_divup(nr, tr)),
-                       dim3(kGradCols), 0, st, (const BoxGeom<T> *)ga + r0, (const float4 *)ra + r0, b1 + r0 * 5, nr, (const BoxGeom<T> *)gb,
-                       (const float4 *)cb, b2, m, grad + r0 * m, g1 + r0 * 5, g2, tr, (const unsigned long long *)bitmap, wpr,
-                       (const unsigned long long *)nmarks);
-            D3D_LAUNCH("k_iou_grad_sparse", (k_iou_grad_sparse<T, ROTATED, G, B>), dim3((unsigned)d3d_divup(nr * wpr, (int64_t)kSparseWords)), dim3(256),
-                       0, st, (const BoxGeom<T> *)ga + r0, b1 + r0 * 5, nr, (const BoxGeom<T> *)gb, b2, m, grad + r0 * m, g1 + r0 * 5, g2,
-                       (const unsigned long long *)bitmap, wpr, (const unsigned long long *)nmarks);
+                       dim3(kGradCols), 0, st, (const BoxGeom<T> *)a.ga + r0, (const float4 *)a.ra + r0, b1 + r0 * 5, nr, (const BoxGeom<T> *)a.gb,
+                       (const float4 *)a.cb, b2, m, grad + r0 * m, g1 + r0 * 5, g2, tr, (const unsigned long long *)a.bitmap, a.wpr,
+                       (const unsigned long long *)a.nmarks);
+            D3D_LAUNCH("k_iou_grad_sparse", (k_iou_grad_sparse<T, ROTATED, G, B>), dim3((unsigned)d3d_divup(nr * a.wpr, (int64_t)kSparseWords)), dim3(256),
+                       0, st, (const BoxGeom<T> *)a.ga + r0, b1 + r0 * 5, nr, (const BoxGeom<T> *)a.gb, b2, m, grad + r0 * m, g1 + r0 * 5, g2,
+                       (const unsigned long long *)a.bitmap, a.wpr, (const unsigned long long *)a.nmarks);
         }
     }
     return D3D_OK;

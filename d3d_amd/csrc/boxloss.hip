@@ -579,26 +579,51 @@ __global__ __launch_bounds__(kCols) void k_pdist_grad(const T *__restrict__ poin
     }
 }
 
+// the two-kernel routes of GRBOX / DRBOX, a matrix of more than kLossWsPairs pairs: geometry and hull terms of both sets, the
+// header, and the forward's list of pairs to redo (list_cap entries) or the backward's bitmap (one bit per pair)
+constexpr int64_t kLossWsPairs = 65536;
+template <typename T> struct LossWs {
+    BoxGeom<T> *ga, *gb;
+    HullPre<T> *ha, *hb;
+    FixList *hdr;
+    unsigned long long *words;
+};
+template <typename T>
+LossWs<T> loss_carve(WsCarver &w, int64_t n, int64_t m, unsigned long long words)
+{
+    LossWs<T> a;
+    a.ga = w.take<BoxGeom<T>>(n);
+    a.gb = w.take<BoxGeom<T>>(m);
+    a.ha = w.take<HullPre<T>>(n);
+    a.hb = w.take<HullPre<T>>(m);
+    a.hdr = w.take<FixList>(1);
+    a.words = w.take<unsigned long long>(words);
+    return a;
+}
+template <typename T>
+size_t loss_bytes(int64_t n, int64_t m, unsigned long long words)
+{
+    if ((int64_t)n * m <= kLossWsPairs) return 0;
+    WsCarver w(nullptr, 0);
+    loss_carve<T>(w, n, m, words);
+    return w.off;
+}
+
 template <typename T, int KIND>
 int loss_forward(const T *b1, int64_t n, const T *b2, int64_t m, T *out, void *ws, size_t ws_bytes, unsigned long long list_cap,
                  hipStream_t st)
 {
     const dim3 grid((unsigned)d3d_divup(m, kCols), (unsigned)d3d_divup(n, kRows));
     const unsigned int *no_gate = nullptr;
-    if (ws && (int64_t)n * m > 65536) {                           // a matrix: two kernels (above)
+    if (ws && (int64_t)n * m > kLossWsPairs) {                    // a matrix: two kernels (above)
         WsCarver w(ws, ws_bytes);
-        BoxGeom<T> *ga = w.take<BoxGeom<T>>(n);
-        BoxGeom<T> *gb = w.take<BoxGeom<T>>(m);
-        HullPre<T> *ha = w.take<HullPre<T>>(n);
-        HullPre<T> *hb = w.take<HullPre<T>>(m);
-        FixList *hdr = w.take<FixList>(1);
-        unsigned long long *list = w.take<unsigned long long>(list_cap);
+        const LossWs<T> a = loss_carve<T>(w, n, m, list_cap);
         if (w.ok() && list_cap > 0) {
-            const unsigned int *redo = &hdr->overflow;
-            D3D_LAUNCH("k_giou_geom", k_giou_geom<T>, dim3((unsigned)d3d_divup(n + m, 256)), dim3(256), 0, st, b1, n, b2, m, ga, ha, gb, hb, hdr);
-            D3D_LAUNCH(KIND ? "k_diou_main" : "k_giou_main", (k_giou_main<T, KIND>), grid, dim3(kCols), 0, st, (const BoxGeom<T> *)ga,
-                       (const HullPre<T> *)ha, n, (const BoxGeom<T> *)gb, (const HullPre<T> *)hb, m, out, hdr, list, list_cap);
-            D3D_LAUNCH(KIND ? "k_diou_fix" : "k_giou_fix", (k_giou_fix<T, KIND>), dim3(256 * 8), dim3(256), 0, st, ga, gb, m, out, hdr, list,
+            const unsigned int *redo = &a.hdr->overflow;
+            D3D_LAUNCH("k_giou_geom", k_giou_geom<T>, dim3((unsigned)d3d_divup(n + m, 256)), dim3(256), 0, st, b1, n, b2, m, a.ga, a.ha, a.gb, a.hb, a.hdr);
+            D3D_LAUNCH(KIND ? "k_diou_main" : "k_giou_main", (k_giou_main<T, KIND>), grid, dim3(kCols), 0, st, (const BoxGeom<T> *)a.ga,
+                       (const HullPre<T> *)a.ha, n, (const BoxGeom<T> *)a.gb, (const HullPre<T> *)a.hb, m, out, a.hdr, a.words, list_cap);
+            D3D_LAUNCH(KIND ? "k_diou_fix" : "k_giou_fix", (k_giou_fix<T, KIND>), dim3(256 * 8), dim3(256), 0, st, a.ga, a.gb, m, out, a.hdr, a.words,
                        list_cap);
             D3D_LAUNCH("k_loss_iou<redo>", (k_loss_iou<T, KIND>), grid, dim3(kCols), 0, st, b1, n, b2, m, out, redo);
             return D3D_OK;
@@ -615,7 +640,7 @@ int loss_backward(const T *b1, int64_t n, const T *b2, int64_t m, const T *grad,
     D3D_HIP_CHECK(hipMemsetAsync(g2, 0, (size_t)m * 5 * sizeof(T), st));
     const dim3 grid((unsigned)d3d_divup(m, kCols), (unsigned)d3d_divup(n, kRows));
     const unsigned long long *all = nullptr;
-    if (ws && (int64_t)n * m > 65536) {                           // a matrix: the pairs apart first, the others by their bitmap
+    if (ws && (int64_t)n * m > kLossWsPairs) {                    // a matrix: the pairs apart first, the others by their bitmap
         const int64_t wpr = d3d_divup(m, 64);
         // rows per workgroup: 64, or fewer while the launch would not give every SIMD of the chip two wavefronts (2 k x 2 k boxes at
         // 64 rows: 256 workgroups = one wavefront per SIMD, each walking its rows' round trips alone)
@@ -623,19 +648,15 @@ int loss_backward(const T *b1, int64_t n, const T *b2, int64_t m, const T *grad,
         while (tr > 8 && d3d_divup(m, kCols) * d3d_divup(n, tr) < 2048) tr >>= 1;
         const dim3 tgrid((unsigned)d3d_divup(m, kCols), (unsigned)d3d_divup(n, tr));
         WsCarver w(ws, ws_bytes);
-        BoxGeom<T> *ga = w.take<BoxGeom<T>>(n);
-        BoxGeom<T> *gb = w.take<BoxGeom<T>>(m);
-        HullPre<T> *ha = w.take<HullPre<T>>(n);
-        HullPre<T> *hb = w.take<HullPre<T>>(m);
-        FixList *hdr = w.take<FixList>(1);
-        unsigned long long *bitmap = w.take<unsigned long long>((size_t)n * (size_t)wpr);
+        const LossWs<T> a = loss_carve<T>(w, n, m, (unsigned long long)n * (unsigned long long)wpr);
         if (w.ok()) {
-            D3D_LAUNCH("k_giou_geom", k_giou_geom<T>, dim3((unsigned)d3d_divup(n + m, 256)), dim3(256), 0, st, b1, n, b2, m, ga, ha, gb, hb, hdr);
+            D3D_LAUNCH("k_giou_geom", k_giou_geom<T>, dim3((unsigned)d3d_divup(n + m, 256)), dim3(256), 0, st, b1, n, b2, m, a.ga, a.ha, a.gb, a.hb,
+                       a.hdr);
             D3D_LAUNCH(KIND ? "k_diou_grad_main" : "k_giou_grad_main", (k_giou_grad_main<T, KIND>), tgrid, dim3(kCols), 0, st,
-                       (const BoxGeom<T> *)ga, (const HullPre<T> *)ha, b1, n, (const BoxGeom<T> *)gb, (const HullPre<T> *)hb, b2, m, grad, g1,
-                       g2, bitmap, wpr, tr);
+                       (const BoxGeom<T> *)a.ga, (const HullPre<T> *)a.ha, b1, n, (const BoxGeom<T> *)a.gb, (const HullPre<T> *)a.hb, b2, m,
+                       grad, g1, g2, a.words, wpr, tr);
             D3D_LAUNCH("k_loss_grad_rest", (k_loss_grad_rest<T, KIND>), tgrid, dim3(kCols), 0, st, b1, n, b2, m, grad, g1, g2,
-                       (const unsigned long long *)bitmap, wpr, tr);
+                       (const unsigned long long *)a.words, wpr, tr);
             return D3D_OK;
         }
     }
@@ -647,8 +668,18 @@ int loss_backward(const T *b1, int64_t n, const T *b2, int64_t m, const T *grad,
 }  // namespace
 
 // called by d3d_iou2d_forward / d3d_iou2d_backward (box.hip) for iou_type GRBOX / DRBOX
-// workspace (optional; GIoU only): geometry of both box sets, the list header, `list_cap` 8-byte entries -- a prefix of what
-// d3d_iou2d_workspace_bytes(n, m, dtype) sizes for the candidate list of RBOX (box.hip)
+// workspace (optional): loss_carve; without one, or with a short one, the single-kernel route runs.  What the two routes take
+// (0 where they use none), for d3d_iou2d_workspace_bytes:
+size_t d3d_internal_loss_iou_forward_bytes(int64_t n, int64_t m, int dtype, unsigned long long list_cap)
+{
+    return dtype != D3D_F32 ? loss_bytes<double>(n, m, list_cap) : loss_bytes<float>(n, m, list_cap);
+}
+size_t d3d_internal_loss_iou_backward_bytes(int64_t n, int64_t m, int dtype)
+{
+    const unsigned long long words = (unsigned long long)n * (unsigned long long)d3d_divup(m, 64);
+    return dtype != D3D_F32 ? loss_bytes<double>(n, m, words) : loss_bytes<float>(n, m, words);
+}
+
 int d3d_internal_loss_iou_forward(const void *b1, int64_t n, const void *b2, int64_t m, int kind, int dtype, void *out, void *ws,
                                   size_t ws_bytes, unsigned long long list_cap, hipStream_t st)
 {

@@ -73,6 +73,9 @@ int d3d_internal_loss_iou_forward(const void *b1, int64_t n, const void *b2, int
                                   size_t ws_bytes, unsigned long long list_cap, hipStream_t st);            // boxloss.hip
 int d3d_internal_loss_iou_backward(const void *b1, int64_t n, const void *b2, int64_t m, const void *grad, int kind, int dtype,
                                    void *g1, void *g2, void *ws, size_t ws_bytes, hipStream_t st);
+// what the two-kernel routes of the two calls above carve (0 where they use no workspace), for d3d_iou2d_workspace_bytes
+__attribute__((visibility("hidden"))) size_t d3d_internal_loss_iou_forward_bytes(int64_t n, int64_t m, int dtype, unsigned long long list_cap);
+__attribute__((visibility("hidden"))) size_t d3d_internal_loss_iou_backward_bytes(int64_t n, int64_t m, int dtype);
 
 static inline size_t d3d_align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 static inline int64_t d3d_divup(int64_t a, int64_t b) { return (a + b - 1) / b; }

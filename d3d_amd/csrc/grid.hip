@@ -374,11 +374,38 @@ __global__ __launch_bounds__(256) void k_sharded_map(int64_t n, const int64_t *_
 
 }  // namespace
 
+// the compact index of ncells cells: one bit per cell, the number of set bits before every 64-bit word, and (for the entries
+// that build it) the block sums of the scan that counts them.  The readers need the first two only: scan = false.
+struct CompactWs {
+    int64_t nw;
+    unsigned long long *bitmap;
+    uint32_t *prefix;
+    unsigned long long *bsum;
+};
+static CompactWs compact_carve(WsCarver &w, int64_t ncells, bool scan)
+{
+    CompactWs c;
+    c.nw = d3d_divup(ncells, 64);
+    c.bitmap = w.take<unsigned long long>(c.nw);
+    c.prefix = w.take<uint32_t>(c.nw);
+    c.bsum = scan ? w.take<unsigned long long>(d3d_divup(c.nw, kScanTile) + 1) : nullptr;
+    return c;
+}
+// ownership bookkeeping of the sharded scatter: k_grid_or writes it, OwnedRows reads it
+struct OwnerWs { unsigned long long *lower, *newc; };
+static OwnerWs owner_carve(WsCarver &w, int64_t ncells)
+{
+    OwnerWs o;
+    o.lower = w.take<unsigned long long>(d3d_divup(ncells, 64));
+    o.newc = w.take<unsigned long long>(kMaxOwnerWorld * kOwnerStride);
+    return o;
+}
+
 extern "C" size_t d3d_grid_compact_workspace_bytes(int64_t ncells)
 {
-    if (ncells < 1) ncells = 1;
-    const size_t nw = (size_t)d3d_divup(ncells, 64);
-    return d3d_align_up(nw * 8) + d3d_align_up(nw * 4) + d3d_align_up(((size_t)d3d_divup((int64_t)nw, kScanTile) + 1) * 8) + 256;
+    WsCarver w(nullptr, 0);
+    compact_carve(w, ncells < 1 ? 1 : ncells, true);
+    return w.off;
 }
 
 // keys[m] (linear cell indices in [0, ncells)) -> occupancy index in `workspace`; counts[0] = number of
@@ -389,16 +416,13 @@ extern "C" int d3d_grid_compact_index(const int64_t *keys, int64_t m, int64_t nc
     hipStream_t st = (hipStream_t)stream;
     if (m < 0 || ncells <= 0 || !counts || (m > 0 && !keys)) return D3D_ERR_BAD_ARG;
     if (ncells >= (1ll << 37)) return D3D_ERR_BAD_ARG;
-    const int64_t nw = d3d_divup(ncells, 64);
     WsCarver w(workspace, workspace_bytes);
-    unsigned long long *bitmap = w.take<unsigned long long>(nw);
-    uint32_t *prefix = w.take<uint32_t>(nw);
-    unsigned long long *bsum = w.take<unsigned long long>(d3d_divup(nw, kScanTile) + 1);
+    const CompactWs c = compact_carve(w, ncells, true);
     if (!workspace || !w.ok()) return D3D_ERR_WORKSPACE;
-    const int rc = d3d_grid_bitmap_mark(keys, m, ncells, bitmap, stream);
+    const int rc = d3d_grid_bitmap_mark(keys, m, ncells, c.bitmap, stream);
     if (rc) return rc;
-    PopcountWords f{bitmap, prefix};
-    return d3d_run_scan(f, nw, bsum, counts, -1, 0, ~0ull, st);
+    PopcountWords f{c.bitmap, c.prefix};
+    return d3d_run_scan(f, c.nw, c.bsum, counts, -1, 0, ~0ull, st);
 }
 
 // bitmap exchange, step 1: this rank's occupancy bitmap (ceil(ncells/64) words; negative keys are ignored)
@@ -417,8 +441,9 @@ extern "C" int d3d_grid_bitmap_mark(const int64_t *keys, int64_t m, int64_t ncel
 // key_of_slot[counts[0]] (cells in ascending order).
 extern "C" size_t d3d_grid_owner_workspace_bytes(int64_t ncells)
 {
-    if (ncells < 1) ncells = 1;
-    return d3d_align_up((size_t)d3d_divup(ncells, 64) * 8) + d3d_align_up((size_t)kMaxOwnerWorld * kOwnerStride * 8) + 256;
+    WsCarver w(nullptr, 0);
+    owner_carve(w, ncells < 1 ? 1 : ncells);
+    return w.off;
 }
 
 extern "C" int d3d_grid_compact_from_bitmaps(const unsigned long long *parts, int64_t stride_words, int32_t world, int64_t ncells,
@@ -431,24 +456,21 @@ extern "C" int d3d_grid_compact_from_bitmaps(const unsigned long long *parts, in
     const int64_t nw = d3d_divup(ncells, 64);
     if (stride_words < nw) return D3D_ERR_BAD_ARG;
     WsCarver w(workspace, workspace_bytes);
-    unsigned long long *bitmap = w.take<unsigned long long>(nw);
-    uint32_t *prefix = w.take<uint32_t>(nw);
-    unsigned long long *bsum = w.take<unsigned long long>(d3d_divup(nw, kScanTile) + 1);
+    const CompactWs c = compact_carve(w, ncells, true);
     if (!workspace || !w.ok()) return D3D_ERR_WORKSPACE;
-    unsigned long long *lower = nullptr, *newc = nullptr;
+    OwnerWs o{nullptr, nullptr};
     if (owner_ws) {                                  // ownership bookkeeping for d3d_sharded_scatter_owned
         if (world > kMaxOwnerWorld || rank < 0 || rank >= world) return D3D_ERR_UNSUPPORTED;
         WsCarver ow(owner_ws, owner_ws_bytes);
-        lower = ow.take<unsigned long long>(nw);
-        newc = ow.take<unsigned long long>(kMaxOwnerWorld * kOwnerStride);
+        o = owner_carve(ow, ncells);
         if (!ow.ok()) return D3D_ERR_WORKSPACE;
-        D3D_HIP_CHECK(hipMemsetAsync(newc, 0, (size_t)kMaxOwnerWorld * kOwnerStride * 8, st));
+        D3D_HIP_CHECK(hipMemsetAsync(o.newc, 0, (size_t)kMaxOwnerWorld * kOwnerStride * 8, st));
     }
     const unsigned nblk = (unsigned)std::min<int64_t>(d3d_divup(nw, 256), 1024);
-    D3D_LAUNCH("k_grid_or", k_grid_or, dim3(nblk), dim3(256), 0, st, parts, stride_words, (int)world, nw, bitmap, (int)rank, lower,
-               newc);
-    PopcountWords f{bitmap, prefix};
-    return d3d_run_scan(f, nw, bsum, counts, -1, 0, ~0ull, st);
+    D3D_LAUNCH("k_grid_or", k_grid_or, dim3(nblk), dim3(256), 0, st, parts, stride_words, (int)world, nw, c.bitmap, (int)rank, o.lower,
+               o.newc);
+    PopcountWords f{c.bitmap, c.prefix};
+    return d3d_run_scan(f, nw, c.bsum, counts, -1, 0, ~0ull, st);
 }
 
 // key of every slot of a compact index (ascending cells): key_of_slot must hold counts[0] entries
@@ -457,12 +479,10 @@ extern "C" int d3d_grid_compact_keys(int64_t ncells, const void *workspace, size
 {
     hipStream_t st = (hipStream_t)stream;
     if (ncells <= 0 || !key_of_slot) return D3D_ERR_BAD_ARG;
-    const int64_t nw = d3d_divup(ncells, 64);
     WsCarver w((void *)workspace, workspace_bytes);
-    unsigned long long *bitmap = w.take<unsigned long long>(nw);
-    uint32_t *prefix = w.take<uint32_t>(nw);
+    const CompactWs c = compact_carve(w, ncells, false);
     if (!workspace || !w.ok()) return D3D_ERR_WORKSPACE;
-    D3D_LAUNCH("k_grid_keys", k_grid_keys, dim3((unsigned)d3d_divup(nw, 256)), dim3(256), 0, st, bitmap, prefix, nw, key_of_slot);
+    D3D_LAUNCH("k_grid_keys", k_grid_keys, dim3((unsigned)d3d_divup(c.nw, 256)), dim3(256), 0, st, c.bitmap, c.prefix, c.nw, key_of_slot);
     return D3D_OK;
 }
 
@@ -472,14 +492,12 @@ extern "C" int d3d_grid_compact_lookup(const int64_t *keys, int64_t m, int64_t n
 {
     hipStream_t st = (hipStream_t)stream;
     if (m < 0 || ncells <= 0 || (m > 0 && (!keys || !slot))) return D3D_ERR_BAD_ARG;
-    const int64_t nw = d3d_divup(ncells, 64);
     WsCarver w((void *)workspace, workspace_bytes);
-    unsigned long long *bitmap = w.take<unsigned long long>(nw);
-    uint32_t *prefix = w.take<uint32_t>(nw);
+    const CompactWs c = compact_carve(w, ncells, false);
     if (!workspace || !w.ok()) return D3D_ERR_WORKSPACE;
     if (m > 0)
         D3D_LAUNCH("k_grid_lookup", k_grid_lookup, dim3((unsigned)d3d_divup(m, 256)), dim3(256), 0, st, keys, m, ncells,
-                   bitmap, prefix, slot, (long long)missing);
+                   c.bitmap, c.prefix, slot, (long long)missing);
     return D3D_OK;
 }
 
@@ -497,10 +515,8 @@ extern "C" int d3d_sharded_scatter(const int64_t *keys_all, int64_t m, int64_t b
     if (nvox > 0 && (!table || !first || (!mean && !cnt_table))) return D3D_ERR_BAD_ARG;
     if (m > 0 && !keys_all) return D3D_ERR_BAD_ARG;
     if (n_local > 0 && (!agg || !cnt || !first_local || !slot_of_local)) return D3D_ERR_BAD_ARG;
-    const int64_t nw = d3d_divup(ncells, 64);
     WsCarver w((void *)compact_ws, compact_ws_bytes);
-    unsigned long long *bitmap = w.take<unsigned long long>(nw);
-    uint32_t *prefix = w.take<uint32_t>(nw);
+    const CompactWs cw = compact_carve(w, ncells, false);
     if (!compact_ws || !w.ok()) return D3D_ERR_WORKSPACE;
     const float identity = mean ? 0.f : (reduction == D3D_REDUCE_MAX ? -INFINITY : INFINITY);
     if (nvox > 0)
@@ -508,7 +524,7 @@ extern "C" int d3d_sharded_scatter(const int64_t *keys_all, int64_t m, int64_t b
                    table_stride, identity, table, mean ? nullptr : cnt_table, first);
     if (m > 0)
         D3D_LAUNCH("k_sharded_scatter", k_sharded_scatter, dim3((unsigned)d3d_divup(m, 256)), dim3(256), 0, st, keys_all, m,
-                   begin, n_local, ncells, bitmap, prefix, c, mean ? 1 : 0, agg, cnt, first_local, table, table_stride,
+                   begin, n_local, ncells, cw.bitmap, cw.prefix, c, mean ? 1 : 0, agg, cnt, first_local, table, table_stride,
                    cnt_table, first, key_of_slot, slot_of_local);
     return D3D_OK;
 }
@@ -532,16 +548,15 @@ extern "C" int d3d_sharded_finalize(int64_t nvox, int32_t c, const int64_t *firs
     if (nvox == 0) return D3D_OK;
     if (!first || !key_of_slot || !table || !vid_of_slot || !coords || !cnt_out || !feats || (!mean && !cnt_in) || !counts)
         return D3D_ERR_BAD_ARG;
-    int rc = d3d_grid_compact_index(first, nvox, n_total > 0 ? n_total : 1, counts, compact_ws, compact_ws_bytes, stream);
+    const int64_t ncells = n_total > 0 ? n_total : 1;          // the index is over the frame's point indices
+    int rc = d3d_grid_compact_index(first, nvox, ncells, counts, compact_ws, compact_ws_bytes, stream);
     if (rc) return rc;
-    const int64_t nw = d3d_divup(n_total > 0 ? n_total : 1, 64);
-    WsCarver w(compact_ws, compact_ws_bytes);
-    unsigned long long *bitmap = w.take<unsigned long long>(nw);
-    uint32_t *prefix = w.take<uint32_t>(nw);
+    WsCarver w(compact_ws, compact_ws_bytes);                 // (d3d_grid_compact_index has checked its size)
+    const CompactWs cw = compact_carve(w, ncells, false);
     const bool al16 = ((reinterpret_cast<uintptr_t>(feats) | reinterpret_cast<uintptr_t>(coords)) & 15) == 0;
     return dispatch(c == 4 && al16, [&](auto packed) -> int {
         D3D_LAUNCH("k_sharded_finalize", k_sharded_finalize<packed>, dim3((unsigned)d3d_divup(nvox, 256)), dim3(256), 0, st, nvox, c,
-                   first, n_total > 0 ? n_total : (int64_t)1, bitmap, prefix, key_of_slot, table, table_stride, mean, cnt_in,
+                   first, ncells, cw.bitmap, cw.prefix, key_of_slot, table, table_stride, mean, cnt_in,
                    (int64_t)shape[1], (int64_t)shape[2], vid_of_slot, coords, cnt_out, feats,
                    (reinterpret_cast<uintptr_t>(feats) & 15) == 0);
         return packed ? sharded_unpack(nvox, shape, coords, cnt_out, st) : D3D_OK;
@@ -562,13 +577,10 @@ extern "C" int d3d_sharded_scatter_owned(const int64_t *keys_local, int64_t n_lo
     if (table_stride < c + (mean ? 2 : 1)) return D3D_ERR_BAD_ARG;
     if (nvox > 0 && (!table || (!mean && !cnt_table))) return D3D_ERR_BAD_ARG;
     if (n_local > 0 && (!keys_local || !agg || !cnt || !slot_of_local)) return D3D_ERR_BAD_ARG;
-    const int64_t nw = d3d_divup(ncells, 64);
     WsCarver w((void *)compact_ws, compact_ws_bytes);
-    unsigned long long *bitmap = w.take<unsigned long long>(nw);
-    uint32_t *prefix = w.take<uint32_t>(nw);
+    const CompactWs cw = compact_carve(w, ncells, false);
     WsCarver ow((void *)owner_ws, owner_ws_bytes);
-    unsigned long long *lower = ow.take<unsigned long long>(nw);
-    unsigned long long *newc = ow.take<unsigned long long>(kMaxOwnerWorld * kOwnerStride);
+    const OwnerWs o = owner_carve(ow, ncells);
     WsCarver sw(scan_ws, scan_ws_bytes);
     unsigned long long *bsum = sw.take<unsigned long long>(d3d_divup(n_local > 0 ? n_local : 1, kScanTile) + 1);
     int64_t *scratch_counts = sw.take<int64_t>(D3D_NUM_COUNTS);
@@ -578,7 +590,7 @@ extern "C" int d3d_sharded_scatter_owned(const int64_t *keys_local, int64_t n_lo
         D3D_LAUNCH("k_sharded_fill_owned", k_sharded_fill_owned, dim3((unsigned)d3d_divup(d3d_divup(nvox * table_stride, 4), 256)), dim3(256), 0,
                    st, nvox, table_stride, identity, table, mean ? nullptr : cnt_table);
     if (n_local == 0) return D3D_OK;
-    OwnedRows f{keys_local, ncells, bitmap, prefix, lower, newc, (int)rank, (int)c, mean ? 1 : 0, (int)table_stride,
+    OwnedRows f{keys_local, ncells, cw.bitmap, cw.prefix, o.lower, o.newc, (int)rank, (int)c, mean ? 1 : 0, (int)table_stride,
                 agg, cnt, table, cnt_table, slot_of_local, identity,
                 ((reinterpret_cast<uintptr_t>(table) & 7) == 0) && ((reinterpret_cast<uintptr_t>(agg) & 15) == 0),
                 (reinterpret_cast<uintptr_t>(table) & 15) == 0};

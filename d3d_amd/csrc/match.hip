@@ -322,35 +322,53 @@ __global__ __launch_bounds__(kStableThreads) void k_match_stable(const int64_t *
 
 }  // namespace
 
+// the workspace of score_match_run: the candidate lists of k_match_candidates, the global bitmap of k_match_greedy, and the
+// ranks, list positions, two queues, holders and walk flags of k_match_stable
+struct MatchWs {
+    int32_t *cand_dst, *cand_cnt, *rank, *ptr, *q0, *q1, *hold, *need_walk;
+    float *cand_dist;
+    unsigned int *taken;
+};
+static size_t match_words(int64_t m) { return ((size_t)m + 31) / 32; }
+static MatchWs match_carve(WsCarver &w, int64_t n_total, int64_t m, int64_t batches)
+{
+    MatchWs c;
+    c.cand_dst = w.take<int32_t>((size_t)n_total * kMaxCand);
+    c.cand_dist = w.take<float>((size_t)n_total * kMaxCand);
+    c.cand_cnt = w.take<int32_t>((size_t)n_total);
+    c.taken = w.take<unsigned int>((size_t)batches * match_words(m));
+    c.rank = w.take<int32_t>((size_t)n_total);
+    c.ptr = w.take<int32_t>((size_t)n_total);
+    c.q0 = w.take<int32_t>((size_t)n_total);
+    c.q1 = w.take<int32_t>((size_t)n_total);
+    c.hold = w.take<int32_t>((size_t)batches * (size_t)m);
+    c.need_walk = w.take<int32_t>((size_t)batches);
+    return c;
+}
+
 // the work of d3d_score_match (batches = 1, no row_off / row_src / mask / row_mask) and d3d_score_match_batched, after their
-// argument checks.  For one batch the carve takes d3d_score_match_workspace_bytes(n, m) less 512 bytes.
+// argument checks
 static int score_match_run(const float *dist, const int64_t *row_src, const uint8_t *mask, const int64_t *row_mask, const int64_t *row_off,
                            int64_t batches, int64_t n_total, int64_t m, const int32_t *src_tag, const int32_t *dst_tag,
                            const float *dst_threshold, const int64_t *order, int32_t *src_match, int32_t *dst_match, int32_t *status,
                            void *workspace, size_t workspace_bytes, hipStream_t st)
 {
-    const size_t words = ((size_t)m + 31) / 32;
+    const size_t words = match_words(m);
     WsCarver w(workspace, workspace_bytes);
-    int32_t *cand_dst = w.take<int32_t>((size_t)n_total * kMaxCand);
-    float *cand_dist = w.take<float>((size_t)n_total * kMaxCand);
-    int32_t *cand_cnt = w.take<int32_t>((size_t)n_total);
-    unsigned int *taken = w.take<unsigned int>((size_t)batches * words);
-    int32_t *rank = w.take<int32_t>((size_t)n_total), *ptr = w.take<int32_t>((size_t)n_total), *q0 = w.take<int32_t>((size_t)n_total),
-            *q1 = w.take<int32_t>((size_t)n_total);
-    int32_t *hold = w.take<int32_t>((size_t)batches * (size_t)m), *need_walk = w.take<int32_t>((size_t)batches);
+    const MatchWs c = match_carve(w, n_total, m, batches);
     if (!workspace || !w.ok()) return D3D_ERR_WORKSPACE;
-    D3D_HIP_CHECK(hipMemsetAsync(taken, 0, (size_t)batches * words * 4, st));
+    D3D_HIP_CHECK(hipMemsetAsync(c.taken, 0, (size_t)batches * words * 4, st));
     D3D_LAUNCH("k_match_candidates", k_match_candidates, dim3((unsigned)d3d_divup(n_total, 256 / kWave)), dim3(256), 0, st, dist, n_total, m,
-               src_tag, dst_tag, dst_threshold, cand_dst, cand_dist, cand_cnt, status, row_src, mask, row_mask);
+               src_tag, dst_tag, dst_threshold, c.cand_dst, c.cand_dist, c.cand_cnt, status, row_src, mask, row_mask);
     const int64_t n = row_off ? 0 : n_total;          // the kernels take a problem's rows from row_off when it is given
-    D3D_LAUNCH("k_match_stable", k_match_stable, dim3((unsigned)batches), dim3(kStableThreads), 0, st, order, n, m, (const int32_t *)cand_dst,
-               (const int32_t *)cand_cnt, src_match, dst_match, rank, ptr, hold, q0, q1, need_walk, row_off);
+    D3D_LAUNCH("k_match_stable", k_match_stable, dim3((unsigned)batches), dim3(kStableThreads), 0, st, order, n, m, (const int32_t *)c.cand_dst,
+               (const int32_t *)c.cand_cnt, src_match, dst_match, c.rank, c.ptr, c.hold, c.q0, c.q1, c.need_walk, row_off);
     const size_t map_bytes = words * 4;
     // (+ 16 KB of staging: inside the 64 KB a workgroup gets without opting in)
     return dispatch(map_bytes <= 32 * 1024, [&](auto lds_map) {
         D3D_LAUNCH("k_match_greedy", k_match_greedy<lds_map>, dim3((unsigned)batches), dim3(64), lds_map ? map_bytes : 0, st, order, n, m,
-                   (const int32_t *)cand_dst, (const int32_t *)cand_cnt, src_match, dst_match, taken, dist, src_tag, dst_tag, dst_threshold,
-                   (const int32_t *)need_walk, row_off, row_src, mask, row_mask);
+                   (const int32_t *)c.cand_dst, (const int32_t *)c.cand_cnt, src_match, dst_match, c.taken, dist, src_tag, dst_tag, dst_threshold,
+                   (const int32_t *)c.need_walk, row_off, row_src, mask, row_mask);
         return D3D_OK;
     });
 }
@@ -367,9 +385,9 @@ extern "C" size_t d3d_score_match_batched_workspace_bytes(int64_t n_total, int64
     if (n_total < 1) n_total = 1;
     if (m < 1) m = 1;
     if (batches < 1) batches = 1;
-    return d3d_align_up((size_t)n_total * kMaxCand * 4) * 2 + d3d_align_up((size_t)n_total * 4) * 5 +
-           d3d_align_up((size_t)batches * (((size_t)m + 31) / 32) * 4) + d3d_align_up((size_t)batches * (size_t)m * 4) +
-           d3d_align_up((size_t)batches * 4) + 1024;
+    WsCarver w(nullptr, 0);
+    match_carve(w, n_total, m, batches);
+    return w.off;
 }
 
 extern "C" int d3d_score_match_batched(const float *dist, const int64_t *row_src, const uint8_t *mask, const int64_t *row_mask,
@@ -392,13 +410,7 @@ extern "C" int d3d_score_match_batched(const float *dist, const int64_t *row_src
                            dst_match, status, workspace, workspace_bytes, st);
 }
 
-extern "C" size_t d3d_score_match_workspace_bytes(int64_t n, int64_t m)
-{
-    if (n < 1) n = 1;
-    if (m < 1) m = 1;
-    return d3d_align_up((size_t)n * kMaxCand * 4) * 2 + d3d_align_up((size_t)n * 4) + d3d_align_up(((size_t)m + 31) / 32 * 4) + 512 +
-           d3d_align_up((size_t)n * 4) * 4 + d3d_align_up((size_t)m * 4) + 256;          // k_match_stable: rank, ptr, two queues, holders
-}
+extern "C" size_t d3d_score_match_workspace_bytes(int64_t n, int64_t m) { return d3d_score_match_batched_workspace_bytes(n, m, 1); }
 
 // status word (device, int32): bit 0 = some row had more than 64 candidates within its threshold (informational: such a row
 // lists its 64 nearest and sweeps its whole row if all of them are taken -- the result is the reference's in every case)

@@ -1372,10 +1372,24 @@ inline unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)std::max
 // ====================================================================== C ABI
 extern "C" int d3d_owner_record_words(int32_t c) { return rec_stride(c); }
 
+// d3d_owner_pack: records and rows per (tile, destination), and their bases per destination
+struct PackWs { uint32_t ntiles, *tilecnt, *dest_base, *tilerows, *dest_rowbase; };
+static PackWs pack_carve(WsCarver &w, int64_t n, int32_t world)
+{
+    PackWs p;
+    p.ntiles = (uint32_t)d3d_divup(n > 0 ? n : 1, kPackTile);
+    p.tilecnt = w.take<uint32_t>((size_t)p.ntiles * world);
+    p.dest_base = w.take<uint32_t>(world + 1);
+    p.tilerows = w.take<uint32_t>((size_t)p.ntiles * world);
+    p.dest_rowbase = w.take<uint32_t>(world + 1);
+    return p;
+}
+
 extern "C" size_t d3d_owner_pack_workspace_bytes(int64_t n, int32_t world)
 {
-    const int64_t ntiles = d3d_divup(n > 0 ? n : 1, kPackTile);
-    return 2 * (d3d_align_up((size_t)ntiles * world * 4) + d3d_align_up((size_t)(world + 1) * 4)) + 256;
+    WsCarver w(nullptr, 0);
+    pack_carve(w, n, world);
+    return w.off;
 }
 
 // local voxels (outputs of d3d_voxelize_3d_reduce: keys[n + 1], cnt[n], agg[n, c], first[n], counts) -> records grouped by
@@ -1397,36 +1411,33 @@ extern "C" int d3d_owner_pack(const int64_t *keys, const int32_t *cnt, const flo
     const bool dense = max_points > 0;
     if (dense && (c != 4 || (n > 0 && (!seg_base || !rows_local || !send_rows)))) return D3D_ERR_BAD_ARG;
     if (dense && ((reinterpret_cast<uintptr_t>(rows_local) | reinterpret_cast<uintptr_t>(send_rows)) & 15)) return D3D_ERR_BAD_ARG;
-    if (!workspace || workspace_bytes < d3d_owner_pack_workspace_bytes(n, world)) return D3D_ERR_WORKSPACE;
-    const uint32_t ntiles = (uint32_t)d3d_divup(n > 0 ? n : 1, kPackTile);
     WsCarver w(workspace, workspace_bytes);
-    uint32_t *tilecnt = w.take<uint32_t>((size_t)ntiles * world);
-    uint32_t *dest_base = w.take<uint32_t>(world + 1);
-    uint32_t *tilerows = w.take<uint32_t>((size_t)ntiles * world);
-    uint32_t *dest_rowbase = w.take<uint32_t>(world + 1);
+    const PackWs p = pack_carve(w, n, world);
+    if (!workspace || !w.ok()) return D3D_ERR_WORKSPACE;
+    const uint32_t ntiles = p.ntiles;
     if (points && (reinterpret_cast<uintptr_t>(points) & 15)) return D3D_ERR_BAD_ARG;
     PackDense pd{(uint32_t)max_points, seg_base, reinterpret_cast<const float4 *>(rows_local), reinterpret_cast<const float4 *>(points),
-                 index_offset, reinterpret_cast<float4 *>(send_rows), tilerows, dest_rowbase};
+                 index_offset, reinterpret_cast<float4 *>(send_rows), p.tilerows, p.dest_rowbase};
     if (n > 0) {
         const int rc = dispatch(dense, [&](auto DENSE) {
-            D3D_LAUNCH("k_owner_count", k_owner_count<DENSE>, dim3(ntiles), dim3(1024), 0, st, keys, cnt, counts, (uint32_t)world, tilecnt, pd);
+            D3D_LAUNCH("k_owner_count", k_owner_count<DENSE>, dim3(ntiles), dim3(1024), 0, st, keys, cnt, counts, (uint32_t)world, p.tilecnt, pd);
             return D3D_OK;
         });
         if (rc) return rc;
     } else {
-        D3D_HIP_CHECK(hipMemsetAsync(tilecnt, 0, (size_t)ntiles * world * 4, st));
-        D3D_HIP_CHECK(hipMemsetAsync(tilerows, 0, (size_t)ntiles * world * 4, st));
+        D3D_HIP_CHECK(hipMemsetAsync(p.tilecnt, 0, (size_t)ntiles * world * 4, st));
+        D3D_HIP_CHECK(hipMemsetAsync(p.tilerows, 0, (size_t)ntiles * world * 4, st));
     }
     // up to kFusedEntries matrix words every scatter workgroup adds up its own offsets (one launch less: -8 us at config 5)
     const bool fused = n > 0 && (uint64_t)ntiles * (uint64_t)world <= (uint64_t)kFusedEntries;
     const int64_t *status_key = keys ? keys + n : (const int64_t *)nullptr;
     if (!fused)
-        D3D_LAUNCH("k_owner_offsets", k_owner_offsets, dim3(1), dim3(1024), 0, st, tilecnt, dense ? tilerows : (uint32_t *)nullptr, ntiles,
-                   (uint32_t)world, send_counts, dest_base, dest_rowbase, status_key);
+        D3D_LAUNCH("k_owner_offsets", k_owner_offsets, dim3(1), dim3(1024), 0, st, p.tilecnt, dense ? p.tilerows : (uint32_t *)nullptr, ntiles,
+                   (uint32_t)world, send_counts, p.dest_base, p.dest_rowbase, status_key);
     if (n == 0) return D3D_OK;
     return dispatch(dense, [&](auto DENSE) {
         D3D_LAUNCH("k_owner_scatter", k_owner_scatter<DENSE>, dim3(ntiles), dim3(1024), 0, st, keys, cnt, agg, first, counts, (int)c,
-                   (uint32_t)world, tilecnt, dest_base, send, perm, pos_of_local, pd, fused ? ntiles : 0u, send_counts, status_key);
+                   (uint32_t)world, p.tilecnt, p.dest_base, send, perm, pos_of_local, pd, fused ? ntiles : 0u, send_counts, status_key);
         return D3D_OK;
     });
 }
@@ -1511,10 +1522,23 @@ extern "C" int d3d_owner_mark_first(const int64_t *first_o, const int64_t *count
     return D3D_OK;
 }
 
+// d3d_owner_number: set bits before every word of the frame's bitmap, and the look-back status of the tiles that count them
+struct NumberWs { int64_t nw; uint32_t ntiles, *pre; u64 *status; };
+static NumberWs number_carve(WsCarver &w, int64_t n_total)
+{
+    NumberWs m;
+    m.nw = d3d_divup(n_total > 0 ? n_total : 1, 64);
+    m.ntiles = (uint32_t)d3d_divup(m.nw, kPrefixTile);
+    m.pre = w.take<uint32_t>(m.nw);
+    m.status = w.take<u64>((size_t)m.ntiles + 1);
+    return m;
+}
+
 extern "C" size_t d3d_owner_number_workspace_bytes(int64_t n_total)
 {
-    const int64_t nw = d3d_divup(n_total > 0 ? n_total : 1, 64);
-    return d3d_align_up((size_t)nw * 4) + d3d_align_up((size_t)(d3d_divup(nw, kPrefixTile) + 1) * 8) + 256;
+    WsCarver w(nullptr, 0);
+    number_carve(w, n_total);
+    return w.off;
 }
 
 // global_bits = the SUM all-reduce of every owner's d3d_owner_mark_first bitmap (disjoint bit sets: their OR; + the status word).  vids[i] =
@@ -1527,17 +1551,14 @@ extern "C" int d3d_owner_number(const uint64_t *global_bits, int64_t n_total, co
     hipStream_t st = (hipStream_t)stream;
     if (n_total < 0 || cap_o < 0 || !counts_o || !counts_out || !global_bits) return D3D_ERR_BAD_ARG;
     if (n_total >= (1ll << 32)) return D3D_ERR_BAD_ARG;
-    if (!workspace || workspace_bytes < d3d_owner_number_workspace_bytes(n_total)) return D3D_ERR_WORKSPACE;
-    const int64_t nw = d3d_divup(n_total > 0 ? n_total : 1, 64);
     WsCarver w(workspace, workspace_bytes);
-    uint32_t *pre = w.take<uint32_t>(nw);
-    const uint32_t ntiles = (uint32_t)d3d_divup(nw, kPrefixTile);
-    u64 *status = w.take<u64>((size_t)ntiles + 1);
-    D3D_HIP_CHECK(hipMemsetAsync(status, 0, ((size_t)ntiles + 1) * 8, st));
-    D3D_LAUNCH("k_first_prefix", k_first_prefix, dim3(ntiles), dim3(kPrefixThreads), 0, st, (const u64 *)global_bits, nw, pre, status, ntiles,
-               counts_out);
+    const NumberWs m = number_carve(w, n_total);
+    if (!workspace || !w.ok()) return D3D_ERR_WORKSPACE;
+    D3D_HIP_CHECK(hipMemsetAsync(m.status, 0, ((size_t)m.ntiles + 1) * 8, st));
+    D3D_LAUNCH("k_first_prefix", k_first_prefix, dim3(m.ntiles), dim3(kPrefixThreads), 0, st, (const u64 *)global_bits, m.nw, m.pre, m.status,
+               m.ntiles, counts_out);
     if (cap_o > 0)
-        D3D_LAUNCH("k_owner_number", k_owner_number, dim3(blocks_for(cap_o)), dim3(256), 0, st, counts_o, (const u64 *)global_bits, pre,
+        D3D_LAUNCH("k_owner_number", k_owner_number, dim3(blocks_for(cap_o)), dim3(256), 0, st, counts_o, (const u64 *)global_bits, m.pre,
                    first_o, vids);
     return D3D_OK;
 }

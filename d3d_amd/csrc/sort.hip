@@ -226,13 +226,26 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_scatter(const K *__restrict__
     }
 }
 
+// the radix path's workspace: carved here for the launcher, and on a null base for the size query
+template <typename U> struct RadixWs {
+    U *kb0, *kb1;
+    uint32_t *vb0, *vb1, *ghist, *tilehist;
+    RsPlan *plan;
+};
 template <typename K>
-size_t radix_bytes(int64_t n)
+RadixWs<typename KeyBits<K>::U> radix_carve(WsCarver &w, int64_t n)
 {
     typedef typename KeyBits<K>::U U;
-    const size_t ntiles = (size_t)d3d_divup(n, kRsTile);
-    return 2 * d3d_align_up(sizeof(U) * (size_t)n) + 2 * d3d_align_up(4 * (size_t)n) + d3d_align_up(sizeof(U) * kRsBins * 4) +
-           d3d_align_up(ntiles * kRsBins * 4) + d3d_align_up((sizeof(U) + 1) * sizeof(RsPlan)) + 256;
+    constexpr int PASSES = sizeof(U);
+    RadixWs<U> r;
+    r.kb0 = w.take<U>(n);
+    r.kb1 = w.take<U>(n);
+    r.vb0 = w.take<uint32_t>(n);
+    r.vb1 = w.take<uint32_t>(n);
+    r.ghist = w.take<uint32_t>((size_t)PASSES * kRsBins);
+    r.tilehist = w.take<uint32_t>((size_t)d3d_divup(n, kRsTile) * kRsBins);
+    r.plan = w.take<RsPlan>(PASSES + 1);              // k_rs_plan: one per pass, and the "every key equal" flag behind them
+    return r;
 }
 
 // order[n] <- stable descending argsort of keys.  n_dev (optional): the number of keys on the device, <= n (the host only has
@@ -246,21 +259,17 @@ int radix_argsort_desc(const K *keys, int64_t n, V *order, void *ws, size_t ws_b
     constexpr int PASSES = sizeof(U);
     const unsigned ntiles = (unsigned)d3d_divup(n, kRsTile);
     WsCarver w(ws, ws_bytes);
-    U *kb0 = w.take<U>(n), *kb1 = w.take<U>(n);
-    uint32_t *vb0 = w.take<uint32_t>(n), *vb1 = w.take<uint32_t>(n);
-    uint32_t *ghist = w.take<uint32_t>((size_t)PASSES * kRsBins);
-    uint32_t *tilehist = w.take<uint32_t>((size_t)ntiles * kRsBins);
-    RsPlan *plan = w.take<RsPlan>(PASSES + 1);
+    const RadixWs<U> r = radix_carve<K>(w, n);
     if (!ws || !w.ok()) return D3D_ERR_WORKSPACE;
     const int npass = key_bits > 0 && key_bits < PASSES * 8 ? (key_bits + 7) / 8 : PASSES;
-    D3D_HIP_CHECK(hipMemsetAsync(ghist, 0, (size_t)PASSES * kRsBins * 4, st));
-    D3D_LAUNCH("k_rs_hist", k_rs_hist<K>, dim3(kRsHistBlocks), dim3(kRsHistThreads), 0, st, keys, (uint32_t)n, ghist, n_dev);
-    D3D_LAUNCH("k_rs_plan", k_rs_plan<PASSES>, dim3(1), dim3(kRsBins), 0, st, ghist, (uint32_t)n, plan, n_dev, 0);
+    D3D_HIP_CHECK(hipMemsetAsync(r.ghist, 0, (size_t)PASSES * kRsBins * 4, st));
+    D3D_LAUNCH("k_rs_hist", k_rs_hist<K>, dim3(kRsHistBlocks), dim3(kRsHistThreads), 0, st, keys, (uint32_t)n, r.ghist, n_dev);
+    D3D_LAUNCH("k_rs_plan", k_rs_plan<PASSES>, dim3(1), dim3(kRsBins), 0, st, r.ghist, (uint32_t)n, r.plan, n_dev, 0);
     for (int p = 0; p < npass; p++) {
-        D3D_LAUNCH("k_rs_tile_hist", k_rs_tile_hist<K>, dim3(ntiles), dim3(kRsThreads), 0, st, keys, kb0, kb1, (uint32_t)n, p,
-                   (const RsPlan *)plan, tilehist, n_dev);
-        D3D_LAUNCH("k_rs_scatter", (k_rs_scatter<K, V>), dim3(ntiles), dim3(kRsThreads), 0, st, keys, kb0, kb1, vb0, vb1, (uint32_t)n, p,
-                   (const RsPlan *)plan, (const uint32_t *)tilehist, (const uint32_t *)ghist, order, n_dev, 0);
+        D3D_LAUNCH("k_rs_tile_hist", k_rs_tile_hist<K>, dim3(ntiles), dim3(kRsThreads), 0, st, keys, r.kb0, r.kb1, (uint32_t)n, p,
+                   (const RsPlan *)r.plan, r.tilehist, n_dev);
+        D3D_LAUNCH("k_rs_scatter", (k_rs_scatter<K, V>), dim3(ntiles), dim3(kRsThreads), 0, st, keys, r.kb0, r.kb1, r.vb0, r.vb1, (uint32_t)n, p,
+                   (const RsPlan *)r.plan, (const uint32_t *)r.tilehist, (const uint32_t *)r.ghist, order, n_dev, 0);
     }
     return D3D_OK;
 }
@@ -400,26 +409,30 @@ __global__ __launch_bounds__(256) void k_cs_rank_big(const int32_t *__restrict__
     if (me < kb) order[rank] = (int32_t)myidx;
 }
 
-size_t counts_argsort_bytes(int64_t n)
+struct CountsWs { uint32_t *tilehist, *bigidx, *kbig; };
+CountsWs counts_carve(WsCarver &w, int64_t n, uint32_t bigcap)
 {
-    return d3d_align_up((size_t)d3d_divup(n, kRsTile) * kRsBins * 4) + d3d_align_up(((size_t)n / 255 + 1) * 4) + 256;
+    CountsWs c;
+    c.tilehist = w.take<uint32_t>((size_t)d3d_divup(n, kRsTile) * kRsBins);
+    c.bigidx = w.take<uint32_t>(bigcap);
+    c.kbig = w.take<uint32_t>(1);
+    return c;
 }
+static inline uint32_t counts_bigcap(int64_t max_key_sum) { return (uint32_t)(max_key_sum / 255 + 1); }
 
 int counts_argsort_desc(const int32_t *keys, int64_t n, const int64_t *n_dev, int64_t max_key_sum, int32_t *order, void *ws, size_t ws_bytes,
                         hipStream_t st)
 {
     const unsigned ntiles = (unsigned)d3d_divup(n, kRsTile);
-    const uint32_t bigcap = (uint32_t)(max_key_sum / 255 + 1);
+    const uint32_t bigcap = counts_bigcap(max_key_sum);
     WsCarver w(ws, ws_bytes);
-    uint32_t *tilehist = w.take<uint32_t>((size_t)ntiles * kRsBins);
-    uint32_t *bigidx = w.take<uint32_t>(bigcap);
-    uint32_t *kbig = w.take<uint32_t>(1);
+    const CountsWs c = counts_carve(w, n, bigcap);
     if (!ws || !w.ok()) return D3D_ERR_WORKSPACE;
-    D3D_LAUNCH("k_cs_tile_hist", k_cs_tile_hist, dim3(ntiles), dim3(kRsThreads), 0, st, keys, (uint32_t)n, tilehist, n_dev);
-    D3D_LAUNCH("k_cs_scatter", k_cs_scatter, dim3(ntiles), dim3(kRsThreads), 0, st, keys, (uint32_t)n, (const uint32_t *)tilehist, order, bigidx,
-               bigcap, kbig, n_dev);
-    D3D_LAUNCH("k_cs_rank_big", k_cs_rank_big, dim3((unsigned)d3d_divup((int64_t)bigcap, 256)), dim3(256), 0, st, keys, (const uint32_t *)bigidx,
-               (const uint32_t *)kbig, order);
+    D3D_LAUNCH("k_cs_tile_hist", k_cs_tile_hist, dim3(ntiles), dim3(kRsThreads), 0, st, keys, (uint32_t)n, c.tilehist, n_dev);
+    D3D_LAUNCH("k_cs_scatter", k_cs_scatter, dim3(ntiles), dim3(kRsThreads), 0, st, keys, (uint32_t)n, (const uint32_t *)c.tilehist, order, c.bigidx,
+               bigcap, c.kbig, n_dev);
+    D3D_LAUNCH("k_cs_rank_big", k_cs_rank_big, dim3((unsigned)d3d_divup((int64_t)bigcap, 256)), dim3(256), 0, st, keys, (const uint32_t *)c.bigidx,
+               (const uint32_t *)c.kbig, order);
     return D3D_OK;
 }
 
@@ -595,14 +608,24 @@ __global__ __launch_bounds__(kSsSortThreads) void k_sort_small(const K *__restri
 static inline int ss_buckets(int64_t n) { return (int)std::min<int64_t>(std::max<int64_t>(n / 192, 16), kSsMaxBuckets); }
 static inline bool ss_eligible(int64_t n) { return n >= kSsMinN && n <= kSsMaxN; }
 
+template <typename U> struct BucketWs {
+    U *spl_d, *dk;
+    uint32_t *spl_i, *pb, *tileoff, *bucket_cnt, *bucket_base, *di;
+};
 template <typename K>
-size_t bucket_bytes(int64_t n)
+BucketWs<typename KeyBits<K>::U> bucket_carve(WsCarver &w, int64_t n)
 {
     typedef typename KeyBits<K>::U U;
-    const size_t ntiles = (size_t)d3d_divup(n, kSsTile);
-    return d3d_align_up(kSsMaxBuckets * sizeof(U)) + d3d_align_up(kSsMaxBuckets * 4) + d3d_align_up((size_t)n * 4) +
-           d3d_align_up(ntiles * kSsMaxBuckets * 4) + 2 * d3d_align_up((kSsMaxBuckets + 1) * 4) + d3d_align_up((size_t)n * sizeof(U)) +
-           d3d_align_up((size_t)n * 4) + 256;
+    BucketWs<U> b;
+    b.spl_d = w.take<U>(kSsMaxBuckets);
+    b.spl_i = w.take<uint32_t>(kSsMaxBuckets);
+    b.pb = w.take<uint32_t>(n);
+    b.tileoff = w.take<uint32_t>((size_t)d3d_divup(n, kSsTile) * kSsMaxBuckets);
+    b.bucket_cnt = w.take<uint32_t>(kSsMaxBuckets + 1);
+    b.bucket_base = w.take<uint32_t>(kSsMaxBuckets + 1);       // k_ss_scatter: the total behind the B bases
+    b.dk = w.take<U>(n);
+    b.di = w.take<uint32_t>(n);
+    return b;
 }
 
 template <typename K, typename V>
@@ -612,30 +635,27 @@ int bucket_argsort_desc(const K *keys, int64_t n, V *order, void *ws, size_t ws_
     const int B = ss_buckets(n);
     const unsigned ntiles = (unsigned)d3d_divup(n, kSsTile);
     WsCarver w(ws, ws_bytes);
-    U *spl_d = w.take<U>(kSsMaxBuckets);
-    uint32_t *spl_i = w.take<uint32_t>(kSsMaxBuckets);
-    uint32_t *pb = w.take<uint32_t>(n);
-    uint32_t *tileoff = w.take<uint32_t>((size_t)ntiles * kSsMaxBuckets);
-    uint32_t *bucket_cnt = w.take<uint32_t>(kSsMaxBuckets + 1);
-    uint32_t *bucket_base = w.take<uint32_t>(kSsMaxBuckets + 1);
-    U *dk = w.take<U>(n);
-    uint32_t *di = w.take<uint32_t>(n);
+    const BucketWs<U> b = bucket_carve<K>(w, n);
     if (!ws || !w.ok()) return D3D_ERR_WORKSPACE;
-    D3D_LAUNCH("k_ss_splitters", k_ss_splitters<K>, dim3(1), dim3(kSsSortThreads), 0, st, keys, (uint32_t)n, B, spl_d, spl_i, bucket_cnt);
-    D3D_LAUNCH("k_ss_count", k_ss_count<K>, dim3(ntiles), dim3(kSsCountThreads), 0, st, keys, (uint32_t)n, B, (const U *)spl_d,
-               (const uint32_t *)spl_i, pb, tileoff, bucket_cnt);
-    D3D_LAUNCH("k_ss_scatter", k_ss_scatter<K>, dim3(ntiles), dim3(kSsCountThreads), 0, st, keys, (uint32_t)n, B, (const uint32_t *)pb,
-               (const uint32_t *)tileoff, (const uint32_t *)bucket_cnt, bucket_base, dk, di);
-    D3D_LAUNCH("k_ss_bucket", (k_ss_bucket<U, V>), dim3((unsigned)B), dim3(kSsSortThreads), 0, st, (const U *)dk, (const uint32_t *)di,
-               (const uint32_t *)bucket_base, order);
+    D3D_LAUNCH("k_ss_splitters", k_ss_splitters<K>, dim3(1), dim3(kSsSortThreads), 0, st, keys, (uint32_t)n, B, b.spl_d, b.spl_i, b.bucket_cnt);
+    D3D_LAUNCH("k_ss_count", k_ss_count<K>, dim3(ntiles), dim3(kSsCountThreads), 0, st, keys, (uint32_t)n, B, (const U *)b.spl_d,
+               (const uint32_t *)b.spl_i, b.pb, b.tileoff, b.bucket_cnt);
+    D3D_LAUNCH("k_ss_scatter", k_ss_scatter<K>, dim3(ntiles), dim3(kSsCountThreads), 0, st, keys, (uint32_t)n, B, (const uint32_t *)b.pb,
+               (const uint32_t *)b.tileoff, (const uint32_t *)b.bucket_cnt, b.bucket_base, b.dk, b.di);
+    D3D_LAUNCH("k_ss_bucket", (k_ss_bucket<U, V>), dim3((unsigned)B), dim3(kSsSortThreads), 0, st, (const U *)b.dk, (const uint32_t *)b.di,
+               (const uint32_t *)b.bucket_base, order);
     return D3D_OK;
 }
 
+// serves both routes of argsort_desc at n keys: the radix carve, and the bucket carve where the bucket path takes n
 template <typename K, typename V>
 size_t argsort_bytes(int64_t n)
 {
     if (n < 1) n = 1;
-    return std::max(radix_bytes<K>(n), ss_eligible(n) ? bucket_bytes<K>(n) : (size_t)0);
+    WsCarver r(nullptr, 0), b(nullptr, 0);
+    radix_carve<K>(r, n);
+    if (ss_eligible(n)) bucket_carve<K>(b, n);
+    return std::max(r.off, b.off);
 }
 
 template <typename K, typename V>
@@ -659,7 +679,12 @@ extern "C" int d3d_internal_argsort_desc_i32(const int32_t *keys, int64_t n, int
 }
 
 // voxel counts on a device-side count: keys >= 0 whose SUM is at most max_key_sum (the points), n_dev <= n of them
-extern "C" size_t d3d_internal_argsort_counts_bytes(int64_t n) { return counts_argsort_bytes(n); }
+extern "C" size_t d3d_internal_argsort_counts_bytes(int64_t n)
+{
+    WsCarver w(nullptr, 0);
+    counts_carve(w, n, counts_bigcap(n));          // (the launcher clamps max_key_sum to n)
+    return w.off;
+}
 extern "C" int d3d_internal_argsort_desc_counts_dev(const int32_t *keys, int64_t n, const int64_t *n_dev, int64_t max_key_sum, int32_t *order,
                                                     void *ws, size_t ws_bytes, hipStream_t st)
 {

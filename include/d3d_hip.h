@@ -513,7 +513,10 @@ int d3d_stream_probe(int mode, void *buf, size_t bytes, void *stream);
  * a rectangle of non-positive area gives 0 for every type.  GBOX / DBOX are D3D_ERR_UNSUPPORTED (the reference's Python
  * layer raises "Unrecognized iou type!" for them, box/__init__.py:216-217).
  * dtype D3D_F64_M32 (BOX / RBOX; GRBOX / DRBOX: D3D_ERR_UNSUPPORTED): boxes f64, ious f32; above 65536 pairs the workspace is
- * required (D3D_ERR_WORKSPACE without it; size: the query with D3D_F64_M32). */
+ * required (D3D_ERR_WORKSPACE without it; size: the query with D3D_F64_M32).
+ * The query is the largest of what the forward, the backward and the two-kernel routes of GRBOX / DRBOX carve for n x m boxes
+ * (fp64 geometry for every dtype but D3D_F32), with one exception: the GRBOX / DRBOX backward of more than 2^33 pairs wants
+ * n x ceil(m / 64) words of marks, which the query does not follow -- it runs its single kernel unless more is passed. */
 size_t d3d_iou2d_workspace_bytes(int64_t n, int64_t m, int32_t dtype);
 int d3d_iou2d_forward(const void *boxes1, int64_t n, const void *boxes2, int64_t m,
                       int32_t iou_type, int32_t dtype, void *ious,
@@ -649,6 +652,8 @@ size_t d3d_argsort_desc_workspace_bytes(int64_t n, int32_t dtype);
 int d3d_argsort_desc(const void *keys, int64_t n, int32_t dtype, int64_t *order,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* the larger of the hard-NMS and the soft-NMS layout for n fp64 boxes, each followed by the score order (n i64) and the
+ * scratch of d3d_argsort_desc that a call with order == NULL uses */
 size_t d3d_nms2d_workspace_bytes(int64_t n);
 
 /* replaces nms2d / nms2d_cuda (reference d3d/box/nms.h:6-18, nms.cpp:10-119,
