@@ -18,12 +18,19 @@ A "step" is one pass of the hot path over one batch of synthetic input already r
 Rank 0 prints ONE JSON line.  `value` is whole-job Mpoints/s, `ms_per_step` the time of one of the K timed steps.
 `--dump-outputs DIR` writes what the last timed step returned to rank 0's caller as DIR/<name>.npy (float32 / float64, a fixed
 seeded sample of rows when the whole result exceeds 60 MB; see dump_outputs): the inputs are seeded, so two builds compare output
-for output.  At N = 1 the line also carries `roofline` (dominant kernel,
-timed with HIP events on its launch stream in a separate pass of the same K steps), `roofline_large` (the same fill kernel
-on config 5's whole 8 M-point frame on one GPU: 3 GB of output, beyond the 256 MB Infinity Cache, next to the stream
-bandwidth measured on the same box), `cpu_baseline` (the REAL reference voxelizer built from /root/reference into
-oracle/_ref, or the C port when that binary is absent) and `extra` (uniform cloud, sparse contract, rotated IoU Mpairs/s,
-NMS boxes/s, iou3d Mpairs/s).
+for output.
+
+A plain run does what that line's headline needs and nothing else: set-up, W warm-up steps, the K timed steps, the dump when asked
+for, the line (`metric`, `value`, `unit`, `ms_per_step`, `dtype`, `higher_is_better`, the workload's description and its voxel
+count).  `--full` runs every other leg as well and adds it to the same line.  At N = 1, all after the timed region:
+`timed_region_repeats` (the region five more times), `roofline` (dominant kernel, timed with HIP events on its launch stream in a separate pass of the
+same K steps, with the event overhead and the stream probes at its footprint), `roofline_operator`, `roofline_large` (the same
+fill kernel on config 5's whole 8 M-point frame on one GPU: 3 GB of output, beyond the 256 MB Infinity Cache, next to the stream
+bandwidth measured in the same process), `cpu_baseline` (the compiled reference voxelizer under oracle/_ref, or the C port when
+that binary is absent), `cpu_baseline_all_cores` and `extra` (uniform cloud, sparse contract, rotated IoU Mpairs/s, NMS boxes/s,
+iou3d Mpairs/s, ...); `--skip-large`, `--skip-cpu`, `--skip-extra` take legs out of a full run.  At N > 1: the single-GPU bases
+(`single_gpu_best`, `single_gpu_whole_frame`, `same_operator_one_rank`), `replicated_result`, `independent_frames_per_rank`, the
+RCCL rank check and the per-step exchange figures.  The `--*-only` options run one leg alone and print it.
 """
 import argparse
 import ctypes
@@ -740,18 +747,114 @@ def extras(args):
     return ex
 
 
-def main():
+def dense_legs(args, step, n, P, V, kept, plan, split_bytes, split_skipped, dt):
+    """what --full adds to the N = 1 line from the headline workload itself, each in passes of its own AFTER the timed region:
+    the region's spread, the per-kernel HIP-event pass and the rooflines priced on it, the event overhead and the stream probes"""
+    out = {}
+    out["timed_region_repeats"] = spread(step, args.steps)
+    prof = kernel_profile(step, args.steps)
+    dom = max(prof.items(), key=lambda kv: kv[1]["total_ms"])
+    # compulsory bytes of each kernel per launch (DESIGN.md "kernels"); C = 4
+    npad = -(-n // 16384) * 16384
+    algo = {
+        # voxels[V,P,4] written; kept rows (16 B) gathered from the staged segments, one 16-byte record per voxel read
+        "k_fill_c4": V * P * 16 + kept * 16 + V * 16,
+        # binned index (n >= 32 k points): partition, per-bucket index in LDS, numbering + per-voxel outputs
+        "k_tile_sort": n * 16 + n * 8 + npad * 4,               # rows read; {cell, index} entries + firstmap reset written
+        "k_bin_count": n * 16 + npad * 8,                       # rows read; bucket word + firstmap reset written
+        "k_bin_scatter": n * (16 + 4) + n * (16 + 4),           # rows + bucket words read; rows + indices written
+        "k_bucket_index": n * (16 + 4) + kept * 16 + V * (16 + 4),   # bucket read; ranked rows, records, firstmap written
+        "k_meta_first": npad * 4 + V * 16 + kept * 16 + V * (16 + 24 + 4 + P + 16),
+        "k_emit": emit_bytes(n, V, P),                          # SURVEY 8(d): 16 B/point in + every output (no scratch)
+        # round 6: the same minus the zero padding stored under the index launches (k_tile_sort's / k_first_count's fillers)
+        "k_emit_split": split_bytes,
+        # hash-table index (other inputs)
+        "k_insert": n * 16 + n * 8 + n * 8,          # points read, pslot+arrival written, one 8-byte slot touched
+        "k_scatter": n * 8 + n * 8 + n * 4 + n * 8,  # pslot+arrival read, aux read, index written, (cnt,base) written
+        "k_select": n * 8 + kept * 4,
+        "k_init": None,
+    }
+    name = dom[0]
+    b_alg = algo.get(name) or (n * 16)
+    ach = b_alg / (dom[1]["avg_us"] * 1e-6) / 1e9
+    out["roofline"] = dict(bound="hbm", kernel=name, achieved=round(ach, 1), peak=HBM_PEAK_GBS, unit="GB/s",
+                           frac=round(ach / HBM_PEAK_GBS, 4), traffic=load_traffic(name, "config2")[0],
+                           traffic_source=load_traffic(name, "config2")[1], avg_us=round(dom[1]["avg_us"], 2), algorithmic_bytes=b_alg,
+                           timing="HIP events on the launch stream, separate pass of the same %d steps" % args.steps,
+                           cache_note="config 2's 345 MB of outputs partly drain through the 256 MB Infinity Cache: this fraction "
+                                      "is cache-assisted; the HBM claim is roofline_large.frac (same kernel, 3.3 GB of outputs)",
+                           bytes_note="algorithmic_bytes = SURVEY 8(d): 16 B/point read + every output of the dense contract "
+                                      "written; scratch_bytes (index entries the launch also reads) are not part of it")
+    if name == "k_emit_split":
+        out["roofline"].update(
+            algorithmic_bytes_operator=emit_bytes(n, V, P), zero_padding_stored_under_index_launches=split_skipped,
+            filler_bytes=dict(k_tile_sort=plan[2], k_first_count=plan[3]), prefilled_voxels=plan[1],
+            split_note="k_emit_split moves the dense contract's 8(d) bytes EXCEPT the zero padding of voxel ids below prefilled_voxels: "
+                       "filler workgroups on the CUs k_tile_sort / k_first_count leave idle store those (plus the rows' lines of the same "
+                       "voxels, which this launch overwrites: filler_bytes > zero_padding_stored).  The operator-level figure on ALL 8(d) "
+                       "bytes is roofline_operator")
+    ov = event_overhead_us()
+    out["roofline"].update(
+        event_overhead_us=ov, avg_us_net=round(dom[1]["avg_us"] - ov, 2),
+        frac_net=round(b_alg / ((dom[1]["avg_us"] - ov) * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
+        event_note="avg_us = HIP events recorded around the launch on its stream; an EMPTY launch measures event_overhead_us that way "
+                   "(the first event waits for the previous launch, the dispatch follows).  rocprofv3's per-dispatch durations (profiles/"
+                   "*_kernel_stats_config2_only.csv) are begin-to-end of the dispatch and compare with avg_us_net; `frac` stays on avg_us")
+    if name in ("k_emit", "k_emit_split"):
+        # what the launch reads from the index's scratch on top of the 8(d) bytes, and the stream probes at THIS launch's
+        # footprint (the outputs' 345 MB, partly absorbed by the 256 MB Infinity Cache exactly as the kernel's are): the
+        # store forms with the work stripped off, on the same box in the same process
+        out["roofline"]["scratch_bytes"] = emit_scratch_bytes(npad, V, kept, kept - V)
+        pr = stream_probe(V * (P * 16 + P + 24 + 4 + 16))
+        out["roofline"].update(peak_measured=pr, frac_of_measured_store=round(ach / pr["store_nt"], 4),
+                               frac_of_measured_chunked_store=round(ach / pr["store_nt_chunked"], 4),
+                               frac_of_measured_best=round(ach / max(pr.values()), 4),
+                               probe_note="probes on a buffer of the outputs' size (V x 588 B): floors of what the box stores in "
+                                          "that form, not ceilings")
+    if name in ("k_bin_scatter", "k_bucket_index"):
+        # limited by scattered 4..16-byte stores, not bytes: measured ceiling ~80 G/s (profiles/r01_g_atomic_bench.txt)
+        req = 2 * n if name == "k_bin_scatter" else kept + V
+        out["roofline"]["requests"] = dict(per_launch=req, achieved_G_per_s=round(req / dom[1]["avg_us"] / 1e3, 2),
+                                           measured_peak_G_per_s=80.0, frac=round(req / dom[1]["avg_us"] / 1e3 / 80.0, 3))
+    if name == "k_insert":
+        # the kernel's real limiter: scattered 8-byte requests (>= one coherent probe load + one atomic per point);
+        # ceiling measured with tools/atomic_bench.hip on MI355X (profiles/r01_g_atomic_bench.txt); 2 per point is a lower
+        # bound (linear probing adds ~0.2 loads, dense voxels serialise on one slot)
+        req = 2 * n
+        out["roofline"]["requests"] = dict(per_launch=req, achieved_G_per_s=round(req / dom[1]["avg_us"] / 1e3, 2),
+                                           measured_peak_G_per_s=REQ_PEAK_GS,
+                                           frac=round(req / dom[1]["avg_us"] / 1e3 / REQ_PEAK_GS, 3))
+    if "k_fill_c4" in prof and name != "k_fill_c4":      # the HBM-bound kernel of the op, priced the same way
+        f_us = prof["k_fill_c4"]["avg_us"]
+        f_ach = algo["k_fill_c4"] / (f_us * 1e-6) / 1e9
+        out["roofline_streaming"] = dict(bound="hbm", kernel="k_fill_c4", achieved=round(f_ach, 1), peak=HBM_PEAK_GBS,
+                                         unit="GB/s", frac=round(f_ach / HBM_PEAK_GBS, 4),
+                                         traffic=load_traffic("k_fill_c4", "config2")[0], avg_us=round(f_us, 2),
+                                         algorithmic_bytes=algo["k_fill_c4"])
+    out["kernels_us"] = {k: round(v["avg_us"], 2) for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["total_ms"])}
+    out["op_algorithmic_GBps"] = round((n * 16 + V * (P * 16 + P + 24 + 4 + 16)) * args.steps / dt / 1e9, 1)
+    # the whole operator (every launch of a step) on the 8(d) bytes: what a caller sees
+    out["roofline_operator"] = dict(bound="hbm", achieved=out["op_algorithmic_GBps"], peak=HBM_PEAK_GBS, unit="GB/s",
+                                    frac=round(out["op_algorithmic_GBps"] / HBM_PEAK_GBS, 4), algorithmic_bytes=emit_bytes(n, V, P),
+                                    us_per_step=round(1e6 * dt / args.steps, 2))
+    return out
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline region, also run every other leg (spread, per-kernel rooflines, the 8 M-point frame, CPU "
+                         "baselines, extras; N > 1: the single-GPU bases and the other forms of the operator) and add them to the line")
     ap.add_argument("--points", type=int, default=1000000, help="points per GPU")
     ap.add_argument("--boxes", type=int, default=100000, help="boxes of config 3 (extra metrics)")
-    ap.add_argument("--skip-cpu", action="store_true")
-    ap.add_argument("--skip-extra", action="store_true")
+    ap.add_argument("--skip-cpu", action="store_true", help="with --full: leave out the CPU baselines")
+    ap.add_argument("--skip-extra", action="store_true", help="with --full: leave out the `extra` metrics")
     ap.add_argument("--dist", choices=["lidar", "uniform"], default="lidar")
     ap.add_argument("--force-sharded", action="store_true", help="run the sharded (RCCL) path even with one rank")
-    ap.add_argument("--skip-large", action="store_true", help="skip the 8 M-point beyond-cache roofline leg")
+    ap.add_argument("--skip-large", action="store_true", help="with --full: leave out the 8 M-point beyond-cache roofline leg")
     ap.add_argument("--large-only", action="store_true", help="run only that leg and print it (rocprofv3 --pmc passes)")
     ap.add_argument("--sparse-only", action="store_true", help="run only config 2's sparse + trim operator (rocprofv3 --pmc passes)")
     ap.add_argument("--iou-only", action="store_true", help="run only config 3's box2d_iou (one n x n rbox fp64 launch) and print its leg")
@@ -759,7 +862,12 @@ def main():
     ap.add_argument("--iou3d-only", action="store_true", help="run only config 4's iou3d (20 k x 5 k fp32) and print its leg")
     ap.add_argument("--master-port", type=int, default=29533, help="rendezvous port when bench.py launches the ranks itself")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (rank 0's) as DIR/<name>.npy")
-    args = ap.parse_args()
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
     if args.dump_outputs and (args.iou_only or args.nms_only or args.iou3d_only or args.large_only or args.sparse_only):
         ap.error("--dump-outputs dumps the headline step: it does not combine with the --*-only legs")
     if args.steps < 1:
@@ -772,7 +880,7 @@ def main():
         # bare `python bench.py --gpus N`: one rank per GPU under torch.distributed.run, started as a CHILD process --
         # nothing in this process has touched the GPU yet (importing torch does not), and this process never will
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-               "--master-addr", "127.0.0.1", "--master-port", str(args.master_port), os.path.abspath(__file__)] + sys.argv[1:]
+               "--master-addr", "127.0.0.1", "--master-port", str(args.master_port), os.path.abspath(__file__)] + (sys.argv[1:] if argv is None else list(argv))
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
         raise SystemExit(subprocess.call(cmd, env=env))
     if args.gpus != world:
@@ -815,9 +923,10 @@ def main():
                              max_voxels=n)
         res = gen(cloud)
         V = int(res.coords.shape[0])
-        kept = int(torch.clamp(res.voxel_npoints, max=P).sum())
-        plan = dense_last_plan()
-        split_bytes, split_skipped = emit_split_bytes(n, P, res.voxel_npoints, plan)
+        if args.full:       # what dense_legs prices the kernels on, read from this first call's result
+            kept = int(torch.clamp(res.voxel_npoints, max=P).sum())
+            plan = dense_last_plan()
+            split_bytes, split_skipped = emit_split_bytes(n, P, res.voxel_npoints, plan)
         del res
         step = lambda: gen(cloud)  # noqa: E731
         last = [None]
@@ -826,94 +935,10 @@ def main():
             dump_outputs(args.dump_outputs, last[0])
         del last[0]
         value = n * args.steps / dt / 1e6
-        out["timed_region_repeats"] = spread(step, args.steps)
         workload = "config2: %d %s points, KITTI range, 0.1 m voxels (704x800x40), dense+MEAN, max 32 pts/voxel" % (
             n, "LiDAR-like" if args.dist == "lidar" else "uniform")
-        prof = kernel_profile(step, args.steps)
-        dom = max(prof.items(), key=lambda kv: kv[1]["total_ms"])
-        # compulsory bytes of each kernel per launch (DESIGN.md "kernels"); C = 4
-        npad = -(-n // 16384) * 16384
-        algo = {
-            # voxels[V,P,4] written; kept rows (16 B) gathered from the staged segments, one 16-byte record per voxel read
-            "k_fill_c4": V * P * 16 + kept * 16 + V * 16,
-            # binned index (n >= 32 k points): partition, per-bucket index in LDS, numbering + per-voxel outputs
-            "k_tile_sort": n * 16 + n * 8 + npad * 4,               # rows read; {cell, index} entries + firstmap reset written
-            "k_bin_count": n * 16 + npad * 8,                       # rows read; bucket word + firstmap reset written
-            "k_bin_scatter": n * (16 + 4) + n * (16 + 4),           # rows + bucket words read; rows + indices written
-            "k_bucket_index": n * (16 + 4) + kept * 16 + V * (16 + 4),   # bucket read; ranked rows, records, firstmap written
-            "k_meta_first": npad * 4 + V * 16 + kept * 16 + V * (16 + 24 + 4 + P + 16),
-            "k_emit": emit_bytes(n, V, P),                          # 16 B/point in + every output (no scratch)
-            # round 6: the same minus the zero padding stored under the index launches (k_tile_sort's / k_first_count's fillers)
-            "k_emit_split": split_bytes,
-            # hash-table index (other inputs)
-            "k_insert": n * 16 + n * 8 + n * 8,          # points read, pslot+arrival written, one 8-byte slot touched
-            "k_scatter": n * 8 + n * 8 + n * 4 + n * 8,  # pslot+arrival read, aux read, index written, (cnt,base) written
-            "k_select": n * 8 + kept * 4,
-            "k_init": None,
-        }
-        name = dom[0]
-        b_alg = algo.get(name) or (n * 16)
-        ach = b_alg / (dom[1]["avg_us"] * 1e-6) / 1e9
-        out["roofline"] = dict(bound="hbm", kernel=name, achieved=round(ach, 1), peak=HBM_PEAK_GBS, unit="GB/s",
-                               frac=round(ach / HBM_PEAK_GBS, 4), traffic=load_traffic(name, "config2")[0],
-                               traffic_source=load_traffic(name, "config2")[1], avg_us=round(dom[1]["avg_us"], 2), algorithmic_bytes=b_alg,
-                               timing="HIP events on the launch stream, separate pass of the same %d steps" % args.steps,
-                               cache_note="config 2's 345 MB of outputs partly drain through the 256 MB Infinity Cache: this fraction "
-                                          "is cache-assisted; the HBM claim is roofline_large.frac (same kernel, 3.3 GB of outputs)",
-                               bytes_note="algorithmic_bytes = SURVEY 8(d): 16 B/point read + every output of the dense contract "
-                                          "written; scratch_bytes (index entries the launch also reads) are not part of it")
-        if name == "k_emit_split":
-            out["roofline"].update(
-                algorithmic_bytes_operator=emit_bytes(n, V, P), zero_padding_stored_under_index_launches=split_skipped,
-                filler_bytes=dict(k_tile_sort=plan[2], k_first_count=plan[3]), prefilled_voxels=plan[1],
-                split_note="k_emit_split moves the dense contract's 8(d) bytes EXCEPT the zero padding of voxel ids below prefilled_voxels: "
-                           "filler workgroups on the CUs k_tile_sort / k_first_count leave idle store those (plus the rows' lines of the same "
-                           "voxels, which this launch overwrites: filler_bytes > zero_padding_stored).  The operator-level figure on ALL 8(d) "
-                           "bytes is roofline_operator")
-        ov = event_overhead_us()
-        out["roofline"].update(
-            event_overhead_us=ov, avg_us_net=round(dom[1]["avg_us"] - ov, 2),
-            frac_net=round(b_alg / ((dom[1]["avg_us"] - ov) * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
-            event_note="avg_us = HIP events recorded around the launch on its stream; an EMPTY launch measures event_overhead_us that way "
-                       "(the first event waits for the previous launch, the dispatch follows).  rocprofv3's per-dispatch durations (profiles/"
-                       "*_kernel_stats_config2_only.csv) are begin-to-end of the dispatch and compare with avg_us_net; `frac` stays on avg_us")
-        if name in ("k_emit", "k_emit_split"):
-            # what the launch reads from the index's scratch on top of the 8(d) bytes, and the stream probes at THIS launch's
-            # footprint (the outputs' 345 MB, partly absorbed by the 256 MB Infinity Cache exactly as the kernel's are): the
-            # store forms with the work stripped off, on the same box in the same process
-            out["roofline"]["scratch_bytes"] = emit_scratch_bytes(npad, V, kept, kept - V)
-            pr = stream_probe(V * (P * 16 + P + 24 + 4 + 16))
-            out["roofline"].update(peak_measured=pr, frac_of_measured_store=round(ach / pr["store_nt"], 4),
-                                   frac_of_measured_chunked_store=round(ach / pr["store_nt_chunked"], 4),
-                                   frac_of_measured_best=round(ach / max(pr.values()), 4),
-                                   probe_note="probes on a buffer of the outputs' size (V x 588 B): floors of what the box stores in "
-                                              "that form, not ceilings")
-        if name in ("k_bin_scatter", "k_bucket_index"):
-            # limited by scattered 4..16-byte stores, not bytes: measured ceiling ~80 G/s (profiles/r01_g_atomic_bench.txt)
-            req = 2 * n if name == "k_bin_scatter" else kept + V
-            out["roofline"]["requests"] = dict(per_launch=req, achieved_G_per_s=round(req / dom[1]["avg_us"] / 1e3, 2),
-                                               measured_peak_G_per_s=80.0, frac=round(req / dom[1]["avg_us"] / 1e3 / 80.0, 3))
-        if name == "k_insert":
-            # the kernel's real limiter: scattered 8-byte requests (>= one coherent probe load + one atomic per point);
-            # ceiling measured with tools/atomic_bench.hip on MI355X (profiles/r01_g_atomic_bench.txt); 2 per point is a lower
-            # bound (linear probing adds ~0.2 loads, dense voxels serialise on one slot)
-            req = 2 * n
-            out["roofline"]["requests"] = dict(per_launch=req, achieved_G_per_s=round(req / dom[1]["avg_us"] / 1e3, 2),
-                                               measured_peak_G_per_s=REQ_PEAK_GS,
-                                               frac=round(req / dom[1]["avg_us"] / 1e3 / REQ_PEAK_GS, 3))
-        if "k_fill_c4" in prof and name != "k_fill_c4":      # the HBM-bound kernel of the op, priced the same way
-            f_us = prof["k_fill_c4"]["avg_us"]
-            f_ach = algo["k_fill_c4"] / (f_us * 1e-6) / 1e9
-            out["roofline_streaming"] = dict(bound="hbm", kernel="k_fill_c4", achieved=round(f_ach, 1), peak=HBM_PEAK_GBS,
-                                             unit="GB/s", frac=round(f_ach / HBM_PEAK_GBS, 4),
-                                             traffic=load_traffic("k_fill_c4", "config2")[0], avg_us=round(f_us, 2),
-                                             algorithmic_bytes=algo["k_fill_c4"])
-        out["kernels_us"] = {k: round(v["avg_us"], 2) for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["total_ms"])}
-        out["op_algorithmic_GBps"] = round((n * 16 + V * (P * 16 + P + 24 + 4 + 16)) * args.steps / dt / 1e9, 1)
-        # the whole operator (every launch of a step) on the 8(d) bytes: what a caller sees
-        out["roofline_operator"] = dict(bound="hbm", achieved=out["op_algorithmic_GBps"], peak=HBM_PEAK_GBS, unit="GB/s",
-                                        frac=round(out["op_algorithmic_GBps"] / HBM_PEAK_GBS, 4), algorithmic_bytes=emit_bytes(n, V, P),
-                                        us_per_step=round(1e6 * dt / args.steps, 2))
+        if args.full:
+            out.update(dense_legs(args, step, n, P, V, kept, plan, split_bytes, split_skipped, dt))
         out["voxels"] = V
         parallelism = "1 GPU"
     else:
@@ -926,7 +951,7 @@ def main():
         # actually run on one GPU: sharded.voxelize_reduce (local index + feature grid, nothing packed / merged / replied) --
         # and (b) the same OPERATOR with a world of one (the full pack / merge / number / reply machinery on one rank)
         whole = best = None
-        if rank == 0:
+        if args.full and rank == 0:
             from d3d_amd.voxel.sharded import voxelize_reduce
             fr = torch.from_numpy(frame).cuda()
             k = max(args.steps // 4, 3)
@@ -936,72 +961,77 @@ def main():
             del solo, fr
             torch.cuda.empty_cache()
         del frame
-        # ... and on this rank's shard alone (the base of the weak-scaling curve)
-        solo = ShardedVoxelGenerator(synth.WAYMO_BOUNDS, synth.WAYMO_SHAPE, reduction="mean", comm=LocalComm(), replicate=False)
-        dt_solo = timed(lambda: solo(cloud), max(args.steps // 2, 3), 2)
-        solo_ms = 1e3 * dt_solo / max(args.steps // 2, 3)
-        del solo
+        solo_ms = dt_rep = dt_frames = 0.0
+        if args.full:
+            # ... and on this rank's shard alone (the base of the weak-scaling curve)
+            solo = ShardedVoxelGenerator(synth.WAYMO_BOUNDS, synth.WAYMO_SHAPE, reduction="mean", comm=LocalComm(), replicate=False)
+            dt_solo = timed(lambda: solo(cloud), max(args.steps // 2, 3), 2)
+            solo_ms = 1e3 * dt_solo / max(args.steps // 2, 3)
+            del solo
         # the scalable form: owner-computes exchange, every rank keeps its owned 1/world of the voxels (replicate=False)
         gen = ShardedVoxelGenerator(synth.WAYMO_BOUNDS, synth.WAYMO_SHAPE, reduction="mean", replicate=False)
         step = lambda: gen(cloud)  # noqa: E731
         out["voxels_global"] = int(step().num_voxels)
-        st = dict(gen.last_stats)
-        # what RCCL itself saw: an all-reduce of ones over the group, and the distinct devices behind the ranks
-        ones = torch.ones((1,), dtype=torch.int64, device="cuda")
-        dist.all_reduce(ones)
-        ids = [None] * world
-        props = torch.cuda.get_device_properties(local_rank)
-        dist.all_gather_object(ids, str(getattr(props, "uuid", "")) or "%s#%d" % (props.name, local_rank))
-        out["rccl_ranks"] = int(ones.item())
-        out["rccl_distinct_devices"] = len(set(ids))
-        out["exchange"] = st["exchange"]
-        out["numbering"] = st["numbering"]
-        out["collectives_per_step"] = dict(
-            {k: v for k, v in st.items() if "bytes" in k}, size_all_gather_bytes=8, count_matrix_all_gather_bytes=8 * (2 * world + 1),
-            note="per rank: all-to-all of the partial voxel records to the cells' owner ranks (a sparse reduce-scatter of the "
-                 "feature grid), SUM all-reduce of the one-bit-per-point first-point bitmap (= OR of disjoint sets), all-to-all "
-                 "of the voxel ids back; no all-gather of the grid (every rank keeps its owned 1/world of the voxels)")
+        if args.full:
+            st = dict(gen.last_stats)
+            # what RCCL itself saw: an all-reduce of ones over the group, and the distinct devices behind the ranks
+            ones = torch.ones((1,), dtype=torch.int64, device="cuda")
+            dist.all_reduce(ones)
+            ids = [None] * world
+            props = torch.cuda.get_device_properties(local_rank)
+            dist.all_gather_object(ids, str(getattr(props, "uuid", "")) or "%s#%d" % (props.name, local_rank))
+            out["rccl_ranks"] = int(ones.item())
+            out["rccl_distinct_devices"] = len(set(ids))
+            out["exchange"] = st["exchange"]
+            out["numbering"] = st["numbering"]
+            out["collectives_per_step"] = dict(
+                {k: v for k, v in st.items() if "bytes" in k}, size_all_gather_bytes=8, count_matrix_all_gather_bytes=8 * (2 * world + 1),
+                note="per rank: all-to-all of the partial voxel records to the cells' owner ranks (a sparse reduce-scatter of the "
+                     "feature grid), SUM all-reduce of the one-bit-per-point first-point bitmap (= OR of disjoint sets), all-to-all "
+                     "of the voxel ids back; no all-gather of the grid (every rank keeps its owned 1/world of the voxels)")
         last = [None]
         dt_local = timed(keep_last(step, last) if args.dump_outputs else step, args.steps, args.warmup, barrier)
         if args.dump_outputs and rank == 0:
             dump_outputs(args.dump_outputs, last[0])
         del last[0]
-        # the same with the final all-gather of the finished grid (replicated result, the frame-sized part)
-        gen_rep = ShardedVoxelGenerator(synth.WAYMO_BOUNDS, synth.WAYMO_SHAPE, reduction="mean", replicate=True)
-        k = max(args.steps // 4, 3)
-        dt_rep = timed(lambda: gen_rep(cloud), k, 2, barrier) / k
-        del gen_rep
-        # the N = 1 line's own workload on every rank at once -- config 2, dense + MEAN, each rank ITS OWN frame, no collective: the
-        # data-parallel use of the operator (a training job voxelizes one batch per GPU) and the curve that is comparable with N = 1
-        gen2 = VoxelGenerator(synth.KITTI_BOUNDS, synth.KITTI_SHAPE, dense=True, reduction="mean", max_points=P, max_voxels=n)
-        cloud2 = torch.from_numpy(synth.lidar_like(n, rank)).cuda()
-        dt_frames = timed(lambda: gen2(cloud2), args.steps, args.warmup, barrier)
-        del gen2, cloud2
+        if args.full:
+            # the same with the final all-gather of the finished grid (replicated result, the frame-sized part)
+            gen_rep = ShardedVoxelGenerator(synth.WAYMO_BOUNDS, synth.WAYMO_SHAPE, reduction="mean", replicate=True)
+            k = max(args.steps // 4, 3)
+            dt_rep = timed(lambda: gen_rep(cloud), k, 2, barrier) / k
+            del gen_rep
+            # the N = 1 line's own workload on every rank at once -- config 2, dense + MEAN, each rank ITS OWN frame, no collective: the
+            # data-parallel use of the operator (a training job voxelizes one batch per GPU) and the curve that is comparable with N = 1
+            gen2 = VoxelGenerator(synth.KITTI_BOUNDS, synth.KITTI_SHAPE, dense=True, reduction="mean", max_points=P, max_voxels=n)
+            cloud2 = torch.from_numpy(synth.lidar_like(n, rank)).cuda()
+            dt_frames = timed(lambda: gen2(cloud2), args.steps, args.warmup, barrier)
+            del gen2, cloud2
         t = torch.tensor([dt_local, solo_ms, dt_rep, dt_frames], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t[0].item())
-        out["independent_frames_per_rank"] = dict(
-            ms_per_step=round(1e3 * float(t[3].item()) / args.steps, 4), mpoints_per_s=round(n * world * args.steps / float(t[3].item()) / 1e6, 2),
-            note="config 2 (dense + MEAN, the workload of the N = 1 line) on every rank's own %d-point frame at once, no collective, max "
-                 "over ranks: the data-parallel use of the operator; `value` above is the point-sharded single frame of config 5" % n)
         value = n * world * args.steps / dt / 1e6
-        out["same_operator_one_rank"] = dict(ms_per_step=round(float(t[1].item()), 4),
-                                             mpoints_per_s=round(n / float(t[1].item()) / 1e3, 2),
-                                             note="the same operator on one rank's shard without collectives (max over ranks)")
-        if whole is not None:
-            out["single_gpu_best"] = dict(
-                ms_per_step=round(best, 4), mpoints_per_s=round(n * world / best / 1e3, 2),
-                note="sharded.voxelize_reduce on the WHOLE %d-point frame on one GPU: the same contract (feature grid + point -> "
-                     "voxel map) with no exchange at all -- the honest single-GPU base of the speed-up" % (n * world))
-            out["speedup_vs_single_gpu_best"] = round(best / (1e3 * dt / args.steps), 3)
-            out["single_gpu_whole_frame"] = dict(
-                ms_per_step=round(whole, 4), mpoints_per_s=round(n * world / whole / 1e3, 2),
-                note="the same OPERATOR (pack / merge / number / reply, world of one) on the whole frame on one GPU: an upper "
-                     "bound of what one GPU needs, not what one would run there")
-            out["speedup_vs_single_gpu_whole_frame"] = round(whole / (1e3 * dt / args.steps), 3)
-        out["replicated_result"] = dict(ms_per_step=round(1e3 * float(t[2].item()), 4),
-                                        note="with replicate=True: + all-gather of the owners' finished rows and the scatter into "
-                                             "voxel-id order on every rank (sized by the frame, not the shard)")
+        if args.full:
+            out["independent_frames_per_rank"] = dict(
+                ms_per_step=round(1e3 * float(t[3].item()) / args.steps, 4), mpoints_per_s=round(n * world * args.steps / float(t[3].item()) / 1e6, 2),
+                note="config 2 (dense + MEAN, the workload of the N = 1 line) on every rank's own %d-point frame at once, no collective, max "
+                     "over ranks: the data-parallel use of the operator; `value` above is the point-sharded single frame of config 5" % n)
+            out["same_operator_one_rank"] = dict(ms_per_step=round(float(t[1].item()), 4),
+                                                 mpoints_per_s=round(n / float(t[1].item()) / 1e3, 2),
+                                                 note="the same operator on one rank's shard without collectives (max over ranks)")
+            if whole is not None:
+                out["single_gpu_best"] = dict(
+                    ms_per_step=round(best, 4), mpoints_per_s=round(n * world / best / 1e3, 2),
+                    note="sharded.voxelize_reduce on the WHOLE %d-point frame on one GPU: the same contract (feature grid + point -> "
+                         "voxel map) with no exchange at all -- the honest single-GPU base of the speed-up" % (n * world))
+                out["speedup_vs_single_gpu_best"] = round(best / (1e3 * dt / args.steps), 3)
+                out["single_gpu_whole_frame"] = dict(
+                    ms_per_step=round(whole, 4), mpoints_per_s=round(n * world / whole / 1e3, 2),
+                    note="the same OPERATOR (pack / merge / number / reply, world of one) on the whole frame on one GPU: an upper "
+                         "bound of what one GPU needs, not what one would run there")
+                out["speedup_vs_single_gpu_whole_frame"] = round(whole / (1e3 * dt / args.steps), 3)
+            out["replicated_result"] = dict(ms_per_step=round(1e3 * float(t[2].item()), 4),
+                                            note="with replicate=True: + all-gather of the owners' finished rows and the scatter into "
+                                                 "voxel-id order on every rank (sized by the frame, not the shard)")
         workload = ("config5 shards: rank k = points [k*%d, (k+1)*%d) of a %d-point LiDAR-like Waymo-range frame (seed 3), "
                     "0.05 m voxels (3008x3008x120), MEAN feature grid: local voxelization + RCCL all-to-all of the partial voxel "
                     "records to the cells' owners + bitmap all-reduce for the first-seen numbering; every rank returns its owned "
@@ -1020,12 +1050,12 @@ def main():
         if not sharded:
             del cloud, gen
             torch.cuda.empty_cache()
-        if not sharded and not args.skip_large:
+        if args.full and not sharded and not args.skip_large:
             line["roofline_large"] = large_frame_leg()
-        if not sharded and not args.skip_cpu:
+        if args.full and not sharded and not args.skip_cpu:
             line["cpu_baseline"] = cpu_baseline_voxel(cloud_h, synth.KITTI_BOUNDS, synth.KITTI_SHAPE, P, n)
             line["cpu_baseline_all_cores"] = cpu_allcore_voxel(cloud_h, synth.KITTI_BOUNDS, synth.KITTI_SHAPE, P, n)
-        if not sharded and not args.skip_extra:
+        if args.full and not sharded and not args.skip_extra:
             line["extra"] = extras(args)
         print(json.dumps(line))
     if sharded:

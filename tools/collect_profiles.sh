@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box, from the repo root): bash tools/collect_profiles.sh <tag> [commit]
 # One collection = the bench line + rocprofv3 kernel stats of EXACTLY the three workloads the line's legs run -- config 2 alone
-# (bench.py --skip-cpu --skip-extra --skip-large), the large frame (--large-only), the sparse operator (--sparse-only) -- + the PMC
+# (bench.py --full --skip-cpu --skip-extra --skip-large), the large frame (--large-only), the sparse operator (--sparse-only) -- + the PMC
 # passes of each (FETCH_SIZE / WRITE_SIZE in SEPARATE runs with --kernel-trace only, as MI355X_MICROARCH.md prescribes) + the SQ
 # counters of k_bucket_index (LDS bank conflicts) -> gpurun_out/<tag>/ ;
 # back in the build container: python tools/finish_collection.py <tag> <commit> copies the kernel stats to profiles/ and runs
@@ -12,10 +12,10 @@ commit=${2:-unknown}
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 echo "$commit" > $out/commit.txt
-python3 bench.py > $out/bench.json 2> $out/bench.err
+python3 bench.py --full > $out/bench.json 2> $out/bench.err
 cd /tmp && export TMPDIR=/tmp
 B=$GRAFT_REPO_ROOT/bench.py
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_cfg2 -o cfg2 -- python3 $B --skip-cpu --skip-extra --skip-large > $out/cfg2_prof.json 2> $out/prof_cfg2.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_cfg2 -o cfg2 -- python3 $B --full --skip-cpu --skip-extra --skip-large > $out/cfg2_prof.json 2> $out/prof_cfg2.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_large -o large -- python3 $B --large-only > $out/large_prof.json 2> $out/prof_large.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_sparse -o sparse -- python3 $B --sparse-only --steps 50 --warmup 5 > $out/sparse_prof.json 2> $out/prof_sparse.err
 # round 6: the box-side legs, each alone -- config 3's one 100 k x 100 k box2d_iou launch, config 3's NMS,
@@ -29,11 +29,11 @@ for leg in iou nms iou3d; do
 done
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/pmc_${c}_sparse -o pmc -- python3 $B --sparse-only --steps 5 --warmup 2 > /dev/null 2> $out/pmc_${c}_sparse.err
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/pmc_${c}_cfg2 -o pmc -- python3 $B --skip-cpu --skip-extra --skip-large --steps 5 --warmup 2 > /dev/null 2> $out/pmc_${c}_cfg2.err
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/pmc_${c}_cfg2 -o pmc -- python3 $B --full --skip-cpu --skip-extra --skip-large --steps 5 --warmup 2 > /dev/null 2> $out/pmc_${c}_cfg2.err
   rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/pmc_${c}_large -o pmc -- python3 $B --large-only > /dev/null 2> $out/pmc_${c}_large.err
 done
 for c in SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES; do
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/sq_$c -o pmc -- python3 $B --skip-cpu --skip-extra --skip-large --steps 5 --warmup 2 > /dev/null 2> $out/sq_$c.err
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/sq_$c -o pmc -- python3 $B --full --skip-cpu --skip-extra --skip-large --steps 5 --warmup 2 > /dev/null 2> $out/sq_$c.err
 done
 python3 - $out <<'PY' > $out/sq_bucket_index.txt
 import csv, glob, os, sys
