@@ -12,6 +12,7 @@ import enum
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from .. import _lib, options
 
@@ -506,6 +507,132 @@ def iou3d(boxes1, boxes2, method="rbox"):
     return out.numpy() if convert_numpy else out
 
 
+def _iou_paired(boxes1, boxes2, cols, kind, code, need_jac):
+    """one launch of d3d_iou2d_paired (cols 5) / d3d_iou3d_paired (cols 7) -> (ious[N] on the caller's device, jac[N, 2 cols] on the GPU
+    or None).  jac is in the arithmetic's dtype: fp64 unless `code` is D3D_F32."""
+    lib = _lib.load()
+    odev = boxes1.device
+    (b1, b2), dev = _to_device(boxes1.detach(), boxes2.detach())
+    n = b1.shape[0]
+    with torch.cuda.device(dev):
+        ious = torch.empty((n,), dtype=b1.dtype, device=dev)
+        jac = torch.empty((n, 2 * cols), dtype=torch.float32 if code == _lib.F32 else torch.float64, device=dev) if need_jac else None
+        if options.current().poison:
+            ious.fill_(float("nan"))
+            if need_jac:
+                jac.fill_(float("nan"))
+        fn = lib.d3d_iou2d_paired if cols == 5 else lib.d3d_iou3d_paired
+        rc = fn(_lib.ptr(b1), _lib.ptr(b2), n, int(kind), code, _lib.ptr(ious), _lib.ptr(jac), _lib.stream_ptr())
+    _lib.check(rc, "iou2d_paired" if cols == 5 else "iou3d_paired")
+    return _lib.to_caller(ious, odev, dev), jac
+
+
+def _paired_forward(ctx, cols, boxes1, boxes2, kind, code):
+    need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+    ious, jac = _iou_paired(boxes1, boxes2, cols, kind, code, need)
+    if need:                                                       # (otherwise jac is not even allocated: the GRAD = false kernel ran)
+        ctx.save_for_backward(jac)
+        ctx.origin = (boxes1.device, boxes1.dtype)
+    return ious
+
+
+def _paired_backward(ctx, cols, grad):
+    jac, = ctx.saved_tensors
+    odev, dtype = ctx.origin
+    g = (grad.to(device=jac.device, dtype=jac.dtype)[:, None] * jac).to(device=odev, dtype=dtype)
+    return g[:, :cols] if ctx.needs_input_grad[0] else None, g[:, cols:] if ctx.needs_input_grad[1] else None, None, None
+
+
+class IouPaired2D(torch.autograd.Function):
+    """box2d_iou_paired: (boxes1[N,5], boxes2[N,5], IouType, dtype code) -> [N].  forward is one launch; when an input needs a
+    gradient the same launch writes the pairs' partial derivatives jac[N,10] (80 bytes per pair in fp64) and backward is
+    grad[:, None] * jac -- every pair owns its rows: no atomics, no kernel, no second pass over the boxes.  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, boxes1, boxes2, iou_type, code):
+        return _paired_forward(ctx, 5, boxes1, boxes2, iou_type, code)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        return _paired_backward(ctx, 5, grad)
+
+
+class IouPaired3D(torch.autograd.Function):
+    """box3d_iou_paired: (boxes1[N,7], boxes2[N,7], rotated, dtype code) -> [N]; as IouPaired2D with jac[N,14] (112 bytes per pair)"""
+
+    @staticmethod
+    def forward(ctx, boxes1, boxes2, rotated, code):
+        return _paired_forward(ctx, 7, boxes1, boxes2, rotated, code)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        return _paired_backward(ctx, 7, grad)
+
+
+def _paired(fn, boxes1, boxes2, kind, precise, was_numpy):
+    """dtype handling of box2d_iou for the paired operators: precise = fp64 arithmetic, the result cast back; on fp32 boxes the
+    widening happens where the kernel loads them (D3D_F32_WIDE) -- no .double() copies, no cast launch"""
+    dtype_in = boxes1.dtype
+    wide32 = precise and dtype_in == torch.float32 and boxes2.dtype == torch.float32
+    if precise and not wide32:
+        boxes1, boxes2 = boxes1.double(), boxes2.double()
+    if boxes1.dtype != boxes2.dtype:
+        raise RuntimeError("boxes1 and boxes2 must have the same dtype")
+    code = _lib.F32_WIDE if wide32 else _dtype_code(boxes1)
+    if len(boxes1) == 0:                                            # nothing to launch (and nothing to differentiate)
+        return _egress(boxes1[:, 0].to(dtype_in), was_numpy)
+    ious = fn.apply(boxes1, boxes2, kind, code)
+    return _egress(ious.to(dtype_in) if precise else ious, was_numpy)
+
+
+def box2d_iou_paired(boxes1, boxes2, method="rbox", precise=True):
+    """IoU of box i of `boxes1` with box i of `boxes2` -- the diagonal of box2d_iou(boxes1, boxes2, method, precise) without its
+    matrix: what a detector's regression loss takes for its N matched (prediction, target) pairs.  Differentiable in both inputs
+    (once); the reference has no counterpart.
+
+    :param boxes1: N x 5 (x,y,w,h,r), torch tensor or numpy array
+    :param boxes2: N x 5
+    :param method: 'box', 'rbox', or the loss variants 'grbox' (GIoU) / 'drbox' (DIoU); resolved like box2d_iou's
+    :param precise: compute in float64 and cast back to the input dtype
+    :return: [N]; 0 (and a zero gradient) for a rectangle without area ('rbox', 'grbox', 'drbox') and for pairs apart ('box', 'rbox')
+    """
+    (boxes1, boxes2), was_numpy = _ingress(boxes1, boxes2)
+    if boxes1.dim() != 2 or boxes2.dim() != 2:
+        raise ValueError("Input of rbox_2d_iou should be Nx2 tensors!")
+    if boxes1.shape[1] != 5 or boxes2.shape[1] != 5:
+        raise ValueError("Input boxes should have 5 fields: x, y, w, h, r")
+    if len(boxes1) != len(boxes2):
+        raise ValueError("Paired boxes should come in equal numbers: %d and %d" % (len(boxes1), len(boxes2)))
+    iou_type = getattr(IouType, method.upper())                   # AttributeError for unknown names, like box2d_iou
+    if iou_type not in _IOU_FUNCTIONS:
+        raise ValueError("Unrecognized iou type!")
+    return _paired(IouPaired2D, boxes1, boxes2, int(iou_type), precise, was_numpy)
+
+
+def box3d_iou_paired(boxes1, boxes2, method="rbox", precise=True):
+    """"3D IoU" of box i of `boxes1` with box i of `boxes2`, the measure of iou3d (the evaluator's and the matcher's): the BEV IoU
+    of (x, y, lx, ly, rz) -- rotated for 'rbox', of the bounding boxes for 'box' -- times the IoU of the z intervals,
+    max(min(zmax) - max(zmin), 0) / max(max(zmax) - min(zmin), 1e-6); 0 where the BEV IoU is 0.  Differentiable in both inputs
+    (once), fp32 and fp64.  The dimensions are not clipped (that is the matcher's guard).  This is NOT the volumetric IoU
+    (intersection volume over union volume), which is a different function and not offered here.
+
+    :param boxes1: N x 7 (x,y,z,lx,ly,lz,rz), torch tensor or numpy array
+    :param boxes2: N x 7
+    :param precise: compute in float64 and cast back to the input dtype
+    """
+    (boxes1, boxes2), was_numpy = _ingress(boxes1, boxes2)
+    key = method.upper()
+    if key not in ("RBOX", "BOX"):
+        raise ValueError("Unrecognized iou type!")
+    if boxes1.dim() != 2 or boxes2.dim() != 2 or boxes1.shape[1] != 7 or boxes2.shape[1] != 7:
+        raise ValueError("Input boxes should have 7 fields: x, y, z, lx, ly, lz, rz")
+    if len(boxes1) != len(boxes2):
+        raise ValueError("Paired boxes should come in equal numbers: %d and %d" % (len(boxes1), len(boxes2)))
+    return _paired(IouPaired3D, boxes1, boxes2, 1 if key == "RBOX" else 0, precise, was_numpy)
+
+
 def crop_2dr(points, boxes):
     """crop_2dr of the reference (utils.cpp:38-47; box_impl.crop_2dr): bool[M,N] indicators, [i,j] = point j is
     inside rotated box i.  points [N,2], boxes [M,5], same floating dtype."""
@@ -679,6 +806,6 @@ nms = box2d_nms
 __all__ = ["Iou2D", "Iou2DR", "GIou2DR", "DIou2DR", "PDist2DR", "iou2d_backward", "iou2dr_backward", "giou2dr_forward",
            "giou2dr_backward", "diou2dr_forward", "diou2dr_backward", "iou2dr_flags", "pdist2dr_forward", "pdist2dr_backward",
            "box2dr_crop", "box3dp_crop", "box2dr_pdist", "box3dr_pdist", "seg1d_pdist", "seg1d_iou", "crop_2dr", "box2d_iou", "box2d_nms",
-           "box2d_nms_batched",
+           "box2d_nms_batched", "box2d_iou_paired", "box3d_iou_paired", "IouPaired2D", "IouPaired3D",
            "iou2d", "iou3d", "nms", "iou2d_forward", "iou2dr_forward", "nms2d", "nms2d_cuda", "argsort_desc", "IouType",
            "SupressionType", "cuda_available"]

@@ -117,26 +117,7 @@ __device__ __forceinline__ void list_reset(IouList *hdr, unsigned int nseg)
     hdr->nseg = nseg;
 }
 
-// conservative fp32 AABB of a box for the candidate test (outward rounding; a degenerate box gets an empty AABB and is
-// never a candidate: its IoU is 0 by the policy of geom.hpp).  Candidates are a superset of the exact AABB overlaps --
-// k_iou_clip computes the exact value, which is 0 for the extra ones -- so the result does not depend on the rounding.
-__device__ __forceinline__ float round_down(double x) { float f = (float)x; return (double)f > x ? nextafterf(f, -INFINITY) : f; }
-__device__ __forceinline__ float round_up(double x) { float f = (float)x; return (double)f < x ? nextafterf(f, INFINITY) : f; }
-__device__ __forceinline__ float round_down(float x) { return x; }
-__device__ __forceinline__ float round_up(float x) { return x; }
-template <typename T> __device__ __forceinline__ float4 cand_aabb(const BoxGeom<T> &g, bool rotated = true)
-{
-    // (method BOX measures the AABB itself, which has an area even when the rectangle has none)
-    if (rotated && !(g.area > 0)) return make_float4(INFINITY, INFINITY, -INFINITY, -INFINITY);
-    return make_float4(round_down(g.xmin), round_down(g.ymin), round_up(g.xmax), round_up(g.ymax));
-}
-// strict overlap in x and y as ONE number: the smallest of the four gaps must be positive
-__device__ __forceinline__ float aabb_gap(const float4 &a, const float4 &b)
-{
-    typedef float f2 __attribute__((ext_vector_type(2)));     // two packed subtractions (v_pk_add_f32) instead of four
-    const f2 d1 = f2{b.z, b.w} - f2{a.x, a.y}, d2 = f2{a.z, a.w} - f2{b.x, b.y};
-    return fminf(fminf(d1.x, d1.y), fminf(d2.x, d2.y));
-}
+// (the candidate test -- cand_aabb, aabb_gap -- lives in geom.hpp: boxpair.hip applies it to its pairs too)
 
 // CORE: the six numbers of a box (centre, half-extent vectors) in one 64-byte (fp64) / 32-byte (fp32) aligned record instead of
 // the 88 / 44-byte BoxGeom: what the rotated clip gathers per candidate -- one sector per box instead of two

@@ -53,12 +53,7 @@ template <typename T> __device__ __forceinline__ T wave_sum5(const T (&v)[5], in
     return c;
 }
 
-// GIoU / DIoU of one pair by the complete routine (clip + hull with the tie rules / diameter), out of line: what the forward-only forms defer
-template <typename T, int KIND> __device__ __noinline__ T loss_complete(const BoxGeom<T> &a, const BoxGeom<T> &b)
-{
-    T da[5], db[5];
-    return loss_iou_rbox<T, KIND, false>(a, b, (T)0, (T)0, (T)0, (T)0, da, db);       // forward: the sizes are not read
-}
+// (loss_complete -- the complete routine out of line, what the forward-only forms defer -- lives in geom.hpp: boxpair.hip calls it too)
 
 // ---------------------------------------------------------------- GIoU / DIoU forward
 template <typename T, int KIND>

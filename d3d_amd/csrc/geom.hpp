@@ -177,6 +177,28 @@ __device__ __forceinline__ bool aabb_disjoint(const BoxGeom<T> &a, const BoxGeom
     return !(a.xmin < b.xmax && b.xmin < a.xmax && a.ymin < b.ymax && b.ymin < a.ymax);
 }
 
+// conservative fp32 AABB of a box for the candidate test (outward rounding; a degenerate box gets an empty AABB and is
+// never a candidate: its IoU is 0 by the policy of this file).  Candidates are a superset of the exact AABB overlaps --
+// the per-pair function computes the exact value, which is 0 for the extra ones -- so the result does not depend on the rounding.
+// (moved here unchanged from box.hip: the matrix kernels there and the paired kernels of boxpair.hip apply the same test)
+__device__ __forceinline__ float round_down(double x) { float f = (float)x; return (double)f > x ? nextafterf(f, -INFINITY) : f; }
+__device__ __forceinline__ float round_up(double x) { float f = (float)x; return (double)f < x ? nextafterf(f, INFINITY) : f; }
+__device__ __forceinline__ float round_down(float x) { return x; }
+__device__ __forceinline__ float round_up(float x) { return x; }
+template <typename T> __device__ __forceinline__ float4 cand_aabb(const BoxGeom<T> &g, bool rotated = true)
+{
+    // (method BOX measures the AABB itself, which has an area even when the rectangle has none)
+    if (rotated && !(g.area > 0)) return make_float4(INFINITY, INFINITY, -INFINITY, -INFINITY);
+    return make_float4(round_down(g.xmin), round_down(g.ymin), round_up(g.xmax), round_up(g.ymax));
+}
+// strict overlap in x and y as ONE number: the smallest of the four gaps must be positive
+__device__ __forceinline__ float aabb_gap(const float4 &a, const float4 &b)
+{
+    typedef float f2 __attribute__((ext_vector_type(2)));     // two packed subtractions (v_pk_add_f32) instead of four
+    const f2 d1 = f2{b.z, b.w} - f2{a.x, a.y}, d2 = f2{a.z, a.w} - f2{b.x, b.y};
+    return fminf(fminf(d1.x, d1.y), fminf(d2.x, d2.y));
+}
+
 // area of A ∩ B for two rectangles (CCW quads given by centre and half-extent vectors).
 // Green's theorem over the boundary of the intersection: every edge P + t D of either quad contributes cross(S, E) / 2 for
 // the piece [S, E] = [P + t0 D, P + t1 D] that survives the four half-planes of the other quad (Cyrus-Beck) -- and
@@ -1156,6 +1178,14 @@ __device__ __forceinline__ T loss_iou_rbox(const BoxGeom<T> &a, const BoxGeom<T>
         }
     }
     return iou - d2 / D2;
+}
+
+// GIoU / DIoU of one pair by the complete routine (clip + hull with the tie rules / diameter), out of line: what the forward-only forms defer
+// (moved here unchanged from boxloss.hip: k_loss_iou / k_giou_fix there and k_iou_paired of boxpair.hip call it)
+template <typename T, int KIND> __device__ __noinline__ T loss_complete(const BoxGeom<T> &a, const BoxGeom<T> &b)
+{
+    T da[5], db[5];
+    return loss_iou_rbox<T, KIND, false>(a, b, (T)0, (T)0, (T)0, (T)0, da, db);       // forward: the sizes are not read
 }
 
 // The same value and feature for a box of POSITIVE size, in the box's own frame (round 4; the forward kernel k_pdist): the

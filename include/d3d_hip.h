@@ -569,6 +569,25 @@ size_t d3d_iou3d_workspace_bytes(int64_t n, int64_t m);
 int d3d_iou3d_forward(const float *boxes1, int64_t n, const float *boxes2, int64_t m,
                       int32_t rotated, float *out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* extension (the reference has the [n,m] matrices only): the PAIRED forms a regression loss wants -- box i of boxes1 against
+ * box i of boxes2, n pairs, one pair per lane in one launch (boxpair.hip).  d3d_iou2d_paired: ious[i] is the DIAGONAL of
+ * d3d_iou2d_forward -- entry [i,i] of the matrix of the same boxes, type and arithmetic, bit for bit where the matrix takes
+ * its single-launch route; iou_type BOX / RBOX / GRBOX / DRBOX, any other: D3D_ERR_UNSUPPORTED.  d3d_iou3d_paired: the diagonal
+ * of d3d_iou3d_forward (rows (x,y,z,lx,ly,lz,rz); rotated = 1: box3dr_iou, 0: box3d_iou), here for f64 as well: BEV IoU times
+ * max(min(zmax) - max(zmin), 0) / max(max(zmax) - min(zmin), 1e-6), 0 where the BEV IoU is 0; no clipping of the dimensions.
+ *   dtype: D3D_F32, D3D_F64, or D3D_F32_WIDE = boxes and ious f32 in memory, the arithmetic (and jac) f64, every value widened
+ *   where it is loaded and rounded once where it is stored; any other: D3D_ERR_UNSUPPORTED.
+ *   jac (may be NULL): [n,10] (2-D) / [n,14] (3-D) in the ARITHMETIC's type (f32 for D3D_F32, f64 otherwise), row i = the partial
+ *   derivatives of ious[i] by the 5 (7) parameters of boxes1[i], then by those of boxes2[i] -- a pair owns its row, so the
+ *   backward pass is grad[i] * jac[i,:] with no atomics.  A box of non-positive area (RBOX / GRBOX / DRBOX), a pair apart (BOX /
+ *   RBOX / 3-D), z ranges that do not overlap: value 0 and a row of zeros, never NaN; the 1e-6 floor, where active, does not move.
+ *   n == 0: nothing is done; a null boxes1 / boxes2 / ious with n > 0, n < 0: D3D_ERR_BAD_ARG, nothing written.  No workspace,
+ *   no allocation, no synchronisation, work on `stream` only, capturable in a graph. */
+int d3d_iou2d_paired(const void *boxes1, const void *boxes2, int64_t n, int32_t iou_type, int32_t dtype,
+                     void *ious, void *jac, void *stream);
+int d3d_iou3d_paired(const void *boxes1, const void *boxes2, int64_t n, int32_t rotated, int32_t dtype,
+                     void *ious, void *jac, void *stream);
+
 /* replaces the pair loops of BaseMatcher.prepare_boxes (reference d3d/tracking/matcher.pyx:46-80) for the metrics IoU
  * (rotated = 0: box3d_iou) and RIoU (rotated = 1: box3dr_iou): src[n,9], dst[m,9] f32 rows = (label, score, x, y, z, lx, ly,
  * lz, yaw) as Target3DArray.to_numpy lays them out (abstraction.pyx:263-272); the dimensions are clipped to +-1e3
