@@ -2707,7 +2707,7 @@ __global__ __launch_bounds__(256) void k_crop2dr(const T *__restrict__ points, i
     }
     __syncthreads();
     if (j0 >= n) return;
-    const bool vec = (n % 4 == 0);
+    const bool vec = (n % 4 == 0) && (reinterpret_cast<uintptr_t>(out) % 4 == 0);    // (as k_crop3dr: rows of words only)
     for (int r = 0; r < nrows; r++) {
         const BoxGeom<T> g = rows[r];
         uint32_t word = 0;

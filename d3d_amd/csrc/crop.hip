@@ -59,7 +59,9 @@ __global__ __launch_bounds__(256) void k_crop3dr(const float *__restrict__ point
     }
     __syncthreads();
     if (j0 >= n) return;
-    const bool vec = (n % 4 == 0);
+    // one 32-bit store per row only where every row of `out` starts on a word: n % 4 == 0 AND a 4-byte aligned `out` (a caller
+    // of the C ABI may hand over any address)
+    const bool vec = (n % 4 == 0) && (reinterpret_cast<uintptr_t>(out) % 4 == 0);
     for (int r = 0; r < nrows; r++) {
         const Box3 b = rows[r];
         uint32_t word = 0;           // (a bounding-box cull per wavefront ahead of this was slower: 704 -> 800 us, the kernel is
@@ -367,7 +369,36 @@ __global__ __launch_bounds__(kGridThreads) void k_crop3dp_grid(const float *__re
     }
 }
 
+// what build_box_grid decides for a set of boxes (tests/test_gpu_crop_routes.py asserts the level every scene is built for)
+__global__ __launch_bounds__(kGridThreads) void k_box_grid_plan(const float *__restrict__ boxes, int64_t m, int bstride, int boff,
+                                                                BoxCols cols, int32_t *__restrict__ plan4)
+{
+    __shared__ BoxGrid G;
+    build_box_grid(G, boxes, m, bstride, boff, cols);
+    if (threadIdx.x == 0) {
+        plan4[0] = G.all ? 0 : G.n;
+        plan4[1] = (int32_t)G.all;
+        plan4[2] = G.all ? 0 : (int32_t)G.start[kGridCellsN];
+        plan4[3] = 0;
+    }
+}
+
 }  // namespace
+
+// The plan of the box grid for these boxes, from ONE workgroup that runs the production build_box_grid: plan4 (device) =
+// {cells per axis, G.all, registrations, 0}; cells and registrations are 0 where G.all is set.  dims 3: 7-float rows
+// (x, y, z, lx, ly, lz, rz) at boxes + i * box_stride + box_offset; dims 2: (x, y, w, h, r) rows.  For tests; no production
+// launch calls it.
+extern "C" int d3d_internal_box_grid_plan(const float *boxes, int64_t m, int32_t box_stride, int32_t box_offset, int32_t dims,
+                                          int32_t *plan4, hipStream_t st)
+{
+    if (m < 0 || box_offset < 0 || (dims != 2 && dims != 3) || box_stride < box_offset + (dims == 3 ? 7 : 5)) return D3D_ERR_BAD_ARG;
+    if (m > kGridMaxBoxes) return D3D_ERR_UNSUPPORTED;
+    if (!plan4 || (m > 0 && !boxes)) return D3D_ERR_BAD_ARG;
+    D3D_LAUNCH("k_box_grid_plan", k_box_grid_plan, dim3(1), dim3(kGridThreads), 0, st, boxes, m, (int)box_stride, (int)box_offset,
+               dims == 3 ? kCols3 : kCols2, plan4);
+    return D3D_OK;
+}
 
 // bool[M,N] of box3dp_crop (reference box/__init__.py:289-315) for project_axis = 2: points[n, point_stride >= 3] f32, boxes
 // [m, box_stride >= 7] f32 rows (x, y, z, lx, ly, lz, rz).  D3D_ERR_UNSUPPORTED (nothing touched) for another axis, more than 4096
