@@ -107,6 +107,9 @@ SIGNATURES = {
     "d3d_iou3d_forward": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _sz, _vp]),
     "d3d_iou2d_paired": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "d3d_iou3d_paired": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "d3d_iou_sparse_workspace_bytes": (_sz, [_i64, _i64]),
+    "d3d_iou_sparse_count": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, ctypes.c_double, _vp, _vp, _sz, _vp]),
+    "d3d_iou_sparse_emit": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, ctypes.c_double, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "d3d_match_distance": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _sz, _vp]),
     "d3d_score_match_workspace_bytes": (_sz, [_i64, _i64]),
     "d3d_score_match": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -633,6 +633,94 @@ def box3d_iou_paired(boxes1, boxes2, method="rbox", precise=True):
     return _paired(IouPaired3D, boxes1, boxes2, 1 if key == "RBOX" else 0, precise, was_numpy)
 
 
+def _sparse_threshold(threshold):
+    try:
+        t = float(threshold)
+    except (TypeError, ValueError):
+        raise ValueError("threshold should be a finite number >= 0, got %r" % (threshold,))
+    if not (0 <= t < float("inf")):                                 # (NaN fails the comparison too)
+        raise ValueError("threshold should be a finite number >= 0, got %r" % (threshold,))
+    return t
+
+
+def _iou_sparse(boxes1, boxes2, cols, iou_type, code, threshold, return_offsets, was_numpy):
+    """d3d_iou_sparse_count, ONE host read (offsets[n] = K), d3d_iou_sparse_emit -> (pairs[K,2] i64, values[K], offsets[n+1] i64)
+    on the caller's device; values in the dtype of `boxes1`"""
+    odev = boxes1.device
+    n, m = boxes1.shape[0], boxes2.shape[0]
+    if n == 0 or m == 0:                                            # no pair: nothing to launch, nothing to load
+        res = (torch.zeros((0, 2), dtype=torch.int64, device=odev), torch.zeros((0,), dtype=boxes1.dtype, device=odev),
+               torch.zeros((n + 1,), dtype=torch.int64, device=odev))
+    else:
+        lib = _lib.load()
+        (b1, b2), dev = _to_device(boxes1.detach(), boxes2.detach())
+        with torch.cuda.device(dev):
+            offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+            ws = _lib.workspace(lib.d3d_iou_sparse_workspace_bytes(n, m), dev)
+            inputs = (_lib.ptr(b1), n, _lib.ptr(b2), m, cols, int(iou_type), code, threshold)
+            _lib.check(lib.d3d_iou_sparse_count(*inputs, _lib.ptr(offsets), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "iou_sparse_count")
+            k = int(offsets[n])                                      # the one host synchronisation of the call
+            pairs = torch.empty((k, 2), dtype=torch.int64, device=dev)
+            values = torch.empty((k,), dtype=b1.dtype, device=dev)
+            if k > 0:
+                _lib.check(lib.d3d_iou_sparse_emit(*inputs, _lib.ptr(offsets), k, _lib.ptr(pairs), _lib.ptr(values), _lib.ptr(ws), ws.numel(),
+                                                   _lib.stream_ptr()), "iou_sparse_emit")
+        res = _lib.to_caller((pairs, values, offsets), odev, dev)
+    res = tuple(_egress(t, was_numpy) for t in res)
+    return res if return_offsets else res[:2]
+
+
+def box2d_iou_sparse(boxes1, boxes2, method="rbox", threshold=0.0, precise=True, return_offsets=False):
+    """The entries of D = box2d_iou(boxes1, boxes2, method, precise) that are above `threshold`, as a list -- without the [N,M]
+    matrix, which for two large sets is almost all zeros (and at 200 k x 200 k boxes does not fit on the card): what matching
+    detections to ground truth, a graph for box fusion or cluster NMS, and an evaluator's association take.  The reference has no
+    counterpart.
+
+    :param boxes1: N x 5 (x,y,w,h,r), torch tensor or numpy array (numpy in, numpy out; CPU or GPU, any strides)
+    :param boxes2: M x 5
+    :param method: 'box' or 'rbox' (the loss variants are nonzero almost everywhere: ValueError)
+    :param threshold: finite, >= 0; the comparison is strict and made on the stored value, the threshold rounded to D's dtype
+    :param precise: compute in float64 and cast back to the input dtype, as box2d_iou does
+    :param return_offsets: also return offsets int64 [N+1] (CSR): pairs[offsets[i]:offsets[i+1]] are row i's pairs
+    :return: pairs int64 [K,2] == (D > threshold).nonzero(), ascending by row and then by column, and
+        values [K] == D[pairs[:,0], pairs[:,1]] bit for bit, in D's dtype.  With threshold 0: exactly the overlapping pairs -- a
+        touching pair (IoU 0), a NaN entry, a rectangle without area ('rbox') have none.
+
+    boxes1 and boxes2 must be both float32 or both float64.  The values carry no gradient:
+    box2d_iou_paired(boxes1[pairs[:,0]], boxes2[pairs[:,1]], method, precise) gives the same bits with autograd.
+    """
+    (boxes1, boxes2), was_numpy = _ingress(boxes1, boxes2)
+    threshold = _sparse_threshold(threshold)
+    if boxes1.dim() != 2 or boxes2.dim() != 2:
+        raise ValueError("Input of rbox_2d_iou should be Nx2 tensors!")
+    if boxes1.shape[1] != 5 or boxes2.shape[1] != 5:
+        raise ValueError("Input boxes should have 5 fields: x, y, w, h, r")
+    iou_type = getattr(IouType, method.upper())                   # AttributeError for unknown names, like box2d_iou
+    if iou_type not in (IouType.BOX, IouType.RBOX):
+        raise ValueError("Unsupported iou type!")
+    if boxes1.dtype != boxes2.dtype:
+        raise RuntimeError("boxes1 and boxes2 must have the same dtype")
+    # box2d_iou's promotion: fp32 boxes, precise -- fp64 arithmetic on rows widened inside the kernels, the value rounded to fp32
+    code = _lib.F32_WIDE if precise and boxes1.dtype == torch.float32 else _dtype_code(boxes1)
+    return _iou_sparse(boxes1, boxes2, 5, iou_type, code, threshold, return_offsets, was_numpy)
+
+
+def iou3d_sparse(boxes1, boxes2, method="rbox", threshold=0.0, return_offsets=False):
+    """The entries of D = iou3d(boxes1, boxes2, method) above `threshold` as a list, without the matrix: box2d_iou_sparse for
+    [N,7] x [M,7] rows (x,y,z,lx,ly,lz,rz), in fp32 as iou3d.  A pair whose BEV footprints overlap while the z ranges are apart or
+    only touch has value 0 and is left out.  box3d_iou_paired(boxes1[pairs[:,0]], boxes2[pairs[:,1]], method, precise=False) on
+    fp32 rows gives the same bits with autograd."""
+    (boxes1, boxes2), was_numpy = _ingress(boxes1, boxes2)
+    threshold = _sparse_threshold(threshold)
+    key = method.upper()
+    if key not in ("RBOX", "BOX"):
+        raise ValueError("Unsupported iou type!" if hasattr(IouType, key) else "Unrecognized iou type!")
+    if len(boxes1.shape) != 2 or len(boxes2.shape) != 2 or boxes1.shape[1] != 7 or boxes2.shape[1] != 7:
+        raise ValueError("Input boxes should have 7 fields: x, y, z, lx, ly, lz, rz")
+    return _iou_sparse(boxes1.to(torch.float32), boxes2.to(torch.float32), 7, getattr(IouType, key), _lib.F32, threshold, return_offsets,
+                       was_numpy)
+
+
 def crop_2dr(points, boxes):
     """crop_2dr of the reference (utils.cpp:38-47; box_impl.crop_2dr): bool[M,N] indicators, [i,j] = point j is
     inside rotated box i.  points [N,2], boxes [M,5], same floating dtype."""
@@ -806,6 +894,6 @@ nms = box2d_nms
 __all__ = ["Iou2D", "Iou2DR", "GIou2DR", "DIou2DR", "PDist2DR", "iou2d_backward", "iou2dr_backward", "giou2dr_forward",
            "giou2dr_backward", "diou2dr_forward", "diou2dr_backward", "iou2dr_flags", "pdist2dr_forward", "pdist2dr_backward",
            "box2dr_crop", "box3dp_crop", "box2dr_pdist", "box3dr_pdist", "seg1d_pdist", "seg1d_iou", "crop_2dr", "box2d_iou", "box2d_nms",
-           "box2d_nms_batched", "box2d_iou_paired", "box3d_iou_paired", "IouPaired2D", "IouPaired3D",
+           "box2d_nms_batched", "box2d_iou_paired", "box3d_iou_paired", "IouPaired2D", "IouPaired3D", "box2d_iou_sparse", "iou3d_sparse",
            "iou2d", "iou3d", "nms", "iou2d_forward", "iou2dr_forward", "nms2d", "nms2d_cuda", "argsort_desc", "IouType",
            "SupressionType", "cuda_available"]

@@ -588,6 +588,30 @@ int d3d_iou2d_paired(const void *boxes1, const void *boxes2, int64_t n, int32_t 
 int d3d_iou3d_paired(const void *boxes1, const void *boxes2, int64_t n, int32_t rotated, int32_t dtype,
                      void *ious, void *jac, void *stream);
 
+/* extension: the SPARSE form of the two matrices (boxsparse.hip) -- the entries of d3d_iou2d_forward (cols = 5, rows (x,y,w,h,r))
+ * or d3d_iou3d_forward (cols = 7, rows (x,y,z,lx,ly,lz,rz)) that are strictly above `threshold`, as a list ordered by row and
+ * then by column, without the matrix: pairs[k] = (i, j), values[k] = entry [i,j] bit for bit, offsets[n + 1] the CSR row starts
+ * (offsets[n] = K).  The comparison is made on the stored value against the threshold rounded to the stored type; NaN is never
+ * above it.  Two phases, because only the device knows K: _count fills offsets; the caller reads offsets[n], allocates and calls
+ * _emit with the same inputs.  Every pair of bounding boxes is tested (no spatial broad phase); only the candidates are clipped,
+ * in both phases.
+ *   iou_type: D3D_IOU_BOX / D3D_IOU_RBOX, any other: D3D_ERR_UNSUPPORTED (the loss variants are nonzero almost everywhere).
+ *   dtype: cols = 5: D3D_F32, D3D_F64, D3D_F32_WIDE (boxes and values f32 in memory, the arithmetic f64, the value rounded to f32
+ *   before the comparison); cols = 7: D3D_F32 only, as d3d_iou3d_forward; any other: D3D_ERR_UNSUPPORTED.
+ *   D3D_ERR_BAD_ARG, nothing written: n or m negative or above 2^31 - 1, cols not 5 or 7, a threshold that is negative, NaN or
+ *   infinite, a null pointer with work to do, _emit with capacity < offsets[n].  n == 0 or m == 0: D3D_OK without a launch, null
+ *   pointers allowed (_count clears a non-null offsets).  pairs[capacity,2] / values[capacity] beyond K stay untouched.
+ *   Workspace: d3d_iou_sparse_workspace_bytes(n, m) -- the bounding boxes of boxes2 and one sum per 1024 rows: O(n + m); each phase
+ *   fills it for itself, nothing has to survive between them but offsets.  _count does not synchronise; _emit waits for `stream`
+ *   once to read offsets[n] (after the caller's own read that word is ready: the wait is a round trip, no more). */
+size_t d3d_iou_sparse_workspace_bytes(int64_t n, int64_t m);
+int d3d_iou_sparse_count(const void *boxes1, int64_t n, const void *boxes2, int64_t m, int32_t cols, int32_t iou_type,
+                         int32_t dtype, double threshold, int64_t *offsets, void *workspace, size_t workspace_bytes,
+                         void *stream);
+int d3d_iou_sparse_emit(const void *boxes1, int64_t n, const void *boxes2, int64_t m, int32_t cols, int32_t iou_type,
+                        int32_t dtype, double threshold, const int64_t *offsets, int64_t capacity, int64_t *pairs,
+                        void *values, void *workspace, size_t workspace_bytes, void *stream);
+
 /* replaces the pair loops of BaseMatcher.prepare_boxes (reference d3d/tracking/matcher.pyx:46-80) for the metrics IoU
  * (rotated = 0: box3d_iou) and RIoU (rotated = 1: box3dr_iou): src[n,9], dst[m,9] f32 rows = (label, score, x, y, z, lx, ly,
  * lz, yaw) as Target3DArray.to_numpy lays them out (abstraction.pyx:263-272); the dimensions are clipped to +-1e3
