@@ -141,6 +141,10 @@ SIGNATURES = {
     "d3d_track_state_bytes": (_sz, [_i64, _i32]),
     "d3d_track_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
     "d3d_track_frame": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3d_deteval_frame_max": (_i32, []),
+    "d3d_deteval_batched_workspace_bytes": (_sz, [_i64, _i32]),
+    "d3d_deteval_batched": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32,
+                                           _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d3d_bessel_e": (ctypes.c_int, [_i32, _vp, _i64, _i32, _vp, _vp]),
     "d3d_i0e_backward": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
 }

@@ -34,7 +34,9 @@ from .utils import Dict
 
 
 class DetectionEvaluator:
-    """Benchmark for object detection; targets association is done by score sorting (benchmarks.pyx:84-149)."""
+    """Benchmark for object detection; targets association is done by score sorting (benchmarks.pyx:84-149).
+
+    Extension beyond the reference: calc_stats_batch evaluates many stacked frames in one call."""
 
     def __init__(self, classes, min_overlaps, pr_sample_count=40, min_score=0, pr_sample_scale="log10", reference_compat=True):
         self.reference_compat = bool(reference_compat)
@@ -209,12 +211,10 @@ class DetectionEvaluator:
         DetectionEvalStats (benchmarks.pyx:60-82, 178-283); both box sets must be in the same frame"""
         gt = np.ascontiguousarray(gt_boxes, dtype=np.float32).reshape(-1, 9)
         dt = np.ascontiguousarray(dt_boxes, dtype=np.float32).reshape(-1, 9)
-        T, classes = self._pr_nsamples, self._classes
-        thr = self._pr_thresholds
         gt_tag, dt_tag = gt[:, 0].astype(np.int64), dt[:, 0].astype(np.int64)
         dt_score = dt[:, 1]
-        out = Dict(ngt={}, ndt={}, tp={}, fp={}, fn={}, acc_iou={}, acc_angular={}, acc_dist={}, acc_box={}, acc_var={})
         if self.reference_compat:
+            out = Dict(ngt={}, ndt={}, tp={}, fp={}, fn={}, acc_iou={}, acc_angular={}, acc_dist={}, acc_box={}, acc_var={})
             return self._calc_stats_per_threshold(gt, dt, out)
         if len(gt) and len(dt):
             cache = prepare_boxes(dt, gt, DistanceTypes.RIoU)                                        # :188-189
@@ -226,8 +226,17 @@ class DetectionEvaluator:
             iou[matched] = (1 - cache[dm[matched], np.nonzero(matched)[0]]).cpu().numpy()            # :243
         else:
             sm, dm = np.full((len(dt),), -1, np.int64), np.full((len(gt),), -1, np.int64)
-            matched = dm >= 0
             iou = np.zeros((len(gt),), np.float32)
+        return self._stats_of_match(gt, dt, sm, dm, iou)
+
+    def _stats_of_match(self, gt, dt, sm, dm, iou):
+        """the stats of a frame from ONE association (reference_compat=False): sm[n] / dm[m] int64 partners or -1, iou[m] fp32
+        = 1 - distance of a ground truth's pair, 0 without one.  calc_stats and calc_stats_batch share it."""
+        T, classes, thr = self._pr_nsamples, self._classes, self._pr_thresholds
+        gt_tag, dt_tag = gt[:, 0].astype(np.int64), dt[:, 0].astype(np.int64)
+        dt_score = dt[:, 1]
+        out = Dict(ngt={}, ndt={}, tp={}, fp={}, fn={}, acc_iou={}, acc_angular={}, acc_dist={}, acc_box={}, acc_var={})
+        matched = dm >= 0
         partner = np.where(matched, dm, 0)
         # a ground-truth box is a true positive at threshold t iff its detection is selected there (score >= t)  (:220-238)
         gscore = np.where(matched, dt_score[partner] if len(dt) else 0.0, -np.inf)
@@ -333,8 +342,196 @@ class DetectionEvaluator:
             out.acc_var[c] = np.where(tp > 0, -np.inf, np.nan).tolist()
         return out
 
+    # ------------------------------------------------------------------ many frames per call
+    def calc_stats_batch(self, gt_boxes, dt_boxes, gt_frame_offsets, dt_frame_offsets):
+        """Extension (not in the reference): F frames stacked, frame f = gt rows gt_frame_offsets[f] .. gt_frame_offsets[f + 1]
+        and dt rows dt_frame_offsets[f] .. dt_frame_offsets[f + 1] (F + 1 offsets each, rising from 0 to the number of rows;
+        numpy arrays or tensors on any device).  -> list of F stats, element f exactly what calc_stats(gt_f, dt_f) returns
+        (the same keys, types and counts, the float fields bit for bit), in both settings of reference_compat; nothing is added
+        to the totals (add_stats does).  The frames go to the device in chunks of at most _DET_MAX_FRAMES frames and
+        _DET_MAX_CACHE_BYTES of distance cache, two launches each (d3d_deteval_batched), with one upload before and one fetch
+        after all of them.  Three kinds of frame go through calc_stats one by one instead: those with more boxes on a side than
+        d3d_deteval_frame_max(); with reference_compat, those whose selected in-class scores hold a NaN or a tie (calc_stats
+        orders every threshold's selection with numpy's unstable argsort, which only a run on the same subset reproduces);
+        and every frame when the score thresholds do not rise."""
+        gt, dt = _host_rows(gt_boxes, np.float32, 9), _host_rows(dt_boxes, np.float32, 9)
+        go, do = _host_rows(gt_frame_offsets, np.int64, 0), _host_rows(dt_frame_offsets, np.int64, 0)
+        for off, n in ((go, len(gt)), (do, len(dt))):
+            if len(off) < 1 or off[0] != 0 or off[-1] != n or np.any(np.diff(off) < 0):
+                raise ValueError("frame offsets must rise from 0 to the number of boxes")
+        if len(go) != len(do):
+            raise ValueError("gt_frame_offsets and dt_frame_offsets must describe the same frames")
+        F = len(go) - 1
+        if F == 0:
+            return []
+        h = self._batch_prepare(gt, dt, go, do)
+        stats = [None] * F
+        fallback = h["fallback"]
+        good = np.nonzero(~fallback)[0]
+        if len(good) < F:                                  # the rows of the frames that stay, stacked anew
+            gsel, dsel = np.repeat(~fallback, np.diff(go)), np.repeat(~fallback, np.diff(do))
+            go2, do2 = np.zeros((len(good) + 1,), np.int64), np.zeros((len(good) + 1,), np.int64)
+            np.cumsum(np.diff(go)[good], out=go2[1:])
+            np.cumsum(np.diff(do)[good], out=do2[1:])
+            h = self._batch_prepare(gt[gsel], dt[dsel], go2, do2) if len(good) else None
+        pending = self._batch_launch(h, _seg_device(gt_boxes, dt_boxes)) if len(good) else None
+        for f in np.nonzero(fallback)[0]:
+            stats[f] = self.calc_stats(gt[go[f]:go[f + 1]], dt[do[f]:do[f + 1]])
+        if pending is not None:
+            for f, st in zip(good, self._batch_stats(h, pending.cpu().numpy())):
+                stats[f] = st
+        return stats
 
-_ACC_FIELDS = ("acc_angular", "acc_box", "acc_iou", "acc_dist", "acc_var")
+    def _batch_prepare(self, gt, dt, go, do):
+        """what the host knows of the stacked frames before the device runs, as flat arrays: class slots, every frame's in-class
+        detections from the best score down (NaN first, ties in index order: torch.sort(descending, stable) as score_match
+        calls it, of which every threshold's selection is a prefix), the selected counts, and which frames fall back"""
+        T, C, thr = self._pr_nsamples, len(self._classes), self._pr_thresholds
+        F = len(go) - 1
+        nf, mf = np.diff(do), np.diff(go)
+        fd, fg = np.repeat(np.arange(F), nf), np.repeat(np.arange(F), mf)
+        by_value = np.argsort(np.asarray(self._classes, np.int64), kind="stable")
+        values = np.asarray(self._classes, np.int64)[by_value]
+
+        def slots(tags):
+            at = np.minimum(np.searchsorted(values, tags), C - 1)
+            return np.where(values[at] == tags, by_value[at], -1).astype(np.int32)
+        gslot, dslot = slots(gt[:, 0].astype(np.int64)), slots(dt[:, 0].astype(np.int64))
+        score = dt[:, 1]
+        nan, inc = np.isnan(score), dslot >= 0
+        order = np.lexsort((np.where(nan, np.float32(0), -score), ~nan, ~inc, fd))
+        base = np.repeat(do[:-1], nf)
+        perm = (order - base).astype(np.int32)
+        rank = np.empty((len(dt),), np.int32)
+        rank[order] = np.arange(len(dt)) - base
+        rank[~inc] = -1
+        # a detection is selected at the thresholds t < sel_upto: `score < thres` skips (:224-225), so a NaN score never does
+        rising = bool(np.all(np.diff(thr) >= 0))
+        sel_upto = np.where(nan, T, np.searchsorted(thr, score, side="right")) if rising else np.full((len(dt),), T)
+        hist = np.bincount(((fd * C + dslot) * (T + 1) + sel_upto)[inc], minlength=F * C * (T + 1)).reshape(F, C, T + 1)
+        ndt = np.cumsum(hist[:, :, ::-1], axis=2)[:, :, ::-1][:, :, 1:]                                # [F, C, T]: #(sel_upto > t)
+        ngt = np.bincount((fg * C + gslot)[gslot >= 0], minlength=F * C).reshape(F, C)
+        bound = _lib.load().d3d_deteval_frame_max()
+        fallback = (nf > bound) | (mf > bound)
+        if self.reference_compat:
+            if not rising:
+                fallback[:] = True
+            fallback[fd[nan & inc]] = True
+            so, fo, io, uo = score[order], fd[order], inc[order], sel_upto[order]
+            tie = (fo[1:] == fo[:-1]) & io[1:] & io[:-1] & (so[1:] == so[:-1]) & (uo[1:] > 0)
+            fallback[fo[1:][tie]] = True
+        return dict(gt=gt, dt=dt, go=go, do=do, nf=nf, mf=mf, gslot=gslot, dslot=dslot, perm=perm, rank=rank, ndt=ndt, ngt=ngt,
+                    fallback=fallback)
+
+    def _batch_launch(self, h, dev):
+        """one upload, d3d_deteval_batched per chunk of frames, no wait -> the device tensor of all chunks' results: int32
+        [gt_match | gt_iou] over the problems' ground truths, then (reference_compat=False) dt_match over the detections"""
+        lib = _lib.load()
+        T, C, literal = self._pr_nsamples, len(self._classes), self.reference_compat
+        go, do, nf, mf = h["go"], h["do"], h["nf"], h["mf"]
+        F, N, M = len(nf), len(h["dt"]), len(h["gt"])
+        P = T if literal else 1
+        # the distance thresholds: a class without one reads 0.0 in the literal association (unordered_map::operator[],
+        # matcher.pyx:112) and takes no part in the other (score_match)
+        maxd = np.array([self._max_distance.get(c, 0.0 if literal else np.nan) for c in self._classes], np.float32)
+        # the slots of a problem: the detections selected at its threshold; every in-class detection of its frame
+        slots = h["ndt"].sum(1).astype(np.int32) if literal else \
+            np.bincount(np.repeat(np.arange(F), nf)[h["dslot"] >= 0], minlength=F).astype(np.int32)
+        pairs = nf * mf
+        chunks, f0 = [], 0
+        while f0 < F:                                      # as many frames as the caps allow, one at least
+            f1, nbytes = f0, 0
+            while f1 < F and (f1 == f0 or (f1 - f0 < _DET_MAX_FRAMES and nbytes + 4 * pairs[f1] <= _DET_MAX_CACHE_BYTES)):
+                nbytes += 4 * int(pairs[f1])
+                f1 += 1
+            chunks.append((f0, f1))
+            f0 = f1
+        parts, pos = [], 0
+
+        def put(a):
+            nonlocal pos
+            b = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+            at, pad = pos, _aligned(len(b)) - len(b)
+            parts.append(b)
+            if pad:
+                parts.append(np.zeros((pad,), np.uint8))
+            pos += len(b) + pad
+            return at
+        at = {k: put(v) for k, v in (("dt", h["dt"]), ("gt", h["gt"]), ("dslot", h["dslot"]), ("gslot", h["gslot"]),
+                                     ("perm", h["perm"]), ("rank", h["rank"]), ("slots", slots), ("maxd", maxd))}
+        offs = []
+        for f0, f1 in chunks:
+            co = np.zeros((f1 - f0 + 1,), np.int64)
+            np.cumsum(pairs[f0:f1], out=co[1:])
+            offs.append((put(do[f0:f1 + 1] - do[f0]), put(go[f0:f1 + 1] - go[f0]), put(co), int(co[-1])))
+        with torch.cuda.device(dev):
+            blob = torch.from_numpy(np.concatenate(parts)).to(dev)
+            out = torch.empty((max(2 * P * M + (0 if literal else N), 1),), dtype=torch.int32, device=dev)
+            base, obase, stream = blob.data_ptr(), out.data_ptr(), _lib.stream_ptr()
+            ws = _lib.workspace(max(lib.d3d_deteval_batched_workspace_bytes(o[3], 0) for o in offs), dev)
+            for (f0, f1), (dof, gof, cof, npairs) in zip(chunks, offs):
+                d0, g0 = int(do[f0]), int(go[f0])
+                rc = lib.d3d_deteval_batched(
+                    ctypes.c_void_p(base + at["dt"] + 36 * d0), ctypes.c_void_p(base + at["gt"] + 36 * g0), ctypes.c_void_p(base + dof),
+                    ctypes.c_void_p(base + gof), ctypes.c_void_p(base + cof), f1 - f0, npairs, int(nf[f0:f1].max()), int(mf[f0:f1].max()),
+                    ctypes.c_void_p(base + at["dslot"] + 4 * d0), ctypes.c_void_p(base + at["gslot"] + 4 * g0),
+                    ctypes.c_void_p(base + at["perm"] + 4 * d0), ctypes.c_void_p(base + at["rank"] + 4 * d0),
+                    ctypes.c_void_p(base + at["slots"] + 4 * P * f0), T, ctypes.c_void_p(base + at["maxd"]), C, 1 if literal else 0,
+                    None, ctypes.c_void_p(obase + 4 * P * g0), ctypes.c_void_p(obase + 4 * (P * M + P * g0)),
+                    None if literal else ctypes.c_void_p(obase + 4 * (2 * M + d0)), _lib.ptr(ws), ws.numel(), stream)
+                _lib.check(rc, "deteval_batched")
+        return out
+
+    def _batch_stats(self, h, res):
+        """the frames' stats from the fetched results (_batch_launch's layout)"""
+        T, C, classes = self._pr_nsamples, len(self._classes), self._classes
+        gt, dt, go, do, mf = h["gt"], h["dt"], h["go"], h["do"], h["mf"]
+        F, N, M = len(mf), len(dt), len(gt)
+        if not self.reference_compat:                      # one association per frame: calc_stats' own epilogue, frame by frame
+            dm, iou, sm = res[:M].astype(np.int64), res[M:2 * M].view(np.float32), res[2 * M:2 * M + N].astype(np.int64)
+            return [self._stats_of_match(gt[go[f]:go[f + 1]], dt[do[f]:do[f + 1]], sm[do[f]:do[f + 1]], dm[go[f]:go[f + 1]],
+                                         iou[go[f]:go[f + 1]]) for f in range(F)]
+        # _calc_stats_per_threshold's epilogue over all frames at once: the K matched (frame, threshold, ground truth) triples in
+        # that order, counts and float64 sums by bincount over (frame, threshold, class) keys -- a bin receives its terms in
+        # ascending ground-truth order, as the per-frame bincount over thresholds does, so the sums have the same bits
+        gm, iou = res[:T * M], res[T * M:2 * T * M].view(np.float32)
+        e = np.nonzero(gm >= 0)[0]
+        fe = np.searchsorted(T * go[1:], e, side="right")             # frame f's [T, m_f] block starts at T * go[f]
+        rem = e - T * go[fe]
+        te = rem // np.maximum(mf[fe], 1)
+        gi, di = go[fe] + (rem - te * mf[fe]), do[fe] + gm[e]
+        ga, da = gt[gi], dt[di]
+        dp, db = ga[:, 2:5] - da[:, 2:5], ga[:, 5:8] - da[:, 5:8]
+        dyaw = ga[:, 8] - da[:, 8]
+        terms = dict(acc_iou=iou[e],
+                     acc_angular=np.abs((dyaw + np.pi) % (2 * np.pi) - np.pi) / np.pi,
+                     acc_dist=np.sqrt((dp[:, 0] * dp[:, 0] + dp[:, 1] * dp[:, 1]) + dp[:, 2] * dp[:, 2]),
+                     acc_box=np.sqrt((db[:, 0] * db[:, 0] + db[:, 1] * db[:, 1]) + db[:, 2] * db[:, 2]))
+        key = (fe * T + te) * C + h["gslot"][gi]
+        tp = np.bincount(key, minlength=F * T * C).reshape(F, T, C).transpose(0, 2, 1)                 # [F, C, T]
+        ndt, ngt = h["ndt"], h["ngt"]
+        cols = dict(ndt=ndt.tolist(), tp=tp.tolist(), fp=(ndt - tp).tolist(), fn=(ngt[:, :, None] - tp).tolist(),
+                    acc_var=np.where(tp > 0, -np.inf, np.nan).tolist())
+        for name, v in terms.items():
+            ssum = np.bincount(key, weights=v.astype(np.float64), minlength=F * T * C).reshape(F, T, C).transpose(0, 2, 1)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                cols[name] = np.where(tp > 0, (ssum / tp).astype(np.float32), np.float32(np.nan)).tolist()
+        ngt_l = ngt.tolist()
+        names = ("ndt", "tp", "fp", "fn", "acc_iou", "acc_angular", "acc_dist", "acc_box", "acc_var")
+        stats = []
+        for f in range(F):
+            st = Dict(ngt={c: ngt_l[f][i] for i, c in enumerate(classes)})
+            for name in names:
+                col = cols[name][f]
+                st[name] = {c: col[i] for i, c in enumerate(classes)}
+            stats.append(st)
+        return stats
+
+
+_DET_MAX_FRAMES = 16384                # frames of one d3d_deteval_batched call (one wavefront per frame and threshold: 40
+                                       # thresholds make 655 k workgroups, seconds of evaluator input to prepare and fetch at once)
+_DET_MAX_CACHE_BYTES = 256 << 20       # and the bytes of its ragged distance cache, which lives in the workspace arena
+_ACC_FIELDS =("acc_angular", "acc_box", "acc_iou", "acc_dist", "acc_var")
 
 
 def _wmean(a, wa, b, wb):
@@ -796,6 +993,11 @@ class TrackingEvaluator(DetectionEvaluator):
         hs = [self._prepare_host(gt[go[f]:go[f + 1]], dt[do[f]:do[f + 1]], gtid[go[f]:go[f + 1]], dtid[do[f]:do[f + 1]])
               for f in range(len(go) - 1)]
         return self._run(hs, _seg_device(gt_boxes, dt_boxes, gt_tids, dt_tids)) if hs else []
+
+    def calc_stats_batch(self, *args, **kwargs):
+        """not for tracking: the frames of a sequence depend on each other and need track ids"""
+        raise TypeError("TrackingEvaluator has no calc_stats_batch (frames carry track ids and depend on their predecessors): "
+                        "use calc_stats_sequence")
 
     def _prepare_host(self, gt, dt, gtid, dtid):
         """what the host knows of a frame before the device runs: the class slots, the selections, the orders, the tid tables"""

@@ -849,6 +849,44 @@ int d3d_track_frame(const D3DTrackFrame *frame, const float *thresholds, int32_t
                     const void *state_in, void *state_out, int32_t *assign, float *iou, int32_t *counts,
                     void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ d3d/benchmarks: detection, many frames */
+
+/* DetectionEvaluator.calc_stats's device work (reference d3d/benchmarks.pyx:188-283: BaseMatcher.prepare_boxes,
+ * d3d/tracking/matcher.pyx:24-82, and one ScoreMatcher.match per score threshold, matcher.pyx:142-162) for `frames` stacked
+ * frames in two launches (deteval.hip).  The reference has no counterpart: it takes one frame per call.  All pointers are device
+ * memory.
+ *   dt_boxes[N,9], gt_boxes[M,9] f32 rows (label, score, x, y, z, lx, ly, lz, yaw); dt_off[frames + 1], gt_off[frames + 1] i64,
+ *   rising from 0 to N / M: frame f owns detections dt_off[f] .. dt_off[f + 1] - 1 (n_f of them) and ground truths gt_off[f] ..
+ *   gt_off[f + 1] - 1 (m_f); cache_off[frames + 1] i64, cache_off[0] = 0, cache_off[f + 1] = cache_off[f] + n_f * m_f;
+ *   pairs = cache_off[frames]; max_n / max_m: the largest n_f / m_f (the host's statement: the offsets are not read back);
+ *   dt_cls[N], gt_cls[M] i32: slots 0 .. C-1 of the evaluator's classes, negative = outside them; max_dist[C] f32;
+ *   dt_perm[N] i32: at dt_off[f] the frame's in-class detections (rows local to the frame) from the best score down, the rest
+ *   of the stretch unused; dt_rank[N] i32: a detection's position in that order, negative outside the classes;
+ *   literal != 0: one problem per (frame, threshold), slots[frames, T] i32 = the detections selected at threshold t (a prefix of
+ *   the order); slot k accepts the ground truths of the k-th best selected detection (its class, its own distance <=
+ *   max_dist) and takes the free one nearest in the cache row of the k-th selected detection IN INDEX ORDER (matcher.pyx:155-158
+ *   as written), ties to the lower index.  Outputs gt_match / gt_iou [T * M]: frame f's block [T, m_f] starts at T * gt_off[f].
+ *   literal == 0: one problem per frame, slots[frames] = its in-class detections, every slot walks its own row; gt_match /
+ *   gt_iou [M] and dt_match[N] (the ground truth of a detection) in the frames' layout.
+ *   gt_match: the matched detection, local to the frame, or -1; gt_iou: 1 - cache of that pair, 0 without one.
+ *   cache: the ragged distance cache, frame f's [n_f, m_f] block at cache_off[f], every entry with d3d_match_distance(rotated =
+ *   1)'s bits -- or NULL: it lives in the workspace then (d3d_deteval_batched_workspace_bytes(pairs, 0); with a cache given
+ *   the workspace is not used and may be NULL).
+ * Frames without detections or without ground truths are legal: nothing matches.  d3d_deteval_frame_max(): the largest n_f
+ * and m_f the call takes (1024: one wavefront walks a problem, with the frame's state in 4 KB of LDS; a larger frame belongs to
+ * d3d_match_distance + d3d_score_match_batched).  Status code; no allocation, no synchronisation, work on `stream` only.
+ * D3D_ERR_UNSUPPORTED: max_n or max_m above d3d_deteval_frame_max() -- nothing is launched or written (a frame above the
+ * bound in spite of the statement is skipped by its workgroups).  D3D_ERR_BAD_ARG: negative sizes, T outside 1 .. 65535, C outside
+ * 1 .. 32767, frames * T >= 2^31, a missing pointer.  D3D_ERR_WORKSPACE: no cache given and the workspace too small. */
+int32_t d3d_deteval_frame_max(void);
+size_t d3d_deteval_batched_workspace_bytes(int64_t pairs, int32_t cache_given);
+int d3d_deteval_batched(const float *dt_boxes, const float *gt_boxes, const int64_t *dt_off, const int64_t *gt_off,
+                        const int64_t *cache_off, int64_t frames, int64_t pairs, int64_t max_n, int64_t max_m,
+                        const int32_t *dt_cls, const int32_t *gt_cls, const int32_t *dt_perm, const int32_t *dt_rank,
+                        const int32_t *slots, int32_t T, const float *max_dist, int32_t C, int32_t literal,
+                        float *cache, int32_t *gt_match, float *gt_iou, int32_t *dt_match,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ d3d/math */
 
 /* replaces i0e / i1e / i0e_cuda / i1e_cuda (reference d3d/math/impl.cpp:16-46, math.h:6-11, over the templates of
