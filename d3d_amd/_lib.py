@@ -23,6 +23,7 @@ OWNER_MERGE_CHAINS, OWNER_MERGE_TEST_TINY = 1, 2
 NMS_BROAD_SWEEP, NMS_FORCE_DENSE, NMS_SOFT_NO_LDS, NMS_GENERAL, NMS_TEST_WITHHOLD, NMS_FORCE_LEVELS, NMS_ONE_LEVEL = 1, 2, 4, 8, 16, 32, 64
 NMS_KEEP_MASK = 128
 PROJECT_ALL_UV, PROJECT_DMASK = 1, 2
+REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN, REDUCE_SUM = 1, 2, 3, 4      # (SUM: d3d_voxelize_3d_reduce, d3d_voxel_pool_*)
 
 
 def nms_cand_cap(k):
@@ -147,6 +148,10 @@ SIGNATURES = {
                                            _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d3d_bessel_e": (ctypes.c_int, [_i32, _vp, _i64, _i32, _vp, _vp]),
     "d3d_i0e_backward": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "d3d_voxel_index_workspace_bytes": (_sz, [_i64, _i64]),
+    "d3d_voxel_index": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3d_voxel_pool_forward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "d3d_voxel_pool_backward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
 }
 
 _lib = None

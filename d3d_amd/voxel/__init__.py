@@ -712,5 +712,7 @@ def _stream_frames(gen, frames, flags, poison):
             torch.cuda.current_stream().wait_stream(s_idx)
 
 
+from .pool import VoxelIndex, voxel_pool, voxel_unpool  # noqa: E402  (point features -> voxels and back: an extension)
+
 __all__ = ["VoxelGenerator", "voxelize_3d_dense", "voxelize_3d_sparse", "voxelize_3d_filter", "release_cached_buffers",
-           "ReductionType", "MaxPointsFilterType", "MaxVoxelsFilterType"]
+           "ReductionType", "MaxPointsFilterType", "MaxVoxelsFilterType", "VoxelIndex", "voxel_pool", "voxel_unpool"]

@@ -904,6 +904,38 @@ int d3d_bessel_e(int32_t order, const void *x, int64_t n, int32_t dtype, void *o
  * Arguments and errors as d3d_bessel_e; grad_x may be x or grad. */
 int d3d_i0e_backward(const void *x, const void *grad, int64_t n, int32_t dtype, void *grad_x, void *stream);
 
+/* ------------------------------------------------------------------ per-voxel pooling of point features (an extension) */
+
+/* Reduces learned per-point rows into their voxels (point -> voxel) and gathers voxel rows back to the points, without float
+ * atomics: the mapping is inverted once into a CSR index and every pooling call folds a voxel's rows STRICTLY in ascending point
+ * index, so the results are the same bits on every run and for every launch shape.  The reference has no counterpart (its
+ * voxelizer reduces the raw input columns only, voxelize.cpp:137-164).
+ *
+ * d3d_voxel_index: mapping[k] = voxel id in [0, v) of point i, or -1 for "belongs to no voxel" (points_mapping of the sparse
+ *   contract).  order[k]: its first K' entries are the mapped points grouped by ascending voxel id, ascending point index inside a
+ *   voxel (the rest is scratch); offsets[v + 1]: voxel j owns order[offsets[j] .. offsets[j + 1]), offsets[v] = K';
+ *   counts[0] = K', counts[1] = the ids outside [-1, v) -- those points are left out like -1, nothing is accessed out of range.
+ *   k and v are at most 2^31 - 1 (D3D_ERR_UNSUPPORTED above).  k == 0: offsets and counts are zeroed.
+ * d3d_voxel_pool_forward: feat[k, c] (D3D_F32 / D3D_F64, c >= 1) -> out[v, c].  reduction: D3D_REDUCE_MEAN / MAX / MIN, 4 = SUM
+ *   as in d3d_voxelize_3d_reduce.  SUM: 0 + x_0 + x_1 + ... in the dtype, in point order; MEAN: that sum / (T)count, one division;
+ *   MAX / MIN: the first point with x > best (x < best) wins, a NaN wins over every number and the first NaN stays, -0.0 == +0.0.
+ *   arg (may be NULL; MAX / MIN only, ignored otherwise): [v, c] the winner's point index.  A voxel without points: 0, arg -1.
+ *   order / offsets as d3d_voxel_index wrote them (they are trusted).  Rows move as 16-byte vectors when c is a multiple of 4 (f32)
+ *   / 2 (f64) and feat, out and arg are 16-byte aligned, element by element otherwise.
+ * d3d_voxel_pool_backward: grad_out[v, c] -> grad_feat[k, c], every row written exactly once: row i = grad_out[m] (SUM),
+ *   grad_out[m] / (T)(offsets[m + 1] - offsets[m]) (MEAN), grad_out[m, ch] where arg[m, ch] == i and 0 elsewhere (MAX / MIN),
+ *   m = mapping[i]; a zero row where m is outside [0, v).  offsets is read for MEAN only, arg for MAX / MIN only.  With SUM this is
+ *   the gather "each point gets its voxel's row".
+ * D3D_ERR_BAD_ARG: a negative size, c < 1, a missing pointer; D3D_ERR_WORKSPACE: workspace missing or smaller than the query;
+ * D3D_ERR_UNSUPPORTED: another reduction or dtype, k or v above 2^31 - 1.  None of them launches anything. */
+size_t d3d_voxel_index_workspace_bytes(int64_t k, int64_t v);
+int d3d_voxel_index(const int64_t *mapping, int64_t k, int64_t v, int32_t *order, int64_t *offsets, int64_t *counts,
+                    void *workspace, size_t workspace_bytes, void *stream);
+int d3d_voxel_pool_forward(const void *feat, int64_t k, int32_t c, int32_t dtype, const int32_t *order, const int64_t *offsets,
+                           int64_t v, int32_t reduction, void *out, int32_t *arg, void *stream);
+int d3d_voxel_pool_backward(const void *grad_out, int64_t v, int32_t c, int32_t dtype, const int64_t *mapping, int64_t k,
+                            const int64_t *offsets, int32_t reduction, const int32_t *arg, void *grad_feat, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
