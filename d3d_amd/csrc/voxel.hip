@@ -1241,6 +1241,7 @@ struct BinnedExtras {
     uint16_t *row_state = nullptr;   // d3d_voxelize_3d_dense_resident: [capacity] rows of voxels[v] that may be non-zero (k_emit<.., true>)
     bool fm_packed = false;          // firstmap entries are {count : 8 | segment : 24} words (k_bucket_index<.., V2>), see kFmShift
     bool early_zero = false;         // k_emit: the all-zero lines of the stretch are stored as soon as the entries are known
+    bool pooled = false;             // d3d_voxelize_3d_dense_pooled: the resident launch is profiled as the dense call's own, "k_emit"
 };
 
 // sparse contract fused with the voxel filter (d3d_voxelize_3d_sparse_filter): only voxels that pass get a first-point
@@ -2083,6 +2084,19 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket_index(Key kf, VoxelPa
                 c[k] = tcnt[threadIdx.x + k * kBucketThreads];
                 cs |= (u64)c[k] << (16 * k);
             }
+            if constexpr (!SP) {
+                // dense contract: every occupied slot is one voxel = one first-point entry below.  Their number goes to the
+                // early totals (one atomic per wavefront, counted on the scalar side), so that k_first_count can tell the host
+                // the voxel count before the output launch starts
+                if (early_tot) {
+                    uint32_t occupied = 0;
+#pragma unroll
+                    for (int k = 0; k < PER; k++) occupied += (uint32_t)__popcll(__ballot(c[k] > 0));
+                    if ((threadIdx.x & (kWave - 1)) == 0 && occupied)
+                        (void)__hip_atomic_fetch_add(early_tot + 16 * (((blockIdx.x << 3) + (threadIdx.x >> 6)) & early_mask), (u64)occupied,
+                                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
             u64 tot_c;
             const u64 ex_c = block_excl_scan_u64_lds<kBucketThreads>(cs, &tot_c, smem);
             D3D_PHASE(0, 7);
@@ -2365,11 +2379,32 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket_index(Key kf, VoxelPa
 
 // 64 firstmap entries -> one count; counts scanned inside the block (fwpre), block totals -> bsumF (<= 1024 of them:
 // k_meta_first adds up the ones before its tile itself, which is cheaper than a scan launch or a last-block pass)
+// (EarlyNote: the dense contract's output sizes ahead of the output launch.  k_bucket_index added up the first-point entries it
+// wrote -- `pairs` words, 16 apart -- so block 0 knows the voxel count before anything is numbered: it writes counts[] and tells
+// the host, which sizes its views and prepares the next frame while the output launch runs.  That launch writes the same
+// counts[] again and does NOT notify: exactly one notification per call.)
+struct EarlyNote {
+    const u64 *tot = nullptr;       // null: the output launch publishes the sizes
+    uint32_t pairs = 0, max_voxels = 0;
+    int64_t aux = 0;                // counts[D3D_COUNT_AUX] of the route
+    int64_t *counts = nullptr, *host = nullptr;
+};
+
 __global__ __launch_bounds__(1024) void k_first_count(const uint32_t *__restrict__ firstmap, uint32_t *fwpre, uint32_t *bsumF,
                                                       uint32_t *clear_word = nullptr /* k_emit_c's overflow-voxel counter */,
-                                                      ZeroFill zf = ZeroFill())
+                                                      ZeroFill zf = ZeroFill(), EarlyNote en = EarlyNote())
 {
     if (zero_fill_role(zf)) return;
+    if (en.tot && blockIdx.x == 0 && threadIdx.x < kWave) {
+        u64 v = 0;
+        for (uint32_t t = threadIdx.x; t < en.pairs; t += kWave) v += en.tot[16 * t];
+        v = wave_sum_u64(v);
+        if (threadIdx.x == 0) {
+            en.counts[D3D_COUNT_VOXELS] = (int64_t)(v < (u64)en.max_voxels ? v : (u64)en.max_voxels);
+            en.counts[D3D_COUNT_AUX] = en.aux;
+            notify_host(en.counts, en.host);
+        }
+    }
     if (clear_word && blockIdx.x == 0 && threadIdx.x == 0) *clear_word = 0;
     __shared__ u64 smem[1024 / kWave];
     __shared__ uint32_t wcnt[256];
@@ -4343,6 +4378,7 @@ struct BinnedPlan {
     uint32_t *precpos, *parr, *vinfo32, *gpos;
     u64 *early_tot;                     // early totals: early_pairs pairs at 16 words each behind the look-back words (0: off)
     uint32_t early_pairs;
+    bool early_note;                    // dense contract: k_first_count's block 0 tells the host the sizes, the output launch does not
     // k_first_count
     uint32_t *fwpre, *bsumF, *big_count;
     // output stage
@@ -4484,6 +4520,22 @@ static BinnedPlan plan_binned(bool rows, int key_bytes, const float *points, int
             : !rows || !(o.emit_voxels || o.emit_reduce) ? Emit::meta_first
             : split ? (n >= (3ll << 20) ? Emit::split512 : Emit::split256)
             : x.row_state && o.emit_voxels ? Emit::resident : Emit::emit;
+    // the dense contract on a one-launch partition, whole call: the voxel count is the number of first-point entries, which
+    // k_bucket_index adds up into early totals at the front of w.fwords (nothing else of this path uses them; the partition
+    // clears them) and k_first_count hands to the host.  No status bit is raised behind k_bucket_index on these routes.
+    p.early_note = false;
+    if (x.host_counts && stage == 0 && !meta_lb && p.table && (o.emit_voxels || o.emit_generic) &&
+        (p.out == Emit::split256 || p.out == Emit::split512 || p.out == Emit::resident || p.out == Emit::emit || p.out == Emit::emit_c)) {
+        const EarlyLayout e = early_layout(0, w.npad, true);
+        if (e.pairs) {
+            p.early_note = true;
+            p.early_pairs = e.pairs;
+            p.early_tot = w.fwords + e.at;
+            p.zero_words = w.fwords;
+            p.nzero = e.at + 16u * e.pairs;
+            p.zero_ticket = p.mlb.ticket;
+        }
+    }
     p.meta_vinfo = o.agg4 || rows || lists ? w.vinfo : nullptr;
     // voxels[0 .. prefilled): as much as the idle CUs of the two launches write in passing, at most the voxels a LiDAR frame of
     // this size has (9 n / 16; config 2: 0.585 n) and never more than the tensor's rows
@@ -4577,7 +4629,17 @@ static int launch_index(const BinnedPlan &p, const Key &kf, const float *points,
     if (rc) return rc;
     if (p.out == Emit::meta_first_lb) return D3D_OK;                // (k_meta_first_lb numbers the voxels itself)
     const unsigned nbF = (unsigned)(p.npad / kFlagTile);            // <= 1024 (n <= 16 M)
-    D3D_LAUNCH("k_first_count", k_first_count, dim3(nbF + p.zf_count.nblk), dim3(1024), 0, st, p.firstmap, p.fwpre, p.bsumF, p.big_count, p.zf_count);
+    EarlyNote en;
+    if (p.early_note) {
+        en.tot = p.early_tot;
+        en.pairs = p.early_pairs;
+        en.max_voxels = o.max_voxels;
+        en.aux = p.out == Emit::emit_c ? 0 : p.x.aux_value;
+        en.counts = counts;
+        en.host = p.x.host_counts;
+    }
+    D3D_LAUNCH("k_first_count", k_first_count, dim3(nbF + p.zf_count.nblk), dim3(1024), 0, st, p.firstmap, p.fwpre, p.bsumF, p.big_count, p.zf_count,
+               en);
     return D3D_OK;
 }
 
@@ -4597,13 +4659,14 @@ static int launch_output(const BinnedPlan &p, const Key &kf, const float *points
         }
     }
     const dim3 grid((unsigned)(p.npad / 256));
+    int64_t *const host_late = p.early_note ? nullptr : x.host_counts;     // (k_first_count has told the host: never twice)
     if constexpr (!ROWS && std::is_same<Key, DenseKey>::value) {
         if (p.out == Emit::emit_c) {
             const int pshift = (o.P & (o.P - 1)) == 0 ? __builtin_ctz(o.P) : -1;
             return dispatch_int<3, 5, 6, 7, 8>(c, [&](auto cc) {        // (voxelize_dense_core sends no other C here)
                 D3D_LAUNCH("k_emit_c", (k_emit_c<Key, cc>), grid, dim3(256), 0, st, kf, p.npad, p.firstmap, p.fwpre, p.bsumF, p.vrec, o.max_voxels,
                            points, p.big_list, o.P, pshift, o.reduction, o.coords, o.npoints, o.fuse_pmask ? o.pmask : nullptr, o.aggregates,
-                           p.voff, o.emit_generic, counts, x.host_counts, p.vinfo32, p.big_count, x.row_state);
+                           p.voff, o.emit_generic, counts, host_late, p.vinfo32, p.big_count, x.row_state);
                 return D3D_OK;
             });
         }
@@ -4626,13 +4689,13 @@ static int launch_output(const BinnedPlan &p, const Key &kf, const float *points
                     D3D_LAUNCH("k_emit_split", (k_emit_split<Key, agg4, wg>), dim3(wide ? grid.x : 2u * grid.x), dim3(wg), 0, st, kf,
                                p.npad, p.firstmap, p.fwpre, p.bsumF, p.vrec, o.max_voxels, p4, p.big_list, p.staged, o.P, pshift,
                                o.reduction, o.coords, o.npoints, o.fuse_pmask ? o.pmask : nullptr, agg, o.emit_voxels, counts,
-                               x.host_counts, p.prefilled, x.aux_value);
+                               host_late, p.prefilled, x.aux_value);
                     return D3D_OK;
                 });
             return dispatch(p.out == Emit::resident, [&](auto resident) {
-                D3D_LAUNCH(resident ? "k_emit_resident" : "k_emit", (k_emit<Key, agg4, resident>), grid, dim3(256), 0, st, kf, p.npad,
+                D3D_LAUNCH(resident && !x.pooled ? "k_emit_resident" : "k_emit", (k_emit<Key, agg4, resident>), grid, dim3(256), 0, st, kf, p.npad,
                            p.firstmap, p.fwpre, p.bsumF, p.vrec, o.max_voxels, p4, p.big_list, p.staged, o.P, pshift, o.reduction,
-                           o.coords, o.npoints, o.fuse_pmask ? o.pmask : nullptr, agg, o.emit_voxels, counts, x.host_counts, x);
+                           o.coords, o.npoints, o.fuse_pmask ? o.pmask : nullptr, agg, o.emit_voxels, counts, host_late, x);
                 return D3D_OK;
             });
         });
@@ -4799,7 +4862,8 @@ static int dense_meta(const DenseKey &kf, const float *points, const VoxelWs &w,
 static int voxelize_dense_core(const float *points, int64_t n, int32_t c, const int32_t *shape, const float *bound,
                                int32_t max_points, int32_t max_voxels, int32_t reduction, float *voxels, int64_t *coords,
                                uint8_t *pmask, int32_t *npoints, float *aggregates, int64_t *counts, void *workspace,
-                               size_t workspace_bytes, void *stream, int64_t *host_counts, uint32_t flags, int stage, uint16_t *row_state)
+                               size_t workspace_bytes, void *stream, int64_t *host_counts, uint32_t flags, int stage, uint16_t *row_state,
+                               bool pooled)
 {
     hipStream_t st = (hipStream_t)stream;
     if (n < 0 || c < 3 || !shape || !bound || !counts || max_points < 0 || max_voxels < 0) return D3D_ERR_BAD_ARG;
@@ -4837,6 +4901,7 @@ static int voxelize_dense_core(const float *points, int64_t n, int32_t c, const 
         // staged calls (d3d_voxelize_3d_dense_staged): only the path whose output is ONE launch
         if (stage != 0 && !(emitted && fuse_pmask)) return D3D_ERR_UNSUPPORTED;
         d.x.row_state = row_state;
+        d.x.pooled = pooled;
         if (vec4) {
             if (row_state && !emitted) return D3D_ERR_UNSUPPORTED;       // (resident rows: the one-launch output kernels only)
             rc = binned_index<DenseKey, true>(kf, points, n, c, w, nbins, hshift, counts, d, st, !(flags & D3D_VOXEL_PARTITION_3PASS), stage);
@@ -4899,10 +4964,10 @@ static int voxelize_dense_impl(const float *points, int64_t n, int32_t c, const 
                                int32_t max_points, int32_t max_voxels, int32_t reduction, float *voxels, int64_t *coords,
                                uint8_t *pmask, int32_t *npoints, float *aggregates, int64_t *counts, void *workspace,
                                size_t workspace_bytes, void *stream, int64_t *host_counts, uint32_t flags, int stage = 0,
-                               uint16_t *row_state = nullptr)
+                               uint16_t *row_state = nullptr, bool pooled = false)
 {
     int rc = voxelize_dense_core(points, n, c, shape, bound, max_points, max_voxels, reduction, voxels, coords, pmask, npoints,
-                                 aggregates, counts, workspace, workspace_bytes, stream, host_counts, flags, stage, row_state);
+                                 aggregates, counts, workspace, workspace_bytes, stream, host_counts, flags, stage, row_state, pooled);
     if (rc == D3D_OK && (flags & D3D_VOXEL_EXACT_MEAN) && reduction == D3D_REDUCE_MEAN && max_points > 0 && max_voxels > 0 && n > 0 &&
         stage != 1) {
         DenseKey kf;
@@ -4968,6 +5033,23 @@ extern "C" int d3d_voxelize_3d_dense_resident(const float *points, int64_t n, in
     if (flags & (D3D_VOXEL_PATH_HASH | D3D_VOXEL_SPLIT_FILL)) return D3D_ERR_UNSUPPORTED;
     return voxelize_dense_impl(points, n, c, shape, bound, max_points, max_voxels, reduction, voxels, coords, pmask, npoints,
                                aggregates, counts, workspace, workspace_bytes, stream, host_counts, flags, 0, row_state);
+}
+
+// d3d_voxelize_3d_dense_resident for a caller that owns the buffer on the user's behalf (VoxelGenerator's pooled default output,
+// which hands `voxels` out only while nobody else can see the buffer): the same launches and results; the output launch is
+// reported by d3d_profile_* under the dense call's own label, k_emit, because it IS that call's output stage there.
+extern "C" int d3d_voxelize_3d_dense_pooled(const float *points, int64_t n, int32_t c, const int32_t *shape, const float *bound,
+                                            int32_t max_points, int32_t max_voxels, int32_t reduction, float *voxels,
+                                            uint16_t *row_state, int64_t *coords, uint8_t *pmask, int32_t *npoints, float *aggregates,
+                                            int64_t *counts, void *workspace, size_t workspace_bytes, void *stream,
+                                            int64_t *host_counts, uint32_t flags)
+{
+    if (!row_state) return D3D_ERR_BAD_ARG;
+    if (max_voxels <= 0 || max_points <= 0) return D3D_ERR_UNSUPPORTED;
+    if (n == 0) row_state = nullptr;               // an empty frame: no voxel, no row, the state stays
+    if (flags & (D3D_VOXEL_PATH_HASH | D3D_VOXEL_SPLIT_FILL)) return D3D_ERR_UNSUPPORTED;
+    return voxelize_dense_impl(points, n, c, shape, bound, max_points, max_voxels, reduction, voxels, coords, pmask, npoints,
+                               aggregates, counts, workspace, workspace_bytes, stream, host_counts, flags, 0, row_state, true);
 }
 
 // d3d_voxelize_3d_dense_notify in two calls, for callers that pipeline a stream of frames (round 4): stage 1 enqueues the

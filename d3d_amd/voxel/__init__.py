@@ -10,6 +10,7 @@ CPU-only operator) or on the GPU (results stay there).
 import ctypes
 import enum
 import threading
+import weakref
 
 import numpy as np
 import torch
@@ -147,12 +148,100 @@ class DenseOutputBuffer:
     frame): voxels[capacity, max_points, C] kept on the device from frame to frame together with, per voxel id, the number of
     rows that may be non-zero.  A call then stores only the rows that hold points and zeros over what the previous frame's
     voxel of the same id held; the padding -- 95 % of the tensor on a LiDAR frame -- stays as it is.  The `voxels` a call
-    returns is a view of this buffer: valid until the next call with it, and not to be written."""
+    returns is a view of this buffer: valid until the next call with it, and not to be written.
+    (pooled: a buffer of a VoxelGenerator's output pool, see _OutputPool -- the same launches under the dense call's own label)"""
 
-    def __init__(self, capacity, max_points, device, columns=4):
+    def __init__(self, capacity, max_points, device, columns=4, pooled=False):
         self.capacity, self.max_points, self.device, self.columns = int(capacity), int(max_points), torch.device(device), int(columns)
-        self.voxels = torch.zeros((self.capacity, self.max_points, self.columns), dtype=torch.float32, device=self.device)
-        self.row_state = torch.zeros((self.capacity,), dtype=torch.int16, device=self.device)       # (uint16 bits)
+        # (ordinary tensors also when the first call comes inside torch.inference_mode(): the buffer outlives that context, and an
+        # inference tensor has no version counter for the pool to read)
+        with torch.inference_mode(False):
+            self.voxels = torch.zeros((self.capacity, self.max_points, self.columns), dtype=torch.float32, device=self.device)
+            self.row_state = torch.zeros((self.capacity,), dtype=torch.int16, device=self.device)       # (uint16 bits)
+        self.pooled = bool(pooled)
+        self.used = False           # the last call with this buffer returned a view of it (else: a fresh tensor, buffer untouched)
+        self.refused = False        # the last call's resident entry did not take the frame at all (D3D_ERR_UNSUPPORTED)
+
+    def rezero(self):
+        """back to the state of a new buffer (somebody wrote it): all rows zero, no row may be non-zero"""
+        self.voxels.zero_()
+        self.row_state.zero_()
+
+
+def _version_of(t):
+    """t's version counter, None where it has none (an inference tensor)"""
+    try:
+        return t._version
+    except RuntimeError:
+        return None
+
+
+def _storage_use_count(t):
+    """how many tensors, views and storage handles share t's memory (None: this torch cannot tell)"""
+    fn = getattr(torch._C, "_storage_Use_Count", None)
+    return None if fn is None else int(fn(t.untyped_storage()._cdata))
+
+
+class _PoolSlot:
+    # storage: the buffer's storage handle, kept so that asking for its use count is one call (the handle is the one torch caches
+    # on the storage: keeping it adds no use)
+    __slots__ = ("buf", "storage", "cdata", "idle_uses", "version")
+
+
+class _OutputPool:
+    """At most two DenseOutputBuffers that a dense VoxelGenerator hands its `voxels` out of (one pool per host thread, device,
+    stream and row width).  The reference returns a tensor of the caller's own, so a buffer is reused only while that is
+    indistinguishable:
+      * sole owner -- the use count of its storage is back to what it was when only the pool held it: no tensor, slice or
+        reshaped view of a result is alive anywhere (torch._C._storage_Use_Count; a torch without it: no pooling);
+      * unwritten -- its version counter is what it was at hand-out (an in-place op on any view bumps it); a written buffer
+        is zeroed in whole, with its row state, before it serves again;
+      * large enough (an idle buffer that is too small is dropped for a larger one).
+    A pool whose buffer the native route refused (refuse()) is off for good: its frames take fresh tensors, nothing is kept.
+    take() -> (buffer, how) with how = "pooled" | "second" (another buffer of the pool is still held outside), or (None,
+    "fresh") when both are busy: the caller then allocates per frame, as before."""
+    SLOTS = 2
+
+    def __init__(self, make):
+        self.make = make            # capacity -> DenseOutputBuffer
+        self.slots = []
+        self.rezeroed = 0
+        self.off = False
+
+    def take(self, need, capacity):
+        """capacity: of a buffer built for this request (a number, or a function of `need`)"""
+        uses = getattr(torch._C, "_storage_Use_Count", None)
+        if uses is None or self.off:
+            return None, "fresh"
+        idle = [slot for slot in self.slots if uses(slot.cdata) == slot.idle_uses]
+        busy = len(self.slots) - len(idle)
+        for slot in idle:
+            if slot.buf.capacity < need:
+                self.slots.remove(slot)
+                continue
+            if _version_of(slot.buf.voxels) != slot.version:
+                slot.buf.rezero()
+                self.rezeroed += 1
+            slot.version = _version_of(slot.buf.voxels)
+            return slot.buf, ("second" if busy else "pooled")
+        if len(self.slots) >= self.SLOTS:
+            return None, "fresh"
+        slot = _PoolSlot()
+        slot.buf = self.make(max(int(capacity(need) if callable(capacity) else capacity), int(need)))
+        slot.storage = slot.buf.voxels.untyped_storage()
+        slot.cdata = slot.storage._cdata
+        slot.idle_uses = _storage_use_count(slot.buf.voxels)
+        slot.version = _version_of(slot.buf.voxels)
+        if slot.version is None:        # (cannot tell a written buffer from a clean one: no pooling)
+            self.off = True
+            return None, "fresh"
+        self.slots.append(slot)
+        return slot.buf, ("second" if busy else "pooled")
+
+    def refuse(self, buf):
+        """the resident route does not take this pool's frames (a limit the caller's gate does not know): drop `buf`, stay off"""
+        self.slots = [slot for slot in self.slots if slot.buf is not buf]
+        self.off = True
 
 
 def voxelize_3d_dense(points, voxel_shape, voxel_bound, max_points, max_voxels, reduction_type, flags=None, poison=None,
@@ -180,6 +269,8 @@ def voxelize_3d_dense(points, voxel_shape, voxel_bound, max_points, max_voxels, 
     if resident is not None and (c != resident.columns or resident.max_points != max_points or resident.capacity < cap or
                                  resident.device != dev or max_points <= 0 or max_voxels <= 0):
         raise ValueError("resident output: needs the buffer's columns, max_points and device, capacity >= min(N, max_voxels)")
+    if resident is not None:
+        resident.used = resident.refused = False
     with _device_ctx(dev):
         voxels = resident.voxels if resident is not None else torch.empty((cap, max_points, c), dtype=torch.float32, device=dev)
         coords = torch.empty((cap, 3), dtype=torch.int64, device=dev)
@@ -198,15 +289,18 @@ def voxelize_3d_dense(points, voxel_shape, voxel_bound, max_points, max_voxels, 
 
         def run_resident(fl):
             note.arm()
-            rc = lib.d3d_voxelize_3d_dense_resident(
+            entry = lib.d3d_voxelize_3d_dense_pooled if resident.pooled else lib.d3d_voxelize_3d_dense_resident
+            rc = entry(
                 _lib.ptr(pts), n, c, ctypes.cast(shape_h, ctypes.c_void_p), ctypes.cast(bound_h, ctypes.c_void_p),
                 max_points, max_voxels, red, _lib.ptr(voxels), _lib.ptr(resident.row_state), _lib.ptr(coords), _lib.ptr(pmask),
                 _lib.ptr(npts), _lib.ptr(agg), _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), note.ptr, fl)
             if rc == _lib.ERR_UNSUPPORTED:
+                resident.refused = True
                 return None                 # nothing was touched: the plain call decides (and reports a bad reduction type)
             _lib.check(rc, "voxelize_3d_dense_resident")
             host = note.wait(counts)
             _check_status(int(host[_lib.COUNT_STATUS]), "voxelize_3d_dense_resident")
+            resident.used = True
             return int(host[_lib.COUNT_VOXELS])
 
         def run(fl):
@@ -357,9 +451,25 @@ def _spare_put(key, n, make):
     _spare.set = (key, cap, make(cap))
 
 
+# The output pools of the dense generators: per host thread, generator -> ({(device, stream, columns): _OutputPool}, route
+# counters).  Kept here and not on the generator (which stays a plain, copyable object); an entry goes with its generator.
+_pool_local = threading.local()
+
+
+def _pool_states():
+    m = getattr(_pool_local, "gens", None)
+    if m is None:
+        m = _pool_local.gens = weakref.WeakKeyDictionary()
+    return m
+
+
 def release_cached_buffers():
-    """drop the spare output set this thread holds for its next sparse VoxelGenerator call (~100 bytes per point)"""
+    """drop what the CALLING thread keeps for later calls: the spare output set of its next sparse VoxelGenerator call (~100
+    bytes per point) and the pooled `voxels` buffers it holds for every dense VoxelGenerator (results still alive keep their own
+    memory).  Buffers that other threads hold are theirs to release: each thread calls this for itself."""
     _spare.set = None
+    for pools, _ in list(_pool_states().values()):
+        pools.clear()
 
 
 class _SparseFilterCall(ctypes.Structure):
@@ -477,9 +587,12 @@ class VoxelGenerator:
     reference's d3d.voxel.VoxelGenerator (voxel/__init__.py:12-104)."""
 
     def __init__(self, bounds, shape, min_points=0, max_points=30, max_voxels=20000,
-                 max_points_filter=None, max_voxels_filter=None, reduction=None, dense=False, resident=False):
-        # resident (beyond the reference; dense only): `voxels` is returned as a view of a buffer the generator keeps on the
-        # device (DenseOutputBuffer) -- same values, valid until the generator's next call.
+                 max_points_filter=None, max_voxels_filter=None, reduction=None, dense=False, resident=None):
+        # resident (beyond the reference; dense only).  True: `voxels` is returned as a view of ONE buffer the generator keeps on
+        # the device (DenseOutputBuffer) -- same values, valid until the generator's next call, not to be written.  None (the
+        # default): the same route through a pool of two such buffers, each reused only when no result that views it is alive
+        # and nobody wrote it (_OutputPool) -- to the caller the result is a tensor of its own, as the reference's; otherwise,
+        # and under the poison test hook, a fresh tensor per frame.  False: always a fresh tensor.
         # The derived grid quantities are tiny fp32 host tensors computed with the same torch
         # ops as the reference so that `size` is bit-identical (it feeds the coordinate division).
         self._bounds = torch.tensor(bounds, dtype=torch.float)
@@ -487,7 +600,9 @@ class VoxelGenerator:
         self._min_points, self._max_points, self._max_voxels, self._dense = min_points, max_points, max_voxels, dense
         if resident and not dense:
             raise ValueError("resident output is for dense voxelization")
-        self._resident, self._resident_buf = bool(resident), None
+        self._resident, self._resident_buf = (None if resident is None else bool(resident)), None
+        # (the grid's cells must fit the binned index's 32-bit keys for the resident route, and with it the pooled output)
+        self._cells_fit_u32 = float(shape[0]) * float(shape[1]) * float(shape[2]) < 4294967295.0
         self._sparse_plan = None             # the prepared argument block of the sparse + filter call (_SparsePlan), made on first use
 
         lohi = self._bounds.reshape(3, 2)
@@ -528,7 +643,7 @@ class VoxelGenerator:
         float32 device tensors): frame k + 1's index launches (latency-bound) go to a side stream, to run under frame k's
         output launch (bandwidth-bound) on another -- two frames in flight, each with its own scratch
         (d3d_voxelize_3d_dense_staged); results are ordinary stream-ordered tensors on the caller's current stream.
-        MEASURED on MI355X / ROCm 7.2 (profiles/r04_pipelined_*): no gain -- the runtime maps both streams to one
+        MEASURED on MI355X / ROCm 7.2 (DESIGN_HISTORY.md 4d, profiles/r04_pipelined_*): no gain -- the runtime maps both streams to one
         hardware queue (144 vs 137 us per frame for the plain loop), and on two queues every cross-queue event wait costs
         50-60 us (247 us per frame).  Hence off by default: the plain loop."""
         if not (pipelined and self._dense) or self._resident:       # (a resident output is ONE buffer: one frame in flight)
@@ -544,7 +659,9 @@ class VoxelGenerator:
         if not points.is_cuda:
             points = points.to(_lib.require_gpu())    # stage once; results go back to the caller's device
         if self._dense:
-            buf = None
+            buf = how = None
+            if self._resident is None and points.dim() == 2 and points.shape[0] > 0:
+                buf, how, pool = self._pooled_buffer(points, poison, flags)
             if self._resident and points.shape[0] > 0:
                 need = min(int(points.shape[0]), int(self._max_voxels))
                 buf = self._resident_buf
@@ -554,6 +671,10 @@ class VoxelGenerator:
                                                                  columns=int(points.shape[1]))
             ret = Dict(voxelize_3d_dense(points, self._shape_h, self._bounds_h, self._max_points,
                                          self._max_voxels, self._reduction, flags=flags, poison=poison, resident=buf))
+            if how is not None:
+                self._pool_stats[how if buf is not None and buf.used else "fresh"] += 1
+                if buf is not None and buf.refused:
+                    pool.refuse(buf)
         else:
             pf, vf = int(self._max_points_filter), int(self._max_voxels_filter)
             ret = None
@@ -581,6 +702,53 @@ class VoxelGenerator:
         if odev != points.device:
             ret = Dict(_lib.to_caller(dict(ret), odev, points.device))
         return ret
+
+
+_POOL_MAX_KEYS = 4          # (device, stream, columns) combinations a thread keeps pools for
+
+
+def _vg_pool_state(self):
+    m = _pool_states()
+    st = m.get(self)
+    if st is None:
+        st = m[self] = ({}, dict(pooled=0, second=0, fresh=0))
+    return st
+
+
+def _vg_pooled_buffer(self, points, poison, flags=None):
+    """-> (DenseOutputBuffer of this thread's pool | None, "pooled" | "second" | "fresh", the pool | None) for a frame already on
+    its device"""
+    P, mv, n, c = int(self._max_points), int(self._max_voxels), int(points.shape[0]), int(points.shape[1])
+    opts = options.current()
+    if (opts.poison if poison is None else poison) or P <= 0 or mv <= 0 or not points.is_cuda:
+        return None, "fresh", None      # (poison fills would break a buffer whose zero padding is an invariant)
+    # what d3d_voxelize_3d_dense_resident takes -- a buffer is built only for frames that will use it: rows of 3 .. 8 floats, up
+    # to 256 rows per voxel (whole 16-byte units when the rows are not), frames of up to 8 M points on the binned index without
+    # the two-launch output, 16-byte aligned contiguous float32 rows, a grid whose cells fit 32 bits.  (Whatever else the
+    # route may refuse: _OutputPool.refuse.)
+    fl = opts.voxel_flags if flags is None else int(flags)
+    if not (3 <= c <= 8 and P <= 256 and (c == 4 or (P * c) % 4 == 0) and n <= (8 << 20) and points.dtype == torch.float32 and
+            not (fl & (_lib.VOXEL_PATH_HASH | _lib.VOXEL_SPLIT_FILL)) and self._cells_fit_u32 and points.is_contiguous() and
+            points.data_ptr() % 16 == 0):
+        return None, "fresh", None
+    dev = points.device
+    pools = _vg_pool_state(self)[0]
+    key = (dev.index, _lib.stream_raw(dev.index), c)
+    pool = pools.get(key)
+    if pool is None:
+        def make(cap):
+            with _device_ctx(dev):
+                return DenseOutputBuffer(cap, P, dev, columns=c, pooled=True)
+        pool = pools[key] = _OutputPool(make)
+        while len(pools) > _POOL_MAX_KEYS:      # (the oldest combination goes)
+            pools.pop(next(iter(pools)))
+    return pool.take(min(n, mv), lambda need: min(_spare_cap(need), mv)) + (pool,)
+
+
+VoxelGenerator._pooled_buffer = _vg_pooled_buffer
+VoxelGenerator._pool_map = property(lambda self: _vg_pool_state(self)[0], doc="the calling thread's {(device, stream, columns): _OutputPool}")
+VoxelGenerator._pool_stats = property(lambda self: _vg_pool_state(self)[1], doc="the calling thread's dense calls by route: views "
+                                      "of the pool's first free buffer, of one while another is still held outside, fresh tensors")
 
 
 def _vg_check_sparse_args(self, pf, vf):

@@ -128,7 +128,10 @@ int d3d_voxelize_3d_dense(const float *points, int64_t n, int32_t c,
  * host_counts[D3D_NUM_COUNTS] = 1 (system-scope release).  host_counts = D3D_NUM_COUNTS + 1 int64 of host-mapped,
  * coherent pinned memory (hipHostMalloc / torch pin_memory) with the flag word cleared by the caller, who polls it:
  * the output sizes (the reference returns exactly-sized tensors, voxelize.cpp:166-180) reach the host while the GPU
- * is still writing the outputs, and the next call can be queued behind them without draining the stream. */
+ * is still writing the outputs, and the next call can be queued behind them without draining the stream.
+ * Exactly ONE notification per call.  Where the binned index with its one-launch partition takes the frame and the output is
+ * one launch, the sizes leave from the launch BEFORE the output launch (the bucket index has added up the voxels by then);
+ * elsewhere from the first workgroup of the output launch. */
 int d3d_voxelize_3d_dense_notify(const float *points, int64_t n, int32_t c,
                           const int32_t *shape, const float *bound,
                           int32_t max_points, int32_t max_voxels, int32_t reduction,
@@ -149,6 +152,16 @@ int d3d_voxelize_3d_dense_notify(const float *points, int64_t n, int32_t c,
  * also max_points * c not a multiple of 4), a frame the binned index does not take (D3D_VOXEL_PATH_HASH, more than 8 M points),
  * D3D_VOXEL_SPLIT_FILL. */
 int d3d_voxelize_3d_dense_resident(const float *points, int64_t n, int32_t c,
+                          const int32_t *shape, const float *bound,
+                          int32_t max_points, int32_t max_voxels, int32_t reduction,
+                          float *voxels, uint16_t *row_state, int64_t *coords, uint8_t *pmask, int32_t *npoints,
+                          float *aggregates, int64_t *counts,
+                          void *workspace, size_t workspace_bytes, void *stream, int64_t *host_counts, uint32_t flags);
+
+/* d3d_voxelize_3d_dense_resident for a caller that keeps the buffer on its user's behalf and hands `voxels` out only while
+ * nobody else can see the buffer (VoxelGenerator's pooled default output): the same arguments, launches and results.  The only
+ * difference is the label of the output launch in d3d_profile_report: k_emit, the dense call's own, instead of k_emit_resident. */
+int d3d_voxelize_3d_dense_pooled(const float *points, int64_t n, int32_t c,
                           const int32_t *shape, const float *bound,
                           int32_t max_points, int32_t max_voxels, int32_t reduction,
                           float *voxels, uint16_t *row_state, int64_t *coords, uint8_t *pmask, int32_t *npoints,
