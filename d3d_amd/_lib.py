@@ -154,6 +154,9 @@ SIGNATURES = {
     "d3d_voxel_index": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d3d_voxel_pool_forward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "d3d_voxel_pool_backward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "d3d_voxel_neighbors_workspace_bytes": (_sz, [_i64]),
+    "d3d_voxel_neighbors": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "d3d_neighbor_gather": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,309 @@
+// vnbr.hip -- the neighbour table of a set of active voxels and the row gather through it on MI355X (gfx950): what a submanifold
+// sparse convolution (SECOND, CenterPoint, PV-RCNN, sparse U-Nets) needs before its GEMM.  An extension: the reference stops at the
+// voxelizer.
+//
+//   d3d_voxel_neighbors  coords[V,3] (+ batch[V]) -> table[V,K] int32: the row of the voxel at every kernel offset, -1 = none
+//   d3d_neighbor_gather  feat[V,C], table[R,K]    -> out[R,K,C]: the neighbours' rows side by side, a zero row where there is none
+//
+// The table: three launches, every dependency a kernel boundary (no workgroup waits on another inside a launch).
+//   k_vn_bounds  min / max of every axis and of the batch value: integer atomicMax, one per wavefront and quantity
+//   k_vn_insert  key = mixed radix over the measured spans (one 64-bit number per voxel, below 2^62) into an open-addressing table
+//                (power-of-two capacity >= 2V, linear probing, {key, row} in one 16-byte slot): atomicCAS on the key, the winner
+//                stores its row; an equal key already there is a duplicate
+//   k_vn_lookup  one lane per (voxel, column), the column fastest: a wavefront's stores to `table` are contiguous.  A neighbour
+//                outside the measured box is absent without a probe, so a shifted key never aliases another row; the centre is
+//                the row itself, without a probe
+// Which slot a key lands in depends on the order the lanes arrive in; what a lookup finds does not: the same table on every run.
+// The relation is symmetric -- table[v,k] == u <=> table[u,K-1-k] == v -- so the gradient of "gather my neighbours' rows" is the
+// gather through the mirrored columns: forward and backward are gathers, nothing is scattered, no float atomics.
+#include <algorithm>
+#include "common.hpp"
+
+namespace {
+
+constexpr int kNbrThreads = 256;
+constexpr int kNbrBoundsBlocks = 1024;                 // grid-stride: 8 atomics per wavefront, 32 k in all at most
+constexpr int64_t kNbrLookupBlocks = 1ll << 24;
+constexpr int64_t kNbrGatherBlocks = 1ll << 30;
+constexpr int64_t kNbrMaxV = 0x7fffffffll;             // rows are int32
+constexpr unsigned long long kNbrEmpty = ~0ull;        // (keys stay below 2^62)
+constexpr unsigned long long kNbrSpanLimit = 1ull << 62;
+constexpr unsigned long long kNbrSign = 1ull << 63;    // x ^ sign: int64 -> uint64, order kept
+constexpr unsigned long long kNbrMix = 0x9e3779b97f4a7c15ull;
+
+struct alignas(16) NbrSlot {
+    unsigned long long key;
+    int32_t row, pad;
+};
+
+struct NbrShape {
+    int32_t k[3], d[3];
+};
+
+struct NbrWs {
+    unsigned long long *bounds;      // [4][2]: max(u), max(~u) of x, y, z, batch (u = value ^ sign); zero = nothing seen
+    NbrSlot *slots;
+    int log2cap;
+};
+// the one layout: carved here for d3d_voxel_neighbors, and on a null base for the size query
+NbrWs nbr_carve(WsCarver &w, int64_t v)
+{
+    NbrWs r;
+    r.log2cap = 6;
+    while ((1ll << r.log2cap) < 2 * v) r.log2cap++;
+    r.bounds = w.take<unsigned long long>(8);
+    r.slots = w.take<NbrSlot>((size_t)1 << r.log2cap);
+    return r;
+}
+
+// the measured box: lo[a] the smallest value of axis a (as uint64 bits of the int64), span[a] = max - min + 1; axis 3 = batch
+struct NbrFrame {
+    unsigned long long lo[4], span[4];
+    bool overflow;
+    // position inside the box; the difference of two int64 fits uint64
+    __device__ unsigned long long rel(int a, int64_t x) const { return (unsigned long long)x - lo[a]; }
+    __device__ unsigned long long key(const unsigned long long r[4]) const { return ((r[3] * span[0] + r[0]) * span[1] + r[1]) * span[2] + r[2]; }
+};
+__device__ __forceinline__ NbrFrame nbr_frame(const unsigned long long *__restrict__ bounds, bool has_batch)
+{
+    NbrFrame f;
+    unsigned long long prod = 1;
+    f.overflow = false;
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+        if (a == 3 && !has_batch) {
+            f.lo[a] = 0;
+            f.span[a] = 1;
+            continue;
+        }
+        const unsigned long long hi = bounds[2 * a], lo = ~bounds[2 * a + 1];
+        f.lo[a] = lo ^ kNbrSign;
+        f.span[a] = hi - lo + 1;                                        // 0: the whole int64 range
+        if (f.span[a] == 0 || f.span[a] > kNbrSpanLimit / prod) f.overflow = true;
+        else prod *= f.span[a];
+    }
+    return f;
+}
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long x)
+{
+#pragma unroll
+    for (int d = kWave / 2; d > 0; d >>= 1) {
+        const unsigned long long y = __shfl_xor(x, d, kWave);
+        x = y > x ? y : x;
+    }
+    return x;
+}
+
+__global__ __launch_bounds__(kNbrThreads) void k_vn_bounds(const int64_t *__restrict__ coords, const int64_t *__restrict__ batch, int64_t v,
+                                                           unsigned long long *__restrict__ bounds)
+{
+    unsigned long long m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int64_t i = (int64_t)blockIdx.x * kNbrThreads + threadIdx.x; i < v; i += (int64_t)gridDim.x * kNbrThreads) {
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+            if (a == 3 && !batch) continue;
+            const unsigned long long u = (unsigned long long)(a < 3 ? coords[i * 3 + a] : batch[i]) ^ kNbrSign;
+            m[2 * a] = u > m[2 * a] ? u : m[2 * a];
+            m[2 * a + 1] = ~u > m[2 * a + 1] ? ~u : m[2 * a + 1];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        const unsigned long long w = wave_max_u64(m[q]);
+        if ((threadIdx.x & (kWave - 1)) == 0 && w) atomicMax(&bounds[q], w);
+    }
+}
+
+__device__ __forceinline__ unsigned long long nbr_hash(unsigned long long key, int log2cap) { return (key * kNbrMix) >> (64 - log2cap); }
+
+__global__ __launch_bounds__(kNbrThreads) void k_vn_insert(const int64_t *__restrict__ coords, const int64_t *__restrict__ batch, int64_t v,
+                                                           const unsigned long long *__restrict__ bounds, NbrSlot *__restrict__ slots,
+                                                           int log2cap, int64_t *__restrict__ counts)
+{
+    const NbrFrame f = nbr_frame(bounds, batch != nullptr);
+    if (f.overflow) {                                                   // (the same verdict in every lane of the launch)
+        if (blockIdx.x == 0 && threadIdx.x == 0) counts[2] = 1;
+        return;
+    }
+    const int64_t i = (int64_t)blockIdx.x * kNbrThreads + threadIdx.x;
+    bool dup = false;
+    if (i < v) {
+        const unsigned long long r[4] = {f.rel(0, coords[i * 3]), f.rel(1, coords[i * 3 + 1]), f.rel(2, coords[i * 3 + 2]),
+                                         batch ? f.rel(3, batch[i]) : 0ull};
+        const unsigned long long key = f.key(r), mask = (1ull << log2cap) - 1;
+        unsigned long long h = nbr_hash(key, log2cap);
+        for (unsigned long long n = 0; n <= mask; n++, h = (h + 1) & mask) {      // (at most V <= capacity / 2 slots are ever taken)
+            const unsigned long long old = atomicCAS(&slots[h].key, kNbrEmpty, key);
+            if (old == kNbrEmpty) {
+                slots[h].row = (int32_t)i;
+                break;
+            }
+            if (old == key) {
+                dup = true;
+                break;
+            }
+        }
+    }
+    const unsigned long long b = __ballot(dup);
+    if (b && (threadIdx.x & (kWave - 1)) == 0) atomicAdd((unsigned long long *)&counts[1], (unsigned long long)__popcll(b));
+}
+
+__global__ __launch_bounds__(kNbrThreads) void k_vn_lookup(const int64_t *__restrict__ coords, const int64_t *__restrict__ batch, int64_t v,
+                                                           NbrShape s, const unsigned long long *__restrict__ bounds,
+                                                           const NbrSlot *__restrict__ slots, int log2cap, int32_t *__restrict__ table,
+                                                           int64_t *__restrict__ counts)
+{
+    const NbrFrame f = nbr_frame(bounds, batch != nullptr);
+    if (f.overflow) return;
+    const uint32_t kyz = (uint32_t)(s.k[1] * s.k[2]), K = (uint32_t)s.k[0] * kyz, centre = (K - 1) / 2;
+    const int64_t n = v * (int64_t)K;
+    const unsigned long long mask = (1ull << log2cap) - 1;
+    unsigned long long found = 0;
+    // (every lane of a workgroup makes the same number of trips: the sum below runs on whole wavefronts)
+    for (int64_t base = (int64_t)blockIdx.x * kNbrThreads; base < n; base += (int64_t)gridDim.x * kNbrThreads) {
+        const int64_t v0 = base / K;                                    // one 64-bit division per workgroup and trip
+        const uint32_t q = (uint32_t)(base - v0 * K) + threadIdx.x;
+        const int64_t vi = v0 + q / K;
+        const uint32_t k = q % K;
+        if (vi >= v) continue;
+        int32_t e = -1;
+        if (k == centre) e = (int32_t)vi;
+        else {
+            const int32_t ik[3] = {(int32_t)(k / kyz), (int32_t)(k % kyz) / s.k[2], (int32_t)(k % kyz) % s.k[2]};
+            unsigned long long r[4];
+            bool inside = true;
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                // a position is below 2^62 and a step below 2^34: the sum stays inside int64
+                const int64_t p = (int64_t)f.rel(a, coords[vi * 3 + a]) + (int64_t)(ik[a] - (s.k[a] - 1) / 2) * s.d[a];
+                inside &= p >= 0 && (unsigned long long)p < f.span[a];
+                r[a] = (unsigned long long)p;
+            }
+            if (inside) {
+                r[3] = batch ? f.rel(3, batch[vi]) : 0ull;
+                const unsigned long long key = f.key(r);
+                unsigned long long h = nbr_hash(key, log2cap);
+                for (unsigned long long t = 0; t <= mask; t++, h = (h + 1) & mask) {
+                    const NbrSlot sl = slots[h];
+                    if (sl.key == key) {
+                        e = sl.row;
+                        break;
+                    }
+                    if (sl.key == kNbrEmpty) break;
+                }
+            }
+        }
+        table[vi * K + k] = e;
+        found += e >= 0;
+    }
+    const unsigned long long total = wave_sum_u64(found);
+    if (total && (threadIdx.x & (kWave - 1)) == 0) atomicAdd((unsigned long long *)&counts[0], total);
+}
+
+// ---------------------------------------------------------------- the gather
+template <typename T, int N> struct alignas(sizeof(T) * N) NbrPack { T v[N]; };
+
+// One lane group (1 << group_log2 lanes) per output row j = r * K + k, lane g of it on the VEC channels from g * VEC, then from
+// (g + group) * VEC, ...  The source row: feat[e] (feat_cols == 1) or feat[e, k] (feat_cols == K: feat is [V, K, C]), with
+// e = table[r, mirrored ? K - 1 - k : k]; a zero row for e == -1.
+template <typename T, int VEC>
+__global__ __launch_bounds__(kNbrThreads) void k_nbr_gather(const T *__restrict__ feat, const int32_t *__restrict__ table, int64_t rows,
+                                                            int32_t K, int32_t c, int32_t feat_cols, int32_t mirrored, int group_log2,
+                                                            int64_t nblk, T *__restrict__ out)
+{
+    typedef NbrPack<T, VEC> P;
+    const int per_block = kNbrThreads >> group_log2, g = (int)(threadIdx.x & ((1u << group_log2) - 1)), step = VEC << group_log2;
+    for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const int64_t j0 = blk * per_block, r0 = j0 / K;               // one 64-bit division per workgroup and trip
+        const uint32_t q = (uint32_t)(j0 - r0 * K) + (threadIdx.x >> group_log2);
+        const int64_t j = j0 + (threadIdx.x >> group_log2), r = r0 + q / (uint32_t)K;
+        const int32_t k = (int32_t)(q % (uint32_t)K);
+        if (j >= rows) continue;
+        const int32_t e = table[r * K + (mirrored ? K - 1 - k : k)];
+        const T *src = e >= 0 ? feat + ((int64_t)e * feat_cols + (feat_cols > 1 ? k : 0)) * c : nullptr;
+        T *dst = out + j * c;
+        for (int c0 = g * VEC; c0 < c; c0 += step) {
+            P o;
+#pragma unroll
+            for (int x = 0; x < VEC; x++) o.v[x] = 0;
+            if (src) o = *(const P *)(src + c0);
+            *(P *)(dst + c0) = o;
+        }
+    }
+}
+
+// the lane group of a row of c channels in units of vec: the smallest power of two >= ceil(c / vec), at most a wavefront
+int nbr_group_log2(int32_t c, int vec)
+{
+    const int64_t units = d3d_divup(c, vec);
+    int g = 0;
+    while (g < 6 && (1ll << g) < units) g++;
+    return g;
+}
+
+bool nbr_aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+
+bool nbr_shape_ok(const NbrShape &s)
+{
+    for (int a = 0; a < 3; a++)
+        if (s.k[a] < 1 || s.k[a] > 7 || s.k[a] % 2 == 0 || s.d[a] < 1) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" size_t d3d_voxel_neighbors_workspace_bytes(int64_t v)
+{
+    WsCarver w(nullptr, 0);
+    nbr_carve(w, std::min(std::max<int64_t>(v, 0), kNbrMaxV));
+    return w.off;
+}
+
+extern "C" int d3d_voxel_neighbors(const int64_t *coords, const int64_t *batch, int64_t v, int32_t kx, int32_t ky, int32_t kz, int32_t dx,
+                                   int32_t dy, int32_t dz, int32_t *table, int64_t *counts, void *workspace, size_t workspace_bytes,
+                                   void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const NbrShape s{{kx, ky, kz}, {dx, dy, dz}};
+    if (v < 0 || !counts || !nbr_shape_ok(s) || (v > 0 && (!coords || !table))) return D3D_ERR_BAD_ARG;
+    if (v > kNbrMaxV) return D3D_ERR_UNSUPPORTED;
+    WsCarver w(workspace, workspace_bytes);
+    const NbrWs ws = nbr_carve(w, v);
+    if (v > 0 && (!workspace || !w.ok())) return D3D_ERR_WORKSPACE;
+    D3D_HIP_CHECK(hipMemsetAsync(counts, 0, 3 * sizeof(int64_t), st));
+    if (v == 0) return D3D_OK;
+    D3D_HIP_CHECK(hipMemsetAsync(ws.bounds, 0, 8 * sizeof(unsigned long long), st));
+    D3D_HIP_CHECK(hipMemsetAsync(ws.slots, 0xff, sizeof(NbrSlot) << ws.log2cap, st));
+    const int64_t vb = d3d_divup(v, kNbrThreads), n = v * (int64_t)(kx * ky * kz);
+    D3D_LAUNCH("k_vn_bounds", k_vn_bounds, dim3((unsigned)std::min<int64_t>(vb, kNbrBoundsBlocks)), dim3(kNbrThreads), 0, st, coords, batch, v,
+               ws.bounds);
+    D3D_LAUNCH("k_vn_insert", k_vn_insert, dim3((unsigned)vb), dim3(kNbrThreads), 0, st, coords, batch, v, ws.bounds, ws.slots, ws.log2cap,
+               counts);
+    D3D_LAUNCH("k_vn_lookup", k_vn_lookup, dim3((unsigned)std::min(d3d_divup(n, kNbrThreads), kNbrLookupBlocks)), dim3(kNbrThreads), 0, st,
+               coords, batch, v, s, ws.bounds, ws.slots, ws.log2cap, table, counts);
+    return D3D_OK;
+}
+
+extern "C" int d3d_neighbor_gather(const void *feat, int64_t v, int32_t c, int32_t dtype, int32_t feat_cols, const int32_t *table, int64_t r,
+                                   int32_t k, int32_t mirrored, void *out, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (v < 0 || r < 0 || c < 1 || k < 1 || (feat_cols != 1 && feat_cols != k)) return D3D_ERR_BAD_ARG;
+    if ((dtype != D3D_F32 && dtype != D3D_F64) || v > kNbrMaxV || k > 343 || r > kNbrMaxV) return D3D_ERR_UNSUPPORTED;
+    if (r == 0) return D3D_OK;
+    if (!table || !out || (v > 0 && !feat)) return D3D_ERR_BAD_ARG;
+    return dispatch_dtype<D3D_F32, D3D_F64>(dtype, [&](auto p) {
+        typedef typename decltype(p)::T T;
+        constexpr int W = 16 / (int)sizeof(T);
+        const bool vec = c % W == 0 && nbr_aligned16(feat) && nbr_aligned16(out);
+        const int gl = nbr_group_log2(c, vec ? W : 1);
+        const int64_t rows = r * k, nblk = d3d_divup(rows, kNbrThreads >> gl);
+        return dispatch(vec, [&](auto wide) {
+            constexpr int VEC = decltype(wide)::value ? W : 1;
+            D3D_LAUNCH("k_nbr_gather", (k_nbr_gather<T, VEC>), dim3((unsigned)std::min(nblk, kNbrGatherBlocks)), dim3(kNbrThreads), 0, st,
+                       (const T *)feat, table, rows, k, c, feat_cols, mirrored, gl, nblk, (T *)out);
+            return D3D_OK;
+        });
+    });
+}

@@ -1,0 +1,304 @@
+"""d3d_amd.voxel.conv -- submanifold sparse convolution on the voxelizer's output: the neighbour table of the active voxels, the
+gather of the neighbours' rows and the convolution built from them, all differentiable: what every voxel backbone (SECOND,
+CenterPoint, PV-RCNN, sparse U-Nets) opens with.  An extension (the reference stops at the voxelizer).
+
+    sp   = VoxelGenerator(bounds, shape, max_points=32, max_points_filter="trim")(pts)    # sparse contract
+    vf   = voxel_pool(mlp(sp.points), VoxelIndex(sp.points_mapping, len(sp.coords)))     # [V, C]
+    nbrs = VoxelNeighbors(sp.coords, kernel_size=3)              # once per frame; every layer and every backward reuses it
+    y    = subm_conv3d(vf, nbrs, weight, bias)                   # [V, Cout], weight [27, C, Cout]
+
+The neighbour relation is symmetric (table[v, k] == u <=> table[u, K-1-k] == v), so the gradient of a gather through the table is
+the gather through the mirrored columns: forward and backward are gathers and GEMMs, nothing is scattered, no float atomics of the
+library's own (kernels and the exact rules: csrc/vnbr.hip, include/d3d_hip.h; the GEMMs are torch's).
+"""
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from .. import _lib
+from .pool import _as_tensor, _dtype_code
+
+_MAX_VOXELS = 2 ** 31 - 1
+_SPAN_LIMIT = 2 ** 62
+_GATHER_BYTES = 1 << 30           # what the default chunk_rows lets one gathered buffer take
+_GEMM_TILE_BYTES = 1 << 28        # the gathered rows of one GEMM call
+_GEMM_TILE_ROWS = (1024, 65536)
+
+
+def _triple(x, what):
+    t = tuple(x) if isinstance(x, (tuple, list)) else (x, x, x)
+    if len(t) != 3 or any(isinstance(a, bool) or not isinstance(a, (int, np.integer)) for a in t):
+        raise ValueError("%s must be an int or three ints, not %r" % (what, x))
+    return tuple(int(a) for a in t)
+
+
+def _host_spans_fit(coords, batch):
+    """host inputs: the span product the device would measure, before anything is copied"""
+    span = 1
+    for col in ([coords[:, a] for a in range(3)] + ([batch] if batch is not None else [])):
+        span *= int(col.max()) - int(col.min()) + 1
+    return span <= _SPAN_LIMIT
+
+
+class VoxelNeighbors:
+    """The neighbour table of one frame's active voxels.
+
+    :param coords: [V, 3] int64 (int32 is widened) voxel coordinates, any values (negative, offset); torch tensor (GPU or host)
+        or numpy array.  (batch, coordinate) must be unique
+    :param kernel_size: an odd int in 1 .. 7, or three of them
+    :param dilation: an int >= 1, or three of them
+    :param batch_index: [V] int64 / int32 or None; voxels of different batch values are never neighbours
+
+    Holds `table` [V, K] int32 on the GPU, K = kx * ky * kz: column k = (ix * ky + iy) * kz + iz is the row of the voxel at
+    coords[v] + ((ix, iy, iz) - (k* - 1) / 2) * dilation, -1 where there is none; `kernel_size`, `dilation`, `num_voxels` and
+    `num_entries` (the entries >= 0).  Building it reads three numbers back, once.  ValueError on duplicates and when the product
+    of the coordinate (and batch) spans exceeds 2^62."""
+
+    def __init__(self, coords, kernel_size=3, dilation=1, batch_index=None):
+        coords, _ = _as_tensor(coords, "coords")
+        if coords.dim() != 2 or coords.shape[1] != 3:
+            raise ValueError("coords must be a [V, 3] tensor of voxel coordinates")
+        if coords.dtype not in (torch.int64, torch.int32):
+            raise ValueError("coords must be int64 or int32, not %s" % coords.dtype)
+        v = coords.shape[0]
+        if batch_index is not None:
+            batch_index, _ = _as_tensor(batch_index, "batch_index")
+            if batch_index.dim() != 1 or batch_index.shape[0] != v:
+                raise ValueError("batch_index must be a [V] tensor, one value per row of coords")
+            if batch_index.dtype not in (torch.int64, torch.int32):
+                raise ValueError("batch_index must be int64 or int32, not %s" % batch_index.dtype)
+        ks, dil = _triple(kernel_size, "kernel_size"), _triple(dilation, "dilation")
+        if any(k < 1 or k > 7 or k % 2 == 0 for k in ks):
+            raise ValueError("kernel_size must be odd and in 1 .. 7, not %r" % (kernel_size,))
+        if any(d < 1 or d >= 2 ** 31 for d in dil):
+            raise ValueError("dilation must be at least 1, not %r" % (dilation,))
+        if v > _MAX_VOXELS:
+            raise ValueError("VoxelNeighbors takes at most 2^31 - 1 voxels")
+        overflow = "the spans of the coordinates (and batch values) multiply to more than 2^62"
+        if v and not coords.is_cuda and not _host_spans_fit(coords, None if batch_index is None or batch_index.is_cuda else batch_index):
+            raise ValueError(overflow)
+        dev = coords.device if coords.is_cuda else _lib.require_gpu()
+        k = ks[0] * ks[1] * ks[2]
+        self.device, self.num_voxels, self.kernel_size, self.dilation, self.kernel_volume = dev, v, ks, dil, k
+        coords = coords.to(device=dev, dtype=torch.int64).contiguous()
+        batch = None if batch_index is None else batch_index.to(device=dev, dtype=torch.int64).contiguous()
+        with torch.cuda.device(dev):
+            self.table = torch.empty((v, k), dtype=torch.int32, device=dev)
+            entries = dups = over = 0
+            if v:
+                lib = _lib.load()
+                counts = torch.empty((3,), dtype=torch.int64, device=dev)
+                ws = _lib.workspace(lib.d3d_voxel_neighbors_workspace_bytes(v), dev)
+                rc = lib.d3d_voxel_neighbors(_lib.ptr(coords), _lib.ptr(batch), v, ks[0], ks[1], ks[2], dil[0], dil[1], dil[2],
+                                             _lib.ptr(self.table), _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+                _lib.check(rc, "voxel_neighbors")
+                entries, dups, over = counts.tolist()            # the one read-back of a frame's table
+        if over:
+            raise ValueError(overflow)
+        if dups:
+            raise ValueError("coords holds %d rows whose (batch, coordinate) an earlier row already has" % dups)
+        self.num_entries = entries
+
+    def _on(self, t):
+        if t.is_cuda and t.device != self.device:
+            raise ValueError("features live on %s, the VoxelNeighbors on %s" % (t.device, self.device))
+
+
+def _gather(feat, nbrs, mirrored, v0=0, rows=None, feat_cols=1, out=None):
+    """feat [V, C] (or [V, K, C] with feat_cols = K) on nbrs.device -> [rows, K, C] for the rows v0 .. v0 + rows of the table (into
+    `out`, contiguous and of that many elements, when given); one launch, every output row written once"""
+    k, c = nbrs.kernel_volume, feat.shape[-1]
+    rows = nbrs.num_voxels - v0 if rows is None else rows
+    with torch.cuda.device(nbrs.device):
+        if rows == 0 or c == 0:
+            return feat.new_zeros((rows, k, c)) if out is None else out
+        if out is None:
+            out = torch.empty((rows, k, c), dtype=feat.dtype, device=nbrs.device)
+        rc = _lib.load().d3d_neighbor_gather(_lib.ptr(feat), nbrs.num_voxels, c, _dtype_code(feat), feat_cols, _lib.ptr(nbrs.table[v0:]),
+                                             rows, k, int(mirrored), _lib.ptr(out), _lib.stream_ptr())
+    _lib.check(rc, "neighbor_gather")
+    return out
+
+
+class NeighborGather(torch.autograd.Function):
+    """neighbor_gather: (features [V, C], VoxelNeighbors) -> [V, K, C], one launch.  backward: the mirrored gather of the gradient
+    (row [table[u, K-1-k], k] of it for every (u, k)), then the sum over k in ascending k.  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, features, nbrs):
+        ctx.nbrs, ctx.odev = nbrs, features.device
+        out = _gather(features.detach().to(nbrs.device).contiguous(), nbrs, False)
+        return _lib.to_caller(out, ctx.odev, nbrs.device)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        nbrs = ctx.nbrs
+        g = _gather(grad.to(nbrs.device).contiguous(), nbrs, True, feat_cols=nbrs.kernel_volume)
+        acc = g[:, 0].clone()
+        for k in range(1, nbrs.kernel_volume):                   # a fixed left fold: the same bits on every run
+            acc += g[:, k]
+        return _lib.to_caller(acc, ctx.odev, nbrs.device), None
+
+
+def _chunks(v, chunk_rows):
+    return [(v0, min(chunk_rows, v - v0)) for v0 in range(0, v, chunk_rows)]
+
+
+def _gemm_rows(row_bytes, v):
+    """the rows of every GEMM call for gathered rows of `row_bytes` on a frame of v voxels: a power of two that keeps a call's
+    gathered rows at about 256 MiB, between 1024 and 65536, and no more than the power of two that covers the frame.  It depends on
+    the row and on V -- not on chunk_rows"""
+    g = _GEMM_TILE_ROWS[0]
+    while g < _GEMM_TILE_ROWS[1] and 2 * g * max(row_bytes, 1) <= _GEMM_TILE_BYTES:
+        g *= 2
+    while g > 1 and g // 2 >= v:
+        g //= 2
+    return g
+
+
+def _gather_times(feat, nbrs, mirrored, v0, r, mat, out):
+    """out[v0 : v0 + r] = (the gathered rows [r, K * C] of the table's rows v0 .. v0 + r) @ mat.
+    Every GEMM call has exactly _gemm_rows(..) rows, the last one of the frame padded with zero rows: torch.matmul picks its kernel,
+    and with it the order of a row's additions, by the shape of the call.  Measured on an MI355X: the same rows differ in the last
+    bits between calls of 4097 and of 1000 rows, in fp32 and fp64, while inside calls of one shape a row's bits depended neither on
+    its position nor on the other rows (an observation about torch's GEMM, not a guarantee of it).  With one shape for every call a
+    row's result does not depend on chunk_rows."""
+    kc = nbrs.kernel_volume * feat.shape[1]
+    tile = _gemm_rows(kc * feat.element_size(), nbrs.num_voxels)
+    padded = -(-r // tile) * tile
+    buf = torch.empty((padded, kc), dtype=feat.dtype, device=nbrs.device)
+    _gather(feat, nbrs, mirrored, v0, r, out=buf[:r])
+    buf[r:].zero_()
+    for t0 in range(0, r, tile):
+        n = min(tile, r - t0)
+        out[v0 + t0:v0 + t0 + n] = torch.matmul(buf[t0:t0 + tile], mat)[:n]
+
+
+def _chunk_rows(chunk_rows, nbrs, cin, cout, itemsize):
+    """the rows per gather step: what the caller asked for (default: a gathered buffer of about 1 GiB), rounded UP to whole GEMM
+    calls of the wider of the two gathers -- a buffer holds at least one call's rows anyway, so a smaller step would only pad every
+    step to that size and multiply zero rows"""
+    k = nbrs.kernel_volume
+    if chunk_rows is None:
+        chunk_rows = max(1, _GATHER_BYTES // (k * max(cin, cout, 1) * itemsize))
+    tile = max(_gemm_rows(k * cin * itemsize, nbrs.num_voxels), _gemm_rows(k * cout * itemsize, nbrs.num_voxels))
+    return -(-chunk_rows // tile) * tile
+
+
+class SubmConv3d(torch.autograd.Function):
+    """subm_conv3d: per chunk of rows one gather [R, K * Cin] and GEMMs of a fixed row count with weight [K * Cin, Cout] (see
+    _gather_times).  backward: grad_features = the mirrored gather of grad_out [R, K * Cout] times weight^T [K * Cout, Cin];
+    grad_weight = the sum over the chunks, in chunk order, of gathered^T @ grad_out (the gather is made again, not kept); grad_bias =
+    the column sum.  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, features, nbrs, weight, bias, chunk_rows):
+        dev, odev = nbrs.device, features.device
+        k, cin, cout = weight.shape
+        f = features.detach().to(dev).contiguous()
+        w = weight.detach().to(dev).contiguous()
+        with torch.cuda.device(dev):
+            out = torch.empty((nbrs.num_voxels, cout), dtype=f.dtype, device=dev)
+            for v0, r in _chunks(nbrs.num_voxels, chunk_rows):
+                _gather_times(f, nbrs, False, v0, r, w.view(k * cin, cout), out)
+            if bias is not None:
+                out += bias.detach().to(dev)
+        ctx.nbrs, ctx.chunk_rows, ctx.odev, ctx.has_bias = nbrs, chunk_rows, odev, bias is not None
+        ctx.wdev, ctx.bdev = weight.device, bias.device if bias is not None else None
+        ctx.save_for_backward(f, w)
+        return _lib.to_caller(out, odev, dev)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        f, w = ctx.saved_tensors
+        nbrs, dev = ctx.nbrs, ctx.nbrs.device
+        k, cin, cout = w.shape
+        g = grad.to(dev).contiguous()
+        need_f, _, need_w, need_b, _ = ctx.needs_input_grad
+        gf = gw = gb = None
+        with torch.cuda.device(dev):
+            if need_f:
+                gf = torch.empty_like(f)
+                wt = w.transpose(1, 2).reshape(k * cout, cin)
+            if need_w:
+                gw = torch.zeros((k * cin, cout), dtype=w.dtype, device=dev)
+            for v0, r in _chunks(nbrs.num_voxels, ctx.chunk_rows):
+                if need_f:
+                    _gather_times(g, nbrs, True, v0, r, wt, gf)
+                if need_w:
+                    gw += torch.matmul(_gather(f, nbrs, False, v0, r).view(r, k * cin).t(), g[v0:v0 + r])
+            if ctx.has_bias and need_b:
+                gb = g.sum(0)
+        if need_f:
+            gf = _lib.to_caller(gf, ctx.odev, dev)
+        if need_w:
+            gw = _lib.to_caller(gw.view(k, cin, cout), ctx.wdev, dev)
+        if gb is not None:
+            gb = _lib.to_caller(gb, ctx.bdev, dev)
+        return gf, None, gw, gb, None
+
+
+def _check_rows(t, nbrs, what):
+    if t.dim() != 2:
+        raise ValueError("%s must be a 2-D tensor of one row per voxel" % what)
+    _dtype_code(t)
+    if t.shape[0] != nbrs.num_voxels:
+        raise ValueError("%s has %d rows, the VoxelNeighbors %d voxels" % (what, t.shape[0], nbrs.num_voxels))
+    nbrs._on(t)
+
+
+def neighbor_gather(features, nbrs):
+    """The rows of every voxel's neighbours, side by side.
+
+    :param features: [V, C] float32 or float64, torch tensor (GPU or host) or numpy array; differentiable (once)
+    :param nbrs: the frame's VoxelNeighbors
+    :return: [V, K, C] on the caller's side: row [v, k] = features[table[v, k]], zero where table[v, k] == -1.  Its gradient is
+        grad_features[u] = grad[table[u, K-1], 0] + grad[table[u, K-2], 1] + ... in that order (absent neighbours add +0)
+    """
+    if not isinstance(nbrs, VoxelNeighbors):
+        raise TypeError("nbrs must be a VoxelNeighbors")
+    features, was_numpy = _as_tensor(features, "features")
+    _check_rows(features, nbrs, "features")
+    out = NeighborGather.apply(features, nbrs)
+    return out.numpy() if was_numpy else out
+
+
+def subm_conv3d(features, nbrs, weight, bias=None, chunk_rows=None):
+    """Submanifold sparse convolution: out[v] = sum over k of features[table[v, k]] @ weight[k] (+ bias), on the active voxels only.
+
+    :param features: [V, Cin] float32 or float64, torch tensor (GPU or host) or numpy array; differentiable (once)
+    :param nbrs: the frame's VoxelNeighbors (its kernel size and dilation are the convolution's)
+    :param weight: [K, Cin, Cout] in the dtype of features, K = nbrs' kernel volume in the table's column order (a dense
+        conv3d weight [Cout, Cin, kx, ky, kz] is weight.permute(2, 3, 4, 1, 0).reshape(K, Cin, Cout)); differentiable
+    :param bias: [Cout] or None; differentiable
+    :param chunk_rows: voxels per gather step, rounded up to whole GEMM calls; the default keeps one gathered buffer at about 1 GiB.
+        Every GEMM call has the same row count (min(65536, a power of two covering V), fewer for rows beyond 4 KiB: about 256 MiB
+        of gathered rows at most), the last call of the frame padded with zero rows, so that a row of the result and of
+        grad_features does not depend on chunk_rows (measured, see _gather_times); a gathered buffer is at least one call's rows
+    :return: [V, Cout] on the side features came from
+    """
+    if not isinstance(nbrs, VoxelNeighbors):
+        raise TypeError("nbrs must be a VoxelNeighbors")
+    features, was_numpy = _as_tensor(features, "features")
+    weight, _ = _as_tensor(weight, "weight")
+    _check_rows(features, nbrs, "features")
+    if weight.dim() != 3 or weight.shape[0] != nbrs.kernel_volume or weight.shape[1] != features.shape[1]:
+        raise ValueError("weight must be [K, Cin, Cout] = [%d, %d, Cout], not %s" % (nbrs.kernel_volume, features.shape[1], tuple(weight.shape)))
+    if weight.dtype != features.dtype:
+        raise ValueError("weight is %s, features %s" % (weight.dtype, features.dtype))
+    if bias is not None:
+        bias, _ = _as_tensor(bias, "bias")
+        if bias.dim() != 1 or bias.shape[0] != weight.shape[2] or bias.dtype != features.dtype:
+            raise ValueError("bias must be [Cout] = [%d] in the dtype of features" % weight.shape[2])
+    if chunk_rows is not None:
+        chunk_rows = int(chunk_rows)
+        if chunk_rows < 1:
+            raise ValueError("chunk_rows must be at least 1")
+    chunk_rows = _chunk_rows(chunk_rows, nbrs, weight.shape[1], weight.shape[2], features.element_size())
+    out = SubmConv3d.apply(features, nbrs, weight, bias, chunk_rows)
+    return out.detach().numpy() if was_numpy else out
+
+
+__all__ = ["VoxelNeighbors", "neighbor_gather", "subm_conv3d", "NeighborGather", "SubmConv3d"]

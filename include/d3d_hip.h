@@ -949,6 +949,40 @@ int d3d_voxel_pool_forward(const void *feat, int64_t k, int32_t c, int32_t dtype
 int d3d_voxel_pool_backward(const void *grad_out, int64_t v, int32_t c, int32_t dtype, const int64_t *mapping, int64_t k,
                             const int64_t *offsets, int32_t reduction, const int32_t *arg, void *grad_feat, void *stream);
 
+/* ------------------------------------------------------------------ voxel neighbours and the row gather through them (an extension) */
+
+/* What a submanifold sparse convolution needs before its GEMM: for every active voxel the rows of its active neighbours, and the
+ * neighbours' feature rows side by side.  No float atomics; the reference has no counterpart.
+ *
+ * d3d_voxel_neighbors: coords[v, 3] int64 and batch[v] int64 (may be NULL: one batch) -> table[v, K] int32, K = kx * ky * kz, every
+ *   k* odd in 1 .. 7, every d* (dilation) >= 1.  Column k = (ix * ky + iy) * kz + iz holds the row of the voxel at
+ *   coords[r] + ((ix, iy, iz) - (k* - 1) / 2) * d* with the same batch value, or -1 when there is none: column K - 1 - k is the
+ *   opposite offset, the centre column (K - 1) / 2 is r itself, and table[r, k] == u <=> table[u, K - 1 - k] == r.
+ *   Any int64 coordinates: the bounds of every axis and of the batch value are measured on the device, one 64-bit mixed-radix key
+ *   per voxel is formed over those spans, and a neighbour outside the measured box is absent without a look-up (a shifted key never
+ *   aliases another row).  When the product of the four spans exceeds 2^62, counts[2] = 1: the launches that follow the
+ *   measurement see it and return at once, table is left untouched.
+ *   counts[3]: [0] the entries >= 0 of the table, centres included; [1] the rows whose (batch, coordinate) an earlier-inserted row
+ *   already had -- with duplicates the table is unspecified, but every entry stays in [-1, v) and nothing is accessed out of range;
+ *   [2] the span overflow flag.  v == 0: counts zeroed, nothing launched.  Launches: bounds, insert (integer atomicCAS into an
+ *   open-addressing table of a power-of-two capacity >= 2 v in the caller's workspace), lookup (one lane per entry); the table does
+ *   not depend on the insertion order: the same on every run.
+ * d3d_neighbor_gather: feat[v, c] (D3D_F32 / D3D_F64, c >= 1) and table[r, k] -> out[r, k, c]: out[i, j, :] = feat[e, :] with
+ *   e = table[i, mirrored ? k - 1 - j : j], a zero row where e == -1; every output row is written exactly once.  feat_cols = 1, or
+ *   = k for a feat of [v, k, c], of which row [e, j, :] is taken (with `mirrored` this is the gradient of the plain gather before
+ *   its sum over j).  table may be any row range of a larger table (table + r0 * k); its entries are trusted to be in [-1, v).
+ *   Rows move as 16-byte vectors when c is a multiple of 4 (f32) / 2 (f64) and feat and out are 16-byte aligned, element by element
+ *   otherwise.  Offsets are 64-bit: r * k * c may pass 2^31.
+ * D3D_ERR_BAD_ARG: a negative size, an even or out-of-range kernel size, a dilation < 1, c < 1, a feat_cols other than 1 or k, a
+ *   missing pointer; D3D_ERR_WORKSPACE: workspace missing or smaller than the query; D3D_ERR_UNSUPPORTED: v or r above 2^31 - 1,
+ *   k above 343, another dtype.  None of these refusals launches anything.  (A span overflow is not a refusal: the entry returns
+ *   D3D_OK, its insert and lookup launches run, find the flag and return at once.) */
+size_t d3d_voxel_neighbors_workspace_bytes(int64_t v);
+int d3d_voxel_neighbors(const int64_t *coords, const int64_t *batch, int64_t v, int32_t kx, int32_t ky, int32_t kz, int32_t dx, int32_t dy,
+                        int32_t dz, int32_t *table, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+int d3d_neighbor_gather(const void *feat, int64_t v, int32_t c, int32_t dtype, int32_t feat_cols, const int32_t *table, int64_t r, int32_t k,
+                        int32_t mirrored, void *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
