@@ -157,6 +157,10 @@ SIGNATURES = {
     "d3d_voxel_neighbors_workspace_bytes": (_sz, [_i64]),
     "d3d_voxel_neighbors": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "d3d_neighbor_gather": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp]),
+    # (kernel_size, stride, padding, dilation: host int32[3]; spatial_shape: host int64[3] or NULL)
+    "d3d_sparse_conv_map_workspace_bytes": (_sz, [_i64, _vp, _vp, _vp]),
+    "d3d_sparse_conv_map_count": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3d_sparse_conv_map_emit": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -6,7 +6,8 @@
 //   d3d_neighbor_gather  feat[V,C], table[R,K]    -> out[R,K,C]: the neighbours' rows side by side, a zero row where there is none
 //
 // The table: three launches, every dependency a kernel boundary (no workgroup waits on another inside a launch).
-//   k_vn_bounds  min / max of every axis and of the batch value: integer atomicMax, one per wavefront and quantity
+//   k_vn_bounds  min / max of every axis and of the batch value: integer atomicMax, one per wavefront and quantity (vkey.hpp: shared
+//                with vstride.hip, as the hash is)
 //   k_vn_insert  key = mixed radix over the measured spans (one 64-bit number per voxel, below 2^62) into an open-addressing table
 //                (power-of-two capacity >= 2V, linear probing, {key, row} in one 16-byte slot): atomicCAS on the key, the winner
 //                stores its row; an equal key already there is a duplicate
@@ -17,19 +18,13 @@
 // The relation is symmetric -- table[v,k] == u <=> table[u,K-1-k] == v -- so the gradient of "gather my neighbours' rows" is the
 // gather through the mirrored columns: forward and backward are gathers, nothing is scattered, no float atomics.
 #include <algorithm>
-#include "common.hpp"
+#include "vkey.hpp"
 
 namespace {
 
-constexpr int kNbrThreads = 256;
-constexpr int kNbrBoundsBlocks = 1024;                 // grid-stride: 8 atomics per wavefront, 32 k in all at most
 constexpr int64_t kNbrLookupBlocks = 1ll << 24;
 constexpr int64_t kNbrGatherBlocks = 1ll << 30;
 constexpr int64_t kNbrMaxV = 0x7fffffffll;             // rows are int32
-constexpr unsigned long long kNbrEmpty = ~0ull;        // (keys stay below 2^62)
-constexpr unsigned long long kNbrSpanLimit = 1ull << 62;
-constexpr unsigned long long kNbrSign = 1ull << 63;    // x ^ sign: int64 -> uint64, order kept
-constexpr unsigned long long kNbrMix = 0x9e3779b97f4a7c15ull;
 
 struct alignas(16) NbrSlot {
     unsigned long long key;
@@ -84,38 +79,6 @@ __device__ __forceinline__ NbrFrame nbr_frame(const unsigned long long *__restri
     }
     return f;
 }
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long x)
-{
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) {
-        const unsigned long long y = __shfl_xor(x, d, kWave);
-        x = y > x ? y : x;
-    }
-    return x;
-}
-
-__global__ __launch_bounds__(kNbrThreads) void k_vn_bounds(const int64_t *__restrict__ coords, const int64_t *__restrict__ batch, int64_t v,
-                                                           unsigned long long *__restrict__ bounds)
-{
-    unsigned long long m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int64_t i = (int64_t)blockIdx.x * kNbrThreads + threadIdx.x; i < v; i += (int64_t)gridDim.x * kNbrThreads) {
-#pragma unroll
-        for (int a = 0; a < 4; a++) {
-            if (a == 3 && !batch) continue;
-            const unsigned long long u = (unsigned long long)(a < 3 ? coords[i * 3 + a] : batch[i]) ^ kNbrSign;
-            m[2 * a] = u > m[2 * a] ? u : m[2 * a];
-            m[2 * a + 1] = ~u > m[2 * a + 1] ? ~u : m[2 * a + 1];
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        const unsigned long long w = wave_max_u64(m[q]);
-        if ((threadIdx.x & (kWave - 1)) == 0 && w) atomicMax(&bounds[q], w);
-    }
-}
-
-__device__ __forceinline__ unsigned long long nbr_hash(unsigned long long key, int log2cap) { return (key * kNbrMix) >> (64 - log2cap); }
 
 __global__ __launch_bounds__(kNbrThreads) void k_vn_insert(const int64_t *__restrict__ coords, const int64_t *__restrict__ batch, int64_t v,
                                                            const unsigned long long *__restrict__ bounds, NbrSlot *__restrict__ slots,

@@ -99,14 +99,28 @@ class VoxelNeighbors:
             raise ValueError("coords holds %d rows whose (batch, coordinate) an earlier row already has" % dups)
         self.num_entries = entries
 
+    @property
+    def src_rows(self):
+        """the rows the table's entries point into: the voxels themselves"""
+        return self.num_voxels
+
     def _on(self, t):
         if t.is_cuda and t.device != self.device:
             raise ValueError("features live on %s, the VoxelNeighbors on %s" % (t.device, self.device))
 
 
+class _TableView:
+    """what _gather, _gather_times and _chunk_rows read of a VoxelNeighbors, for any table [num_voxels, K] whose entries point into
+    src_rows feature rows (the two tables of a SparseConvMap)"""
+
+    def __init__(self, table, src_rows, kernel_volume, device):
+        self.table, self.num_voxels, self.src_rows, self.kernel_volume, self.device = table, table.shape[0], src_rows, kernel_volume, device
+
+
 def _gather(feat, nbrs, mirrored, v0=0, rows=None, feat_cols=1, out=None):
     """feat [V, C] (or [V, K, C] with feat_cols = K) on nbrs.device -> [rows, K, C] for the rows v0 .. v0 + rows of the table (into
-    `out`, contiguous and of that many elements, when given); one launch, every output row written once"""
+    `out`, contiguous and of that many elements, when given); one launch, every output row written once.  nbrs: a VoxelNeighbors or
+    a _TableView (V = nbrs.src_rows, the table has nbrs.num_voxels rows)"""
     k, c = nbrs.kernel_volume, feat.shape[-1]
     rows = nbrs.num_voxels - v0 if rows is None else rows
     with torch.cuda.device(nbrs.device):
@@ -114,7 +128,7 @@ def _gather(feat, nbrs, mirrored, v0=0, rows=None, feat_cols=1, out=None):
             return feat.new_zeros((rows, k, c)) if out is None else out
         if out is None:
             out = torch.empty((rows, k, c), dtype=feat.dtype, device=nbrs.device)
-        rc = _lib.load().d3d_neighbor_gather(_lib.ptr(feat), nbrs.num_voxels, c, _dtype_code(feat), feat_cols, _lib.ptr(nbrs.table[v0:]),
+        rc = _lib.load().d3d_neighbor_gather(_lib.ptr(feat), nbrs.src_rows, c, _dtype_code(feat), feat_cols, _lib.ptr(nbrs.table[v0:]),
                                              rows, k, int(mirrored), _lib.ptr(out), _lib.stream_ptr())
     _lib.check(rc, "neighbor_gather")
     return out

@@ -983,6 +983,62 @@ int d3d_voxel_neighbors(const int64_t *coords, const int64_t *batch, int64_t v, 
 int d3d_neighbor_gather(const void *feat, int64_t v, int32_t c, int32_t dtype, int32_t feat_cols, const int32_t *table, int64_t r, int32_t k,
                         int32_t mirrored, void *out, void *stream);
 
+/* ------------------------------------------------------------------ the map of a strided sparse convolution (an extension) */
+
+/* From the active input voxels to the active OUTPUT voxels of a convolution with kernel size k, stride s, padding p and dilation d
+ * per axis (spconv's SparseConv3d / SparseInverseConv3d), and the two tables that relate their rows.  kernel_size, stride, padding,
+ * dilation: three host int32 each (x, y, z); k in 1 .. 7 (even sizes too), s and d in 1 .. 2^24, p in 0 .. 2^24.  K = kx ky kz,
+ * column k = (ix ky + iy) kz + iz as in d3d_voxel_neighbors, the offsets uncentred.
+ *
+ * The map: input i feeds output o through column (ix, iy, iz) when o * s - p + (ix, iy, iz) * d == i on every axis, i.e. when
+ *   i + p - (ix, iy, iz) * d is divisible by s (mathematical modulo: negative coordinates floor) and o is the quotient.  An output is
+ *   active iff at least one input feeds it; voxels of different batch values never meet.  A pair (v, k) that has an output is a
+ *   candidate, numbered v K + k; OUTPUT ROWS ARE NUMBERED IN THE ORDER OF THEIR FIRST CANDIDATE (the reference voxelizer's
+ *   first-seen rule): deterministic, a function of the input alone.
+ *     table_out[r, k] == v  : output row r reads input row v through column k;   -1: none
+ *     table_in[v, k]  == r  : holds exactly when table_out[r, k] == v;           -1: (v, k) is no candidate
+ *   so the convolution, its gradient and the inverse convolution are all d3d_neighbor_gather with mirrored = 0 through one of the
+ *   two tables (out[r] = sum_k feat[table_out[r,k]] W[k]; grad_feat[v] = sum_k grad_out[table_in[v,k]] W[k]^T).
+ * spatial_shape: NULL, or three host int64 (X, Y, Z), each in 1 .. 2^31 - 1.  When given, outputs are kept only for
+ *   0 <= o < floor((S + 2 p - d (k - 1) - 1) / s) + 1 (dense conv3d's output size; below 1 on an axis: D3D_ERR_BAD_ARG), and an
+ *   input outside [0, S) sets counts[4] = 1.  When NULL every output with a non-empty receptive field is active.
+ * Any int64 coordinates: the bounds of the input are measured on the device, the output box is derived from them (and clipped by
+ *   spatial_shape), and one 64-bit mixed-radix key per output is formed over the spans of that box and of the batch value.
+ *   counts[3] = 1 (span overflow) when those spans multiply to more than 2^62, or when the inputs span 2^62 or more on an axis (the
+ *   box arithmetic needs that headroom).  With counts[3] or counts[4] set every later launch of both entries returns at once:
+ *   counts[0] = counts[1] = 0 and nothing but counts and the workspace is written.
+ *
+ * Two entries with ONE host read between them (only the device knows Vout):
+ * d3d_sparse_conv_map_count: coords[v, 3] int64, batch[v] int64 (may be NULL) -> counts[5] int64: [0] Vout, [1] the entries >= 0 of
+ *   either table (the same number), [2] 0, [3] span overflow, [4] an input outside spatial_shape.  Launches: bounds, frame (one
+ *   lane: the box, the verdicts), clear, insert (one lane per (v, k): integer atomicCAS of the output's key into an
+ *   open-addressing table, then a 64-bit integer atomicMin of the candidate number on the slot's second word -- the winner is the
+ *   first candidate whatever order the lanes arrive in), and the count half of a scan over the marks "first of its slot".
+ * d3d_sparse_conv_map_emit: the same inputs and the SAME workspace, untouched since _count; num_out = counts[0] as read by the host
+ *   -> out_coords[num_out, 3] int64, out_batch[num_out] int64 (ignored when batch is NULL), table_in[v, K] int32,
+ *   table_out[num_out, K] int32, and counts[2] += the failed claims.  Launches: the scan's apply half (the first candidates write
+ *   out_coords, out_batch and their row into their slot), then one lane per (v, k), the column fastest: table_in[v, k] = row or -1
+ *   (contiguous stores), and the claim of table_out[row, k] (prefilled with -1) by an integer atomicCAS -1 -> v.  A failed claim
+ *   means two inputs share (batch, coordinate): (batch, coordinate) must be unique, counts[2] > 0 is how a violation shows (for
+ *   inputs that feed at least one output; others are not examined).  Even then, and with a num_out smaller than counts[0] (rows
+ *   from num_out on are dropped), every entry of table_in stays in [-1, num_out) and of table_out in [-1, v).  Integer atomics
+ *   only; the same bits on every run.  v == 0: counts zeroed / nothing written, nothing launched.
+ * Workspace (d3d_sparse_conv_map_workspace_bytes; 0 for arguments the entries refuse): 256 B of bounds, 256 B of frame, 16 B x C
+ *   slots with C the smallest power of two >= max(64, 2 v P), and 8 B per 1024 candidates numbers (v K / 1024, rounded up to 256 B):
+ *   O(v P), where P = the product over the axes of ceil(k / (s / gcd(s, d))) is the largest number of outputs one input can feed
+ *   (v P bounds Vout).  The launches use the smallest power of two >= max(64, 2 min(v P, cells of the output box)) of those slots.
+ * D3D_ERR_BAD_ARG: a negative size, a kernel size outside 1 .. 7, s or d < 1, p < 0, a spatial_shape below 1 or without a dense
+ *   output, a missing pointer, num_out < 0 or > v P; D3D_ERR_UNSUPPORTED: s, p or d above 2^24, a spatial_shape above 2^31 - 1,
+ *   v P above 2^31 - 1; D3D_ERR_WORKSPACE: workspace missing or smaller than the query.  None of these launches anything. */
+size_t d3d_sparse_conv_map_workspace_bytes(int64_t v, const int32_t *kernel_size, const int32_t *stride, const int32_t *dilation);
+int d3d_sparse_conv_map_count(const int64_t *coords, const int64_t *batch, int64_t v, const int32_t *kernel_size, const int32_t *stride,
+                              const int32_t *padding, const int32_t *dilation, const int64_t *spatial_shape, int64_t *counts,
+                              void *workspace, size_t workspace_bytes, void *stream);
+int d3d_sparse_conv_map_emit(const int64_t *coords, const int64_t *batch, int64_t v, const int32_t *kernel_size, const int32_t *stride,
+                             const int32_t *padding, const int32_t *dilation, const int64_t *spatial_shape, int64_t num_out,
+                             int64_t *out_coords, int64_t *out_batch, int32_t *table_in, int32_t *table_out, int64_t *counts,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
