@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libd3d_hip.so")
 OK, ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_WORKSPACE, ERR_HIP = 0, -1, -2, -3, -4
 COUNT_VOXELS, COUNT_POINTS, COUNT_STATUS, COUNT_AUX, NUM_COUNTS = 0, 1, 2, 3, 4
 STATUS_COORD_OVERFLOW, STATUS_TABLE_FULL, STATUS_PACK_OVERFLOW, STATUS_BIN_OVERFLOW = 1, 2, 4, 8
-F32, F64, F64_M32, F32_WIDE = 0, 1, 2, 3      # (F64_M32: d3d_iou2d_forward / _backward -- fp64 boxes and arithmetic, fp32 [n,m] matrix)
+F32, F64, F64_M32, F32_WIDE, F16, BF16 = 0, 1, 2, 3, 4, 5      # (F64_M32: d3d_iou2d_forward / _backward -- fp64 boxes and arithmetic, fp32 [n,m] matrix)
 # per-call option bits (include/d3d_hip.h)
 VOXEL_PATH_HASH, VOXEL_PARTITION_3PASS, VOXEL_PLAIN_SLOTS, VOXEL_SPLIT_FILL, VOXEL_EXACT_MEAN, VOXEL_WIDE_KEYS = 1, 2, 4, 8, 16, 64
 OWNER_MERGE_CHAINS, OWNER_MERGE_TEST_TINY = 1, 2
@@ -161,6 +161,9 @@ SIGNATURES = {
     "d3d_sparse_conv_map_workspace_bytes": (_sz, [_i64, _vp, _vp, _vp]),
     "d3d_sparse_conv_map_count": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d3d_sparse_conv_map_emit": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3d_table_conv": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "d3d_table_conv_wgrad_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "d3d_table_conv_wgrad": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -10,6 +10,11 @@ CenterPoint, PV-RCNN, sparse U-Nets) opens with.  An extension (the reference st
 The neighbour relation is symmetric (table[v, k] == u <=> table[u, K-1-k] == v), so the gradient of a gather through the table is
 the gather through the mirrored columns: forward and backward are gathers and GEMMs, nothing is scattered, no float atomics of the
 library's own (kernels and the exact rules: csrc/vnbr.hip, include/d3d_hip.h; the GEMMs are torch's).
+
+    y    = subm_conv3d(vf.bfloat16(), nbrs, weight.bfloat16(), method="fused")      # fp32 / fp16 / bf16 on the matrix cores
+
+method="fused" (the only route of fp16 and bf16) runs the convolution and its gradients as MFMA kernels that gather the rows straight
+into LDS: no [V, K * C] buffer exists (csrc/vconv.hip).
 """
 import numpy as np
 import torch
@@ -254,10 +259,102 @@ class SubmConv3d(torch.autograd.Function):
         return gf, None, gw, gb, None
 
 
-def _check_rows(t, nbrs, what):
+_FUSED_CODES = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
+_METHODS = (None, "gather", "fused")
+
+
+def _conv_dtype(t):
+    """the dtypes a convolution takes (neighbor_gather and voxel_pool keep to pool._dtype_code)"""
+    if t.dtype not in _FUSED_CODES and t.dtype != torch.float64:
+        raise ValueError("voxel features must be float32, float64, float16 or bfloat16, not %s" % t.dtype)
+
+
+def _conv_route(features, weight, method):
+    """"gather" or "fused" for features [*, Cin] and weight [K, Cin, Cout] of one dtype: fp32 / fp64 take the gather route unless
+    asked, half precision exists on the fused kernels only; ValueError for what the chosen route does not serve"""
+    if method not in _METHODS:
+        raise ValueError("method must be None, \"gather\" or \"fused\", not %r" % (method,))
+    if features.dtype in (torch.float16, torch.bfloat16):
+        if method == "gather":
+            raise ValueError("%s runs on the fused kernels only: method=\"gather\" takes float32 and float64" % features.dtype)
+        method = "fused"
+    if method != "fused":
+        return "gather"
+    if features.dtype == torch.float64:
+        raise ValueError("method=\"fused\" takes float32, float16 and bfloat16, not float64")
+    for c, what in ((weight.shape[1], "Cin"), (weight.shape[2], "Cout")):
+        if c < 16 or c > 256 or c % 16:
+            raise ValueError("the fused kernels take channel counts that are multiples of 16 in 16 .. 256, not %s = %d" % (what, c))
+    return "fused"
+
+
+def _table_conv(feat, view, mirrored, weight, bias):
+    """d3d_table_conv: out[r] = bias + sum_k feat[view.table[r, mirrored ? K - 1 - k : k]] @ weight[k], one launch, no workspace"""
+    k, cin, cout = weight.shape
+    with torch.cuda.device(view.device):
+        out = torch.empty((view.num_voxels, cout), dtype=feat.dtype, device=view.device)
+        rc = _lib.load().d3d_table_conv(_lib.ptr(feat), view.src_rows, cin, _lib.ptr(view.table), view.num_voxels, k, int(mirrored),
+                                        _lib.ptr(weight), _lib.ptr(bias), cout, _FUSED_CODES[feat.dtype], _lib.ptr(out), _lib.stream_ptr())
+    _lib.check(rc, "table_conv")
+    return out
+
+
+def _table_conv_wgrad(feat, view, mirrored, grad, k):
+    """d3d_table_conv_wgrad: grad_weight[k] = sum_r feat[view.table[r, k]]^T (x) grad[r], fp32 partials per row slab folded in order"""
+    cin, cout, rows = feat.shape[1], grad.shape[1], view.num_voxels
+    with torch.cuda.device(view.device):
+        lib = _lib.load()
+        gw = torch.empty((k, cin, cout), dtype=feat.dtype, device=view.device)
+        ws = _lib.workspace(lib.d3d_table_conv_wgrad_workspace_bytes(rows, k, cin, cout), view.device)
+        rc = lib.d3d_table_conv_wgrad(_lib.ptr(feat), view.src_rows, cin, _lib.ptr(view.table), rows, k, int(mirrored), _lib.ptr(grad), cout,
+                                      _FUSED_CODES[feat.dtype], _lib.ptr(gw), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+    _lib.check(rc, "table_conv_wgrad")
+    return gw
+
+
+class FusedTableConv(torch.autograd.Function):
+    """out[r] = sum_k features[fwd.table[r, k]] @ weight[k] (+ bias) on the MFMA kernels of csrc/vconv.hip, for subm_conv3d (fwd = bwd =
+    the VoxelNeighbors, the backward mirrored) and the two tables of a SparseConvMap (unmirrored).  backward: grad_features =
+    d3d_table_conv of grad_out through bwd with weight transposed to [K, Cout, Cin]; grad_weight = d3d_table_conv_wgrad through fwd;
+    grad_bias = the column sum, accumulated in fp32.  Everything comes back in the dtype of features.  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, features, fwd, bwd, bwd_mirrored, weight, bias):
+        dev, odev = fwd.device, features.device
+        f = features.detach().to(dev).contiguous()
+        w = weight.detach().to(dev).contiguous()
+        b = None if bias is None else bias.detach().to(dev).contiguous()
+        out = _table_conv(f, fwd, False, w, b)
+        ctx.fwd, ctx.bwd, ctx.bwd_mirrored, ctx.odev, ctx.has_bias = fwd, bwd, bwd_mirrored, odev, bias is not None
+        ctx.wdev, ctx.bdev = weight.device, bias.device if bias is not None else None
+        ctx.save_for_backward(f, w)
+        return _lib.to_caller(out, odev, dev)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        f, w = ctx.saved_tensors
+        fwd, dev = ctx.fwd, ctx.fwd.device
+        g = grad.to(dev).contiguous()
+        need_f, _, _, _, need_w, need_b = ctx.needs_input_grad
+        gf = gw = gb = None
+        with torch.cuda.device(dev):
+            if need_f:
+                gf = _lib.to_caller(_table_conv(g, ctx.bwd, ctx.bwd_mirrored, w.transpose(1, 2).contiguous(), None), ctx.odev, dev)
+            if need_w:
+                gw = _lib.to_caller(_table_conv_wgrad(f, fwd, False, g, w.shape[0]), ctx.wdev, dev)
+            if ctx.has_bias and need_b:
+                gb = _lib.to_caller(g.sum(0, dtype=torch.float32).to(g.dtype), ctx.bdev, dev)
+        return gf, None, None, None, gw, gb
+
+
+def _check_rows(t, nbrs, what, conv=False):
     if t.dim() != 2:
         raise ValueError("%s must be a 2-D tensor of one row per voxel" % what)
-    _dtype_code(t)
+    if conv:
+        _conv_dtype(t)
+    else:
+        _dtype_code(t)
     if t.shape[0] != nbrs.num_voxels:
         raise ValueError("%s has %d rows, the VoxelNeighbors %d voxels" % (what, t.shape[0], nbrs.num_voxels))
     nbrs._on(t)
@@ -279,10 +376,11 @@ def neighbor_gather(features, nbrs):
     return out.numpy() if was_numpy else out
 
 
-def subm_conv3d(features, nbrs, weight, bias=None, chunk_rows=None):
+def subm_conv3d(features, nbrs, weight, bias=None, chunk_rows=None, method=None):
     """Submanifold sparse convolution: out[v] = sum over k of features[table[v, k]] @ weight[k] (+ bias), on the active voxels only.
 
-    :param features: [V, Cin] float32 or float64, torch tensor (GPU or host) or numpy array; differentiable (once)
+    :param features: [V, Cin] float32, float64, float16 or bfloat16 (half precision: `method`), torch tensor (GPU or host) or numpy
+        array; differentiable (once)
     :param nbrs: the frame's VoxelNeighbors (its kernel size and dilation are the convolution's)
     :param weight: [K, Cin, Cout] in the dtype of features, K = nbrs' kernel volume in the table's column order (a dense
         conv3d weight [Cout, Cin, kx, ky, kz] is weight.permute(2, 3, 4, 1, 0).reshape(K, Cin, Cout)); differentiable
@@ -291,13 +389,18 @@ def subm_conv3d(features, nbrs, weight, bias=None, chunk_rows=None):
         Every GEMM call has the same row count (min(65536, a power of two covering V), fewer for rows beyond 4 KiB: about 256 MiB
         of gathered rows at most), the last call of the frame padded with zero rows, so that a row of the result and of
         grad_features does not depend on chunk_rows (measured, see _gather_times); a gathered buffer is at least one call's rows
+    :param method: "gather" (the default of float32 / float64, what is described above), or "fused" (float32, float16, bfloat16; the
+        default and the only route of the half types): the MFMA kernels of csrc/vconv.hip, which gather the rows straight into LDS --
+        no [V, K * C] buffer, chunk_rows is checked and ignored.  Cin and Cout must be multiples of 16 in 16 .. 256 (ValueError).
+        Products accumulate in fp32, the result is rounded once; outputs and all three gradients come back in the dtype of features,
+        a row's bits depend on that row's neighbours alone, and every run gives the same bits
     :return: [V, Cout] on the side features came from
     """
     if not isinstance(nbrs, VoxelNeighbors):
         raise TypeError("nbrs must be a VoxelNeighbors")
     features, was_numpy = _as_tensor(features, "features")
     weight, _ = _as_tensor(weight, "weight")
-    _check_rows(features, nbrs, "features")
+    _check_rows(features, nbrs, "features", conv=True)
     if weight.dim() != 3 or weight.shape[0] != nbrs.kernel_volume or weight.shape[1] != features.shape[1]:
         raise ValueError("weight must be [K, Cin, Cout] = [%d, %d, Cout], not %s" % (nbrs.kernel_volume, features.shape[1], tuple(weight.shape)))
     if weight.dtype != features.dtype:
@@ -310,9 +413,12 @@ def subm_conv3d(features, nbrs, weight, bias=None, chunk_rows=None):
         chunk_rows = int(chunk_rows)
         if chunk_rows < 1:
             raise ValueError("chunk_rows must be at least 1")
-    chunk_rows = _chunk_rows(chunk_rows, nbrs, weight.shape[1], weight.shape[2], features.element_size())
-    out = SubmConv3d.apply(features, nbrs, weight, bias, chunk_rows)
+    if _conv_route(features, weight, method) == "fused":
+        out = FusedTableConv.apply(features, nbrs, nbrs, True, weight, bias)
+    else:
+        chunk_rows = _chunk_rows(chunk_rows, nbrs, weight.shape[1], weight.shape[2], features.element_size())
+        out = SubmConv3d.apply(features, nbrs, weight, bias, chunk_rows)
     return out.detach().numpy() if was_numpy else out
 
 
-__all__ = ["VoxelNeighbors", "neighbor_gather", "subm_conv3d", "NeighborGather", "SubmConv3d"]
+__all__ = ["VoxelNeighbors", "neighbor_gather", "subm_conv3d", "NeighborGather", "SubmConv3d", "FusedTableConv"]

@@ -10,7 +10,8 @@ submanifold stages of a voxel backbone (SECOND, CenterPoint, PV-RCNN), and the o
 The relation between input and output rows is not symmetric, but it is a bijection between the entries of two tables
 (table_out[r, k] == v <=> table_in[v, k] == r), so forward, backward and the inverse convolution are all plain gathers through one
 of them and GEMMs: nothing is scattered, no float atomics of the library's own (kernels and the exact rules: csrc/vstride.hip,
-include/d3d_hip.h; the gather is csrc/vnbr.hip's, the GEMMs are torch's).
+include/d3d_hip.h; the gather is csrc/vnbr.hip's, the GEMMs are torch's).  method="fused" -- the only route of fp16 and bf16 -- runs
+all of it on the MFMA kernels of csrc/vconv.hip instead, without the gathered buffer (see conv.subm_conv3d).
 """
 import ctypes
 from math import gcd
@@ -19,8 +20,8 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
-from .conv import _TableView, _chunk_rows, _chunks, _gather, _gather_times, _triple
-from .pool import _as_tensor, _dtype_code
+from .conv import FusedTableConv, _TableView, _chunk_rows, _chunks, _conv_dtype, _conv_route, _gather, _gather_times, _triple
+from .pool import _as_tensor
 
 _MAX_ROWS = 2 ** 31 - 1
 _MAX_STEP = 2 ** 24
@@ -195,14 +196,14 @@ class TableConv(torch.autograd.Function):
         return gf, None, None, gw, gb, None, None
 
 
-def _table_conv(features, cmap, fwd, bwd, weight, bias, chunk_rows):
+def _table_conv(features, cmap, fwd, bwd, weight, bias, chunk_rows, method):
     if not isinstance(cmap, SparseConvMap):
         raise TypeError("cmap must be a SparseConvMap")
     features, was_numpy = _as_tensor(features, "features")
     weight, _ = _as_tensor(weight, "weight")
     if features.dim() != 2:
         raise ValueError("features must be a 2-D tensor of one row per voxel")
-    _dtype_code(features)
+    _conv_dtype(features)
     if features.shape[0] != fwd.src_rows:
         raise ValueError("features has %d rows, the SparseConvMap %d on that side" % (features.shape[0], fwd.src_rows))
     cmap._on(features)
@@ -219,29 +220,35 @@ def _table_conv(features, cmap, fwd, bwd, weight, bias, chunk_rows):
         if chunk_rows < 1:
             raise ValueError("chunk_rows must be at least 1")
     cin, cout, size = weight.shape[1], weight.shape[2], features.element_size()
-    out = TableConv.apply(features, fwd, bwd, weight, bias, _chunk_rows(chunk_rows, fwd, cin, cout, size),
-                          _chunk_rows(chunk_rows, bwd, cin, cout, size))
+    if _conv_route(features, weight, method) == "fused":
+        out = FusedTableConv.apply(features, fwd, bwd, False, weight, bias)
+    else:
+        out = TableConv.apply(features, fwd, bwd, weight, bias, _chunk_rows(chunk_rows, fwd, cin, cout, size),
+                              _chunk_rows(chunk_rows, bwd, cin, cout, size))
     return out.detach().numpy() if was_numpy else out
 
 
-def sparse_conv3d(features, cmap, weight, bias=None, chunk_rows=None):
+def sparse_conv3d(features, cmap, weight, bias=None, chunk_rows=None, method=None):
     """Strided sparse convolution: out[r] = sum over k of features[table_out[r, k]] @ weight[k] (+ bias), on the active outputs only.
 
-    :param features: [V, Cin] float32 or float64, torch tensor (GPU or host) or numpy array; differentiable (once)
+    :param features: [V, Cin] float32, float64, float16 or bfloat16 (half precision: `method`), torch tensor (GPU or host) or numpy
+        array; differentiable (once)
     :param cmap: the layer's SparseConvMap (its kernel size, stride, padding and dilation are the convolution's)
     :param weight: [K, Cin, Cout] in the dtype of features, K = cmap's kernel volume in the tables' column order (a dense conv3d
         weight [Cout, Cin, kx, ky, kz] is weight.permute(2, 3, 4, 1, 0).reshape(K, Cin, Cout), as for subm_conv3d); differentiable
     :param bias: [Cout] or None; differentiable
     :param chunk_rows: rows per gather step, as for subm_conv3d: every GEMM call has one fixed row count, so a row of the result and
         of grad_features does not depend on it
+    :param method: "gather" (the default of float32 / float64) or "fused" (float32, float16, bfloat16; the default and the only route
+        of the half types): as for subm_conv3d -- MFMA kernels, no gathered buffer, Cin and Cout multiples of 16 in 16 .. 256
     :return: [Vout, Cout] on the side features came from; row r belongs to cmap.out_coords[r].  It equals dense conv3d at the
         active outputs.  Gradients: grad_features[v] = sum_k grad_out[table_in[v, k]] @ weight[k]^T (a gather through table_in, no
         mirroring), grad_weight = the sum over the chunks, in chunk order, of gathered^T @ grad_out, grad_bias = the column sum
     """
-    return _table_conv(features, cmap, getattr(cmap, "_down", None), getattr(cmap, "_up", None), weight, bias, chunk_rows)
+    return _table_conv(features, cmap, getattr(cmap, "_down", None), getattr(cmap, "_up", None), weight, bias, chunk_rows, method)
 
 
-def sparse_inverse_conv3d(features, cmap, weight, bias=None, chunk_rows=None):
+def sparse_inverse_conv3d(features, cmap, weight, bias=None, chunk_rows=None, method=None):
     """Inverse sparse convolution (spconv's SparseInverseConv3d): out[v] = sum over k of features[table_in[v, k]] @ weight[k]
     (+ bias) -- conv_transpose3d of the output-side rows, evaluated on the ORIGINAL input sites of `cmap`.
 
@@ -249,11 +256,11 @@ def sparse_inverse_conv3d(features, cmap, weight, bias=None, chunk_rows=None):
     :param cmap: the SparseConvMap of the strided layer this one undoes
     :param weight: [K, Cin, Cout] in the tables' column order (a conv_transpose3d weight [Cin, Cout, kx, ky, kz] is
         weight.permute(2, 3, 4, 0, 1).reshape(K, Cin, Cout)); differentiable
-    :param bias, chunk_rows: as for sparse_conv3d
+    :param bias, chunk_rows, method: as for sparse_conv3d
     :return: [V, Cout] on the side features came from; row v belongs to the coords[v] cmap was built from.  Its backward runs
         through table_out the same way
     """
-    return _table_conv(features, cmap, getattr(cmap, "_up", None), getattr(cmap, "_down", None), weight, bias, chunk_rows)
+    return _table_conv(features, cmap, getattr(cmap, "_up", None), getattr(cmap, "_down", None), weight, bias, chunk_rows, method)
 
 
 __all__ = ["SparseConvMap", "sparse_conv3d", "sparse_inverse_conv3d", "TableConv"]

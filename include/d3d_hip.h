@@ -53,7 +53,9 @@ enum { D3D_F32 = 0, D3D_F64 = 1,
        /* d3d_iou2d_forward / _backward (BOX / RBOX), d3d_nms2d: everything in memory f32 (boxes, scores, the matrix), the arithmetic f64 --
         * every value widened where it is loaded.  box2d_iou / box2d_nms (precise=True) on fp32 tensors without the .double()
         * copies either (box/__init__.py:204-205, 254-255). */
-       D3D_F32_WIDE = 3 };
+       D3D_F32_WIDE = 3,
+       /* d3d_table_conv / d3d_table_conv_wgrad only: IEEE half and bfloat16 in memory, fp32 accumulation on the matrix cores */
+       D3D_F16 = 4, D3D_BF16 = 5 };
 
 /* status bits OR-ed into counts[D3D_COUNT_STATUS] by the voxel kernels */
 enum { D3D_VOXEL_STATUS_COORD_OVERFLOW = 1,   /* sparse: 2^20 <= |floor(p/size)| < 2^31 (NaN, inf and
@@ -1038,6 +1040,35 @@ int d3d_sparse_conv_map_emit(const int64_t *coords, const int64_t *batch, int64_
                              const int32_t *padding, const int32_t *dilation, const int64_t *spatial_shape, int64_t num_out,
                              int64_t *out_coords, int64_t *out_batch, int32_t *table_in, int32_t *table_out, int64_t *counts,
                              void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------ the table form of a sparse convolution on the matrix cores */
+
+/* out[r] = sum_k feat[table[r, k]] @ W[k] without the gathered [rows, K * C] buffer (csrc/vconv.hip): what subm_conv3d, sparse_conv3d
+ * and sparse_inverse_conv3d compute, their forward and both of their matrix gradients, in fp32, fp16 and bf16.
+ *
+ * d3d_table_conv: feat[src_rows, cin], table[rows, k] int32 (entries in [-1, src_rows), trusted), weight[k, cin, cout], bias[cout] or
+ *   NULL -> out[rows, cout] = bias + the sum over kk, in ascending order, of feat[e] @ weight[kk] with
+ *   e = table[r, mirrored ? k - 1 - kk : kk] (d3d_neighbor_gather's meaning); entries -1 contribute nothing.  The forward of the three
+ *   operators, and their grad_features through the backward table (the mirrored one, or table_in / table_out) with the weight
+ *   transposed to [k, cout, cin] by the caller.  One launch, no workspace.  Products accumulate in fp32 on the MFMA units (fp32: the
+ *   exact f32 form), the bias is added in fp32 and the sum is rounded once, to nearest even, to the output type.  A row's bits depend
+ *   on its own table row, the feat rows it names, the weight and the bias only (finite weights): not on its position, on the other
+ *   rows of the launch or on the run.  16-byte loads where feat and weight are 16-byte aligned; offsets are 64-bit.
+ * d3d_table_conv_wgrad: grad_weight[kk] = sum_r feat[table[r, col(kk)]]^T (x) grad_out[r] for grad_out[rows, cout] ->
+ *   grad_weight[k, cin, cout], the present (row, entry) pairs of a column compacted in row order before they meet the MFMA.  Two
+ *   launches: fp32 partial sums per (column, row slab) into the workspace (d3d_table_conv_wgrad_workspace_bytes: slabs x k x cin x
+ *   cout floats, the slab count a function of the four sizes), then the slabs added in ascending order and rounded once.  No float
+ *   atomics; the order of every sum is fixed by the table and the sizes: the same bits on every run.  rows == 0: grad_weight zeroed.
+ * dtype: D3D_F32, D3D_F16 or D3D_BF16 (every array in it).  D3D_ERR_UNSUPPORTED, nothing touched: D3D_F64, cin or cout that is no
+ *   multiple of 16 in 16 .. 256, k above 343, rows or src_rows above 2^31 - 1.  D3D_ERR_BAD_ARG: a negative size, k < 1, another
+ *   dtype code, a missing pointer; D3D_ERR_WORKSPACE: workspace missing or smaller than the query.  d3d_table_conv with rows == 0
+ *   returns D3D_OK before any HIP call. */
+int d3d_table_conv(const void *feat, int64_t src_rows, int32_t cin, const int32_t *table, int64_t rows, int32_t k, int32_t mirrored,
+                   const void *weight, const void *bias, int32_t cout, int32_t dtype, void *out, void *stream);
+size_t d3d_table_conv_wgrad_workspace_bytes(int64_t rows, int32_t k, int32_t cin, int32_t cout);
+int d3d_table_conv_wgrad(const void *feat, int64_t src_rows, int32_t cin, const int32_t *table, int64_t rows, int32_t k, int32_t mirrored,
+                         const void *grad_out, int32_t cout, int32_t dtype, void *grad_weight, void *workspace, size_t workspace_bytes,
+                         void *stream);
 
 #ifdef __cplusplus
 }
