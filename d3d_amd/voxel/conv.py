@@ -15,13 +15,17 @@ library's own (kernels and the exact rules: csrc/vnbr.hip, include/d3d_hip.h; th
 
 method="fused" (the only route of fp16 and bf16) runs the convolution and its gradients as MFMA kernels that gather the rows straight
 into LDS: no [V, K * C] buffer exists (csrc/vconv.hip).
+
+Everything that convolves through a table lives here, once, for subm_conv3d and for sparse_conv.py's two operators: a _TableView per
+table, _conv_front (the argument checks and the choice of the route), and one autograd.Function per route, TableConv (gather) and
+FusedTableConv, over a forward and a backward view: out[r] = sum_k features[fwd.table[r, k]] @ weight[k] (+ bias).
 """
 import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
-from .pool import _as_tensor, _dtype_code
+from .pool import _as_tensor, _dtype_code, _on
 
 _MAX_VOXELS = 2 ** 31 - 1
 _SPAN_LIMIT = 2 ** 62
@@ -45,6 +49,32 @@ def _host_spans_fit(coords, batch):
     return span <= _SPAN_LIMIT
 
 
+def _check_coords(coords, batch_index):
+    """coords [V, 3] and batch_index [V] or None, int64 or int32, as given to a VoxelNeighbors or a SparseConvMap
+    -> (coords, batch_index, V) as tensors where they are; nothing here needs a GPU"""
+    coords, _ = _as_tensor(coords, "coords")
+    if coords.dim() != 2 or coords.shape[1] != 3:
+        raise ValueError("coords must be a [V, 3] tensor of voxel coordinates")
+    if coords.dtype not in (torch.int64, torch.int32):
+        raise ValueError("coords must be int64 or int32, not %s" % coords.dtype)
+    v = coords.shape[0]
+    if batch_index is not None:
+        batch_index, _ = _as_tensor(batch_index, "batch_index")
+        if batch_index.dim() != 1 or batch_index.shape[0] != v:
+            raise ValueError("batch_index must be a [V] tensor, one value per row of coords")
+        if batch_index.dtype not in (torch.int64, torch.int32):
+            raise ValueError("batch_index must be int64 or int32, not %s" % batch_index.dtype)
+    return coords, batch_index, v
+
+
+class _TableView:
+    """what the gathers, the fused launchers and _chunk_rows read of a table [num_voxels, K] whose entries point into src_rows feature
+    rows: the one table of a VoxelNeighbors (src_rows = num_voxels), the two of a SparseConvMap"""
+
+    def __init__(self, table, src_rows, kernel_volume, device):
+        self.table, self.num_voxels, self.src_rows, self.kernel_volume, self.device = table, table.shape[0], src_rows, kernel_volume, device
+
+
 class VoxelNeighbors:
     """The neighbour table of one frame's active voxels.
 
@@ -60,18 +90,7 @@ class VoxelNeighbors:
     of the coordinate (and batch) spans exceeds 2^62."""
 
     def __init__(self, coords, kernel_size=3, dilation=1, batch_index=None):
-        coords, _ = _as_tensor(coords, "coords")
-        if coords.dim() != 2 or coords.shape[1] != 3:
-            raise ValueError("coords must be a [V, 3] tensor of voxel coordinates")
-        if coords.dtype not in (torch.int64, torch.int32):
-            raise ValueError("coords must be int64 or int32, not %s" % coords.dtype)
-        v = coords.shape[0]
-        if batch_index is not None:
-            batch_index, _ = _as_tensor(batch_index, "batch_index")
-            if batch_index.dim() != 1 or batch_index.shape[0] != v:
-                raise ValueError("batch_index must be a [V] tensor, one value per row of coords")
-            if batch_index.dtype not in (torch.int64, torch.int32):
-                raise ValueError("batch_index must be int64 or int32, not %s" % batch_index.dtype)
+        coords, batch_index, v = _check_coords(coords, batch_index)
         ks, dil = _triple(kernel_size, "kernel_size"), _triple(dilation, "dilation")
         if any(k < 1 or k > 7 or k % 2 == 0 for k in ks):
             raise ValueError("kernel_size must be odd and in 1 .. 7, not %r" % (kernel_size,))
@@ -103,29 +122,13 @@ class VoxelNeighbors:
         if dups:
             raise ValueError("coords holds %d rows whose (batch, coordinate) an earlier row already has" % dups)
         self.num_entries = entries
-
-    @property
-    def src_rows(self):
-        """the rows the table's entries point into: the voxels themselves"""
-        return self.num_voxels
-
-    def _on(self, t):
-        if t.is_cuda and t.device != self.device:
-            raise ValueError("features live on %s, the VoxelNeighbors on %s" % (t.device, self.device))
-
-
-class _TableView:
-    """what _gather, _gather_times and _chunk_rows read of a VoxelNeighbors, for any table [num_voxels, K] whose entries point into
-    src_rows feature rows (the two tables of a SparseConvMap)"""
-
-    def __init__(self, table, src_rows, kernel_volume, device):
-        self.table, self.num_voxels, self.src_rows, self.kernel_volume, self.device = table, table.shape[0], src_rows, kernel_volume, device
+        self._view = _TableView(self.table, v, k, dev)           # the voxels read the voxels: forward as it is, backward mirrored
 
 
 def _gather(feat, nbrs, mirrored, v0=0, rows=None, feat_cols=1, out=None):
     """feat [V, C] (or [V, K, C] with feat_cols = K) on nbrs.device -> [rows, K, C] for the rows v0 .. v0 + rows of the table (into
-    `out`, contiguous and of that many elements, when given); one launch, every output row written once.  nbrs: a VoxelNeighbors or
-    a _TableView (V = nbrs.src_rows, the table has nbrs.num_voxels rows)"""
+    `out`, contiguous and of that many elements, when given); one launch, every output row written once.  nbrs: a _TableView
+    (V = nbrs.src_rows, the table has nbrs.num_voxels rows)"""
     k, c = nbrs.kernel_volume, feat.shape[-1]
     rows = nbrs.num_voxels - v0 if rows is None else rows
     with torch.cuda.device(nbrs.device):
@@ -140,8 +143,8 @@ def _gather(feat, nbrs, mirrored, v0=0, rows=None, feat_cols=1, out=None):
 
 
 class NeighborGather(torch.autograd.Function):
-    """neighbor_gather: (features [V, C], VoxelNeighbors) -> [V, K, C], one launch.  backward: the mirrored gather of the gradient
-    (row [table[u, K-1-k], k] of it for every (u, k)), then the sum over k in ascending k.  Differentiable once."""
+    """neighbor_gather: (features [V, C], the view of a VoxelNeighbors) -> [V, K, C], one launch.  backward: the mirrored gather of
+    the gradient (row [table[u, K-1-k], k] of it for every (u, k)), then the sum over k in ascending k.  Differentiable once."""
 
     @staticmethod
     def forward(ctx, features, nbrs):
@@ -205,58 +208,70 @@ def _chunk_rows(chunk_rows, nbrs, cin, cout, itemsize):
     return -(-chunk_rows // tile) * tile
 
 
-class SubmConv3d(torch.autograd.Function):
-    """subm_conv3d: per chunk of rows one gather [R, K * Cin] and GEMMs of a fixed row count with weight [K * Cin, Cout] (see
-    _gather_times).  backward: grad_features = the mirrored gather of grad_out [R, K * Cout] times weight^T [K * Cout, Cin];
-    grad_weight = the sum over the chunks, in chunk order, of gathered^T @ grad_out (the gather is made again, not kept); grad_bias =
-    the column sum.  Differentiable once."""
+def _conv_enter(ctx, features, fwd, bwd, bwd_mirrored, weight, bias):
+    """what both routes' forward begins with: -> (features, weight, bias or None) detached, contiguous and on the tables' device;
+    on ctx the two views, the two of them saved, and the device each of the three came from"""
+    dev = fwd.device
+    f, w = features.detach().to(dev).contiguous(), weight.detach().to(dev).contiguous()
+    b = None if bias is None else bias.detach().to(dev).contiguous()
+    ctx.fwd, ctx.bwd, ctx.bwd_mirrored = fwd, bwd, bwd_mirrored
+    ctx.devs = (features.device, weight.device, None if bias is None else bias.device)
+    ctx.save_for_backward(f, w)
+    return f, w, b
+
+
+def _conv_grads(ctx, gf, gw, gb):
+    """what both routes' backward ends with: the gradients that were asked for (None: not), each on its caller's device, in the
+    places of (features, fwd, bwd, bwd_mirrored, weight, bias)"""
+    gf, gw, gb = (None if g is None else _lib.to_caller(g, odev, ctx.fwd.device) for g, odev in zip((gf, gw, gb), ctx.devs))
+    return gf, None, None, None, gw, gb
+
+
+class TableConv(torch.autograd.Function):
+    """The gather route of all three operators: out[r] = sum_k features[fwd.table[r, k]] @ weight[k] (+ bias) for two views that are
+    each other's transposed map: subm_conv3d passes a VoxelNeighbors' one view twice and reads it mirrored on the way back
+    (table[v, k] == u <=> table[u, K-1-k] == v), the operators of a SparseConvMap its two views, unmirrored (fwd.table[r, k] == v <=>
+    bwd.table[v, k] == r).  Per chunk of rows one gather [R, K * Cin] and GEMMs of a fixed row count with weight [K * Cin, Cout]
+    (_gather_times).  backward: grad_features = the gather of grad_out through bwd.table [R', K * Cout] times weight^T [K * Cout,
+    Cin]; grad_weight = the sum over the chunks of fwd, in chunk order, of gathered^T @ grad_out (the gather is made again, not
+    kept); grad_bias = the column sum.  Differentiable once."""
 
     @staticmethod
-    def forward(ctx, features, nbrs, weight, bias, chunk_rows):
-        dev, odev = nbrs.device, features.device
-        k, cin, cout = weight.shape
-        f = features.detach().to(dev).contiguous()
-        w = weight.detach().to(dev).contiguous()
-        with torch.cuda.device(dev):
-            out = torch.empty((nbrs.num_voxels, cout), dtype=f.dtype, device=dev)
-            for v0, r in _chunks(nbrs.num_voxels, chunk_rows):
-                _gather_times(f, nbrs, False, v0, r, w.view(k * cin, cout), out)
-            if bias is not None:
-                out += bias.detach().to(dev)
-        ctx.nbrs, ctx.chunk_rows, ctx.odev, ctx.has_bias = nbrs, chunk_rows, odev, bias is not None
-        ctx.wdev, ctx.bdev = weight.device, bias.device if bias is not None else None
-        ctx.save_for_backward(f, w)
-        return _lib.to_caller(out, odev, dev)
+    def forward(ctx, features, fwd, bwd, bwd_mirrored, weight, bias, chunk_fwd, chunk_bwd):
+        f, w, b = _conv_enter(ctx, features, fwd, bwd, bwd_mirrored, weight, bias)
+        k, cin, cout = w.shape
+        ctx.chunks = (chunk_fwd, chunk_bwd)
+        with torch.cuda.device(fwd.device):
+            out = torch.empty((fwd.num_voxels, cout), dtype=f.dtype, device=fwd.device)
+            for r0, r in _chunks(fwd.num_voxels, chunk_fwd):
+                _gather_times(f, fwd, False, r0, r, w.view(k * cin, cout), out)
+            if b is not None:
+                out += b
+        return _lib.to_caller(out, features.device, fwd.device)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad):
         f, w = ctx.saved_tensors
-        nbrs, dev = ctx.nbrs, ctx.nbrs.device
+        fwd, bwd = ctx.fwd, ctx.bwd
         k, cin, cout = w.shape
-        g = grad.to(dev).contiguous()
-        need_f, _, need_w, need_b, _ = ctx.needs_input_grad
+        g = grad.to(fwd.device).contiguous()
+        need_f, _, _, _, need_w, need_b, _, _ = ctx.needs_input_grad
         gf = gw = gb = None
-        with torch.cuda.device(dev):
+        with torch.cuda.device(fwd.device):
             if need_f:
                 gf = torch.empty_like(f)
                 wt = w.transpose(1, 2).reshape(k * cout, cin)
+                for v0, r in _chunks(bwd.num_voxels, ctx.chunks[1]):
+                    _gather_times(g, bwd, ctx.bwd_mirrored, v0, r, wt, gf)
             if need_w:
-                gw = torch.zeros((k * cin, cout), dtype=w.dtype, device=dev)
-            for v0, r in _chunks(nbrs.num_voxels, ctx.chunk_rows):
-                if need_f:
-                    _gather_times(g, nbrs, True, v0, r, wt, gf)
-                if need_w:
-                    gw += torch.matmul(_gather(f, nbrs, False, v0, r).view(r, k * cin).t(), g[v0:v0 + r])
-            if ctx.has_bias and need_b:
+                gw = torch.zeros((k * cin, cout), dtype=w.dtype, device=fwd.device)
+                for r0, r in _chunks(fwd.num_voxels, ctx.chunks[0]):
+                    gw += torch.matmul(_gather(f, fwd, False, r0, r).view(r, k * cin).t(), g[r0:r0 + r])
+                gw = gw.view(k, cin, cout)
+            if need_b:
                 gb = g.sum(0)
-        if need_f:
-            gf = _lib.to_caller(gf, ctx.odev, dev)
-        if need_w:
-            gw = _lib.to_caller(gw.view(k, cin, cout), ctx.wdev, dev)
-        if gb is not None:
-            gb = _lib.to_caller(gb, ctx.bdev, dev)
-        return gf, None, gw, gb, None
+        return _conv_grads(ctx, gf, gw, gb) + (None, None)
 
 
 _FUSED_CODES = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
@@ -313,51 +328,69 @@ def _table_conv_wgrad(feat, view, mirrored, grad, k):
 
 
 class FusedTableConv(torch.autograd.Function):
-    """out[r] = sum_k features[fwd.table[r, k]] @ weight[k] (+ bias) on the MFMA kernels of csrc/vconv.hip, for subm_conv3d (fwd = bwd =
-    the VoxelNeighbors, the backward mirrored) and the two tables of a SparseConvMap (unmirrored).  backward: grad_features =
-    d3d_table_conv of grad_out through bwd with weight transposed to [K, Cout, Cin]; grad_weight = d3d_table_conv_wgrad through fwd;
-    grad_bias = the column sum, accumulated in fp32.  Everything comes back in the dtype of features.  Differentiable once."""
+    """The fused route of all three operators: TableConv's result from the same two views on the MFMA kernels of csrc/vconv.hip,
+    without chunks, the bias added inside the kernel.  backward: grad_features = d3d_table_conv of grad_out through bwd with weight
+    transposed to [K, Cout, Cin]; grad_weight = d3d_table_conv_wgrad through fwd; grad_bias = the column sum, accumulated in fp32.
+    Everything comes back in the dtype of features.  Differentiable once."""
 
     @staticmethod
     def forward(ctx, features, fwd, bwd, bwd_mirrored, weight, bias):
-        dev, odev = fwd.device, features.device
-        f = features.detach().to(dev).contiguous()
-        w = weight.detach().to(dev).contiguous()
-        b = None if bias is None else bias.detach().to(dev).contiguous()
-        out = _table_conv(f, fwd, False, w, b)
-        ctx.fwd, ctx.bwd, ctx.bwd_mirrored, ctx.odev, ctx.has_bias = fwd, bwd, bwd_mirrored, odev, bias is not None
-        ctx.wdev, ctx.bdev = weight.device, bias.device if bias is not None else None
-        ctx.save_for_backward(f, w)
-        return _lib.to_caller(out, odev, dev)
+        f, w, b = _conv_enter(ctx, features, fwd, bwd, bwd_mirrored, weight, bias)
+        return _lib.to_caller(_table_conv(f, fwd, False, w, b), features.device, fwd.device)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad):
         f, w = ctx.saved_tensors
-        fwd, dev = ctx.fwd, ctx.fwd.device
-        g = grad.to(dev).contiguous()
+        g = grad.to(ctx.fwd.device).contiguous()
         need_f, _, _, _, need_w, need_b = ctx.needs_input_grad
         gf = gw = gb = None
-        with torch.cuda.device(dev):
+        with torch.cuda.device(ctx.fwd.device):
             if need_f:
-                gf = _lib.to_caller(_table_conv(g, ctx.bwd, ctx.bwd_mirrored, w.transpose(1, 2).contiguous(), None), ctx.odev, dev)
+                gf = _table_conv(g, ctx.bwd, ctx.bwd_mirrored, w.transpose(1, 2).contiguous(), None)
             if need_w:
-                gw = _lib.to_caller(_table_conv_wgrad(f, fwd, False, g, w.shape[0]), ctx.wdev, dev)
-            if ctx.has_bias and need_b:
-                gb = _lib.to_caller(g.sum(0, dtype=torch.float32).to(g.dtype), ctx.bdev, dev)
-        return gf, None, None, None, gw, gb
+                gw = _table_conv_wgrad(f, ctx.fwd, False, g, w.shape[0])
+            if need_b:
+                gb = g.sum(0, dtype=torch.float32).to(g.dtype)
+        return _conv_grads(ctx, gf, gw, gb)
 
 
-def _check_rows(t, nbrs, what, conv=False):
+def _check_rows(t, owner, rows, check_dtype):
+    """features of a gather or a convolution through a table of `owner` whose entries point into `rows` feature rows"""
     if t.dim() != 2:
-        raise ValueError("%s must be a 2-D tensor of one row per voxel" % what)
-    if conv:
-        _conv_dtype(t)
+        raise ValueError("features must be a 2-D tensor of one row per voxel")
+    check_dtype(t)
+    if t.shape[0] != rows:
+        raise ValueError("features has %d rows where the %s expects %d" % (t.shape[0], type(owner).__name__, rows))
+    _on(owner, t)
+
+
+def _conv_front(features, owner, fwd, bwd, bwd_mirrored, weight, bias, chunk_rows, method):
+    """What subm_conv3d, sparse_conv3d and sparse_inverse_conv3d do once each has checked its owner's type and picked the forward and
+    the backward view of it: numpy in and out, every check of the arguments (shapes first, then what the route refuses), the route,
+    the chunk sizes of the gather route, and the call of that route's Function"""
+    features, was_numpy = _as_tensor(features, "features")
+    weight, _ = _as_tensor(weight, "weight")
+    _check_rows(features, owner, fwd.src_rows, _conv_dtype)
+    if weight.dim() != 3 or weight.shape[0] != fwd.kernel_volume or weight.shape[1] != features.shape[1]:
+        raise ValueError("weight must be [K, Cin, Cout] = [%d, %d, Cout], not %s" % (fwd.kernel_volume, features.shape[1], tuple(weight.shape)))
+    if weight.dtype != features.dtype:
+        raise ValueError("weight is %s, features %s" % (weight.dtype, features.dtype))
+    cin, cout, size = weight.shape[1], weight.shape[2], features.element_size()
+    if bias is not None:
+        bias, _ = _as_tensor(bias, "bias")
+        if bias.dim() != 1 or bias.shape[0] != cout or bias.dtype != features.dtype:
+            raise ValueError("bias must be [Cout] = [%d] in %s, the dtype of features" % (cout, features.dtype))
+    if chunk_rows is not None:
+        chunk_rows = int(chunk_rows)
+        if chunk_rows < 1:
+            raise ValueError("chunk_rows must be at least 1, not %d" % chunk_rows)
+    if _conv_route(features, weight, method) == "fused":
+        out = FusedTableConv.apply(features, fwd, bwd, bwd_mirrored, weight, bias)
     else:
-        _dtype_code(t)
-    if t.shape[0] != nbrs.num_voxels:
-        raise ValueError("%s has %d rows, the VoxelNeighbors %d voxels" % (what, t.shape[0], nbrs.num_voxels))
-    nbrs._on(t)
+        out = TableConv.apply(features, fwd, bwd, bwd_mirrored, weight, bias, _chunk_rows(chunk_rows, fwd, cin, cout, size),
+                              _chunk_rows(chunk_rows, bwd, cin, cout, size))
+    return out.detach().numpy() if was_numpy else out
 
 
 def neighbor_gather(features, nbrs):
@@ -371,8 +404,8 @@ def neighbor_gather(features, nbrs):
     if not isinstance(nbrs, VoxelNeighbors):
         raise TypeError("nbrs must be a VoxelNeighbors")
     features, was_numpy = _as_tensor(features, "features")
-    _check_rows(features, nbrs, "features")
-    out = NeighborGather.apply(features, nbrs)
+    _check_rows(features, nbrs, nbrs.num_voxels, _dtype_code)
+    out = NeighborGather.apply(features, nbrs._view)
     return out.numpy() if was_numpy else out
 
 
@@ -398,27 +431,7 @@ def subm_conv3d(features, nbrs, weight, bias=None, chunk_rows=None, method=None)
     """
     if not isinstance(nbrs, VoxelNeighbors):
         raise TypeError("nbrs must be a VoxelNeighbors")
-    features, was_numpy = _as_tensor(features, "features")
-    weight, _ = _as_tensor(weight, "weight")
-    _check_rows(features, nbrs, "features", conv=True)
-    if weight.dim() != 3 or weight.shape[0] != nbrs.kernel_volume or weight.shape[1] != features.shape[1]:
-        raise ValueError("weight must be [K, Cin, Cout] = [%d, %d, Cout], not %s" % (nbrs.kernel_volume, features.shape[1], tuple(weight.shape)))
-    if weight.dtype != features.dtype:
-        raise ValueError("weight is %s, features %s" % (weight.dtype, features.dtype))
-    if bias is not None:
-        bias, _ = _as_tensor(bias, "bias")
-        if bias.dim() != 1 or bias.shape[0] != weight.shape[2] or bias.dtype != features.dtype:
-            raise ValueError("bias must be [Cout] = [%d] in the dtype of features" % weight.shape[2])
-    if chunk_rows is not None:
-        chunk_rows = int(chunk_rows)
-        if chunk_rows < 1:
-            raise ValueError("chunk_rows must be at least 1")
-    if _conv_route(features, weight, method) == "fused":
-        out = FusedTableConv.apply(features, nbrs, nbrs, True, weight, bias)
-    else:
-        chunk_rows = _chunk_rows(chunk_rows, nbrs, weight.shape[1], weight.shape[2], features.element_size())
-        out = SubmConv3d.apply(features, nbrs, weight, bias, chunk_rows)
-    return out.detach().numpy() if was_numpy else out
+    return _conv_front(features, nbrs, nbrs._view, nbrs._view, True, weight, bias, chunk_rows, method)
 
 
-__all__ = ["VoxelNeighbors", "neighbor_gather", "subm_conv3d", "NeighborGather", "SubmConv3d", "FusedTableConv"]
+__all__ = ["VoxelNeighbors", "neighbor_gather", "subm_conv3d", "NeighborGather", "TableConv", "FusedTableConv"]

@@ -28,6 +28,12 @@ def _as_tensor(x, what):
     return x, False
 
 
+def _on(owner, t):
+    """a tensor already on a GPU must be on the one its owner (a VoxelIndex, VoxelNeighbors or SparseConvMap) was built on"""
+    if t.is_cuda and t.device != owner.device:
+        raise ValueError("features live on %s, the %s on %s" % (t.device, type(owner).__name__, owner.device))
+
+
 def _dtype_code(t):
     if t.dtype == torch.float32:
         return _lib.F32
@@ -80,10 +86,6 @@ class VoxelIndex:
             raise ValueError("mapping holds %d voxel ids outside [-1, %d)" % (bad, v))
         self.num_mapped = mapped
         self.order = order[:mapped]
-
-    def _on(self, t):
-        if t.is_cuda and t.device != self.device:
-            raise ValueError("features live on %s, the VoxelIndex on %s" % (t.device, self.device))
 
 
 def _index_of(index_or_mapping, num_voxels):
@@ -202,7 +204,7 @@ def voxel_pool(features, index_or_mapping, num_voxels=None, reduction="max"):
         raise ValueError("features has %d rows, the mapping %d points" % (features.shape[0], k))
     if idx is None:
         idx = VoxelIndex(_beside(mapping, features), num_voxels)
-    idx._on(features)
+    _on(idx, features)
     out = VoxelPool.apply(features, idx, red)
     return out.numpy() if was_numpy else out
 
@@ -221,7 +223,7 @@ def voxel_unpool(voxel_features, index_or_mapping, num_voxels=None):
         idx = VoxelIndex(_beside(mapping, voxel_features), voxel_features.shape[0])
     if voxel_features.shape[0] != idx.num_voxels:
         raise ValueError("voxel_features has %d rows, the index %d voxels" % (voxel_features.shape[0], idx.num_voxels))
-    idx._on(voxel_features)
+    _on(idx, voxel_features)
     out = VoxelUnpool.apply(voxel_features, idx)
     return out.numpy() if was_numpy else out
 

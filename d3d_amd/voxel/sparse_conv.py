@@ -12,16 +12,17 @@ The relation between input and output rows is not symmetric, but it is a bijecti
 of them and GEMMs: nothing is scattered, no float atomics of the library's own (kernels and the exact rules: csrc/vstride.hip,
 include/d3d_hip.h; the gather is csrc/vnbr.hip's, the GEMMs are torch's).  method="fused" -- the only route of fp16 and bf16 -- runs
 all of it on the MFMA kernels of csrc/vconv.hip instead, without the gathered buffer (see conv.subm_conv3d).
+
+This module builds the map and its two views; the convolution through them is conv.py's (_conv_front, TableConv, FusedTableConv):
+sparse_conv3d reads `_down` and goes back through `_up`, sparse_inverse_conv3d the other way round.
 """
 import ctypes
 from math import gcd
 
 import torch
-from torch.autograd.function import once_differentiable
 
 from .. import _lib
-from .conv import FusedTableConv, _TableView, _chunk_rows, _chunks, _conv_dtype, _conv_route, _gather, _gather_times, _triple
-from .pool import _as_tensor
+from .conv import _TableView, _check_coords, _conv_front, _triple
 
 _MAX_ROWS = 2 ** 31 - 1
 _MAX_STEP = 2 ** 24
@@ -68,18 +69,7 @@ class SparseConvMap:
     of ceil(k / (s / gcd(s, d))), the most outputs one input can feed)."""
 
     def __init__(self, coords, kernel_size, stride, padding=0, dilation=1, batch_index=None, spatial_shape=None):
-        coords, _ = _as_tensor(coords, "coords")
-        if coords.dim() != 2 or coords.shape[1] != 3:
-            raise ValueError("coords must be a [V, 3] tensor of voxel coordinates")
-        if coords.dtype not in (torch.int64, torch.int32):
-            raise ValueError("coords must be int64 or int32, not %s" % coords.dtype)
-        v = coords.shape[0]
-        if batch_index is not None:
-            batch_index, _ = _as_tensor(batch_index, "batch_index")
-            if batch_index.dim() != 1 or batch_index.shape[0] != v:
-                raise ValueError("batch_index must be a [V] tensor, one value per row of coords")
-            if batch_index.dtype not in (torch.int64, torch.int32):
-                raise ValueError("batch_index must be int64 or int32, not %s" % batch_index.dtype)
+        coords, batch_index, v = _check_coords(coords, batch_index)
         ks, st = _triple(kernel_size, "kernel_size"), _triple(stride, "stride")
         pad, dil = _triple(padding, "padding"), _triple(dilation, "dilation")
         if any(k < 1 or k > 7 for k in ks):
@@ -137,96 +127,6 @@ class SparseConvMap:
         self._down = _TableView(self.table_out, v, k, dev)               # output rows read input rows
         self._up = _TableView(self.table_in, vout, k, dev)               # input rows read output rows
 
-    def _on(self, t):
-        if t.is_cuda and t.device != self.device:
-            raise ValueError("features live on %s, the SparseConvMap on %s" % (t.device, self.device))
-
-
-class TableConv(torch.autograd.Function):
-    """out[r] = sum_k features[fwd.table[r, k]] @ weight[k] (+ bias) for two tables that are each other's transposed map
-    (fwd.table[r, k] == v <=> bwd.table[v, k] == r).  Per chunk of rows one gather [R, K * Cin] and GEMMs of a fixed row count with
-    weight [K * Cin, Cout] (conv._gather_times).  backward: grad_features = the gather of grad_out through bwd.table, UNMIRRORED,
-    [R', K * Cout] times weight^T [K * Cout, Cin]; grad_weight = the sum over the chunks of fwd, in chunk order, of gathered^T @
-    grad_out (the gather is made again, not kept); grad_bias = the column sum.  Differentiable once."""
-
-    @staticmethod
-    def forward(ctx, features, fwd, bwd, weight, bias, chunk_fwd, chunk_bwd):
-        dev, odev = fwd.device, features.device
-        k, cin, cout = weight.shape
-        f = features.detach().to(dev).contiguous()
-        w = weight.detach().to(dev).contiguous()
-        with torch.cuda.device(dev):
-            out = torch.empty((fwd.num_voxels, cout), dtype=f.dtype, device=dev)
-            for r0, r in _chunks(fwd.num_voxels, chunk_fwd):
-                _gather_times(f, fwd, False, r0, r, w.view(k * cin, cout), out)
-            if bias is not None:
-                out += bias.detach().to(dev)
-        ctx.fwd, ctx.bwd, ctx.chunks, ctx.odev, ctx.has_bias = fwd, bwd, (chunk_fwd, chunk_bwd), odev, bias is not None
-        ctx.wdev, ctx.bdev = weight.device, bias.device if bias is not None else None
-        ctx.save_for_backward(f, w)
-        return _lib.to_caller(out, odev, dev)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad):
-        f, w = ctx.saved_tensors
-        fwd, bwd, dev = ctx.fwd, ctx.bwd, ctx.fwd.device
-        k, cin, cout = w.shape
-        g = grad.to(dev).contiguous()
-        need_f, _, _, need_w, need_b, _, _ = ctx.needs_input_grad
-        gf = gw = gb = None
-        with torch.cuda.device(dev):
-            if need_f:
-                gf = torch.empty_like(f)
-                wt = w.transpose(1, 2).reshape(k * cout, cin)
-                for v0, r in _chunks(bwd.num_voxels, ctx.chunks[1]):
-                    _gather_times(g, bwd, False, v0, r, wt, gf)
-            if need_w:
-                gw = torch.zeros((k * cin, cout), dtype=w.dtype, device=dev)
-                for r0, r in _chunks(fwd.num_voxels, ctx.chunks[0]):
-                    gw += torch.matmul(_gather(f, fwd, False, r0, r).view(r, k * cin).t(), g[r0:r0 + r])
-            if ctx.has_bias and need_b:
-                gb = g.sum(0)
-        if need_f:
-            gf = _lib.to_caller(gf, ctx.odev, dev)
-        if need_w:
-            gw = _lib.to_caller(gw.view(k, cin, cout), ctx.wdev, dev)
-        if gb is not None:
-            gb = _lib.to_caller(gb, ctx.bdev, dev)
-        return gf, None, None, gw, gb, None, None
-
-
-def _table_conv(features, cmap, fwd, bwd, weight, bias, chunk_rows, method):
-    if not isinstance(cmap, SparseConvMap):
-        raise TypeError("cmap must be a SparseConvMap")
-    features, was_numpy = _as_tensor(features, "features")
-    weight, _ = _as_tensor(weight, "weight")
-    if features.dim() != 2:
-        raise ValueError("features must be a 2-D tensor of one row per voxel")
-    _conv_dtype(features)
-    if features.shape[0] != fwd.src_rows:
-        raise ValueError("features has %d rows, the SparseConvMap %d on that side" % (features.shape[0], fwd.src_rows))
-    cmap._on(features)
-    if weight.dim() != 3 or weight.shape[0] != cmap.kernel_volume or weight.shape[1] != features.shape[1]:
-        raise ValueError("weight must be [K, Cin, Cout] = [%d, %d, Cout], not %s" % (cmap.kernel_volume, features.shape[1], tuple(weight.shape)))
-    if weight.dtype != features.dtype:
-        raise ValueError("weight is %s, features %s" % (weight.dtype, features.dtype))
-    if bias is not None:
-        bias, _ = _as_tensor(bias, "bias")
-        if bias.dim() != 1 or bias.shape[0] != weight.shape[2] or bias.dtype != features.dtype:
-            raise ValueError("bias must be [Cout] = [%d] in the dtype of features" % weight.shape[2])
-    if chunk_rows is not None:
-        chunk_rows = int(chunk_rows)
-        if chunk_rows < 1:
-            raise ValueError("chunk_rows must be at least 1")
-    cin, cout, size = weight.shape[1], weight.shape[2], features.element_size()
-    if _conv_route(features, weight, method) == "fused":
-        out = FusedTableConv.apply(features, fwd, bwd, False, weight, bias)
-    else:
-        out = TableConv.apply(features, fwd, bwd, weight, bias, _chunk_rows(chunk_rows, fwd, cin, cout, size),
-                              _chunk_rows(chunk_rows, bwd, cin, cout, size))
-    return out.detach().numpy() if was_numpy else out
-
 
 def sparse_conv3d(features, cmap, weight, bias=None, chunk_rows=None, method=None):
     """Strided sparse convolution: out[r] = sum over k of features[table_out[r, k]] @ weight[k] (+ bias), on the active outputs only.
@@ -245,14 +145,17 @@ def sparse_conv3d(features, cmap, weight, bias=None, chunk_rows=None, method=Non
         active outputs.  Gradients: grad_features[v] = sum_k grad_out[table_in[v, k]] @ weight[k]^T (a gather through table_in, no
         mirroring), grad_weight = the sum over the chunks, in chunk order, of gathered^T @ grad_out, grad_bias = the column sum
     """
-    return _table_conv(features, cmap, getattr(cmap, "_down", None), getattr(cmap, "_up", None), weight, bias, chunk_rows, method)
+    if not isinstance(cmap, SparseConvMap):
+        raise TypeError("cmap must be a SparseConvMap")
+    return _conv_front(features, cmap, cmap._down, cmap._up, False, weight, bias, chunk_rows, method)
 
 
 def sparse_inverse_conv3d(features, cmap, weight, bias=None, chunk_rows=None, method=None):
     """Inverse sparse convolution (spconv's SparseInverseConv3d): out[v] = sum over k of features[table_in[v, k]] @ weight[k]
     (+ bias) -- conv_transpose3d of the output-side rows, evaluated on the ORIGINAL input sites of `cmap`.
 
-    :param features: [Vout, Cin] float32 or float64, one row per cmap.out_coords; torch tensor (GPU or host) or numpy array
+    :param features: [Vout, Cin] float32, float64, float16 or bfloat16 (half precision: `method`), one row per cmap.out_coords; torch
+        tensor (GPU or host) or numpy array; differentiable (once)
     :param cmap: the SparseConvMap of the strided layer this one undoes
     :param weight: [K, Cin, Cout] in the tables' column order (a conv_transpose3d weight [Cin, Cout, kx, ky, kz] is
         weight.permute(2, 3, 4, 0, 1).reshape(K, Cin, Cout)); differentiable
@@ -260,7 +163,9 @@ def sparse_inverse_conv3d(features, cmap, weight, bias=None, chunk_rows=None, me
     :return: [V, Cout] on the side features came from; row v belongs to the coords[v] cmap was built from.  Its backward runs
         through table_out the same way
     """
-    return _table_conv(features, cmap, getattr(cmap, "_up", None), getattr(cmap, "_down", None), weight, bias, chunk_rows, method)
+    if not isinstance(cmap, SparseConvMap):
+        raise TypeError("cmap must be a SparseConvMap")
+    return _conv_front(features, cmap, cmap._up, cmap._down, False, weight, bias, chunk_rows, method)
 
 
-__all__ = ["SparseConvMap", "sparse_conv3d", "sparse_inverse_conv3d", "TableConv"]
+__all__ = ["SparseConvMap", "sparse_conv3d", "sparse_inverse_conv3d"]

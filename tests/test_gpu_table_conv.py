@@ -1,6 +1,7 @@
 """GPU: the fused table convolution (csrc/vconv.hip; method="fused" of subm_conv3d / sparse_conv3d / sparse_inverse_conv3d) against
 the fp64 model of table_conv_reference.py: bit for bit on integer data, within the fp32-accumulation bound on random data, the same
-bits for a row wherever it sits and on every run, and the routing of `method`."""
+bits for a row wherever it sits and on every run, the routing of `method`, and one list of malformed calls that all three operators
+refuse alike."""
 import functools
 
 import numpy as np
@@ -10,6 +11,7 @@ import torch
 import sparse_conv_cases as scases
 import table_conv_cases as cases
 import table_conv_reference as ref
+import voxel_conv_cases as vcases
 import voxel_conv_reference as vref
 
 pytestmark = pytest.mark.gpu
@@ -185,6 +187,46 @@ def test_refusals():
     with pytest.raises(ValueError):
         fn(x.to(torch.int32), w.to(torch.int32))
     assert fn(x.bfloat16(), w.bfloat16()).dtype == torch.bfloat16 and fn(x.half(), w.half(), method="fused").dtype == torch.float16
+
+
+BOTH = ("gather", "fused")
+# (what is wrong, the exception, the methods it is tried with, (x [rows, 16], w [27, 16, 32], b [32], all fp32) -> (features, weight, bias, kw))
+MALFORMED = (
+    ("features 1-D", ValueError, BOTH, lambda x, w, b: (x[:, 0], w, b, {})),
+    ("features of one row too few", ValueError, BOTH, lambda x, w, b: (x[:-1], w, b, {})),
+    ("features int32", ValueError, BOTH, lambda x, w, b: (x.to(torch.int32), w, b, {})),
+    ("weight with K - 1 slices", ValueError, BOTH, lambda x, w, b: (x, w[:-1], b, {})),
+    ("weight with Cin + 1", ValueError, BOTH, lambda x, w, b: (x, torch.cat([w, w[:, :1]], 1), b, {})),
+    ("weight in another dtype", ValueError, BOTH, lambda x, w, b: (x, w.double(), b, {})),
+    ("bias of Cout + 1", ValueError, BOTH, lambda x, w, b: (x, w, torch.cat([b, b[:1]]), {})),
+    ("bias in another dtype", ValueError, BOTH, lambda x, w, b: (x, w, b.double(), {})),
+    ("chunk_rows = 0", ValueError, BOTH, lambda x, w, b: (x, w, b, {"chunk_rows": 0})),
+    ("an unknown method", ValueError, ("mfma",), lambda x, w, b: (x, w, b, {})),
+    ("fp64 on the fused route", ValueError, ("fused",), lambda x, w, b: (x.double(), w.double(), b.double(), {})),
+    ("fp16 on the gather route", ValueError, ("gather",), lambda x, w, b: (x.half(), w.half(), b.half(), {})),
+    ("Cin = 24 on the fused route", ValueError, ("fused",), lambda x, w, b: (torch.cat([x, x[:, :8]], 1), torch.cat([w, w[:, :8]], 1), b, {})),
+    ("host features with a weight that is no tensor", TypeError, BOTH, lambda x, w, b: (x.cpu(), w.tolist(), b, {})),
+)
+
+
+def test_one_argument_check_serves_all_three_operators():
+    """every malformed call is refused with the same exception type by subm_conv3d, sparse_conv3d and sparse_inverse_conv3d, on
+    both routes where the call leaves the route open; the well-formed call passes on each"""
+    from d3d_amd.voxel import SparseConvMap, VoxelNeighbors, sparse_conv3d, sparse_inverse_conv3d, subm_conv3d
+    coords = T(vcases.fill((5, 5, 5), 60, 12))
+    nbrs, cmap = VoxelNeighbors(coords, 3), SparseConvMap(coords, 3, 2, 1)
+    w, b = torch.ones((27, 16, 32), device="cuda"), torch.ones(32, device="cuda")
+    for op, owner, rows, out_rows in ((subm_conv3d, nbrs, 60, 60), (sparse_conv3d, cmap, 60, cmap.num_out),
+                                      (sparse_inverse_conv3d, cmap, cmap.num_out, 60)):
+        x = torch.ones((rows, 16), device="cuda")
+        for method in BOTH:
+            assert op(x, owner, w, b, method=method).shape == (out_rows, 32)
+        for what, exception, methods, bend in MALFORMED:
+            for method in methods:
+                features, weight, bias, kw = bend(x, w, b)
+                with pytest.raises(exception):
+                    op(features, owner, weight, bias, method=method, **kw)
+                    pytest.fail("%s, method=%r: %s took it" % (what, method, op.__name__))
 
 
 def test_host_tensors_numpy_and_empty_inputs():
