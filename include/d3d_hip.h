@@ -1070,6 +1070,42 @@ int d3d_table_conv_wgrad(const void *feat, int64_t src_rows, int32_t cin, const 
                          const void *grad_out, int32_t cout, int32_t dtype, void *grad_weight, void *workspace, size_t workspace_bytes,
                          void *stream);
 
+/* ------------------------------------------------------------------ pooling through the tables of the sparse convolutions */
+
+/* out[r] = the sum / mean / max / min over the rows table[r, :] names (spconv's SparseMaxPool3d / SparseAvgPool3d) and its gradient
+ * (csrc/vtpool.hip), through the tables of d3d_voxel_neighbors and d3d_sparse_conv_map_emit.  One launch each, no workspace, no float
+ * atomics; the gathered [rows, k, c] buffer of d3d_neighbor_gather never exists.  The reference has no counterpart.
+ *
+ * dtype: D3D_F32, D3D_F64, D3D_F16 or D3D_BF16 (feat, out, grad_out and grad_feat in it); c >= 1, k in 1 .. 343; rows, src_rows and
+ *   out_rows at most 2^31 - 1.  reduction: D3D_REDUCE_MEAN / MAX / MIN, 4 = SUM as in d3d_voxel_pool_forward.  Offsets are 64-bit:
+ *   rows * c may pass 2^31.
+ * d3d_table_pool_forward: feat[src_rows, c], table[rows, k] int32 (entries in [-1, src_rows), trusted) -> out[rows, c]: the reduction
+ *   over the PRESENT entries of the row only (an absent neighbour is not a zero), column by column in ascending kk, by
+ *   d3d_voxel_pool_forward's rules.  SUM: 0 + x_0 + x_1 + ...; MEAN: that sum / (T)n, one IEEE division, n the present entries;
+ *   MAX / MIN: the first x > best (x < best) wins, a NaN wins over every number and the first NaN stays, -0.0 == +0.0.  D3D_F16 /
+ *   D3D_BF16: SUM and MEAN accumulate and divide in fp32 and round once, to nearest even, to the output type; MAX / MIN are exact
+ *   in every type.  arg (may be NULL; MAX / MIN only, ignored otherwise): [rows, c] int16, the winning column kk (int16: k goes to
+ *   343, a byte would wrap at kernel size 7).  count (may be NULL): [rows] int32, the present entries of the row.  A row without
+ *   present entries: out 0, arg -1, count 0.
+ * d3d_table_pool_backward: grad_out[out_rows, c], back_table[rows, k] int32 (entries in [-1, out_rows), trusted) ->
+ *   grad_feat[rows, c], every row written exactly once.  back_table is the transposed map of the forward's table: table_in for a
+ *   forward through table_out and the other way round (mirrored = 0), a d3d_voxel_neighbors table for itself with mirrored = 1.
+ *   Entry e = back_table[v, kk] >= 0 reached row v in the forward through column fk = mirrored ? k - 1 - kk : kk and contributes
+ *   grad_out[e] (SUM), grad_out[e] / (T)count[e] (MEAN), grad_out[e, ch] where arg[e, ch] == fk and nothing elsewhere (MAX / MIN);
+ *   the contributions are added to 0 in ascending kk.  D3D_F16 / D3D_BF16: contributions and sum in fp32, one rounding.  arg and
+ *   count: [out_rows, c] and [out_rows] as the forward wrote them; arg is read for MAX / MIN only, count for MEAN only.
+ * Rows move as 16-byte vectors when c is a multiple of 4 (f32) / 2 (f64) / 8 (f16, bf16) and feat, out, arg (grad_out, grad_feat,
+ *   arg) are 16-byte aligned, element by element otherwise: the same bits on both paths.  A row's bits depend on its table row and
+ *   on the rows that names only: not on its position in the launch, and not on the run.
+ * D3D_ERR_BAD_ARG: a negative size, c < 1, k < 1, a missing pointer (arg for a MAX / MIN backward and count for a MEAN backward
+ *   among them); D3D_ERR_UNSUPPORTED: another dtype or reduction code, k above 343, rows, src_rows or out_rows above 2^31 - 1.
+ *   None of them launches anything.  rows == 0 returns D3D_OK before any HIP call. */
+int d3d_table_pool_forward(const void *feat, int64_t src_rows, int32_t c, int32_t dtype, const int32_t *table, int64_t rows, int32_t k,
+                           int32_t reduction, void *out, int16_t *arg, int32_t *count, void *stream);
+int d3d_table_pool_backward(const void *grad_out, int64_t out_rows, int32_t c, int32_t dtype, const int32_t *back_table, int64_t rows,
+                            int32_t k, int32_t mirrored, int32_t reduction, const int16_t *arg, const int32_t *count,
+                            void *grad_feat, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
