@@ -42,6 +42,8 @@ template <> struct PrecOf<D3D_F32> { typedef Prec<float> type; };
 template <> struct PrecOf<D3D_F64> { typedef Prec<double> type; };
 template <> struct PrecOf<D3D_F64_M32> { typedef Prec<double, double, float> type; };      // fp64 boxes, fp32 matrix
 template <> struct PrecOf<D3D_F32_WIDE> { typedef Prec<double, float, float> type; };      // fp32 in memory, fp64 arithmetic
+template <> struct PrecOf<D3D_F16> { typedef Prec<_Float16> type; };
+template <> struct PrecOf<D3D_BF16> { typedef Prec<__bf16> type; };
 // dtype -> f(PrecOf<dtype>::type{}) for the codes a site handles (only those are instantiated), D3D_ERR_BAD_ARG for any other
 template <int... CODES, class F>
 static inline int dispatch_dtype(int dtype, F &&f)

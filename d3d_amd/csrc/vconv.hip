@@ -26,10 +26,7 @@
 //   go to the workspace; k_table_conv_fold adds the slabs in ascending order and rounds once.  No float atomics; every dependency
 //   is a kernel boundary; the order of every sum is fixed by the table and the sizes.
 #include <algorithm>
-#include "common.hpp"
-
-template <> struct PrecOf<D3D_F16> { typedef Prec<_Float16> type; };
-template <> struct PrecOf<D3D_BF16> { typedef Prec<__bf16> type; };
+#include "vrow.hpp"                         // (the alignment test and the row limit)
 
 namespace {
 
@@ -37,7 +34,6 @@ constexpr int kTcThreads = 256;
 constexpr int kTcTile = 128;                 // output rows of a workgroup (32 per wavefront)
 constexpr int kTcStageBytes = 128;           // input channels of a stage, in bytes
 constexpr int kTcRowStride = 144;            // an LDS row of a stage: 128 bytes + 16 (rows 36 banks apart)
-constexpr int64_t kTcMaxRows = 0x7fffffffll;
 constexpr int kWgPairsHalf = 128, kWgPairsF32 = 64;      // pairs of a wgrad batch
 constexpr int kWgStrideHalf = 272;           // bytes: 128 pairs x 2 + 16
 constexpr int kWgStrideF32 = 80;             // floats: 64 channels + 16 (rows 16 banks apart)
@@ -350,7 +346,6 @@ __global__ __launch_bounds__(kTcThreads) void k_table_conv_fold(const float *__r
     gw[i] = (T)s;
 }
 
-bool tc_aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 bool tc_channels_ok(int32_t c) { return c >= 16 && c <= 256 && c % 16 == 0; }
 
 // D3D_OK when the sizes and the dtype are served, the refusal otherwise (nothing touched either way)
@@ -358,7 +353,7 @@ int tc_check(int64_t src_rows, int32_t cin, int64_t rows, int32_t k, int32_t cou
 {
     if (src_rows < 0 || rows < 0 || k < 1 || cin < 1 || cout < 1) return D3D_ERR_BAD_ARG;
     if (dtype != D3D_F32 && dtype != D3D_F64 && dtype != D3D_F16 && dtype != D3D_BF16) return D3D_ERR_BAD_ARG;
-    if (dtype == D3D_F64 || !tc_channels_ok(cin) || !tc_channels_ok(cout) || k > 343 || rows > kTcMaxRows || src_rows > kTcMaxRows)
+    if (dtype == D3D_F64 || !tc_channels_ok(cin) || !tc_channels_ok(cout) || k > 343 || rows > kRowMax || src_rows > kRowMax)
         return D3D_ERR_UNSUPPORTED;
     return D3D_OK;
 }
@@ -373,7 +368,7 @@ extern "C" int d3d_table_conv(const void *feat, int64_t src_rows, int32_t cin, c
     if (rc != D3D_OK) return rc;
     if (rows == 0) return D3D_OK;
     if (!table || !out || !weight || (src_rows > 0 && !feat)) return D3D_ERR_BAD_ARG;
-    const int32_t al = tc_aligned16(feat) && tc_aligned16(weight);
+    const int32_t al = row_aligned16(feat) && row_aligned16(weight);
     return dispatch_dtype<D3D_F32, D3D_F16, D3D_BF16>(dtype, [&](auto p) {
         typedef typename decltype(p)::T T;
         const int nt = cout <= 16 ? 1 : cout <= 32 ? 2 : cout <= 64 ? 4 : cout <= 128 ? 8 : 16;
@@ -389,7 +384,7 @@ extern "C" int d3d_table_conv(const void *feat, int64_t src_rows, int32_t cin, c
 
 extern "C" size_t d3d_table_conv_wgrad_workspace_bytes(int64_t rows, int32_t k, int32_t cin, int32_t cout)
 {
-    if (rows < 1 || rows > kTcMaxRows || k < 1 || k > 343 || !tc_channels_ok(cin) || !tc_channels_ok(cout)) return 0;
+    if (rows < 1 || rows > kRowMax || k < 1 || k > 343 || !tc_channels_ok(cin) || !tc_channels_ok(cout)) return 0;
     return d3d_align_up((size_t)wg_plan(rows, k, cin, cout).slabs * k * cin * cout * sizeof(float));
 }
 
@@ -409,7 +404,7 @@ extern "C" int d3d_table_conv_wgrad(const void *feat, int64_t src_rows, int32_t 
     if (!table || !grad_out || (src_rows > 0 && !feat)) return D3D_ERR_BAD_ARG;
     if (!workspace || workspace_bytes < d3d_table_conv_wgrad_workspace_bytes(rows, k, cin, cout)) return D3D_ERR_WORKSPACE;
     const WgPlan plan = wg_plan(rows, k, cin, cout);
-    const int32_t al = tc_aligned16(feat) && tc_aligned16(grad_out);
+    const int32_t al = row_aligned16(feat) && row_aligned16(grad_out);
     const int ci_tiles = (cin + 63) / 64, co_tiles = (cout + 63) / 64;
     return dispatch_dtype<D3D_F32, D3D_F16, D3D_BF16>(dtype, [&](auto p) {
         typedef typename decltype(p)::T T;

@@ -7,10 +7,10 @@
 //
 // The table: three launches, every dependency a kernel boundary (no workgroup waits on another inside a launch).
 //   k_vn_bounds  min / max of every axis and of the batch value: integer atomicMax, one per wavefront and quantity (vkey.hpp: shared
-//                with vstride.hip, as the hash is)
-//   k_vn_insert  key = mixed radix over the measured spans (one 64-bit number per voxel, below 2^62) into an open-addressing table
-//                (power-of-two capacity >= 2V, linear probing, {key, row} in one 16-byte slot): atomicCAS on the key, the winner
-//                stores its row; an equal key already there is a duplicate
+//                with vstride.hip, as the table is)
+//   k_vn_insert  key = mixed radix over the measured spans (one 64-bit number per voxel, below 2^62) into the open-addressing table
+//                of vkey.hpp, {key, row} in one 16-byte slot: who claims the key stores its row; an equal key already there is a
+//                duplicate
 //   k_vn_lookup  one lane per (voxel, column), the column fastest: a wavefront's stores to `table` are contiguous.  A neighbour
 //                outside the measured box is absent without a probe, so a shifted key never aliases another row; the centre is
 //                the row itself, without a probe
@@ -19,12 +19,12 @@
 // gather through the mirrored columns: forward and backward are gathers, nothing is scattered, no float atomics.
 #include <algorithm>
 #include "vkey.hpp"
+#include "vrow.hpp"
 
 namespace {
 
 constexpr int64_t kNbrLookupBlocks = 1ll << 24;
 constexpr int64_t kNbrGatherBlocks = 1ll << 30;
-constexpr int64_t kNbrMaxV = 0x7fffffffll;             // rows are int32
 
 struct alignas(16) NbrSlot {
     unsigned long long key;
@@ -44,8 +44,7 @@ struct NbrWs {
 NbrWs nbr_carve(WsCarver &w, int64_t v)
 {
     NbrWs r;
-    r.log2cap = 6;
-    while ((1ll << r.log2cap) < 2 * v) r.log2cap++;
+    r.log2cap = nbr_log2cap((unsigned long long)v);
     r.bounds = w.take<unsigned long long>(8);
     r.slots = w.take<NbrSlot>((size_t)1 << r.log2cap);
     return r;
@@ -71,7 +70,8 @@ __device__ __forceinline__ NbrFrame nbr_frame(const unsigned long long *__restri
             f.span[a] = 1;
             continue;
         }
-        const unsigned long long hi = bounds[2 * a], lo = ~bounds[2 * a + 1];
+        unsigned long long lo, hi;
+        nbr_axis(bounds, a, lo, hi);
         f.lo[a] = lo ^ kNbrSign;
         f.span[a] = hi - lo + 1;                                        // 0: the whole int64 range
         if (f.span[a] == 0 || f.span[a] > kNbrSpanLimit / prod) f.overflow = true;
@@ -94,19 +94,10 @@ __global__ __launch_bounds__(kNbrThreads) void k_vn_insert(const int64_t *__rest
     if (i < v) {
         const unsigned long long r[4] = {f.rel(0, coords[i * 3]), f.rel(1, coords[i * 3 + 1]), f.rel(2, coords[i * 3 + 2]),
                                          batch ? f.rel(3, batch[i]) : 0ull};
-        const unsigned long long key = f.key(r), mask = (1ull << log2cap) - 1;
-        unsigned long long h = nbr_hash(key, log2cap);
-        for (unsigned long long n = 0; n <= mask; n++, h = (h + 1) & mask) {      // (at most V <= capacity / 2 slots are ever taken)
-            const unsigned long long old = atomicCAS(&slots[h].key, kNbrEmpty, key);
-            if (old == kNbrEmpty) {
-                slots[h].row = (int32_t)i;
-                break;
-            }
-            if (old == key) {
-                dup = true;
-                break;
-            }
-        }
+        bool fresh = false;
+        const int64_t h = nbr_claim(slots, f.key(r), log2cap, fresh);
+        if (h >= 0 && fresh) slots[h].row = (int32_t)i;
+        dup = h >= 0 && !fresh;                                         // (the key was there: the same batch value and coordinate)
     }
     const unsigned long long b = __ballot(dup);
     if (b && (threadIdx.x & (kWave - 1)) == 0) atomicAdd((unsigned long long *)&counts[1], (unsigned long long)__popcll(b));
@@ -119,9 +110,8 @@ __global__ __launch_bounds__(kNbrThreads) void k_vn_lookup(const int64_t *__rest
 {
     const NbrFrame f = nbr_frame(bounds, batch != nullptr);
     if (f.overflow) return;
-    const uint32_t kyz = (uint32_t)(s.k[1] * s.k[2]), K = (uint32_t)s.k[0] * kyz, centre = (K - 1) / 2;
+    const uint32_t K = (uint32_t)(s.k[0] * s.k[1] * s.k[2]), centre = (K - 1) / 2;
     const int64_t n = v * (int64_t)K;
-    const unsigned long long mask = (1ull << log2cap) - 1;
     unsigned long long found = 0;
     // (every lane of a workgroup makes the same number of trips: the sum below runs on whole wavefronts)
     for (int64_t base = (int64_t)blockIdx.x * kNbrThreads; base < n; base += (int64_t)gridDim.x * kNbrThreads) {
@@ -133,7 +123,8 @@ __global__ __launch_bounds__(kNbrThreads) void k_vn_lookup(const int64_t *__rest
         int32_t e = -1;
         if (k == centre) e = (int32_t)vi;
         else {
-            const int32_t ik[3] = {(int32_t)(k / kyz), (int32_t)(k % kyz) / s.k[2], (int32_t)(k % kyz) % s.k[2]};
+            int32_t ik[3];
+            nbr_column(k, s.k, ik);
             unsigned long long r[4];
             bool inside = true;
 #pragma unroll
@@ -145,16 +136,8 @@ __global__ __launch_bounds__(kNbrThreads) void k_vn_lookup(const int64_t *__rest
             }
             if (inside) {
                 r[3] = batch ? f.rel(3, batch[vi]) : 0ull;
-                const unsigned long long key = f.key(r);
-                unsigned long long h = nbr_hash(key, log2cap);
-                for (unsigned long long t = 0; t <= mask; t++, h = (h + 1) & mask) {
-                    const NbrSlot sl = slots[h];
-                    if (sl.key == key) {
-                        e = sl.row;
-                        break;
-                    }
-                    if (sl.key == kNbrEmpty) break;
-                }
+                NbrSlot sl;
+                if (nbr_find(slots, f.key(r), log2cap, sl) >= 0) e = sl.row;
             }
         }
         table[vi * K + k] = e;
@@ -165,8 +148,6 @@ __global__ __launch_bounds__(kNbrThreads) void k_vn_lookup(const int64_t *__rest
 }
 
 // ---------------------------------------------------------------- the gather
-template <typename T, int N> struct alignas(sizeof(T) * N) NbrPack { T v[N]; };
-
 // One lane group (1 << group_log2 lanes) per output row j = r * K + k, lane g of it on the VEC channels from g * VEC, then from
 // (g + group) * VEC, ...  The source row: feat[e] (feat_cols == 1) or feat[e, k] (feat_cols == K: feat is [V, K, C]), with
 // e = table[r, mirrored ? K - 1 - k : k]; a zero row for e == -1.
@@ -175,7 +156,7 @@ __global__ __launch_bounds__(kNbrThreads) void k_nbr_gather(const T *__restrict_
                                                             int32_t K, int32_t c, int32_t feat_cols, int32_t mirrored, int group_log2,
                                                             int64_t nblk, T *__restrict__ out)
 {
-    typedef NbrPack<T, VEC> P;
+    typedef RowPack<T, VEC> P;
     const int per_block = kNbrThreads >> group_log2, g = (int)(threadIdx.x & ((1u << group_log2) - 1)), step = VEC << group_log2;
     for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
         const int64_t j0 = blk * per_block, r0 = j0 / K;               // one 64-bit division per workgroup and trip
@@ -196,17 +177,6 @@ __global__ __launch_bounds__(kNbrThreads) void k_nbr_gather(const T *__restrict_
     }
 }
 
-// the lane group of a row of c channels in units of vec: the smallest power of two >= ceil(c / vec), at most a wavefront
-int nbr_group_log2(int32_t c, int vec)
-{
-    const int64_t units = d3d_divup(c, vec);
-    int g = 0;
-    while (g < 6 && (1ll << g) < units) g++;
-    return g;
-}
-
-bool nbr_aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
-
 bool nbr_shape_ok(const NbrShape &s)
 {
     for (int a = 0; a < 3; a++)
@@ -219,7 +189,7 @@ bool nbr_shape_ok(const NbrShape &s)
 extern "C" size_t d3d_voxel_neighbors_workspace_bytes(int64_t v)
 {
     WsCarver w(nullptr, 0);
-    nbr_carve(w, std::min(std::max<int64_t>(v, 0), kNbrMaxV));
+    nbr_carve(w, std::min(std::max<int64_t>(v, 0), kRowMax));
     return w.off;
 }
 
@@ -230,7 +200,7 @@ extern "C" int d3d_voxel_neighbors(const int64_t *coords, const int64_t *batch, 
     hipStream_t st = (hipStream_t)stream;
     const NbrShape s{{kx, ky, kz}, {dx, dy, dz}};
     if (v < 0 || !counts || !nbr_shape_ok(s) || (v > 0 && (!coords || !table))) return D3D_ERR_BAD_ARG;
-    if (v > kNbrMaxV) return D3D_ERR_UNSUPPORTED;
+    if (v > kRowMax) return D3D_ERR_UNSUPPORTED;
     WsCarver w(workspace, workspace_bytes);
     const NbrWs ws = nbr_carve(w, v);
     if (v > 0 && (!workspace || !w.ok())) return D3D_ERR_WORKSPACE;
@@ -253,20 +223,14 @@ extern "C" int d3d_neighbor_gather(const void *feat, int64_t v, int32_t c, int32
 {
     hipStream_t st = (hipStream_t)stream;
     if (v < 0 || r < 0 || c < 1 || k < 1 || (feat_cols != 1 && feat_cols != k)) return D3D_ERR_BAD_ARG;
-    if ((dtype != D3D_F32 && dtype != D3D_F64) || v > kNbrMaxV || k > 343 || r > kNbrMaxV) return D3D_ERR_UNSUPPORTED;
+    if ((dtype != D3D_F32 && dtype != D3D_F64) || v > kRowMax || k > 343 || r > kRowMax) return D3D_ERR_UNSUPPORTED;
     if (r == 0) return D3D_OK;
     if (!table || !out || (v > 0 && !feat)) return D3D_ERR_BAD_ARG;
-    return dispatch_dtype<D3D_F32, D3D_F64>(dtype, [&](auto p) {
+    return row_dispatch<D3D_F32, D3D_F64>(dtype, c, row_aligned16(feat) && row_aligned16(out), [&](auto p, auto vec, int gl) {
         typedef typename decltype(p)::T T;
-        constexpr int W = 16 / (int)sizeof(T);
-        const bool vec = c % W == 0 && nbr_aligned16(feat) && nbr_aligned16(out);
-        const int gl = nbr_group_log2(c, vec ? W : 1);
         const int64_t rows = r * k, nblk = d3d_divup(rows, kNbrThreads >> gl);
-        return dispatch(vec, [&](auto wide) {
-            constexpr int VEC = decltype(wide)::value ? W : 1;
-            D3D_LAUNCH("k_nbr_gather", (k_nbr_gather<T, VEC>), dim3((unsigned)std::min(nblk, kNbrGatherBlocks)), dim3(kNbrThreads), 0, st,
-                       (const T *)feat, table, rows, k, c, feat_cols, mirrored, gl, nblk, (T *)out);
-            return D3D_OK;
-        });
+        D3D_LAUNCH("k_nbr_gather", (k_nbr_gather<T, decltype(vec)::value>), dim3((unsigned)std::min(nblk, kNbrGatherBlocks)), dim3(kNbrThreads), 0,
+                   st, (const T *)feat, table, rows, k, c, feat_cols, mirrored, gl, nblk, (T *)out);
+        return D3D_OK;
     });
 }

@@ -12,16 +12,12 @@
 // depend on the fold, so four rows are in flight per step.  The backward pass / unpool is a gather, one lane group per point
 // row: every output row is written exactly once (a zero row for a point without a voxel), nothing is zeroed beforehand.
 #include <algorithm>
-#include "common.hpp"
+#include "vrow.hpp"
 
 namespace {
 
-constexpr int kPoolSum = 4;                   // the code d3d_voxelize_3d_reduce takes for SUM
 constexpr int kPoolThreads = 256;
 constexpr int kPoolAhead = 4;                 // rows in flight per lane and step of the fold
-constexpr int64_t kPoolMaxK = 0x7fffffffll;   // order and arg are int32
-
-template <typename T, int N> struct alignas(sizeof(T) * N) Pack { T v[N]; };
 
 // ---------------------------------------------------------------- the index
 // keys[i] = V - 1 - id for a mapped point (the argsort is DESCENDING and keeps ties in index order), -1 otherwise: after the
@@ -75,43 +71,25 @@ IndexWs index_carve(WsCarver &w, int64_t k, int64_t v)
 }
 
 // ---------------------------------------------------------------- forward
-// IS_MAX: the first point in point order with x > best wins (x < best for min); a NaN wins over every number and the FIRST NaN
-// stays; -0.0 == +0.0, so the earlier one stays.
-template <typename T, bool IS_MAX> __device__ __forceinline__ bool pool_takes(T best, T x)
-{
-    return !(best != best) & ((IS_MAX ? x > best : x < best) | (x != x));
-}
-
 // One lane group (1 << group_log2 lanes) per voxel, lane g of it on the VEC channels from g * VEC, then from
-// (g + group) * VEC, ... (a C the group does not cover in one pass).  Empty voxel: 0, arg -1.
+// (g + group) * VEC, ... (a C the group does not cover in one pass).  The rows are folded in point order by row_fold (vrow.hpp:
+// max / min name the winning point).  Empty voxel: 0, arg -1.
 template <typename T, int VEC, int RED, bool ARG>
 __global__ __launch_bounds__(kPoolThreads) void k_vpool_fwd(const T *__restrict__ feat, const int32_t *__restrict__ order,
                                                             const int64_t *__restrict__ offsets, int64_t v, int32_t c, int group_log2,
                                                             T *__restrict__ out, int32_t *__restrict__ arg)
 {
-    typedef Pack<T, VEC> P;
+    typedef RowPack<T, VEC> P;
     const int64_t t = (int64_t)blockIdx.x * kPoolThreads + threadIdx.x, vox = t >> group_log2;
     if (vox >= v) return;
     const int g = (int)(t & ((1 << group_log2) - 1)), step = VEC << group_log2;
     const int64_t beg = offsets[vox], end = offsets[vox + 1];
-    constexpr bool EXTREME = RED == D3D_REDUCE_MAX || RED == D3D_REDUCE_MIN;
     for (int c0 = g * VEC; c0 < c; c0 += step) {
         T acc[VEC];
         int32_t win[VEC];
 #pragma unroll
         for (int q = 0; q < VEC; q++) { acc[q] = 0; win[q] = -1; }
-        auto fold = [&](const P &x, int32_t p) {
-#pragma unroll
-            for (int q = 0; q < VEC; q++) {
-                if constexpr (EXTREME) {
-                    // two selects on one flag, no branch: as `if (take) { acc = x; win = p; }` hipcc 7.2 dropped the update of
-                    // win for the channels after the first (it kept `win < 0 ? p : win`)
-                    const bool take = (win[q] < 0) | pool_takes<T, RED == D3D_REDUCE_MAX>(acc[q], x.v[q]);
-                    acc[q] = take ? x.v[q] : acc[q];
-                    win[q] = take ? p : win[q];
-                } else acc[q] += x.v[q];
-            }
-        };
+        auto fold = [&](const P &x, int32_t p) { row_fold<RED>(acc, win, x, p); };
         int64_t j = beg;
         for (; j + kPoolAhead <= end; j += kPoolAhead) {
             int32_t p[kPoolAhead];
@@ -132,10 +110,10 @@ __global__ __launch_bounds__(kPoolThreads) void k_vpool_fwd(const T *__restrict_
         for (int q = 0; q < VEC; q++) o.v[q] = (RED == D3D_REDUCE_MEAN && end > beg) ? acc[q] / (T)(end - beg) : acc[q];
         *(P *)(out + vox * c + c0) = o;
         if constexpr (ARG) {
-            Pack<int32_t, VEC> w;
+            RowPack<int32_t, VEC> w;
 #pragma unroll
             for (int q = 0; q < VEC; q++) w.v[q] = win[q];
-            *(Pack<int32_t, VEC> *)(arg + vox * c + c0) = w;
+            *(RowPack<int32_t, VEC> *)(arg + vox * c + c0) = w;
         }
     }
 }
@@ -148,7 +126,7 @@ __global__ __launch_bounds__(kPoolThreads) void k_vpool_bwd(const T *__restrict_
                                                             const int64_t *__restrict__ offsets, const int32_t *__restrict__ arg,
                                                             int64_t k, int64_t v, int32_t c, int group_log2, T *__restrict__ grad_feat)
 {
-    typedef Pack<T, VEC> P;
+    typedef RowPack<T, VEC> P;
     const int64_t t = (int64_t)blockIdx.x * kPoolThreads + threadIdx.x, i = t >> group_log2;
     if (i >= k) return;
     const int g = (int)(t & ((1 << group_log2) - 1)), step = VEC << group_log2;
@@ -165,7 +143,7 @@ __global__ __launch_bounds__(kPoolThreads) void k_vpool_bwd(const T *__restrict_
         if (ok) {
             const P gv = *(const P *)(grad_out + m * c + c0);
             if constexpr (RED == D3D_REDUCE_MAX || RED == D3D_REDUCE_MIN) {
-                const Pack<int32_t, VEC> w = *(const Pack<int32_t, VEC> *)(arg + m * c + c0);
+                const RowPack<int32_t, VEC> w = *(const RowPack<int32_t, VEC> *)(arg + m * c + c0);
 #pragma unroll
                 for (int q = 0; q < VEC; q++) o.v[q] = (int64_t)w.v[q] == i ? gv.v[q] : (T)0;
             } else {
@@ -176,19 +154,6 @@ __global__ __launch_bounds__(kPoolThreads) void k_vpool_bwd(const T *__restrict_
         *(P *)(grad_feat + i * c + c0) = o;
     }
 }
-
-// the lane group of a row of c channels in units of vec: the smallest power of two >= ceil(c / vec), at most a wavefront
-int pool_group_log2(int32_t c, int vec)
-{
-    const int64_t units = d3d_divup(c, vec);
-    int g = 0;
-    while (g < 6 && (1ll << g) < units) g++;
-    return g;
-}
-
-bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
-
-bool pool_reduction_ok(int32_t r) { return r == D3D_REDUCE_MEAN || r == D3D_REDUCE_MAX || r == D3D_REDUCE_MIN || r == kPoolSum; }
 
 }  // namespace
 
@@ -204,7 +169,7 @@ extern "C" int d3d_voxel_index(const int64_t *mapping, int64_t k, int64_t v, int
 {
     hipStream_t st = (hipStream_t)stream;
     if (k < 0 || v < 0 || !offsets || !counts || (k > 0 && (!mapping || !order))) return D3D_ERR_BAD_ARG;
-    if (k > kPoolMaxK || v > kPoolMaxK) return D3D_ERR_UNSUPPORTED;
+    if (k > kRowMax || v > kRowMax) return D3D_ERR_UNSUPPORTED;
     WsCarver w(workspace, workspace_bytes);
     const IndexWs ws = index_carve(w, k, v);
     if (!workspace || !w.ok()) return D3D_ERR_WORKSPACE;
@@ -224,28 +189,20 @@ extern "C" int d3d_voxel_pool_forward(const void *feat, int64_t k, int32_t c, in
 {
     hipStream_t st = (hipStream_t)stream;
     if (k < 0 || v < 0 || c < 1) return D3D_ERR_BAD_ARG;
-    if (!pool_reduction_ok(reduction) || (dtype != D3D_F32 && dtype != D3D_F64) || k > kPoolMaxK || v > kPoolMaxK) return D3D_ERR_UNSUPPORTED;
+    if (!row_reduction_ok(reduction) || (dtype != D3D_F32 && dtype != D3D_F64) || k > kRowMax || v > kRowMax) return D3D_ERR_UNSUPPORTED;
     if (v == 0) return D3D_OK;
     if (!out || !offsets || (k > 0 && (!feat || !order))) return D3D_ERR_BAD_ARG;
     const bool extreme = reduction == D3D_REDUCE_MAX || reduction == D3D_REDUCE_MIN;
     if (!extreme) arg = nullptr;                 // (there is no winner to name)
-    return dispatch_dtype<D3D_F32, D3D_F64>(dtype, [&](auto p) {
+    const bool aligned = row_aligned16(feat) && row_aligned16(out) && row_aligned16(arg);
+    return row_dispatch<D3D_F32, D3D_F64>(dtype, c, aligned, reduction, [&](auto p, auto vec, auto red, int gl) {
         typedef typename decltype(p)::T T;
-        constexpr int W = 16 / (int)sizeof(T);
-        const bool vec = c % W == 0 && aligned16(feat) && aligned16(out) && aligned16(arg);
-        const int gl = pool_group_log2(c, vec ? W : 1);
-        const dim3 grid((unsigned)d3d_divup(v << gl, kPoolThreads));
-        return dispatch(vec, [&](auto wide) {
-            constexpr int VEC = decltype(wide)::value ? W : 1;
-            return dispatch_int<D3D_REDUCE_MEAN, D3D_REDUCE_MAX, D3D_REDUCE_MIN, kPoolSum>(reduction, [&](auto r) {
-                constexpr int RED = decltype(r)::value;
-                return dispatch(arg != nullptr, [&](auto a) {
-                    constexpr bool ARG = decltype(a)::value && (RED == D3D_REDUCE_MAX || RED == D3D_REDUCE_MIN);
-                    D3D_LAUNCH(ARG ? "k_vpool_fwd<arg>" : "k_vpool_fwd", (k_vpool_fwd<T, VEC, RED, ARG>), grid, dim3(kPoolThreads), 0, st,
-                               (const T *)feat, order, offsets, v, c, gl, (T *)out, arg);
-                    return D3D_OK;
-                });
-            });
+        constexpr int VEC = decltype(vec)::value, RED = decltype(red)::value;
+        return dispatch(arg != nullptr, [&](auto a) {
+            constexpr bool ARG = decltype(a)::value && (RED == D3D_REDUCE_MAX || RED == D3D_REDUCE_MIN);
+            D3D_LAUNCH(ARG ? "k_vpool_fwd<arg>" : "k_vpool_fwd", (k_vpool_fwd<T, VEC, RED, ARG>), dim3((unsigned)d3d_divup(v << gl, kPoolThreads)),
+                       dim3(kPoolThreads), 0, st, (const T *)feat, order, offsets, v, c, gl, (T *)out, arg);
+            return D3D_OK;
         });
     });
 }
@@ -255,25 +212,16 @@ extern "C" int d3d_voxel_pool_backward(const void *grad_out, int64_t v, int32_t 
 {
     hipStream_t st = (hipStream_t)stream;
     if (k < 0 || v < 0 || c < 1) return D3D_ERR_BAD_ARG;
-    if (!pool_reduction_ok(reduction) || (dtype != D3D_F32 && dtype != D3D_F64) || k > kPoolMaxK || v > kPoolMaxK) return D3D_ERR_UNSUPPORTED;
+    if (!row_reduction_ok(reduction) || (dtype != D3D_F32 && dtype != D3D_F64) || k > kRowMax || v > kRowMax) return D3D_ERR_UNSUPPORTED;
     if (k == 0) return D3D_OK;
     const bool extreme = reduction == D3D_REDUCE_MAX || reduction == D3D_REDUCE_MIN;
     if (!grad_feat || !mapping || (v > 0 && (!grad_out || (extreme && !arg) || (reduction == D3D_REDUCE_MEAN && !offsets))))
         return D3D_ERR_BAD_ARG;
-    return dispatch_dtype<D3D_F32, D3D_F64>(dtype, [&](auto p) {
+    const bool aligned = row_aligned16(grad_out) && row_aligned16(grad_feat) && (!extreme || row_aligned16(arg));
+    return row_dispatch<D3D_F32, D3D_F64>(dtype, c, aligned, reduction, [&](auto p, auto vec, auto red, int gl) {
         typedef typename decltype(p)::T T;
-        constexpr int W = 16 / (int)sizeof(T);
-        const bool vec = c % W == 0 && aligned16(grad_out) && aligned16(grad_feat) && (!extreme || aligned16(arg));
-        const int gl = pool_group_log2(c, vec ? W : 1);
-        const dim3 grid((unsigned)d3d_divup(k << gl, kPoolThreads));
-        return dispatch(vec, [&](auto wide) {
-            constexpr int VEC = decltype(wide)::value ? W : 1;
-            return dispatch_int<D3D_REDUCE_MEAN, D3D_REDUCE_MAX, D3D_REDUCE_MIN, kPoolSum>(reduction, [&](auto r) {
-                constexpr int RED = decltype(r)::value;
-                D3D_LAUNCH("k_vpool_bwd", (k_vpool_bwd<T, VEC, RED>), grid, dim3(kPoolThreads), 0, st, (const T *)grad_out, mapping, offsets,
-                           arg, k, v, c, gl, (T *)grad_feat);
-                return D3D_OK;
-            });
-        });
+        D3D_LAUNCH("k_vpool_bwd", (k_vpool_bwd<T, decltype(vec)::value, decltype(red)::value>), dim3((unsigned)d3d_divup(k << gl, kPoolThreads)),
+                   dim3(kPoolThreads), 0, st, (const T *)grad_out, mapping, offsets, arg, k, v, c, gl, (T *)grad_feat);
+        return D3D_OK;
     });
 }

@@ -9,11 +9,11 @@
 // Input i feeds output o through column k = (ix ky + iy) kz + iz when o * stride - padding + (ix,iy,iz) * dilation == i on every
 // axis; a pair (v, k) of an input row and a column that has such an o is a CANDIDATE, numbered c = v K + k.  Output rows are numbered
 // in the order of their FIRST candidate.  The launches, every dependency a kernel boundary (no workgroup waits on another):
-//   k_vn_bounds       min / max of every input axis and of the batch value (vkey.hpp, shared with vnbr.hip)
+//   k_vn_bounds       min / max of every input axis and of the batch value (vkey.hpp, shared with vnbr.hip, as the table is)
 //   k_sc_frame        one lane: the output box from the bounds (clipped by spatial_shape), its spans, the verdicts, the table's capacity
 //   k_sc_clear        the slots {key, first} of the open-addressing table <- all ones
-//   k_sc_insert       one lane per (v, k): the key of o over the OUTPUT box, atomicCAS on the key, then a 64-bit integer atomicMin of c
-//                     on the slot's second word: the winner is the first candidate whatever order the lanes arrive in
+//   k_sc_insert       one lane per (v, k): the key of o over the OUTPUT box, the claim of its slot (vkey.hpp), then a 64-bit integer
+//                     atomicMin of c on the slot's second word: the winner is the first candidate whatever order the lanes arrive in
 //   k_scan_count / k_scan_bsum (common.hpp) over the marks "c is its slot's minimum"  -> Vout               ... the host reads counts
 //   k_scan_apply      the first candidates write out_coords, out_batch and their row number into their slot
 //   k_sc_tables       one lane per (v, k), the column fastest: table_in[v,k] = row (-1: no candidate; contiguous stores), and the
@@ -21,10 +21,10 @@
 // Integer atomics only; the same result on every run.
 #include <algorithm>
 #include "vkey.hpp"
+#include "vrow.hpp"                                    // (the row limit)
 
 namespace {
 
-constexpr int64_t kScMaxRows = 0x7fffffffll;           // rows are int32
 constexpr int64_t kScBlocks = 1ll << 24;
 constexpr int kScClearBlocks = 4096;
 constexpr int32_t kScMaxStep = 1 << 24;                // stride, padding, dilation: their sums with a position stay far inside int64
@@ -60,8 +60,7 @@ struct ScWs {
 ScWs sc_carve(WsCarver &w, int64_t vp, int64_t n)
 {
     ScWs r;
-    r.log2cap = 6;
-    while ((1ll << r.log2cap) < 2 * vp) r.log2cap++;
+    r.log2cap = nbr_log2cap((unsigned long long)vp);
     r.bounds = w.take<unsigned long long>(8);
     r.frame = w.take<ScFrame>(1);
     r.slots = w.take<ScSlot>((size_t)1 << r.log2cap);
@@ -94,7 +93,9 @@ __global__ void k_sc_frame(const unsigned long long *__restrict__ bounds, int ha
     bool overflow = false, outside = false, empty = false;
 #pragma unroll                                                                            // (static indices: the frame stays in registers)
     for (int a = 0; a < 3; a++) {
-        const unsigned long long hi = bounds[2 * a], lo = ~bounds[2 * a + 1], ispan = hi - lo;      // max - min fits uint64
+        unsigned long long lo, hi;
+        nbr_axis(bounds, a, lo, hi);
+        const unsigned long long ispan = hi - lo;
         const int64_t imin = (int64_t)(lo ^ kNbrSign), imax = (int64_t)(hi ^ kNbrSign), st = s.s[a];
         f.ilo[a] = lo ^ kNbrSign;
         f.olo[a] = 0, f.span[a] = 0, f.base[a] = 0;
@@ -119,7 +120,8 @@ __global__ void k_sc_frame(const unsigned long long *__restrict__ bounds, int ha
     }
     f.ilo[3] = 0, f.span[3] = 1;
     if (has_batch) {
-        const unsigned long long hi = bounds[6], lo = ~bounds[7];
+        unsigned long long lo, hi;
+        nbr_axis(bounds, 3, lo, hi);
         f.ilo[3] = lo ^ kNbrSign;
         f.span[3] = hi - lo + 1;
         if (f.span[3] == 0) overflow = true;                                              // the whole int64 range
@@ -136,9 +138,7 @@ __global__ void k_sc_frame(const unsigned long long *__restrict__ bounds, int ha
     if (cells == 0)
 #pragma unroll
         for (int a = 0; a < 3; a++) f.span[a] = 0;                                        // nothing is a candidate
-    const unsigned long long most = cells < (unsigned long long)vp ? cells : (unsigned long long)vp;
-    f.log2cap = 6;
-    while ((1ull << f.log2cap) < 2 * most) f.log2cap++;
+    f.log2cap = nbr_log2cap(cells < (unsigned long long)vp ? cells : (unsigned long long)vp);
     f.refused = overflow || outside;
     *frame = f;
     if (overflow) counts[3] = 1;
@@ -177,8 +177,8 @@ __device__ __forceinline__ bool sc_candidate(const ScFrame &f, const ScShape &s,
                                              const int64_t *__restrict__ batch, int64_t v, uint32_t k, unsigned long long pos[3],
                                              unsigned long long &key)
 {
-    const uint32_t kyz = (uint32_t)(s.k[1] * s.k[2]);
-    const int32_t ik[3] = {(int32_t)(k / kyz), (int32_t)(k % kyz) / s.k[2], (int32_t)(k % kyz) % s.k[2]};
+    int32_t ik[3];
+    nbr_column(k, s.k, ik);
 #pragma unroll
     for (int a = 0; a < 3; a++) {
         // an input lies inside the measured box (below 2^62 from its start), base and the step are below 2^57: inside int64
@@ -201,22 +201,6 @@ __device__ __forceinline__ bool sc_candidate(const ScFrame &f, const ScShape &s,
     return true;
 }
 
-// the slot of a key that was inserted, -1 for one that was not; first: the slot's second word
-__device__ __forceinline__ int64_t sc_find(const ScSlot *slots, unsigned long long key, int log2cap, unsigned long long &first)
-{
-    const unsigned long long mask = (1ull << log2cap) - 1;
-    unsigned long long h = nbr_hash(key, log2cap);
-    for (unsigned long long t = 0; t <= mask; t++, h = (h + 1) & mask) {
-        const ScSlot sl = slots[h];
-        if (sl.key == key) {
-            first = sl.first;
-            return (int64_t)h;
-        }
-        if (sl.key == kNbrEmpty) break;
-    }
-    return -1;
-}
-
 __global__ __launch_bounds__(kNbrThreads) void k_sc_insert(const int64_t *__restrict__ coords, const int64_t *__restrict__ batch, int64_t v,
                                                            ScShape s, const ScFrame *__restrict__ frame, int max_log2cap,
                                                            ScSlot *__restrict__ slots, int64_t *__restrict__ counts)
@@ -225,7 +209,6 @@ __global__ __launch_bounds__(kNbrThreads) void k_sc_insert(const int64_t *__rest
     if (f.refused) return;
     const uint32_t K = (uint32_t)(s.k[0] * s.k[1] * s.k[2]);
     const int64_t n = v * (int64_t)K;
-    const unsigned long long mask = (1ull << f.log2cap) - 1;
     unsigned long long entries = 0;
     // (every lane of a workgroup makes the same number of trips: the sum below runs on whole wavefronts)
     for (int64_t base = (int64_t)blockIdx.x * kNbrThreads; base < n; base += (int64_t)gridDim.x * kNbrThreads) {
@@ -237,14 +220,9 @@ __global__ __launch_bounds__(kNbrThreads) void k_sc_insert(const int64_t *__rest
         unsigned long long pos[3], key;
         if (!sc_candidate(f, s, coords, batch, vi, k, pos, key)) continue;
         entries++;
-        unsigned long long h = nbr_hash(key, f.log2cap);
-        for (unsigned long long t = 0; t <= mask; t++, h = (h + 1) & mask) {      // (at most capacity / 2 slots are ever taken)
-            const unsigned long long old = atomicCAS(&slots[h].key, kNbrEmpty, key);
-            if (old == kNbrEmpty || old == key) {
-                atomicMin(&slots[h].first, (unsigned long long)c);
-                break;
-            }
-        }
+        bool fresh;
+        const int64_t h = nbr_claim(slots, key, f.log2cap, fresh);
+        if (h >= 0) atomicMin(&slots[h].first, (unsigned long long)c);
     }
     const unsigned long long total = wave_sum_u64(entries);
     if (total && (threadIdx.x & (kWave - 1)) == 0) atomicAdd((unsigned long long *)&counts[1], total);
@@ -268,10 +246,11 @@ struct ScNumber {
         if (f.refused) return -1;
         uint32_t k;
         sc_split(c, K, vi, k);
-        unsigned long long key, first;
+        unsigned long long key;
+        ScSlot sl;
         if (!sc_candidate(f, s, coords, batch, vi, k, pos, key)) return -1;
-        const int64_t h = sc_find(slots, key, f.log2cap, first);
-        return h >= 0 && first == (unsigned long long)c ? h : -1;
+        const int64_t h = nbr_find(slots, key, f.log2cap, sl);
+        return h >= 0 && sl.first == (unsigned long long)c ? h : -1;
     }
     __device__ unsigned long long value(int64_t c) const
     {
@@ -313,11 +292,12 @@ __global__ __launch_bounds__(kNbrThreads) void k_sc_tables(const int64_t *__rest
         int64_t vi;
         uint32_t k;
         sc_split(c, K, vi, k);
-        unsigned long long pos[3], key, row = ~0ull;
+        unsigned long long pos[3], key;
+        ScSlot sl;                                                      // (first: the output row by now)
         int32_t e = -1;
-        if (sc_candidate(f, s, coords, batch, vi, k, pos, key) && sc_find(slots, key, f.log2cap, row) >= 0 && row < (unsigned long long)num_out) {
-            e = (int32_t)row;
-            dups += atomicCAS(&table_out[(int64_t)row * K + k], -1, (int32_t)vi) != -1;
+        if (sc_candidate(f, s, coords, batch, vi, k, pos, key) && nbr_find(slots, key, f.log2cap, sl) >= 0 && sl.first < (unsigned long long)num_out) {
+            e = (int32_t)sl.first;
+            dups += atomicCAS(&table_out[(int64_t)sl.first * K + k], -1, (int32_t)vi) != -1;
         }
         table_in[c] = e;
     }
@@ -346,9 +326,9 @@ int sc_shape(int64_t v, const int32_t *ksz, const int32_t *stride, const int32_t
         if (room < 0) return D3D_ERR_BAD_ARG;                           // dense conv3d has no output on this axis
         s.out[a] = room / s.s[a] + 1;
     }
-    if (v > kScMaxRows) return D3D_ERR_UNSUPPORTED;
+    if (v > kRowMax) return D3D_ERR_UNSUPPORTED;
     const int64_t fan = sc_fanout(s);                                   // <= 343
-    if (v > kScMaxRows / fan) return D3D_ERR_UNSUPPORTED;
+    if (v > kRowMax / fan) return D3D_ERR_UNSUPPORTED;
     vp = v * fan;
     return D3D_OK;
 }

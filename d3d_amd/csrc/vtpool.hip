@@ -18,34 +18,14 @@
 // so a row's bits depend on its table row and the rows it names alone -- not on its position, the launch shape, the path (vector or
 // scalar) or the run.  Half types: sums in fp32, one rounding (to nearest even) at the store; max / min are exact in every type.
 #include <algorithm>
-#include "common.hpp"
-
-template <> struct PrecOf<D3D_F16> { typedef Prec<_Float16> type; };
-template <> struct PrecOf<D3D_BF16> { typedef Prec<__bf16> type; };
+#include "vrow.hpp"
 
 namespace {
 
-constexpr int kTpSum = 4;                     // the code d3d_voxel_pool_forward takes for SUM
 constexpr int kTpThreads = 256;
 constexpr int kTpAhead = 4;                   // rows in flight per lane and step of the walk
 constexpr int kTpEntries = 4;                 // table entries per lane and piece of the table row (tp_walk selects among exactly 4)
 constexpr int kTpMaxK = 343;                  // 7^3: arg is int16
-constexpr int64_t kTpMaxRows = 0x7fffffffll;  // table entries are int32
-
-template <typename T, int N> struct alignas(sizeof(T) * N) TpPack { T v[N]; };
-
-// the type the sums are kept in (and the comparisons made in: the conversion is exact and keeps the order, NaN and the zeros)
-template <typename T> struct TpAcc { typedef T type; };
-template <> struct TpAcc<_Float16> { typedef float type; };
-template <> struct TpAcc<__bf16> { typedef float type; };
-
-// d3d_voxel_pool_forward's rule: the first x > best wins (x < best for min); a NaN wins over every number and the FIRST NaN stays;
-// -0.0 == +0.0, so the earlier one stays
-// (two comparisons: !(x <= best) holds for x > best and for an unordered pair, best == best leaves the NaN already there alone)
-template <typename A, bool IS_MAX> __device__ __forceinline__ bool tp_takes(A best, A x)
-{
-    return (best == best) & !(IS_MAX ? x <= best : x >= best);
-}
 
 // The walk of one table row by its lane group (lane g of 1 << gl, the group's first lane of the wavefront lane0): load(e, a)
 // starts the loads of entry e into slot a, fold(kk, a) folds slot a as column kk; per step up to kTpAhead loads, then their folds,
@@ -94,15 +74,15 @@ __device__ __forceinline__ int tp_walk(const int32_t *__restrict__ trow, int K, 
 
 // ---------------------------------------------------------------- forward
 // Lane g of the group on the VEC channels from g * VEC, then from (g + group) * VEC, ... (a C the group does not cover in one
-// pass; the table row is walked once per pass).  A row without entries: 0, arg -1, count 0.
+// pass; the table row is walked once per pass).  The rows are folded in ascending column by row_fold (vrow.hpp: max / min name
+// the winning column).  A row without entries: 0, arg -1, count 0.
 template <typename T, int VEC, int RED, bool ARG>
 __global__ __launch_bounds__(kTpThreads) void k_tpool_fwd(const T *__restrict__ feat, const int32_t *__restrict__ table, int64_t rows,
                                                           int32_t K, int32_t c, int gl, T *__restrict__ out, int16_t *__restrict__ arg,
                                                           int32_t *__restrict__ count)
 {
-    typedef TpPack<T, VEC> P;
-    typedef typename TpAcc<T>::type A;
-    constexpr bool EXTREME = RED == D3D_REDUCE_MAX || RED == D3D_REDUCE_MIN;
+    typedef RowPack<T, VEC> P;
+    typedef typename RowAcc<T>::type A;
     const int64_t t = (int64_t)blockIdx.x * kTpThreads + threadIdx.x, r = t >> gl;
     if (r >= rows) return;                                                   // (whole groups leave: a row never spans two of them)
     const int g = (int)(t & ((1 << gl) - 1)), step = VEC << gl, lane0 = (int)(threadIdx.x & (kWave - 1)) & ~((1 << gl) - 1);
@@ -121,18 +101,7 @@ __global__ __launch_bounds__(kTpThreads) void k_tpool_fwd(const T *__restrict__ 
             for (int q = 0; q < VEC; q++) x[a].v[q] = 0;
         const int n = tp_walk(trow, K, g, gl, lane0,
             [&](int32_t e, int a) { if (live) x[a] = *(const P *)(feat + (int64_t)e * c + c0); },
-            [&](int kk, int a) {
-#pragma unroll
-                for (int q = 0; q < VEC; q++) {
-                    if constexpr (EXTREME) {
-                        // two selects on one flag, no branch (see k_vpool_fwd)
-                        const A xq = (A)x[a].v[q];
-                        const bool take = (win[q] < 0) | tp_takes<A, RED == D3D_REDUCE_MAX>(acc[q], xq);
-                        acc[q] = take ? xq : acc[q];
-                        win[q] = take ? kk : win[q];
-                    } else acc[q] += (A)x[a].v[q];
-                }
-            });
+            [&](int kk, int a) { row_fold<RED>(acc, win, x[a], kk); });
         if (count && cb == 0 && g == 0) count[r] = n;
         if (!live) continue;
         P o;
@@ -140,10 +109,10 @@ __global__ __launch_bounds__(kTpThreads) void k_tpool_fwd(const T *__restrict__ 
         for (int q = 0; q < VEC; q++) o.v[q] = (T)((RED == D3D_REDUCE_MEAN && n > 0) ? acc[q] / (A)n : acc[q]);
         *(P *)(out + r * c + c0) = o;
         if constexpr (ARG) {
-            TpPack<int16_t, VEC> w;
+            RowPack<int16_t, VEC> w;
 #pragma unroll
             for (int q = 0; q < VEC; q++) w.v[q] = (int16_t)win[q];
-            *(TpPack<int16_t, VEC> *)(arg + r * c + c0) = w;
+            *(RowPack<int16_t, VEC> *)(arg + r * c + c0) = w;
         }
     }
 }
@@ -157,9 +126,9 @@ __global__ __launch_bounds__(kTpThreads) void k_tpool_bwd(const T *__restrict__ 
                                                           int32_t K, int32_t c, int32_t mirrored, int gl, const int16_t *__restrict__ arg,
                                                           const int32_t *__restrict__ count, T *__restrict__ grad_feat)
 {
-    typedef TpPack<T, VEC> P;
-    typedef TpPack<int16_t, VEC> W;
-    typedef typename TpAcc<T>::type A;
+    typedef RowPack<T, VEC> P;
+    typedef RowPack<int16_t, VEC> W;
+    typedef typename RowAcc<T>::type A;
     constexpr bool EXTREME = RED == D3D_REDUCE_MAX || RED == D3D_REDUCE_MIN;
     const int64_t t = (int64_t)blockIdx.x * kTpThreads + threadIdx.x, r = t >> gl;
     if (r >= rows) return;
@@ -204,19 +173,6 @@ __global__ __launch_bounds__(kTpThreads) void k_tpool_bwd(const T *__restrict__ 
     }
 }
 
-// the lane group of a row of c channels in units of vec: the smallest power of two >= ceil(c / vec), at most a wavefront
-int tp_group_log2(int32_t c, int vec)
-{
-    const int64_t units = d3d_divup(c, vec);
-    int g = 0;
-    while (g < 6 && (1ll << g) < units) g++;
-    return g;
-}
-
-bool tp_aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
-
-bool tp_reduction_ok(int32_t r) { return r == D3D_REDUCE_MEAN || r == D3D_REDUCE_MAX || r == D3D_REDUCE_MIN || r == kTpSum; }
-
 bool tp_dtype_ok(int32_t d) { return d == D3D_F32 || d == D3D_F64 || d == D3D_F16 || d == D3D_BF16; }
 
 }  // namespace
@@ -226,28 +182,20 @@ extern "C" int d3d_table_pool_forward(const void *feat, int64_t src_rows, int32_
 {
     hipStream_t st = (hipStream_t)stream;
     if (src_rows < 0 || rows < 0 || c < 1 || k < 1) return D3D_ERR_BAD_ARG;
-    if (!tp_reduction_ok(reduction) || !tp_dtype_ok(dtype) || k > kTpMaxK || rows > kTpMaxRows || src_rows > kTpMaxRows) return D3D_ERR_UNSUPPORTED;
+    if (!row_reduction_ok(reduction) || !tp_dtype_ok(dtype) || k > kTpMaxK || rows > kRowMax || src_rows > kRowMax) return D3D_ERR_UNSUPPORTED;
     if (rows == 0) return D3D_OK;
     if (!table || !out || (src_rows > 0 && !feat)) return D3D_ERR_BAD_ARG;
     const bool extreme = reduction == D3D_REDUCE_MAX || reduction == D3D_REDUCE_MIN;
     if (!extreme) arg = nullptr;                 // (there is no winner to name)
-    return dispatch_dtype<D3D_F32, D3D_F64, D3D_F16, D3D_BF16>(dtype, [&](auto p) {
+    const bool aligned = row_aligned16(feat) && row_aligned16(out) && row_aligned16(arg);
+    return row_dispatch<D3D_F32, D3D_F64, D3D_F16, D3D_BF16>(dtype, c, aligned, reduction, [&](auto p, auto vec, auto red, int gl) {
         typedef typename decltype(p)::T T;
-        constexpr int W = 16 / (int)sizeof(T);
-        const bool vec = c % W == 0 && tp_aligned16(feat) && tp_aligned16(out) && tp_aligned16(arg);
-        const int gl = tp_group_log2(c, vec ? W : 1);
-        const dim3 grid((unsigned)d3d_divup(rows << gl, kTpThreads));
-        return dispatch(vec, [&](auto wide) {
-            constexpr int VEC = decltype(wide)::value ? W : 1;
-            return dispatch_int<D3D_REDUCE_MEAN, D3D_REDUCE_MAX, D3D_REDUCE_MIN, kTpSum>(reduction, [&](auto r) {
-                constexpr int RED = decltype(r)::value;
-                return dispatch(arg != nullptr, [&](auto a) {
-                    constexpr bool ARG = decltype(a)::value && (RED == D3D_REDUCE_MAX || RED == D3D_REDUCE_MIN);
-                    D3D_LAUNCH(ARG ? "k_tpool_fwd<arg>" : "k_tpool_fwd", (k_tpool_fwd<T, VEC, RED, ARG>), grid, dim3(kTpThreads), 0, st,
-                               (const T *)feat, table, rows, k, c, gl, (T *)out, arg, count);
-                    return D3D_OK;
-                });
-            });
+        constexpr int VEC = decltype(vec)::value, RED = decltype(red)::value;
+        return dispatch(arg != nullptr, [&](auto a) {
+            constexpr bool ARG = decltype(a)::value && (RED == D3D_REDUCE_MAX || RED == D3D_REDUCE_MIN);
+            D3D_LAUNCH(ARG ? "k_tpool_fwd<arg>" : "k_tpool_fwd", (k_tpool_fwd<T, VEC, RED, ARG>), dim3((unsigned)d3d_divup(rows << gl, kTpThreads)),
+                       dim3(kTpThreads), 0, st, (const T *)feat, table, rows, k, c, gl, (T *)out, arg, count);
+            return D3D_OK;
         });
     });
 }
@@ -258,25 +206,16 @@ extern "C" int d3d_table_pool_backward(const void *grad_out, int64_t out_rows, i
 {
     hipStream_t st = (hipStream_t)stream;
     if (out_rows < 0 || rows < 0 || c < 1 || k < 1) return D3D_ERR_BAD_ARG;
-    if (!tp_reduction_ok(reduction) || !tp_dtype_ok(dtype) || k > kTpMaxK || rows > kTpMaxRows || out_rows > kTpMaxRows) return D3D_ERR_UNSUPPORTED;
+    if (!row_reduction_ok(reduction) || !tp_dtype_ok(dtype) || k > kTpMaxK || rows > kRowMax || out_rows > kRowMax) return D3D_ERR_UNSUPPORTED;
     if (rows == 0) return D3D_OK;
     const bool extreme = reduction == D3D_REDUCE_MAX || reduction == D3D_REDUCE_MIN;
     if (!back_table || !grad_feat || (out_rows > 0 && (!grad_out || (extreme && !arg) || (reduction == D3D_REDUCE_MEAN && !count))))
         return D3D_ERR_BAD_ARG;
-    return dispatch_dtype<D3D_F32, D3D_F64, D3D_F16, D3D_BF16>(dtype, [&](auto p) {
+    const bool aligned = row_aligned16(grad_out) && row_aligned16(grad_feat) && (!extreme || row_aligned16(arg));
+    return row_dispatch<D3D_F32, D3D_F64, D3D_F16, D3D_BF16>(dtype, c, aligned, reduction, [&](auto p, auto vec, auto red, int gl) {
         typedef typename decltype(p)::T T;
-        constexpr int W = 16 / (int)sizeof(T);
-        const bool vec = c % W == 0 && tp_aligned16(grad_out) && tp_aligned16(grad_feat) && (!extreme || tp_aligned16(arg));
-        const int gl = tp_group_log2(c, vec ? W : 1);
-        const dim3 grid((unsigned)d3d_divup(rows << gl, kTpThreads));
-        return dispatch(vec, [&](auto wide) {
-            constexpr int VEC = decltype(wide)::value ? W : 1;
-            return dispatch_int<D3D_REDUCE_MEAN, D3D_REDUCE_MAX, D3D_REDUCE_MIN, kTpSum>(reduction, [&](auto r) {
-                constexpr int RED = decltype(r)::value;
-                D3D_LAUNCH("k_tpool_bwd", (k_tpool_bwd<T, VEC, RED>), grid, dim3(kTpThreads), 0, st, (const T *)grad_out, back_table, rows, k,
-                           c, mirrored, gl, arg, count, (T *)grad_feat);
-                return D3D_OK;
-            });
-        });
+        D3D_LAUNCH("k_tpool_bwd", (k_tpool_bwd<T, decltype(vec)::value, decltype(red)::value>), dim3((unsigned)d3d_divup(rows << gl, kTpThreads)),
+                   dim3(kTpThreads), 0, st, (const T *)grad_out, back_table, rows, k, c, mirrored, gl, arg, count, (T *)grad_feat);
+        return D3D_OK;
     });
 }

@@ -17,6 +17,8 @@ from torch.autograd.function import once_differentiable
 from .. import _lib
 
 _REDUCTIONS = {"sum": _lib.REDUCE_SUM, "mean": _lib.REDUCE_MEAN, "max": _lib.REDUCE_MAX, "min": _lib.REDUCE_MIN}
+_EXTREME = (_lib.REDUCE_MAX, _lib.REDUCE_MIN)
+_CODES = {torch.float32: _lib.F32, torch.float64: _lib.F64, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}   # (half: sparse_pool)
 _MAX_POINTS = 2 ** 31 - 1
 
 
@@ -35,11 +37,9 @@ def _on(owner, t):
 
 
 def _dtype_code(t):
-    if t.dtype == torch.float32:
-        return _lib.F32
-    if t.dtype == torch.float64:
-        return _lib.F64
-    raise ValueError("voxel features must be float32 or float64, not %s" % t.dtype)
+    if t.dtype not in (torch.float32, torch.float64):
+        raise ValueError("voxel features must be float32 or float64, not %s" % t.dtype)
+    return _CODES[t.dtype]
 
 
 class VoxelIndex:
@@ -143,8 +143,7 @@ class VoxelPool(torch.autograd.Function):
     def forward(ctx, features, idx, red):
         odev = features.device
         need = ctx.needs_input_grad[0]
-        extreme = red in (_lib.REDUCE_MAX, _lib.REDUCE_MIN)
-        out, arg = _forward(features.detach().to(idx.device).contiguous(), idx, red, need and extreme)
+        out, arg = _forward(features.detach().to(idx.device).contiguous(), idx, red, need and red in _EXTREME)
         if need:
             ctx.idx, ctx.red, ctx.odev = idx, red, odev
             ctx.save_for_backward(*([arg] if arg is not None else []))

@@ -16,11 +16,8 @@ from torch.autograd.function import once_differentiable
 
 from .. import _lib
 from .conv import VoxelNeighbors
-from .pool import _REDUCTIONS, _as_tensor, _on
+from .pool import _CODES, _EXTREME, _REDUCTIONS, _as_tensor, _on
 from .sparse_conv import SparseConvMap
-
-_CODES = {torch.float32: _lib.F32, torch.float64: _lib.F64, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
-_EXTREME = (_lib.REDUCE_MAX, _lib.REDUCE_MIN)
 
 
 def _pool_forward(feat, view, red, need_arg, need_count):
