@@ -4266,18 +4266,27 @@ static int dense_index(const DenseKey &kf, const float *points, int64_t n, int c
     return build_index(kf, tab, points, n, c, w, counts, o, st);
 }
 
-struct DenseOut {
-    uint32_t P, max_voxels;
-    int reduction;
-    bool agg4, fuse_pmask;
-    int64_t *coords;
-    int32_t *npoints;
-    unsigned char *pmask;
-    float *aggregates;
-    BinnedExtras x;           // all null for the dense contract
-    int64_t *mapping;
+static BinnedExtras no_extras()       // (the kernel argument's own leading fields carry no defaults)
+{
+    BinnedExtras x{};
+    x.status_row = -1;
+    return x;
+}
+
+// What one call of the binned index is asked for: the dense, reduce, sparse and fused sparse + filter contracts each set the
+// fields they use, by name; everything else stays at "not asked for".
+struct BinnedRequest {
+    uint32_t P = 0, max_voxels = 0xffffffffu;
+    int reduction = D3D_REDUCE_NONE;
+    bool agg4 = false, fuse_pmask = false;
+    int64_t *coords = nullptr;
+    int32_t *npoints = nullptr;
+    unsigned char *pmask = nullptr;
+    float *aggregates = nullptr;
+    BinnedExtras x = no_extras();       // all null for the dense contract but host_counts, row_state, pooled
+    int64_t *mapping = nullptr;
     unsigned char *trimmed = nullptr;   // sparse contract: flag the points beyond P of their voxel (for the TRIM filter)
-    VoxelPass pass = {false, 0, {0, 0, 0}, {0, 0, 0}};   // sparse contract fused with the voxel filter
+    VoxelPass pass{};                   // sparse contract fused with the voxel filter (off)
     int32_t *keepid = nullptr;          // ... then: filtered voxel id of every point (-1: dropped) instead of `mapping`
     bool map_later = false;             // ... computed by the caller's point scan (FilterPoints), not by k_map_binned here
     int64_t *early_counts = nullptr;    // ... whose output sizes k_meta_first then publishes: counts of the filter call
@@ -4441,7 +4450,7 @@ static EarlyLayout early_layout(uint32_t lb_tiles, int64_t npad, bool on)
 
 // rows: dense contract on C == 4 rows, else keys only; key_bytes: sizeof(Key::bin_key_t); stage: 0, or 1 / 2 of the staged call
 static BinnedPlan plan_binned(bool rows, int key_bytes, const float *points, int64_t n, int c, const VoxelWs &w, uint32_t nbins, int hshift,
-                              const DenseOut &o, bool tile_sort, int stage)
+                              const BinnedRequest &o, bool tile_sort, int stage)
 {
     BinnedPlan p;
     p.nbins = nbins;
@@ -4579,7 +4588,7 @@ static BinnedPlan plan_binned(bool rows, int key_bytes, const float *points, int
 
 // job 2 of the binned index: partition -> k_bucket_index -> k_first_count
 template <class Key, bool ROWS>
-static int launch_index(const BinnedPlan &p, const Key &kf, const float *points, int64_t n, int c, int64_t *counts, const DenseOut &o,
+static int launch_index(const BinnedPlan &p, const Key &kf, const float *points, int64_t n, int c, int64_t *counts, const BinnedRequest &o,
                         hipStream_t st)
 {
     typedef BinEntry<ROWS> E;
@@ -4645,7 +4654,7 @@ static int launch_index(const BinnedPlan &p, const Key &kf, const float *points,
 
 // job 3: the output stage of the plan (+ k_map_binned)
 template <class Key, bool ROWS>
-static int launch_output(const BinnedPlan &p, const Key &kf, const float *points, int64_t n, int c, int64_t *counts, const DenseOut &o,
+static int launch_output(const BinnedPlan &p, const Key &kf, const float *points, int64_t n, int c, int64_t *counts, const BinnedRequest &o,
                          hipStream_t st)
 {
     typedef BinEntry<ROWS> E;
@@ -4712,7 +4721,7 @@ static int launch_output(const BinnedPlan &p, const Key &kf, const float *points
 // ROWS: dense contract on C == 4 rows (ranked rows staged, reductions); !ROWS: keys only (sparse contract, any C)
 template <class Key, bool ROWS>
 static int binned_index(const Key &kf, const float *points, int64_t n, int c, const VoxelWs &w, uint32_t nbins, int hshift,
-                        int64_t *counts, const DenseOut &o, hipStream_t st, bool tile_sort, int stage = 0)
+                        int64_t *counts, const BinnedRequest &o, hipStream_t st, bool tile_sort, int stage = 0)
 {
     const BinnedPlan p = plan_binned(ROWS, (int)sizeof(typename Key::bin_key_t), points, n, c, w, nbins, hshift, o, tile_sort, stage);
     if (o.emit_voxels && stage == 0) {
@@ -4727,19 +4736,82 @@ static int binned_index(const Key &kf, const float *points, int64_t n, int c, co
     return D3D_OK;
 }
 
-// Round 5: the fused sparse + filter call in THREE launches on the dense contract's index machinery (BoundKey: the cell inside
-// the filter's coordinate bounds is a 32-bit key): k_tile_sort -> k_bucket_index<.., V2> (the voxel filter and the TRIM point
-// filter inside; a handle of its voxel per kept point) -> k_sparse_finish (numbering, per-voxel outputs, compaction).
-// Returns D3D_ERR_UNSUPPORTED when the frame does not take this path (the caller then runs round 4's four launches).
-static int sparse_fused_index(const BoundKey &kf, const float *points, int64_t n, int c, const VoxelWs &w, uint32_t nbins, int hshift,
-                              const VoxelPass &pass, uint32_t P /* 0: no point filter */, uint32_t max_voxels, uint32_t npoints_clamp,
-                              const int64_t *coord_offset, float *out_feats, int64_t *out_mask, int64_t *out_mapping,
-                              int32_t *out_npoints, int64_t *out_coords, int64_t *sparse_counts, int64_t *counts, int64_t *host,
-                              hipStream_t st)
+static SparseKey make_sparse_key(const float *voxel_size, bool tolerant)
+{
+    SparseKey kf;
+    for (int d = 0; d < 3; d++) kf.size[d] = voxel_size[d];
+    kf.tolerant = tolerant;
+    return kf;
+}
+
+static VoxelPass make_voxel_pass(const int64_t *coords_bound, int32_t min_points)
+{
+    VoxelPass vp{};
+    vp.on = true;
+    vp.min_points = min_points;
+    for (int k = 0; k < 3; k++) { vp.lo[k] = coords_bound[2 * k]; vp.hi[k] = coords_bound[2 * k + 1]; }
+    return vp;
+}
+
+// the cell inside the filter's coordinate bounds as a 32-bit key; false: boxes of 2^32 - 1 cells and more, or reaching INT_MIN
+// -- where the reference files its NaN points -- keep the 63-bit keys
+static bool make_bound_key(const float *voxel_size, const int64_t *coords_bound, BoundKey &bk)
+{
+    double cells = 1.0;
+    bool ok = true;
+    for (int d = 0; d < 3; d++) {
+        const int64_t lo = coords_bound[2 * d], hi = coords_bound[2 * d + 1];
+        ok = ok && lo > (int64_t)INT_MIN && hi <= (int64_t)INT_MAX + 1 && hi > lo && hi - lo < (1ll << 32);
+        bk.size[d] = voxel_size[d];
+        bk.lo[d] = (long long)lo;
+        bk.ext[d] = ok ? (unsigned)(hi - lo) : 1u;
+        cells *= (double)(hi - lo);
+    }
+    return ok && cells < 4294967295.0;
+}
+
+// what d3d_voxelize_3d_sparse_filter takes, by name
+struct SparseFilterArgs {
+    const float *points;
+    int64_t n;
+    int32_t c;
+    const float *voxel_size;
+    const int64_t *coords_bound;
+    int32_t min_points, max_points, max_voxels, max_points_filter, max_voxels_filter;
+    int64_t *points_mapping, *coords;       // the intermediate sparse outputs (DESCENDING and the two-operator route only)
+    int32_t *npoints;
+    int64_t *sparse_counts;
+    float *out_feats;
+    int64_t *out_mask, *out_mapping, *out_coords, *counts;
+    int32_t *out_npoints;
+    void *workspace;
+    size_t workspace_bytes;
+    hipStream_t stream;
+    int64_t *host_counts;
+    uint32_t flags;
+    const int64_t *coord_offset;
+    bool trim() const { return max_points_filter == D3D_MAXPTS_TRIM; }
+    bool desc() const { return max_voxels_filter == D3D_MAXVOX_DESCENDING; }
+    uint32_t npoints_clamp() const { return trim() ? (uint32_t)max_points : 0xffffffffu; }   // voxel_npoints = min(count, max_points)
+};
+
+// Route 1 of the fused sparse + filter call, taken when the voxel filter is not DESCENDING (whose sort sits between the numbering
+// and the compaction), D3D_VOXEL_PARTITION_3PASS does not ask for round 4's kernels and the coordinate bounds make a 32-bit key:
+// THREE launches on the dense contract's index machinery (BoundKey): k_tile_sort -> k_bucket_index<.., V2> (the voxel filter and
+// the TRIM point filter inside; a handle of its voxel per kept point) -> k_sparse_finish (numbering, per-voxel outputs, compaction).
+// Returns D3D_ERR_UNSUPPORTED when the frame does not take this path (the caller then runs sparse_filter_binned's four launches).
+static int sparse_filter_bound(const SparseFilterArgs &a, const VoxelWs &w, uint32_t nbins, int hshift)
 {
     typedef BinEntry<true> E;
+    BoundKey kf;
+    if (!make_bound_key(a.voxel_size, a.coords_bound, kf)) return D3D_ERR_UNSUPPORTED;
+    const int64_t n = a.n;
     if (n > kFmMaxPoints) return D3D_ERR_UNSUPPORTED;
-    const bool vec4 = c == 4 && ((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(out_feats)) & 15) == 0;
+    hipStream_t st = a.stream;
+    const VoxelPass pass = make_voxel_pass(a.coords_bound, a.min_points);
+    const uint32_t P = a.trim() ? (uint32_t)a.max_points : 0u;      // 0: no point filter
+    const uint32_t max_voxels = a.max_voxels_filter == D3D_MAXVOX_NONE ? 0xffffffffu : (uint32_t)a.max_voxels;
+    const bool vec4 = a.c == 4 && ((reinterpret_cast<uintptr_t>(a.points) | reinterpret_cast<uintptr_t>(a.out_feats)) & 15) == 0;
     // binned_index's tiles on 4-byte keys with rows, without fillers; no three-pass partition behind this call
     const bool big_tiles = wants_big_tiles(true, vec4, (int)sizeof(BoundKey::bin_key_t), n);
     const TilePlan t = plan_tiles(big_tiles, wants_small_tiles(true, vec4, big_tiles, w.npad, false), true, true, n, nbins, w);
@@ -4760,23 +4832,24 @@ static int sparse_fused_index(const BoundKey &kf, const float *points, int64_t n
     unsigned int *ticket = w.big_count + 40;
     const size_t lds = ((size_t)1 << tshift) * (sizeof(uint32_t) + 2) + (size_t)nbins * 4;
     if (const int rc = dispatch(vec4, [&](auto v4) {
-            return launch_tile_sort<BoundKey, v4, true>(tshift, lds, dim3(((stiles + 7u) >> 3) << 3), st, kf, points, n, c, nbins, stiles,
-                                                        bent, table, tileinfo, phandle, firstmap, sparse_counts, (int64_t *)nullptr,
+            return launch_tile_sort<BoundKey, v4, true>(tshift, lds, dim3(((stiles + 7u) >> 3) << 3), st, kf, a.points, n, (int)a.c, nbins, stiles,
+                                                        bent, table, tileinfo, phandle, firstmap, a.sparse_counts, (int64_t *)nullptr,
                                                         (unsigned char *)nullptr, (int32_t *)nullptr, w.fwords,
                                                         early_at + 16u * early_pairs, ticket, false);
         }))
         return rc;
     D3D_LAUNCH("k_bucket_index", (k_bucket_index<BoundKey, true, true, false, true>), dim3(nbins), dim3(kBucketThreads), 0, st, kf, pass, bent,
                (const float4 *)nullptr, (const uint32_t *)nullptr, hshift, P, (int)D3D_REDUCE_NONE, (float4 *)nullptr, vrec, firstmap,
-               sparse_counts, (uint32_t *)nullptr, w.parr, reinterpret_cast<uint32_t *>(w.vinfo), (unsigned char *)nullptr, w.big_list,
-               (uint32_t *)nullptr, table, stiles, tshift, tileinfo, gpos, phandle, early_tot, npoints_clamp,
+               a.sparse_counts, (uint32_t *)nullptr, w.parr, reinterpret_cast<uint32_t *>(w.vinfo), (unsigned char *)nullptr, w.big_list,
+               (uint32_t *)nullptr, table, stiles, tshift, tileinfo, gpos, phandle, early_tot, a.npoints_clamp(),
                early_pairs ? early_pairs - 1u : 0u, bits_for((u64)(n > 1 ? n - 1 : 1)));
-    SparseFin lb{w.fwords, w.fwords + ftiles, ticket, host, early_tot, early_pairs, {0, 0, 0}};
-    if (coord_offset)
-        for (int k = 0; k < 3; k++) lb.coord_sub[k] = (long long)coord_offset[k];
+    SparseFin lb{w.fwords, w.fwords + ftiles, ticket, a.host_counts, early_tot, early_pairs, {0, 0, 0}};
+    if (a.coord_offset)
+        for (int k = 0; k < 3; k++) lb.coord_sub[k] = (long long)a.coord_offset[k];
     return dispatch(vec4, [&](auto v4) {
         D3D_LAUNCH("k_sparse_finish", k_sparse_finish<v4>, dim3(ftiles), dim3(kFinThreads), 0, st, kf, n, firstmap, phandle, vrec,
-                   points, c, max_voxels, npoints_clamp, out_coords, out_npoints, out_feats, out_mask, out_mapping, sparse_counts, counts, lb);
+                   a.points, (int)a.c, max_voxels, a.npoints_clamp(), a.out_coords, a.out_npoints, a.out_feats, a.out_mask, a.out_mapping,
+                   a.sparse_counts, a.counts, lb);
         return D3D_OK;
     });
 }
@@ -4859,123 +4932,156 @@ static int dense_meta(const DenseKey &kf, const float *points, const VoxelWs &w,
     return D3D_OK;
 }
 
-static int voxelize_dense_core(const float *points, int64_t n, int32_t c, const int32_t *shape, const float *bound,
-                               int32_t max_points, int32_t max_voxels, int32_t reduction, float *voxels, int64_t *coords,
-                               uint8_t *pmask, int32_t *npoints, float *aggregates, int64_t *counts, void *workspace,
-                               size_t workspace_bytes, void *stream, int64_t *host_counts, uint32_t flags, int stage, uint16_t *row_state,
-                               bool pooled)
-{
-    hipStream_t st = (hipStream_t)stream;
-    if (n < 0 || c < 3 || !shape || !bound || !counts || max_points < 0 || max_voxels < 0) return D3D_ERR_BAD_ARG;
-    if (flags & ~(uint32_t)D3D_VOXEL_FLAGS_ALL) return D3D_ERR_BAD_ARG;
-    if (n > 0 && !points) return D3D_ERR_BAD_ARG;
-    if (n >= (1ll << 31) - kFlagTile) return D3D_ERR_BAD_ARG;
-    if (reduction < D3D_REDUCE_NONE || reduction > D3D_REDUCE_MIN) return D3D_ERR_UNSUPPORTED;  // voxelize.cpp:196
-    if (reduction != D3D_REDUCE_NONE && !aggregates && n > 0 && max_voxels > 0) return D3D_ERR_BAD_ARG;
-    if (reduction != D3D_REDUCE_NONE && max_points == 0 && n > 0 && max_voxels > 0) return D3D_ERR_UNSUPPORTED;   // aggregates need the lists
-    DenseKey kf;
-    int rc = make_dense_key(shape, bound, kf);
-    if (rc) return rc;
-    VoxelWs w = carve(workspace, workspace_bytes, n, 0);
-    if (!workspace || w.bytes > workspace_bytes) return D3D_ERR_WORKSPACE;
-    if ((max_voxels > 0 && n > 0) && (!voxels || !coords || !pmask || !npoints)) return D3D_ERR_BAD_ARG;
+// What the dense family of entries takes (d3d_voxelize_3d_dense and _notify, _resident, _pooled, _staged), by name
+struct DenseCall {
+    const float *points;
+    int64_t n;
+    int32_t c;
+    const int32_t *shape;
+    const float *bound;
+    int32_t max_points, max_voxels, reduction;
+    float *voxels;
+    int64_t *coords;
+    uint8_t *pmask;
+    int32_t *npoints;
+    float *aggregates;
+    int64_t *counts;
+    void *workspace;
+    size_t workspace_bytes;
+    hipStream_t stream;
+    int64_t *host_counts = nullptr;     // _notify and later: the host-mapped copy of counts[]
+    uint32_t flags = 0;
+    int stage = 0;                      // _staged: 1 = the index launches, 2 = the output launch, 0 = the whole call
+    uint16_t *row_state = nullptr;      // _resident, _pooled
+    bool pooled = false;
+};
 
-    const bool al16 = ((reinterpret_cast<uintptr_t>(points) & 15) == 0) && ((reinterpret_cast<uintptr_t>(voxels) & 15) == 0);
-    const bool vec4 = (c == 4) && al16 && (reduction == D3D_REDUCE_NONE || (reinterpret_cast<uintptr_t>(aggregates) & 15) == 0);
-    const int64_t cap = n < max_voxels ? n : (int64_t)max_voxels;
-    const uint32_t P = (uint32_t)max_points;
-    const bool fuse_pmask = P > 0 && (P % 16 == 0) && ((reinterpret_cast<uintptr_t>(pmask) & 15) == 0);
-    const bool agg4 = vec4 && reduction != D3D_REDUCE_NONE && P > 0;
-    uint32_t nbins = 0;
-    int hshift = 0;
-    bool lists_ready = false;           // C != 4 on the binned index: w.big_list / w.unsorted / w.voff hold the lists
-    bool emitted = false;               // k_emit wrote voxels[V,P,4] as well
-    bool emitted_generic = false;       // k_emit_c wrote voxels[V,P,C], the per-voxel outputs and the aggregates of voxels within P
-    if (max_voxels > 0 && dense_cells_fit_u32(kf) && binned_eligible(n, w, flags, &nbins, &hshift)) {
-        DenseOut d{P, (uint32_t)max_voxels, reduction, agg4, fuse_pmask, coords, npoints, pmask, aggregates,
-                   BinnedExtras{nullptr, 0, nullptr, -1, nullptr, host_counts}, nullptr};
-        if (vec4 && P > 0 && P <= (uint32_t)kEmitCap && !(flags & D3D_VOXEL_SPLIT_FILL)) {
-            d.emit_voxels = reinterpret_cast<float4 *>(voxels);
-            emitted = true;
-        }
-        // staged calls (d3d_voxelize_3d_dense_staged): only the path whose output is ONE launch
-        if (stage != 0 && !(emitted && fuse_pmask)) return D3D_ERR_UNSUPPORTED;
-        d.x.row_state = row_state;
-        d.x.pooled = pooled;
-        if (vec4) {
-            if (row_state && !emitted) return D3D_ERR_UNSUPPORTED;       // (resident rows: the one-launch output kernels only)
-            rc = binned_index<DenseKey, true>(kf, points, n, c, w, nbins, hshift, counts, d, st, !(flags & D3D_VOXEL_PARTITION_3PASS), stage);
-        } else {
-            // any C: the {cell, index} entries travel alone, the bucket kernel leaves per-voxel index lists in point order
-            // and the generic output kernels below gather through them
-            lists_ready = true;
-            if ((c == 3 || (c >= 5 && c <= 8)) && P > 0 && P <= (uint32_t)kEmitCap && (P * (uint32_t)c) % 4 == 0 &&
-                (reinterpret_cast<uintptr_t>(voxels) & 15) == 0 && !(flags & D3D_VOXEL_SPLIT_FILL)) {
-                d.emit_generic = voxels;
-                emitted_generic = true;
-            }
-            if (row_state && !emitted_generic) return D3D_ERR_UNSUPPORTED;
-            rc = binned_index<DenseKey, false>(kf, points, n, c, w, nbins, hshift, counts, d, st, !(flags & D3D_VOXEL_PARTITION_3PASS), stage);
-        }
-        if (rc) return rc;
-    } else {
-        if (stage != 0 || row_state) return D3D_ERR_UNSUPPORTED;
-        IndexOpts o{(uint32_t)max_points, (uint32_t)max_voxels, nullptr, 0, nullptr, vec4};
-        rc = dense_index(kf, points, n, c, w, counts, o, flags, st);
-        if (rc) return rc;
-        if (host_counts) D3D_LAUNCH("k_notify_host", k_notify_host, dim3(1), dim3(64), 0, st, counts, host_counts);
-        if (n == 0 || max_voxels == 0) return D3D_OK;
-        rc = dense_meta(kf, points, w, counts, dim3(grid_for(cap, 256)), P, reduction, agg4, coords, npoints, w.voff,
-                        fuse_pmask ? pmask : nullptr, aggregates, nullptr, -1, st);
-        if (rc) return rc;
-    }
-    if (P == 0) return D3D_OK;
-    const bool fill = !emitted && !emitted_generic;          // (else the output launch of the index wrote voxels[] already)
-    if (!fill) {
-    } else if (vec4 && n <= kFillRowsMaxPoints) {
+// the checks every points-taking entry repeats (all D3D_ERR_BAD_ARG): n in [0, 2^31 - kFlagTile), rows of x, y, z at least, no
+// unknown flag
+static bool points_args_ok(int64_t n, int32_t c, uint32_t flags)
+{
+    return n >= 0 && n < (1ll << 31) - kFlagTile && c >= 3 && !(flags & ~(uint32_t)D3D_VOXEL_FLAGS_ALL);
+}
+
+enum class VoxelsBy { fill, emit, emit_c };     // who writes voxels[]: the fill launches below, k_emit*, k_emit_c
+
+// The dense contract behind its index: voxels[V,P,C] unless the index's output launch wrote them (`by`), the point mask unless
+// that launch fused it, and the aggregates the index did not reduce (lists_ready: C != 4 on the binned index, w.big_list /
+// w.unsorted / w.voff hold the lists)
+static int launch_dense_fill(const DenseCall &a, const VoxelWs &w, VoxelsBy by, bool lists_ready, bool vec4, bool fuse_pmask, bool agg4)
+{
+    hipStream_t st = a.stream;
+    const uint32_t P = (uint32_t)a.max_points;
+    const int64_t cap = a.n < a.max_voxels ? a.n : (int64_t)a.max_voxels;
+    const int c = a.c;
+    int64_t *counts = a.counts;
+    if (by != VoxelsBy::fill) {
+    } else if (vec4 && a.n <= kFillRowsMaxPoints) {
         D3D_LAUNCH("k_fill_c4", k_fill_c4_rows, dim3(grid_for(cap * P, 256, 256 * 32)), dim3(256), 0, st, w.staged, counts, w.vinfo,
-                   P, reinterpret_cast<float4 *>(voxels));
+                   P, reinterpret_cast<float4 *>(a.voxels));
     } else if (vec4) {
         // large frames: 64 voxels per wavefront (the wavefronts past the actual voxel count exit at once)
         const int pshift = (P & (P - 1)) == 0 ? __builtin_ctz(P) : -1;
         const dim3 fgrid((unsigned)d3d_divup(d3d_divup(cap > 0 ? cap : 1, 64), 256 / kWave));
         D3D_LAUNCH("k_fill_c4", k_fill_c4<64>, fgrid, dim3(256), 0, st, w.staged, counts, w.vinfo, P, pshift,
-                   reinterpret_cast<float4 *>(voxels));
+                   reinterpret_cast<float4 *>(a.voxels));
     }
-    else if (c <= kFillLdsMaxC && (reinterpret_cast<uintptr_t>(voxels) & 15) == 0)
-        D3D_LAUNCH("k_fill_generic_lds", k_fill_generic_lds, dim3(grid_for(cap * P, 256, 256 * 32)), dim3(256), 0, st, points, c,
-                   counts, w.vinfo, lists_ready ? w.big_list : w.list, P, voxels);
+    else if (c <= kFillLdsMaxC && (reinterpret_cast<uintptr_t>(a.voxels) & 15) == 0)
+        D3D_LAUNCH("k_fill_generic_lds", k_fill_generic_lds, dim3(grid_for(cap * P, 256, 256 * 32)), dim3(256), 0, st, a.points, c,
+                   counts, w.vinfo, lists_ready ? w.big_list : w.list, P, a.voxels);
     else
-        D3D_LAUNCH("k_fill_generic", k_fill_generic, dim3(grid_for(cap * P, 256, 256 * 32)), dim3(256), 0, st, points, c,
-                   counts, w.vinfo, lists_ready ? w.big_list : w.list, P, voxels);
+        D3D_LAUNCH("k_fill_generic", k_fill_generic, dim3(grid_for(cap * P, 256, 256 * 32)), dim3(256), 0, st, a.points, c,
+                   counts, w.vinfo, lists_ready ? w.big_list : w.list, P, a.voxels);
     if (!fuse_pmask)
-        D3D_LAUNCH("k_pmask", k_pmask, dim3(grid_for(d3d_divup(cap * P, 16), 256)), dim3(256), 0, st, counts, npoints, P, pmask);
-    if (emitted_generic && reduction != D3D_REDUCE_NONE)          // voxels with more than P points: all their points count
-        D3D_LAUNCH("k_aggregate_overflow", k_aggregate_overflow, dim3(1024), dim3(256), 0, st, points, c,
-                   (const uint32_t *)reinterpret_cast<uint32_t *>(w.vinfo), (const uint32_t *)w.big_count, (const int32_t *)npoints,
-                   (const uint32_t *)w.voff, (const uint32_t *)w.unsorted, reduction, aggregates);
-    if (fill && reduction != D3D_REDUCE_NONE && !agg4)
-        D3D_LAUNCH("k_aggregate", k_aggregate, dim3(grid_for(cap * c, 256)), dim3(256), 0, st, points, c, counts, npoints,
-                   w.voff, lists_ready ? w.big_list : w.list, w.unsorted, P, reduction, aggregates);
+        D3D_LAUNCH("k_pmask", k_pmask, dim3(grid_for(d3d_divup(cap * P, 16), 256)), dim3(256), 0, st, counts, a.npoints, P, a.pmask);
+    if (by == VoxelsBy::emit_c && a.reduction != D3D_REDUCE_NONE)          // voxels with more than P points: all their points count
+        D3D_LAUNCH("k_aggregate_overflow", k_aggregate_overflow, dim3(1024), dim3(256), 0, st, a.points, c,
+                   (const uint32_t *)reinterpret_cast<uint32_t *>(w.vinfo), (const uint32_t *)w.big_count, (const int32_t *)a.npoints,
+                   (const uint32_t *)w.voff, (const uint32_t *)w.unsorted, a.reduction, a.aggregates);
+    if (by == VoxelsBy::fill && a.reduction != D3D_REDUCE_NONE && !agg4)
+        D3D_LAUNCH("k_aggregate", k_aggregate, dim3(grid_for(cap * c, 256)), dim3(256), 0, st, a.points, c, counts, a.npoints,
+                   w.voff, lists_ready ? w.big_list : w.list, w.unsorted, P, a.reduction, a.aggregates);
     return D3D_OK;
 }
 
-static int voxelize_dense_impl(const float *points, int64_t n, int32_t c, const int32_t *shape, const float *bound,
-                               int32_t max_points, int32_t max_voxels, int32_t reduction, float *voxels, int64_t *coords,
-                               uint8_t *pmask, int32_t *npoints, float *aggregates, int64_t *counts, void *workspace,
-                               size_t workspace_bytes, void *stream, int64_t *host_counts, uint32_t flags, int stage = 0,
-                               uint16_t *row_state = nullptr, bool pooled = false)
+// kf, w: the grid key and the workspace layout of this call, left for voxelize_dense_impl's second pass
+static int voxelize_dense_core(const DenseCall &a, DenseKey &kf, VoxelWs &w)
 {
-    int rc = voxelize_dense_core(points, n, c, shape, bound, max_points, max_voxels, reduction, voxels, coords, pmask, npoints,
-                                 aggregates, counts, workspace, workspace_bytes, stream, host_counts, flags, stage, row_state, pooled);
-    if (rc == D3D_OK && (flags & D3D_VOXEL_EXACT_MEAN) && reduction == D3D_REDUCE_MEAN && max_points > 0 && max_voxels > 0 && n > 0 &&
-        stage != 1) {
-        DenseKey kf;
-        rc = make_dense_key(shape, bound, kf);
+    hipStream_t st = a.stream;
+    const int64_t n = a.n;
+    if (!points_args_ok(n, a.c, a.flags) || !a.shape || !a.bound || !a.counts || a.max_points < 0 || a.max_voxels < 0) return D3D_ERR_BAD_ARG;
+    if (n > 0 && !a.points) return D3D_ERR_BAD_ARG;
+    if (a.reduction < D3D_REDUCE_NONE || a.reduction > D3D_REDUCE_MIN) return D3D_ERR_UNSUPPORTED;  // voxelize.cpp:196
+    if (a.reduction != D3D_REDUCE_NONE && !a.aggregates && n > 0 && a.max_voxels > 0) return D3D_ERR_BAD_ARG;
+    if (a.reduction != D3D_REDUCE_NONE && a.max_points == 0 && n > 0 && a.max_voxels > 0) return D3D_ERR_UNSUPPORTED;   // aggregates need the lists
+    int rc = make_dense_key(a.shape, a.bound, kf);
+    if (rc) return rc;
+    w = carve(a.workspace, a.workspace_bytes, n, 0);
+    if (!a.workspace || w.bytes > a.workspace_bytes) return D3D_ERR_WORKSPACE;
+    if ((a.max_voxels > 0 && n > 0) && (!a.voxels || !a.coords || !a.pmask || !a.npoints)) return D3D_ERR_BAD_ARG;
+
+    const bool al16 = ((reinterpret_cast<uintptr_t>(a.points) & 15) == 0) && ((reinterpret_cast<uintptr_t>(a.voxels) & 15) == 0);
+    const bool vec4 = (a.c == 4) && al16 && (a.reduction == D3D_REDUCE_NONE || (reinterpret_cast<uintptr_t>(a.aggregates) & 15) == 0);
+    const uint32_t P = (uint32_t)a.max_points;
+    const bool fuse_pmask = P > 0 && (P % 16 == 0) && ((reinterpret_cast<uintptr_t>(a.pmask) & 15) == 0);
+    const bool agg4 = vec4 && a.reduction != D3D_REDUCE_NONE && P > 0;
+    const bool emit_ok = P > 0 && P <= (uint32_t)kEmitCap && !(a.flags & D3D_VOXEL_SPLIT_FILL);
+    uint32_t nbins = 0;
+    int hshift = 0;
+    bool lists_ready = false;
+    VoxelsBy by = VoxelsBy::fill;
+    if (a.max_voxels > 0 && dense_cells_fit_u32(kf) && binned_eligible(n, w, a.flags, &nbins, &hshift)) {
+        BinnedRequest d;
+        d.P = P; d.max_voxels = (uint32_t)a.max_voxels; d.reduction = a.reduction; d.agg4 = agg4; d.fuse_pmask = fuse_pmask;
+        d.coords = a.coords; d.npoints = a.npoints; d.pmask = a.pmask; d.aggregates = a.aggregates;
+        d.x.host_counts = a.host_counts; d.x.row_state = a.row_state; d.x.pooled = a.pooled;
+        const bool tile_sort = !(a.flags & D3D_VOXEL_PARTITION_3PASS);
+        if (vec4 && emit_ok) {
+            d.emit_voxels = reinterpret_cast<float4 *>(a.voxels);
+            by = VoxelsBy::emit;
+        }
+        // staged calls (d3d_voxelize_3d_dense_staged): only the path whose output is ONE launch
+        if (a.stage != 0 && !(by == VoxelsBy::emit && fuse_pmask)) return D3D_ERR_UNSUPPORTED;
+        if (vec4) {
+            if (a.row_state && by != VoxelsBy::emit) return D3D_ERR_UNSUPPORTED;     // (resident rows: the one-launch output kernels only)
+            rc = binned_index<DenseKey, true>(kf, a.points, n, a.c, w, nbins, hshift, a.counts, d, st, tile_sort, a.stage);
+        } else {
+            // any C: the {cell, index} entries travel alone, the bucket kernel leaves per-voxel index lists in point order
+            // and the generic output kernels of launch_dense_fill gather through them
+            lists_ready = true;
+            if ((a.c == 3 || (a.c >= 5 && a.c <= 8)) && emit_ok && (P * (uint32_t)a.c) % 4 == 0 &&
+                (reinterpret_cast<uintptr_t>(a.voxels) & 15) == 0) {
+                d.emit_generic = a.voxels;
+                by = VoxelsBy::emit_c;
+            }
+            if (a.row_state && by != VoxelsBy::emit_c) return D3D_ERR_UNSUPPORTED;
+            rc = binned_index<DenseKey, false>(kf, a.points, n, a.c, w, nbins, hshift, a.counts, d, st, tile_sort, a.stage);
+        }
         if (rc) return rc;
-        const VoxelWs w = carve(workspace, workspace_bytes, n, 0);
-        rc = exact_mean_pass(kf, points, n, c, (uint32_t)max_points, coords, npoints, aggregates, counts, w, (hipStream_t)stream);
+    } else {
+        if (a.stage != 0 || a.row_state) return D3D_ERR_UNSUPPORTED;
+        IndexOpts o{P, (uint32_t)a.max_voxels, nullptr, 0, nullptr, vec4};
+        rc = dense_index(kf, a.points, n, a.c, w, a.counts, o, a.flags, st);
+        if (rc) return rc;
+        if (a.host_counts) D3D_LAUNCH("k_notify_host", k_notify_host, dim3(1), dim3(64), 0, st, a.counts, a.host_counts);
+        if (n == 0 || a.max_voxels == 0) return D3D_OK;
+        const int64_t cap = n < a.max_voxels ? n : (int64_t)a.max_voxels;
+        rc = dense_meta(kf, a.points, w, a.counts, dim3(grid_for(cap, 256)), P, a.reduction, agg4, a.coords, a.npoints, w.voff,
+                        fuse_pmask ? a.pmask : nullptr, a.aggregates, nullptr, -1, st);
+        if (rc) return rc;
     }
+    if (P == 0) return D3D_OK;
+    return launch_dense_fill(a, w, by, lists_ready, vec4, fuse_pmask, agg4);
+}
+
+static int voxelize_dense_impl(const DenseCall &a)
+{
+    DenseKey kf;
+    VoxelWs w;
+    int rc = voxelize_dense_core(a, kf, w);
+    if (rc == D3D_OK && (a.flags & D3D_VOXEL_EXACT_MEAN) && a.reduction == D3D_REDUCE_MEAN && a.max_points > 0 && a.max_voxels > 0 &&
+        a.n > 0 && a.stage != 1)
+        rc = exact_mean_pass(kf, a.points, a.n, a.c, (uint32_t)a.max_points, a.coords, a.npoints, a.aggregates, a.counts, w, a.stream);
     return rc;
 }
 
@@ -4994,8 +5100,11 @@ extern "C" int d3d_voxelize_3d_dense(const float *points, int64_t n, int32_t c, 
                                      int64_t *coords, uint8_t *pmask, int32_t *npoints, float *aggregates,
                                      int64_t *counts, void *workspace, size_t workspace_bytes, void *stream, uint32_t flags)
 {
-    return voxelize_dense_impl(points, n, c, shape, bound, max_points, max_voxels, reduction, voxels, coords, pmask, npoints,
-                               aggregates, counts, workspace, workspace_bytes, stream, nullptr, flags);
+    DenseCall a;
+    a.points = points; a.n = n; a.c = c; a.shape = shape; a.bound = bound; a.max_points = max_points; a.max_voxels = max_voxels;
+    a.reduction = reduction; a.voxels = voxels; a.coords = coords; a.pmask = pmask; a.npoints = npoints; a.aggregates = aggregates;
+    a.counts = counts; a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.stream = (hipStream_t)stream; a.flags = flags;
+    return voxelize_dense_impl(a);
 }
 
 // Same, and as soon as counts[] are final -- before the HBM-bound fill of voxels[V,P,C] is launched -- they are also
@@ -5009,8 +5118,22 @@ extern "C" int d3d_voxelize_3d_dense_notify(const float *points, int64_t n, int3
                                             int64_t *host_counts, uint32_t flags)
 {
     if (!host_counts) return D3D_ERR_BAD_ARG;
-    return voxelize_dense_impl(points, n, c, shape, bound, max_points, max_voxels, reduction, voxels, coords, pmask, npoints,
-                               aggregates, counts, workspace, workspace_bytes, stream, host_counts, flags);
+    DenseCall a;
+    a.points = points; a.n = n; a.c = c; a.shape = shape; a.bound = bound; a.max_points = max_points; a.max_voxels = max_voxels;
+    a.reduction = reduction; a.voxels = voxels; a.coords = coords; a.pmask = pmask; a.npoints = npoints; a.aggregates = aggregates;
+    a.counts = counts; a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.stream = (hipStream_t)stream;
+    a.host_counts = host_counts; a.flags = flags;
+    return voxelize_dense_impl(a);
+}
+
+// the guards and the call that d3d_voxelize_3d_dense_resident and _pooled share: a.pooled alone tells them apart
+static int voxelize_dense_resident(DenseCall a)
+{
+    if (!a.row_state) return D3D_ERR_BAD_ARG;
+    if (a.max_voxels <= 0 || a.max_points <= 0) return D3D_ERR_UNSUPPORTED;
+    if (a.n == 0) a.row_state = nullptr;           // an empty frame: no voxel, no row, the state stays
+    if (a.flags & (D3D_VOXEL_PATH_HASH | D3D_VOXEL_SPLIT_FILL)) return D3D_ERR_UNSUPPORTED;
+    return voxelize_dense_impl(a);
 }
 
 // The dense contract into a RESIDENT output (round 4): `voxels` is a buffer [capacity >= min(n, max_voxels) of any call, max_points,
@@ -5027,12 +5150,12 @@ extern "C" int d3d_voxelize_3d_dense_resident(const float *points, int64_t n, in
                                               int64_t *counts, void *workspace, size_t workspace_bytes, void *stream,
                                               int64_t *host_counts, uint32_t flags)
 {
-    if (!row_state) return D3D_ERR_BAD_ARG;
-    if (max_voxels <= 0 || max_points <= 0) return D3D_ERR_UNSUPPORTED;
-    if (n == 0) row_state = nullptr;               // an empty frame: no voxel, no row, the state stays
-    if (flags & (D3D_VOXEL_PATH_HASH | D3D_VOXEL_SPLIT_FILL)) return D3D_ERR_UNSUPPORTED;
-    return voxelize_dense_impl(points, n, c, shape, bound, max_points, max_voxels, reduction, voxels, coords, pmask, npoints,
-                               aggregates, counts, workspace, workspace_bytes, stream, host_counts, flags, 0, row_state);
+    DenseCall a;
+    a.points = points; a.n = n; a.c = c; a.shape = shape; a.bound = bound; a.max_points = max_points; a.max_voxels = max_voxels;
+    a.reduction = reduction; a.voxels = voxels; a.coords = coords; a.pmask = pmask; a.npoints = npoints; a.aggregates = aggregates;
+    a.counts = counts; a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.stream = (hipStream_t)stream;
+    a.host_counts = host_counts; a.flags = flags; a.row_state = row_state;
+    return voxelize_dense_resident(a);
 }
 
 // d3d_voxelize_3d_dense_resident for a caller that owns the buffer on the user's behalf (VoxelGenerator's pooled default output,
@@ -5044,12 +5167,12 @@ extern "C" int d3d_voxelize_3d_dense_pooled(const float *points, int64_t n, int3
                                             int64_t *counts, void *workspace, size_t workspace_bytes, void *stream,
                                             int64_t *host_counts, uint32_t flags)
 {
-    if (!row_state) return D3D_ERR_BAD_ARG;
-    if (max_voxels <= 0 || max_points <= 0) return D3D_ERR_UNSUPPORTED;
-    if (n == 0) row_state = nullptr;               // an empty frame: no voxel, no row, the state stays
-    if (flags & (D3D_VOXEL_PATH_HASH | D3D_VOXEL_SPLIT_FILL)) return D3D_ERR_UNSUPPORTED;
-    return voxelize_dense_impl(points, n, c, shape, bound, max_points, max_voxels, reduction, voxels, coords, pmask, npoints,
-                               aggregates, counts, workspace, workspace_bytes, stream, host_counts, flags, 0, row_state, true);
+    DenseCall a;
+    a.points = points; a.n = n; a.c = c; a.shape = shape; a.bound = bound; a.max_points = max_points; a.max_voxels = max_voxels;
+    a.reduction = reduction; a.voxels = voxels; a.coords = coords; a.pmask = pmask; a.npoints = npoints; a.aggregates = aggregates;
+    a.counts = counts; a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.stream = (hipStream_t)stream;
+    a.host_counts = host_counts; a.flags = flags; a.row_state = row_state; a.pooled = true;
+    return voxelize_dense_resident(a);
 }
 
 // d3d_voxelize_3d_dense_notify in two calls, for callers that pipeline a stream of frames (round 4): stage 1 enqueues the
@@ -5066,8 +5189,12 @@ extern "C" int d3d_voxelize_3d_dense_staged(const float *points, int64_t n, int3
 {
     if (stage < 0 || stage > 2) return D3D_ERR_BAD_ARG;
     if (n <= 0 && stage != 0) return D3D_ERR_UNSUPPORTED;
-    return voxelize_dense_impl(points, n, c, shape, bound, max_points, max_voxels, reduction, voxels, coords, pmask, npoints,
-                               aggregates, counts, workspace, workspace_bytes, stream, host_counts, flags, stage);
+    DenseCall a;
+    a.points = points; a.n = n; a.c = c; a.shape = shape; a.bound = bound; a.max_points = max_points; a.max_voxels = max_voxels;
+    a.reduction = reduction; a.voxels = voxels; a.coords = coords; a.pmask = pmask; a.npoints = npoints; a.aggregates = aggregates;
+    a.counts = counts; a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.stream = (hipStream_t)stream;
+    a.host_counts = host_counts; a.flags = flags; a.stage = stage;
+    return voxelize_dense_impl(a);
 }
 
 // The "voxel feature grid" without the dense [V,P,C] copy: first-seen voxel ids, counts, per-voxel
@@ -5085,8 +5212,7 @@ extern "C" int d3d_voxelize_3d_reduce(const float *points, int64_t n, int32_t c,
     hipStream_t st = (hipStream_t)stream;
     if (flags & ~(uint32_t)D3D_VOXEL_FLAGS_ALL) return D3D_ERR_BAD_ARG;
     if (keys && n >= 0) D3D_HIP_CHECK(hipMemsetAsync(keys, 0xff, (size_t)(n + 1) * 8, st));   // -1 = no voxel in this row
-    if (n < 0 || c < 3 || !shape || !bound || !counts) return D3D_ERR_BAD_ARG;
-    if (n >= (1ll << 31) - kFlagTile) return D3D_ERR_BAD_ARG;
+    if (!points_args_ok(n, c, flags) || !shape || !bound || !counts) return D3D_ERR_BAD_ARG;
     if (reduction < D3D_REDUCE_MEAN || reduction > kReduceSum) return D3D_ERR_UNSUPPORTED;
     if (n > 0 && (!points || !npoints || !aggregates || (!coords && !keys))) return D3D_ERR_BAD_ARG;
     DenseKey kf;
@@ -5104,8 +5230,11 @@ extern "C" int d3d_voxelize_3d_reduce(const float *points, int64_t n, int32_t c,
     uint32_t nbins = 0;
     int hshift = 0;
     if (agg4 && dense_cells_fit_u32(kf) && binned_eligible(n, w, flags, &nbins, &hshift)) {
-        DenseOut d{P, 0xffffffffu, reduction, true, false, coords, npoints, nullptr, aggregates,
-                   BinnedExtras{first, index_offset, keys, keys ? n : (int64_t)-1, nullptr, nullptr}, mapping};
+        BinnedRequest d;
+        d.P = P; d.reduction = reduction; d.agg4 = true;
+        d.coords = coords; d.npoints = npoints; d.aggregates = aggregates; d.mapping = mapping;
+        d.x.first_out = first; d.x.index_offset = index_offset; d.x.keys_out = keys;
+        if (keys) d.x.status_row = n;
         d.seg_out = seg_base;
         d.emit_reduce = P <= (uint32_t)kEmitCap && !(flags & D3D_VOXEL_SPLIT_FILL);
         // With `rows` on this path NO row is moved: the caller's buffer receives the voxels' ranked point INDICES (uint32; entry
@@ -5139,10 +5268,8 @@ static int voxelize_sparse_impl(const float *points, int64_t n, int32_t c, const
                                 int64_t ws_nvox, void *stream, uint32_t flags, bool tolerant)
 {
     hipStream_t st = (hipStream_t)stream;
-    if (n < 0 || c < 3 || !voxel_size || !counts) return D3D_ERR_BAD_ARG;
-    if (flags & ~(uint32_t)D3D_VOXEL_FLAGS_ALL) return D3D_ERR_BAD_ARG;
+    if (!points_args_ok(n, c, flags) || !voxel_size || !counts) return D3D_ERR_BAD_ARG;
     if (n > 0 && (!points || !points_mapping || !coords || !npoints)) return D3D_ERR_BAD_ARG;
-    if (n >= (1ll << 31) - kFlagTile) return D3D_ERR_BAD_ARG;
     VoxelWs w = carve(workspace, workspace_bytes, n, ws_nvox);   // (the arrays used here do not move with ws_nvox)
     if (!workspace || w.bytes > workspace_bytes) return D3D_ERR_WORKSPACE;
     uint32_t nbins = 0;
@@ -5163,12 +5290,9 @@ static int voxelize_sparse_impl(const float *points, int64_t n, int32_t c, const
     if (binned_eligible(n, w, flags, &nbins, &hshift)) {
         // up to 16 M points: partition by hash(cell) and index every bucket in LDS -- the 63-bit cell key itself is the
         // table key there, so no bounding box pass and no packed-slot limits
-        SparseKey kf;
-        for (int d = 0; d < 3; d++) kf.size[d] = voxel_size[d];
-        kf.tolerant = tolerant;
-        DenseOut d{0u, 0xffffffffu, D3D_REDUCE_NONE, false, false, coords, npoints, nullptr, nullptr,
-                   BinnedExtras{nullptr, 0, nullptr, -1, nullptr, nullptr}, points_mapping};
-        return binned_index<SparseKey, false>(kf, points, n, c, w, nbins, hshift, counts, d, st, !(flags & D3D_VOXEL_PARTITION_3PASS));
+        BinnedRequest d;
+        d.coords = coords; d.npoints = npoints; d.mapping = points_mapping;
+        return binned_index<SparseKey, false>(make_sparse_key(voxel_size, tolerant), points, n, c, w, nbins, hshift, counts, d, st, !(flags & D3D_VOXEL_PARTITION_3PASS));
     }
     IndexOpts o{0u, 0xffffffffu, nullptr, 0, points_mapping, false};
     auto hash_index = [&](const auto &kf, const auto &tab) -> int {
@@ -5191,10 +5315,7 @@ static int voxelize_sparse_impl(const float *points, int64_t n, int32_t c, const
         kf.kb_max = 56 - ib;
         return hash_index(kf, TabPacked{w.tabA, ib, 0, reinterpret_cast<uint32_t *>(w.tabB), kf.prm});
     }
-    SparseKey kf;
-    for (int d = 0; d < 3; d++) kf.size[d] = voxel_size[d];
-    kf.tolerant = tolerant;
-    return hash_index(kf, TabPlain{w.tabA, w.tabB});
+    return hash_index(make_sparse_key(voxel_size, tolerant), TabPlain{w.tabA, w.tabB});
 }
 
 // order (descending stable argsort of voxel_npoints) for MAXVOX_DESCENDING, implemented in sort.hip
@@ -5308,6 +5429,81 @@ extern "C" int d3d_voxelize_3d_filter_chained(const float *feats, int64_t n, int
                        out_mask, out_mapping, out_npoints, out_coords, counts, workspace, workspace_bytes, stream);
 }
 
+// Route 2 of the fused sparse + filter call, taken by every frame of the binned index that sparse_filter_bound does not take:
+// binned index + voxel filter in one numbering.  A voxel that fails the filter (coordinate bounds, min_points) gets no
+// first-point entry, so the first-seen numbering IS the filtered numbering (and its max_voxels cut the TRIM voxel filter); the
+// per-voxel outputs are written once, filtered; k_bucket_index leaves every point's filtered voxel (or none: no voxel /
+// filtered voxel / trimmed point), which is all the point compaction needs.  The intermediate sparse outputs (points_mapping,
+// coords, npoints) are not materialised on this path but as DESCENDING's scratch rows; sparse_counts holds the status bits (and
+// the filtered voxel count).
+static int sparse_filter_binned(const SparseFilterArgs &a, const VoxelWs &w, uint32_t nbins, int hshift, bool tolerant)
+{
+    hipStream_t st = a.stream;
+    const int64_t n = a.n;
+    const bool desc = a.desc();
+    // DESCENDING (voxelize.cpp:404-420): first-seen numbering of ALL passing voxels into scratch rows, then a stable
+    // sort of their counts decides the ranks, the first max_voxels of which are the result (k_desc_finish)
+    int32_t *desc_keys = reinterpret_cast<int32_t *>(w.big_list), *desc_order = reinterpret_cast<int32_t *>(w.parr);
+    BinnedRequest d;
+    d.P = a.trim() ? (uint32_t)a.max_points : 0u;
+    d.max_voxels = (a.max_voxels_filter == D3D_MAXVOX_NONE || desc) ? 0xffffffffu : (uint32_t)a.max_voxels;
+    d.coords = desc ? a.coords : a.out_coords;
+    d.npoints = desc ? a.npoints : a.out_npoints;
+    if (desc) { d.count_out = desc_keys; d.first_out = a.points_mapping; }
+    d.pass = make_voxel_pass(a.coords_bound, a.min_points);
+    d.npoints_clamp = a.npoints_clamp();
+    // the compaction maps the points itself, in point order: k_bucket_index leaves every kept point's voxel (its
+    // first point) by point index, trimmed points and filtered voxels already taken out (k_map_binned as a launch of
+    // its own: 21 us of kernel, 173 vs 158 us per call)
+    d.map_later = true;
+    d.early_host = desc ? nullptr : a.host_counts;     // output sizes to the host right after the numbering (DESCENDING:
+                                                       // they are known after the sort; k_compact_kept's last tile tells)
+    d.coord_offset = a.coord_offset;
+    d.compact_stat = w.bsum;                // look-back words of k_compact_kept: k_meta_first clears them
+    d.compact_tiles = (uint32_t)d3d_divup(n, kCompactTile);
+    int rc = binned_index<SparseKey, false>(make_sparse_key(a.voxel_size, tolerant), a.points, n, a.c, w, nbins, hshift, a.sparse_counts, d, st,
+                                            !(a.flags & D3D_VOXEL_PARTITION_3PASS));
+    if (rc) return rc;
+    if (desc) {
+        // (one counting pass on min(count, 255) + the few larger ones ranked among themselves: sort.hip)
+        const size_t sort_bytes = d3d_internal_argsort_counts_bytes(n);
+        if (sort_bytes > w.tab_bytes) return D3D_ERR_WORKSPACE;
+        rc = d3d_internal_argsort_desc_counts_dev(desc_keys, n, a.sparse_counts + D3D_COUNT_VOXELS, n, desc_order, w.tabA, w.tab_bytes, st);
+        if (rc) return rc;
+        D3D_LAUNCH("k_desc_finish", k_desc_finish, dim3((unsigned)d3d_divup(n, 256)), dim3(256), 0, st, (const int32_t *)desc_order,
+                   a.sparse_counts, (uint32_t)a.max_voxels, (const int64_t *)a.coords, (const int32_t *)a.npoints,
+                   (const int64_t *)a.points_mapping, a.out_coords, a.out_npoints, w.voff, a.sparse_counts + D3D_COUNT_AUX);
+    }
+    // (both output sizes went to the host from k_meta_first_lb's last tile, before this launch; DESCENDING: from this one's)
+    const int vix = desc ? D3D_COUNT_AUX : D3D_COUNT_VOXELS;
+    int64_t *late_host = desc ? a.host_counts : nullptr;
+    const bool v4 = a.c == 4 && ((reinterpret_cast<uintptr_t>(a.points) | reinterpret_cast<uintptr_t>(a.out_feats)) & 15) == 0;
+    unsigned int *cticket = w.big_count + 41;
+    return dispatch(v4, [&](auto vec4) {
+        D3D_LAUNCH("k_compact_kept", k_compact_kept<vec4>, dim3(d.compact_tiles), dim3(kCompactThreads), 0, st, a.points, (int)a.c,
+                   n, w.npad, (const uint32_t *)w.pslot, (const uint32_t *)w.voff, a.out_feats, a.out_mask, a.out_mapping, w.bsum,
+                   cticket, a.counts, (const int64_t *)a.sparse_counts, late_host, vix);
+        return D3D_OK;
+    });
+}
+
+// Route 3, taken by the other filter combinations and sizes (wide keys, more than 16 M points, the hash path on request, missing
+// buffers -- which the two operators then report): the two operators one after the other, the voxel count staying on the device
+static int sparse_filter_two_calls(const SparseFilterArgs &a, bool tolerant)
+{
+    int rc = voxelize_sparse_impl(a.points, a.n, a.c, a.voxel_size, a.points_mapping, a.coords, a.npoints, a.sparse_counts, a.workspace,
+                                  a.workspace_bytes, a.n, a.stream, a.flags, tolerant);
+    if (rc) return rc;
+    rc = filter_impl(a.points, a.n, a.c, a.points_mapping, a.coords, a.npoints, a.n, a.sparse_counts + D3D_COUNT_VOXELS, a.coords_bound,
+                     a.min_points, a.max_points, a.max_voxels, a.max_points_filter, a.max_voxels_filter, a.out_feats, a.out_mask,
+                     a.out_mapping, a.out_npoints, a.out_coords, a.counts, a.workspace, a.workspace_bytes, a.stream, a.host_counts,
+                     a.sparse_counts);
+    if (rc == D3D_OK && a.coord_offset && a.n > 0)
+        D3D_LAUNCH("k_sub_offset", k_sub_offset, dim3(grid_for(a.n * 3, 256)), dim3(256), 0, a.stream, a.out_coords,
+                   (const int64_t *)a.counts, a.n, (long long)a.coord_offset[0], (long long)a.coord_offset[1], (long long)a.coord_offset[2]);
+    return rc;
+}
+
 // VoxelGenerator.__call__'s sparse branch in one call (voxel/__init__.py:93-102): voxelize_sparse followed by
 // voxelize_filter on its outputs, the voxel count staying on the device.  With the TRIM point filter the ranking "is this
 // point among the first max_points of its voxel" (voxelize.cpp:457-463) is taken from the binned index, which has every
@@ -5324,120 +5520,42 @@ extern "C" int d3d_voxelize_3d_sparse_filter(const float *points, int64_t n, int
 {
     if (!sparse_counts || max_points < 0) return D3D_ERR_BAD_ARG;
     if (flags & ~(uint32_t)D3D_VOXEL_FLAGS_ALL) return D3D_ERR_BAD_ARG;
-    const bool desc = max_voxels_filter == D3D_MAXVOX_DESCENDING;     // fused below; the two-operator form needs the count on the host
+    SparseFilterArgs a;
+    a.points = points; a.n = n; a.c = c; a.voxel_size = voxel_size; a.coords_bound = coords_bound;
+    a.min_points = min_points; a.max_points = max_points; a.max_voxels = max_voxels;
+    a.max_points_filter = max_points_filter; a.max_voxels_filter = max_voxels_filter;
+    a.points_mapping = points_mapping; a.coords = coords; a.npoints = npoints; a.sparse_counts = sparse_counts;
+    a.out_feats = out_feats; a.out_mask = out_mask; a.out_mapping = out_mapping; a.out_npoints = out_npoints; a.out_coords = out_coords;
+    a.counts = counts; a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.stream = (hipStream_t)stream;
+    a.host_counts = host_counts; a.flags = flags; a.coord_offset = coord_offset;
+    const bool desc = a.desc();     // fused below; the two-operator form needs the count on the host
     // points outside the 3 x 21-bit key range (NaN / inf, |floor(p/size)| >= 2^20): the reference gives them a far-away
     // voxel (voxelize.cpp:309) that its coordinate-bound filter drops (:376-384).  With the bounds inside the key range the
     // same points are simply dropped here; only bounds reaching beyond it keep the COORD_OVERFLOW error.
     bool tolerant = coords_bound != nullptr;
     for (int k = 0; tolerant && k < 3; k++)
         tolerant = coords_bound[2 * k] >= -1048576 && coords_bound[2 * k + 1] <= 1048576;
-    {
-        // Binned index + voxel filter in one numbering: a voxel that fails the filter (coordinate bounds, min_points) gets no
-        // first-point entry, so the first-seen numbering IS the filtered numbering (and its max_voxels cut the TRIM voxel
-        // filter); the per-voxel outputs are written once, filtered; k_map_binned leaves every point's filtered voxel id
-        // (or -1: no voxel / filtered voxel / trimmed point), which is all the point compaction needs.  The intermediate
-        // sparse outputs (points_mapping, coords, npoints) are not materialised on this path; sparse_counts holds the
-        // status bits (and the filtered voxel count).
-        hipStream_t st = (hipStream_t)stream;
-        const bool pf_ok = max_points_filter == D3D_MAXPTS_NONE || (max_points_filter == D3D_MAXPTS_TRIM && max_points > 0);
-        const bool vf_ok = max_voxels_filter == D3D_MAXVOX_NONE || max_voxels_filter == D3D_MAXVOX_TRIM ||
-                           (desc && points_mapping && coords && npoints);
-        if (!(flags & D3D_VOXEL_WIDE_KEYS) && pf_ok && vf_ok && n > 0 && c >= 3 && n < (1ll << 31) - kFlagTile && points && voxel_size && coords_bound && counts &&
-            out_feats && out_mask && out_mapping && out_npoints && out_coords && workspace && max_voxels >= 0) {
-            VoxelWs w = carve(workspace, workspace_bytes, n, n);
-            if (w.bytes > workspace_bytes) return D3D_ERR_WORKSPACE;
-            uint32_t nbins = 0;
-            int hshift = 0;
-            if (binned_eligible(n, w, flags, &nbins, &hshift)) {
-                const bool trim = max_points_filter == D3D_MAXPTS_TRIM;
-                // round 5: three launches on 32-bit cells inside the coordinate bounds (not DESCENDING, whose sort sits between
-                // the numbering and the compaction; not on request of round 4's kernels; boxes of 2^32 - 1 cells and more, or
-                // reaching INT_MIN -- where the reference files its NaN points -- keep the 63-bit keys)
-                if (!desc && !(flags & D3D_VOXEL_PARTITION_3PASS)) {
-                    BoundKey bk;
-                    double cells = 1.0;
-                    bool ok = true;
-                    for (int d = 0; d < 3; d++) {
-                        const int64_t lo = coords_bound[2 * d], hi = coords_bound[2 * d + 1];
-                        ok = ok && lo > (int64_t)INT_MIN && hi <= (int64_t)INT_MAX + 1 && hi > lo && hi - lo < (1ll << 32);
-                        bk.size[d] = voxel_size[d];
-                        bk.lo[d] = (long long)lo;
-                        bk.ext[d] = ok ? (unsigned)(hi - lo) : 1u;
-                        cells *= (double)(hi - lo);
-                    }
-                    if (ok && cells < 4294967295.0) {
-                        VoxelPass vp{true, min_points, {0, 0, 0}, {0, 0, 0}};
-                        for (int k = 0; k < 3; k++) { vp.lo[k] = coords_bound[2 * k]; vp.hi[k] = coords_bound[2 * k + 1]; }
-                        const uint32_t vcap2 = max_voxels_filter == D3D_MAXVOX_NONE ? 0xffffffffu : (uint32_t)max_voxels;
-                        int rc = sparse_fused_index(bk, points, n, c, w, nbins, hshift, vp, trim ? (uint32_t)max_points : 0u, vcap2,
-                                                    trim ? (uint32_t)max_points : 0xffffffffu, coord_offset, out_feats, out_mask, out_mapping,
-                                                    out_npoints, out_coords, sparse_counts, counts, host_counts, st);
-                        if (rc != D3D_ERR_UNSUPPORTED) return rc;
-                    }
-                }
-                SparseKey kf;
-                for (int d = 0; d < 3; d++) kf.size[d] = voxel_size[d];
-                kf.tolerant = tolerant;
-                // DESCENDING (voxelize.cpp:404-420): first-seen numbering of ALL passing voxels into scratch rows, then a stable
-                // sort of their counts decides the ranks, the first max_voxels of which are the result (k_desc_finish)
-                const uint32_t vcap = (max_voxels_filter == D3D_MAXVOX_NONE || desc) ? 0xffffffffu : (uint32_t)max_voxels;
-                DenseOut d{trim ? (uint32_t)max_points : 0u, vcap, D3D_REDUCE_NONE, false, false, desc ? coords : out_coords,
-                           desc ? npoints : out_npoints, nullptr, nullptr, BinnedExtras{nullptr, 0, nullptr, -1, nullptr, nullptr}, nullptr};
-                int32_t *desc_keys = reinterpret_cast<int32_t *>(w.big_list), *desc_order = reinterpret_cast<int32_t *>(w.parr);
-                if (desc) { d.count_out = desc_keys; d.first_out = points_mapping; }
-                d.pass.on = true;
-                d.pass.min_points = min_points;
-                for (int k = 0; k < 3; k++) { d.pass.lo[k] = coords_bound[2 * k]; d.pass.hi[k] = coords_bound[2 * k + 1]; }
-                d.npoints_clamp = trim ? (uint32_t)max_points : 0xffffffffu;
-                // the compaction maps the points itself, in point order: k_bucket_index leaves every kept point's voxel (its
-                // first point) by point index, trimmed points and filtered voxels already taken out (k_map_binned as a launch of
-                // its own: 21 us of kernel, 173 vs 158 us per call)
-                d.map_later = true;
-                d.early_host = desc ? nullptr : host_counts;     // output sizes to the host right after the numbering (DESCENDING:
-                                                                 // they are known after the sort; k_compact_kept's last tile tells)
-                d.coord_offset = coord_offset;
-                d.compact_stat = w.bsum;                // look-back words of k_compact_kept: k_meta_first clears them
-                d.compact_tiles = (uint32_t)d3d_divup(n, kCompactTile);
-                int rc = binned_index<SparseKey, false>(kf, points, n, c, w, nbins, hshift, sparse_counts, d, st, !(flags & D3D_VOXEL_PARTITION_3PASS));
-                if (rc) return rc;
-                if (desc) {
-                    // (one counting pass on min(count, 255) + the few larger ones ranked among themselves: sort.hip)
-                    const size_t sort_bytes = d3d_internal_argsort_counts_bytes(n);
-                    if (sort_bytes > w.tab_bytes) return D3D_ERR_WORKSPACE;
-                    rc = d3d_internal_argsort_desc_counts_dev(desc_keys, n, sparse_counts + D3D_COUNT_VOXELS, n, desc_order, w.tabA,
-                                                              w.tab_bytes, st);
-                    if (rc) return rc;
-                    D3D_LAUNCH("k_desc_finish", k_desc_finish, dim3((unsigned)d3d_divup(n, 256)), dim3(256), 0, st, (const int32_t *)desc_order,
-                               sparse_counts, (uint32_t)max_voxels, (const int64_t *)coords, (const int32_t *)npoints,
-                               (const int64_t *)points_mapping, out_coords, out_npoints, w.voff, sparse_counts + D3D_COUNT_AUX);
-                }
-                // (both output sizes went to the host from k_meta_first_lb's last tile, before this launch; DESCENDING: from this one's)
-                const int vix = desc ? D3D_COUNT_AUX : D3D_COUNT_VOXELS;
-                int64_t *late_host = desc ? host_counts : nullptr;
-                const bool v4 = c == 4 && ((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(out_feats)) & 15) == 0;
-                unsigned int *cticket = w.big_count + 41;
-                return dispatch(v4, [&](auto vec4) {
-                    D3D_LAUNCH("k_compact_kept", k_compact_kept<vec4>, dim3(d.compact_tiles), dim3(kCompactThreads), 0, st, points, (int)c,
-                               n, w.npad, (const uint32_t *)w.pslot, (const uint32_t *)w.voff, out_feats, out_mask, out_mapping, w.bsum,
-                               cticket, counts, (const int64_t *)sparse_counts, late_host, vix);
-                    return D3D_OK;
-                });
-            }
-        }
+    // the fused routes: a frame of the binned index with every buffer in place and filters they implement
+    const bool pf_ok = max_points_filter == D3D_MAXPTS_NONE || (a.trim() && max_points > 0);
+    const bool vf_ok = max_voxels_filter == D3D_MAXVOX_NONE || max_voxels_filter == D3D_MAXVOX_TRIM ||
+                       (desc && points_mapping && coords && npoints);
+    VoxelWs w{};
+    uint32_t nbins = 0;
+    int hshift = 0;
+    bool binned = false;
+    if (!(flags & D3D_VOXEL_WIDE_KEYS) && pf_ok && vf_ok && n > 0 && points_args_ok(n, c, flags) && points && voxel_size && coords_bound &&
+        counts && out_feats && out_mask && out_mapping && out_npoints && out_coords && workspace && max_voxels >= 0) {
+        w = carve(workspace, workspace_bytes, n, n);
+        if (w.bytes > workspace_bytes) return D3D_ERR_WORKSPACE;
+        binned = binned_eligible(n, w, flags, &nbins, &hshift);
     }
+    if (binned && !desc && !(flags & D3D_VOXEL_PARTITION_3PASS)) {
+        const int rc = sparse_filter_bound(a, w, nbins, hshift);
+        if (rc != D3D_ERR_UNSUPPORTED) return rc;
+    }
+    if (binned) return sparse_filter_binned(a, w, nbins, hshift, tolerant);
     if (desc) return D3D_ERR_UNSUPPORTED;      // (the two-operator form sorts on a host-side count: the caller runs the two calls)
-    // other filter combinations / sizes: the two operators one after the other, the voxel count staying on the device
-    int rc = voxelize_sparse_impl(points, n, c, voxel_size, points_mapping, coords, npoints, sparse_counts, workspace,
-                                  workspace_bytes, n, stream, flags, tolerant);
-    if (rc) return rc;
-    rc = filter_impl(points, n, c, points_mapping, coords, npoints, n, sparse_counts + D3D_COUNT_VOXELS, coords_bound,
-                     min_points, max_points, max_voxels, max_points_filter, max_voxels_filter, out_feats, out_mask,
-                     out_mapping, out_npoints, out_coords, counts, workspace, workspace_bytes, stream, host_counts,
-                     sparse_counts);
-    if (rc == D3D_OK && coord_offset && n > 0)
-        D3D_LAUNCH("k_sub_offset", k_sub_offset, dim3(grid_for(n * 3, 256)), dim3(256), 0, (hipStream_t)stream, out_coords,
-                   (const int64_t *)counts, n, (long long)coord_offset[0], (long long)coord_offset[1], (long long)coord_offset[2]);
-    return rc;
+    return sparse_filter_two_calls(a, tolerant);
 }
 
 // d3d_voxelize_3d_sparse_filter through one prepared argument block (include/d3d_hip.h, D3DSparseFilterCall)

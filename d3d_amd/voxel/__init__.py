@@ -158,6 +158,7 @@ class DenseOutputBuffer:
         with torch.inference_mode(False):
             self.voxels = torch.zeros((self.capacity, self.max_points, self.columns), dtype=torch.float32, device=self.device)
             self.row_state = torch.zeros((self.capacity,), dtype=torch.int16, device=self.device)       # (uint16 bits)
+        self.row_arg = (_lib.ptr(self.row_state),)     # the resident entries' row_state argument, marshalled once
         self.pooled = bool(pooled)
         self.used = False           # the last call with this buffer returned a view of it (else: a fresh tensor, buffer untouched)
         self.refused = False        # the last call's resident entry did not take the frame at all (D3D_ERR_UNSUPPORTED)
@@ -244,6 +245,41 @@ class _OutputPool:
         self.off = True
 
 
+def _dense_outputs(cap, max_points, c, red, dev, voxels=None):
+    """-> (voxels, coords, pmask, npoints, aggregates | None, counts): the dense contract's output buffers for up to `cap` voxels
+    (voxels: a resident buffer's, in the place of a fresh tensor)"""
+    if voxels is None:
+        voxels = torch.empty((cap, max_points, c), dtype=torch.float32, device=dev)
+    return (voxels, torch.empty((cap, 3), dtype=torch.int64, device=dev), torch.empty((cap, max_points), dtype=torch.uint8, device=dev),
+            torch.empty((cap,), dtype=torch.int32, device=dev), torch.empty((cap, c), dtype=torch.float32, device=dev) if red != 0 else None,
+            torch.empty((_lib.NUM_COUNTS,), dtype=torch.int64, device=dev))
+
+
+def _poison_outputs(out, voxels_too=True):
+    voxels, coords, pmask, npts, agg, _ = out
+    if voxels_too:
+        voxels.fill_(float("nan"))
+    coords.fill_(-(1 << 62)); pmask.fill_(0xff); npts.fill_(-7)
+    if agg is not None:
+        agg.fill_(float("nan"))
+
+
+def _dense_result(out, nv):
+    voxels, coords, pmask, npts, agg, _ = out
+    ret = {"voxels": voxels[:nv], "coords": coords[:nv], "voxel_pmask": pmask[:nv].view(torch.bool), "voxel_npoints": npts[:nv]}
+    if agg is not None:
+        ret["aggregates"] = agg[:nv]
+    return ret
+
+
+def _dense_args(pts, shape_h, bound_h, max_points, max_voxels, red, out, ws, row=()):
+    """the 16 arguments every dense entry of the C ABI begins with (include/d3d_hip.h); row: (pointer to the row state,) for the
+    resident entries, which take it behind `voxels`.  The host arrays go as they are: for a void pointer ctypes passes their address."""
+    voxels, coords, pmask, npts, agg, counts = out
+    return (_lib.ptr(pts), pts.shape[0], pts.shape[1], shape_h, bound_h, max_points, max_voxels, red, _lib.ptr(voxels), *row,
+            _lib.ptr(coords), _lib.ptr(pmask), _lib.ptr(npts), _lib.ptr(agg), _lib.ptr(counts), _lib.ptr(ws), ws.numel())
+
+
 def voxelize_3d_dense(points, voxel_shape, voxel_bound, max_points, max_voxels, reduction_type, flags=None, poison=None,
                       resident=None):
     """voxelize_3d_dense of the reference (voxelize.h:9-12; voxelize.cpp:45-199).
@@ -272,68 +308,44 @@ def voxelize_3d_dense(points, voxel_shape, voxel_bound, max_points, max_voxels, 
     if resident is not None:
         resident.used = resident.refused = False
     with _device_ctx(dev):
-        voxels = resident.voxels if resident is not None else torch.empty((cap, max_points, c), dtype=torch.float32, device=dev)
-        coords = torch.empty((cap, 3), dtype=torch.int64, device=dev)
-        pmask = torch.empty((cap, max_points), dtype=torch.uint8, device=dev)
-        npts = torch.empty((cap,), dtype=torch.int32, device=dev)
-        agg = torch.empty((cap, c), dtype=torch.float32, device=dev) if red != 0 else None
-        counts = torch.empty((_lib.NUM_COUNTS,), dtype=torch.int64, device=dev)
+        out = _dense_outputs(cap, max_points, c, red, dev, None if resident is None else resident.voxels)
         ws = _lib.workspace(_workspace_bytes(lib, n), dev)
         note = _lib.NotifyBuffer.get()
         if options.current().poison if poison is None else poison:
-            if resident is None:
-                voxels.fill_(float("nan"))
-            coords.fill_(-(1 << 62)); pmask.fill_(0xff); npts.fill_(-7)
-            if agg is not None:
-                agg.fill_(float("nan"))
+            _poison_outputs(out, voxels_too=resident is None)
 
-        def run_resident(fl):
-            note.arm()
-            entry = lib.d3d_voxelize_3d_dense_pooled if resident.pooled else lib.d3d_voxelize_3d_dense_resident
-            rc = entry(
-                _lib.ptr(pts), n, c, ctypes.cast(shape_h, ctypes.c_void_p), ctypes.cast(bound_h, ctypes.c_void_p),
-                max_points, max_voxels, red, _lib.ptr(voxels), _lib.ptr(resident.row_state), _lib.ptr(coords), _lib.ptr(pmask),
-                _lib.ptr(npts), _lib.ptr(agg), _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), note.ptr, fl)
-            if rc == _lib.ERR_UNSUPPORTED:
-                resident.refused = True
-                return None                 # nothing was touched: the plain call decides (and reports a bad reduction type)
-            _lib.check(rc, "voxelize_3d_dense_resident")
-            host = note.wait(counts)
-            _check_status(int(host[_lib.COUNT_STATUS]), "voxelize_3d_dense_resident")
-            resident.used = True
-            return int(host[_lib.COUNT_VOXELS])
-
-        def run(fl):
-            nonlocal voxels
-            if resident is not None:
-                if not (fl & _lib.VOXEL_PATH_HASH):
-                    nv_res = run_resident(fl)
-                    if nv_res is not None:
-                        return nv_res
-                # (a frame the binned index does not take -- above 8 M points, or a bucket overflowed and the call is repeated
-                # on the hash path: those paths write whole tensors, a fresh one for this frame; the buffer's invariant is
-                # untouched and the next frame uses it again)
-                voxels = torch.empty((cap, max_points, c), dtype=torch.float32, device=dev)
+        def call(entry, what, fl, row=()):
+            """-> the voxel count, None when the entry does not take the call (D3D_ERR_UNSUPPORTED: nothing was touched)"""
             # the voxel count reaches the host through pinned memory as soon as it is final, while the GPU is still
             # writing voxels[V,P,C]: the call returns views of outputs in flight on the current stream, like any torch op
             note.arm()
-            rc = lib.d3d_voxelize_3d_dense_notify(
-                _lib.ptr(pts), n, c, ctypes.cast(shape_h, ctypes.c_void_p), ctypes.cast(bound_h, ctypes.c_void_p),
-                max_points, max_voxels, red, _lib.ptr(voxels), _lib.ptr(coords), _lib.ptr(pmask), _lib.ptr(npts),
-                _lib.ptr(agg), _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), note.ptr, fl)
+            rc = entry(*_dense_args(pts, shape_h, bound_h, max_points, max_voxels, red, out, ws, row), _lib.stream_ptr(), note.ptr, fl)
             if rc == _lib.ERR_UNSUPPORTED:
-                raise ValueError("Unsupported reduction type in voxelization!")   # voxelize.cpp:196
-            _lib.check(rc, "voxelize_3d_dense")
-            host = note.wait(counts)
-            _check_status(int(host[_lib.COUNT_STATUS]), "voxelize_3d_dense")
+                return None
+            _lib.check(rc, what)
+            host = note.wait(out[5])
+            _check_status(int(host[_lib.COUNT_STATUS]), what)
             return int(host[_lib.COUNT_VOXELS])
+
+        def run(fl):
+            nonlocal out
+            if resident is not None:
+                if not (fl & _lib.VOXEL_PATH_HASH):
+                    entry = lib.d3d_voxelize_3d_dense_pooled if resident.pooled else lib.d3d_voxelize_3d_dense_resident
+                    nv = call(entry, "voxelize_3d_dense_resident", fl, resident.row_arg)
+                    resident.used, resident.refused = nv is not None, nv is None
+                    if nv is not None:
+                        return nv               # (else the plain call decides, and reports a bad reduction type)
+                # (a frame the binned index does not take -- above 8 M points, or a bucket overflowed and the call is repeated
+                # on the hash path: those paths write whole tensors, a fresh one for this frame; the buffer's invariant is
+                # untouched and the next frame uses it again)
+                out = (torch.empty((cap, max_points, c), dtype=torch.float32, device=dev),) + out[1:]
+            nv = call(lib.d3d_voxelize_3d_dense_notify, "voxelize_3d_dense", fl)
+            if nv is None:
+                raise ValueError("Unsupported reduction type in voxelization!")   # voxelize.cpp:196
+            return nv
         nv = _with_retry(run, flags)
-    ret = dict(voxels=voxels[:nv], coords=coords[:nv], voxel_pmask=pmask[:nv].view(torch.bool),
-               voxel_npoints=npts[:nv])
-    if red != 0:
-        ret["aggregates"] = agg[:nv]
-    ret = _lib.to_caller(ret, odev, dev)
-    return ret
+    return _lib.to_caller(_dense_result(out, nv), odev, dev)
 
 
 def voxelize_3d_sparse(points, voxel_size, ndim=3, flags=None):
@@ -788,20 +800,15 @@ def _stream_frames(gen, frames, flags, poison):
 
     def finish(item):
         slot, out, pts = item
-        voxels, coords, pmask, npts, agg, counts = out
         # the outputs (and `counts`) are written on the side stream: the caller's stream waits for them BEFORE anything reads
         # them there -- note.wait() polls host memory, but its fallback after 50 ms is a device read of `counts` on this stream
         torch.cuda.current_stream().wait_event(slot.out_done)
-        host = slot.note.wait(counts)
+        host = slot.note.wait(out[5])
         slot.busy = False
         if int(host[_lib.COUNT_STATUS]) != 0:                       # a capacity limit of the fast index: this frame again, alone
             torch.cuda.current_stream().synchronize()
             return gen(pts, flags=flags, poison=poison)
-        nv = int(host[_lib.COUNT_VOXELS])
-        ret = Dict(voxels=voxels[:nv], coords=coords[:nv], voxel_pmask=pmask[:nv].view(torch.bool), voxel_npoints=npts[:nv])
-        if red != 0:
-            ret["aggregates"] = agg[:nv]
-        return ret
+        return Dict(_dense_result(out, int(host[_lib.COUNT_VOXELS])))
 
     k = 0
     try:
@@ -826,22 +833,13 @@ def _stream_frames(gen, frames, flags, poison):
                 if slot.busy:                                            # (cannot happen: a slot's frame is finished two frames on)
                     raise RuntimeError("frame slot still in flight")
                 cur = torch.cuda.current_stream()
-                voxels = torch.empty((cap, P, 4), dtype=torch.float32, device=dev)
-                coords = torch.empty((cap, 3), dtype=torch.int64, device=dev)
-                pmask = torch.empty((cap, P), dtype=torch.uint8, device=dev)
-                npts = torch.empty((cap,), dtype=torch.int32, device=dev)
-                agg = torch.empty((cap, 4), dtype=torch.float32, device=dev) if red != 0 else None
-                counts = torch.empty((_lib.NUM_COUNTS,), dtype=torch.int64, device=dev)
+                out = _dense_outputs(cap, P, 4, red, dev)
                 if poison:
-                    voxels.fill_(float("nan")); coords.fill_(-(1 << 62)); pmask.fill_(0xff); npts.fill_(-7)
-                    if agg is not None:
-                        agg.fill_(float("nan"))
+                    _poison_outputs(out)
                 need = _workspace_bytes(lib, n)
                 if slot.ws is None or slot.ws.numel() < need:
                     slot.ws = torch.empty(int(need * 1.25), dtype=torch.uint8, device=dev)
-                args = (_lib.ptr(pts), n, 4, ctypes.cast(gen._shape_h, ctypes.c_void_p), ctypes.cast(gen._bounds_h, ctypes.c_void_p),
-                        P, mv, red, _lib.ptr(voxels), _lib.ptr(coords), _lib.ptr(pmask), _lib.ptr(npts), _lib.ptr(agg),
-                        _lib.ptr(counts), _lib.ptr(slot.ws), slot.ws.numel())
+                args = _dense_args(pts, gen._shape_h, gen._bounds_h, P, mv, red, out, slot.ws)
                 s_idx.wait_stream(cur)                                   # the frame (and the poison fills) are ready
                 if slot.used:
                     s_idx.wait_event(slot.out_done)                      # this slot's scratch: its last frame's output has read it
@@ -869,7 +867,7 @@ def _stream_frames(gen, frames, flags, poison):
                 # per frame, 314 us per frame measured)
             if pending is not None:
                 yield finish(pending)
-            pending = (slot, (voxels, coords, pmask, npts, agg, counts), pts)
+            pending = (slot, out, pts)
         if pending is not None:
             yield finish(pending)
     finally:

@@ -164,3 +164,119 @@ def test_sparse_call_block_layout_matches_the_header(tmp_path):
         assert list(off)[0] == 0 and all(o % 256 == 0 for o in off)
         assert all(off[k] + sizes[k] <= (off[k + 1] if k < 4 else total) for k in range(5))
         assert lib.d3d_voxelize_3d_sparse_filter_call_workspace_bytes(n) > lib.d3d_voxelize_workspace_bytes(n, n)
+
+
+# ---- the voxel entries' argument checks (they run before the first HIP call: no device needed) ----
+_DENSE_HEAD = "points n c shape bound max_points max_voxels reduction voxels"
+_DENSE_TAIL = "coords pmask npoints aggregates counts workspace workspace_bytes stream"
+_FILTER_TAIL = ("coords_bound min_points max_points max_voxels max_points_filter max_voxels_filter out_feats out_mask out_mapping "
+                "out_npoints out_coords counts workspace workspace_bytes stream")
+_VOXEL_PARAMS = {
+    "dense": "%s %s flags" % (_DENSE_HEAD, _DENSE_TAIL),
+    "dense_notify": "%s %s host_counts flags" % (_DENSE_HEAD, _DENSE_TAIL),
+    "dense_resident": "%s row_state %s host_counts flags" % (_DENSE_HEAD, _DENSE_TAIL),
+    "dense_pooled": "%s row_state %s host_counts flags" % (_DENSE_HEAD, _DENSE_TAIL),
+    "dense_staged": "%s %s host_counts flags stage" % (_DENSE_HEAD, _DENSE_TAIL),
+    "reduce": ("points n c shape bound reduction index_offset coords npoints aggregates first mapping keys max_points seg_base rows "
+               "counts workspace workspace_bytes stream flags"),
+    "sparse": "points n c voxel_size points_mapping coords npoints counts workspace workspace_bytes stream flags",
+    "filter": "feats n c points_mapping coords voxel_npoints nvox " + _FILTER_TAIL,
+    "filter_chained": "feats n c points_mapping coords voxel_npoints nvox sparse_counts " + _FILTER_TAIL,
+    "sparse_filter": ("points n c voxel_size coords_bound min_points max_points max_voxels max_points_filter max_voxels_filter "
+                      "points_mapping coords npoints sparse_counts out_feats out_mask out_mapping out_npoints out_coords counts "
+                      "workspace workspace_bytes stream host_counts flags coord_offset"),
+}
+_MEAN, _HASH, _SPLIT_FILL, _TRIM, _FARTHEST, _DESCENDING = 1, 1, 8, 1, 2, 2
+_BAD, _UNSUP, _WS = -1, -2, -3              # D3D_ERR_BAD_ARG, D3D_ERR_UNSUPPORTED, D3D_ERR_WORKSPACE
+_DENSE_FAMILY = ("dense", "dense_notify", "dense_resident", "dense_pooled", "dense_staged")
+# (entry, what is wrong, the code a library built from the PARENT of the commit that added this test returns).  Cases the parent
+# answered with D3D_ERR_HIP had reached a HIP call and are not in the table.
+# (max_points = -1: _resident and _pooled refuse max_points <= 0 as unsupported before the common checks see it)
+_VOXEL_REJECTIONS = [(e, wrong, code[e in ("dense_resident", "dense_pooled")] if isinstance(code, tuple) else code)
+                     for e in _DENSE_FAMILY for wrong, code in (
+    (dict(n=-1), _BAD), (dict(c=2), _BAD), (dict(shape=None), _BAD), (dict(counts=None), _BAD), (dict(max_points=-1), (_BAD, _UNSUP)),
+    (dict(flags=0x100), _BAD), (dict(points=None), _BAD), (dict(reduction=-1), _UNSUP), (dict(reduction=4), _UNSUP),
+    (dict(reduction=_MEAN, aggregates=None), _BAD), (dict(reduction=_MEAN, max_points=0), _UNSUP), (dict(shape=(0, 10, 10)), _BAD),
+    (dict(workspace=None), _WS), (dict(workspace_bytes=16), _WS), (dict(voxels=None), _BAD),
+    (dict(reduction=9, workspace_bytes=16), _UNSUP), (dict(shape=(0, 10, 10), workspace_bytes=16), _BAD))]
+_VOXEL_REJECTIONS += [("dense_notify", dict(host_counts=None), _BAD)]
+_VOXEL_REJECTIONS += [(e, wrong, code) for e in ("dense_resident", "dense_pooled") for wrong, code in (
+    (dict(row_state=None), _BAD), (dict(max_points=0), _UNSUP), (dict(flags=_HASH), _UNSUP), (dict(flags=_SPLIT_FILL), _UNSUP),
+    (dict(c=9), _UNSUP), (dict(row_state=None, max_points=0), _BAD), (dict(max_points=0, flags=0x100), _UNSUP))]
+_VOXEL_REJECTIONS += [
+    ("dense_staged", dict(stage=3), _BAD), ("dense_staged", dict(n=0, stage=1), _UNSUP), ("dense_staged", dict(stage=1, max_points=8), _UNSUP),
+    ("reduce", dict(reduction=0), _UNSUP), ("reduce", dict(seg_base=True), _BAD), ("reduce", dict(seg_base=True, rows=True, c=5), _UNSUP),
+    ("reduce", dict(workspace_bytes=16), _WS),
+    ("sparse", dict(n=-1), _BAD), ("sparse", dict(voxel_size=None), _BAD), ("sparse", dict(flags=0x100), _BAD),
+    ("sparse", dict(points_mapping=None), _BAD), ("sparse", dict(workspace_bytes=16), _WS),
+    ("filter", dict(nvox=-1), _BAD), ("filter", dict(c=0), _BAD), ("filter", dict(coords_bound=None), _BAD),
+    ("filter", dict(max_points_filter=_FARTHEST), _UNSUP), ("filter", dict(max_points_filter=3), _BAD),
+    ("filter", dict(max_voxels_filter=3), _BAD), ("filter", dict(max_points=-1), _BAD), ("filter", dict(workspace_bytes=16), _WS),
+    ("filter_chained", dict(sparse_counts=None), _BAD), ("filter_chained", dict(max_voxels_filter=_DESCENDING), _UNSUP),
+    ("sparse_filter", dict(sparse_counts=None), _BAD), ("sparse_filter", dict(max_points=-1), _BAD),
+    ("sparse_filter", dict(flags=0x100), _BAD), ("sparse_filter", dict(max_voxels_filter=_DESCENDING, flags=_HASH), _UNSUP),
+    ("sparse_filter", dict(workspace_bytes=16), _WS),
+    ("sparse_filter_call", dict(block=None), _BAD), ("sparse_filter_call", dict(n=-1), _BAD), ("sparse_filter_call", dict(outputs=None), _BAD),
+    ("sparse_filter_call", dict(outputs_short=1), _BAD), ("sparse_filter_call", dict(workspace_short=1), _WS)]
+
+
+def _voxel_rejection_codes(lib):
+    """-> [(entry, what is wrong, expected, returned)] of _VOXEL_REJECTIONS on `lib`: n = 10 points of c = 4 columns, a grid of
+    10 x 10 x 10 cells over the unit cube, max_points = 4, max_voxels = 8; host arrays for what the entries read on the host, and
+    ONE 4 MiB host buffer whose address stands in for every device pointer"""
+    from d3d_amd.voxel import _SparseFilterCall
+    arena = (ctypes.c_char * (4 << 20))()
+    dev = ctypes.addressof(arena)
+    host = dict(shape=(ctypes.c_int32 * 3)(10, 10, 10), bound=(ctypes.c_float * 6)(0, 1, 0, 1, 0, 1),
+                voxel_size=(ctypes.c_float * 3)(0.1, 0.1, 0.1), coords_bound=(ctypes.c_int64 * 6)(0, 10, 0, 10, 0, 10))
+    scalars = dict(n=10, c=4, max_points=4, max_voxels=8, reduction=0, min_points=0, max_points_filter=0, max_voxels_filter=0,
+                   index_offset=0, nvox=5, workspace_bytes=len(arena), flags=0, stage=0)
+    absent = ("stream", "keys", "seg_base", "rows", "coord_offset")       # NULL unless the case sets them
+    keep = []
+
+    def value(name, wrong):
+        v = wrong.get(name, scalars.get(name, host.get(name, None if name in absent else dev)))
+        if isinstance(v, tuple):                    # another host array in the place of the default one
+            v = type(host[name])(*v)
+            keep.append(v)
+        if v is True:
+            v = dev
+        return ctypes.addressof(v) if isinstance(v, ctypes.Array) else v
+
+    out = []
+    for entry, wrong, expected in _VOXEL_REJECTIONS:
+        if entry == "sparse_filter_call":
+            off = (ctypes.c_size_t * 5)()
+            blk = _SparseFilterCall()
+            blk.points, blk.n, blk.c, blk.max_points, blk.max_voxels = dev, wrong.get("n", 10), 4, 4, 8
+            blk.voxel_size[:] = list(host["voxel_size"])
+            blk.coords_bound[:] = list(host["coords_bound"])
+            blk.outputs = wrong.get("outputs", dev)
+            blk.outputs_bytes = lib.d3d_voxelize_3d_sparse_filter_call_layout(10, 4, off) - wrong.get("outputs_short", 0)
+            blk.workspace = dev
+            blk.workspace_bytes = lib.d3d_voxelize_3d_sparse_filter_call_workspace_bytes(10) - wrong.get("workspace_short", 0)
+            assert blk.workspace_bytes <= len(arena) and blk.outputs_bytes <= len(arena)
+            rc = lib.d3d_voxelize_3d_sparse_filter_call(ctypes.byref(blk) if wrong.get("block", blk) is not None else None)
+        else:
+            reduce_defaults = dict(reduction=_MEAN) if entry == "reduce" else {}
+            args = [value(name, dict(reduce_defaults, **wrong)) for name in _VOXEL_PARAMS[entry].split()]
+            rc = getattr(lib, "d3d_voxelize_3d_" + entry)(*args)
+        out.append((entry, wrong, expected, rc))
+    return out
+
+
+def test_voxel_entries_reject_bad_arguments_before_any_launch():
+    """every voxel entry of the C ABI, one wrong argument per call (and a few pairs, for which of two codes wins): the status
+    code, fixed as literals recorded on the library of this test's parent commit.  The checks run before the first HIP call;
+    not for a machine with a GPU, where a table of deliberately wrong arguments has no business."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("host-side argument checks: run where there is no GPU")
+    from d3d_amd import _lib
+    lib = _lib.load()
+    assert lib.d3d_voxelize_workspace_bytes(10, 10) < (4 << 20)
+    got = _voxel_rejection_codes(lib)
+    assert len(got) == len(_VOXEL_REJECTIONS) >= 5 * 17 + 1 + 2 * 7 + 3 + 4 + 5 + 8 + 2 + 5 + 5
+    assert all(code in (_BAD, _UNSUP, _WS) for _, _, code in _VOXEL_REJECTIONS)
+    wrong = [(e, w, "expected %d, got %d" % (x, rc)) for e, w, x, rc in got if rc != x]
+    assert not wrong, wrong
