@@ -166,6 +166,10 @@ SIGNATURES = {
     "d3d_table_conv_wgrad": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
     "d3d_table_pool_forward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "d3d_table_pool_backward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "d3d_voxel_corners_workspace_bytes": (_sz, [_i64]),
+    "d3d_voxel_corners": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3d_table_interp_forward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "d3d_table_interp_backward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _vp]),
 }
 
 _lib = None

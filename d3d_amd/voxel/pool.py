@@ -48,12 +48,15 @@ class VoxelIndex:
     :param mapping: [K] int64 (int32 is widened) voxel id of every point in [0, num_voxels), or -1 for "belongs to no voxel"
         (`points_mapping` of the sparse VoxelGenerator); torch tensor or numpy array, on the GPU or the host
     :param num_voxels: V
+    :param keep_mapping: False: `mapping` is None once the index is built -- for an owner that has the mapping in another form and
+        only folds through `order` / `offsets` (VoxelInterp: the widened copy of its int32 table would stay for the whole frame);
+        voxel_unpool and the backward of voxel_pool need it
 
     Holds `mapping` [K] int64, `order` [K'] int32 (the mapped points by ascending voxel id, ascending point index inside a voxel),
     `offsets` [V+1] int64 (CSR) and `num_mapped` = K', all on the GPU.  Building it reads two numbers back (K' and the count of
     ids outside [-1, V): ValueError if that is not 0); no pooling call reads anything back."""
 
-    def __init__(self, mapping, num_voxels):
+    def __init__(self, mapping, num_voxels, keep_mapping=True):
         mapping, _ = _as_tensor(mapping, "mapping")
         if mapping.dim() != 1:
             raise ValueError("mapping must be a [K] tensor of voxel ids")
@@ -86,6 +89,8 @@ class VoxelIndex:
             raise ValueError("mapping holds %d voxel ids outside [-1, %d)" % (bad, v))
         self.num_mapped = mapped
         self.order = order[:mapped]
+        if not keep_mapping:
+            self.mapping = None
 
 
 def _index_of(index_or_mapping, num_voxels):

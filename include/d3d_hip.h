@@ -1106,6 +1106,55 @@ int d3d_table_pool_backward(const void *grad_out, int64_t out_rows, int32_t c, i
                             int32_t k, int32_t mirrored, int32_t reduction, const int16_t *arg, const int32_t *count,
                             void *grad_feat, void *stream);
 
+/* ------------------------------------------------------------------ voxel features at arbitrary points: interpolation and splat */
+
+/* From the voxels back to ARBITRARY points: trilinear (or nearest) interpolation of sparse voxel features at fractional positions
+ * -- the devoxelize step of SPVCNN / PVCNN, PV-RCNN's keypoint features, the point head of a sparse U-Net -- and its transpose, the
+ * splat of point rows onto the voxels (csrc/vnbr.hip: the corner table; csrc/vinterp.hip: the two folds).  No float atomics; the
+ * [K, 8, C] buffer of gathered corner rows never exists.  The reference has no counterpart.
+ *
+ * d3d_voxel_corners: coords[v, 3] int64 and batch[v] int64 (may be NULL: one batch), unique as for d3d_voxel_neighbors;
+ *   positions[k, 3] in `dtype` (D3D_F32 / D3D_F64) in VOXEL UNITS, integer n the centre of voxel n; position_batch[k] int64 (given
+ *   exactly when batch is) -> table[k, J] int32 and weights[k, J] in `dtype`, J = corners = 8 (trilinear) or 1 (nearest).
+ *   The rules, every operation one rounding in `dtype` (the build does not contract):
+ *     per axis b = floor(x), f = x - b (f may come out as exactly 1 for a tiny negative x: that is the rule);
+ *     corner j = dx * 4 + dy * 2 + dz is the voxel at b + (dx, dy, dz) with the point's batch value (the last axis fastest);
+ *     w_j = (wx * wy) * wz with wa = f_a where the corner's bit on axis a is set, else 1 - f_a;
+ *     J = 1: the one corner floor(x + 0.5), weight 1;
+ *     a position that is not finite, or not in [-2^62, 2^62) on an axis, has no corners;
+ *     a corner outside the measured box of the coordinates (and of the batch values) is absent without a look-up;
+ *     an absent corner: table -1, weight 0;
+ *     normalize != 0: s = 0 + w_j0 + w_j1 + ... over the PRESENT corners in ascending j, every present weight is stored as w_j / s;
+ *       all weights stay 0 where no corner is present or s == 0.
+ *   counts[3] as d3d_voxel_neighbors': [0] the entries >= 0 of the table, [1] duplicate (batch, coordinate) rows, [2] the span
+ *   overflow flag (then table and weights are left untouched).  Launches: bounds, insert (both d3d_voxel_neighbors' own, also with
+ *   k == 0), look-up (one lane per (point, corner), the corner fastest); every dependency is a kernel boundary.  v == 0: table -1
+ *   and weights 0 by two fills, counts zeroed.  Workspace: d3d_voxel_corners_workspace_bytes(v), d3d_voxel_neighbors' layout.
+ * d3d_table_interp_forward: feat[v, c], table[rows, j], weights[rows, j] -> out[rows, c]: row r is 0, then + (w[r, jj] * feat[table[r,
+ *   jj]]) per present entry in ascending jj -- a rounding after the product and one after the sum; absent entries are skipped.
+ * d3d_table_interp_backward: grad[rows, c], weights[rows * j] -> grad_feat[v, c], the transpose: voxel u is 0, then + (w[e] * grad[e / j])
+ *   over e in order[offsets[u] .. offsets[u + 1]) in that order; order / offsets are what d3d_voxel_index returns for the flattened
+ *   table [rows * j] taken as the mapping (ascending voxel, ascending entry number inside one; they are trusted).  A voxel without
+ *   entries gets a zero row; every row is written exactly once.  This is also the forward of a splat, whose gradient is
+ *   d3d_table_interp_forward.
+ * dtype of the two folds: D3D_F32, D3D_F64, D3D_F16 or D3D_BF16 (feat, out, grad, grad_feat in it).  weights: fp64 for D3D_F64, fp32
+ *   otherwise.  D3D_F16 / D3D_BF16 multiply and add in fp32 and round once, to nearest even, at the store.  c >= 1; j is 1 or 8;
+ *   v and rows * j at most 2^31 - 1; offsets are 64-bit: rows * c may pass 2^31.  Rows move as 16-byte vectors when c is a multiple
+ *   of 4 (f32) / 2 (f64) / 8 (f16, bf16) and the feature and output pointers are 16-byte aligned, element by element otherwise: the
+ *   same bits on both paths.  A row's bits depend on its own entries only, and every run gives the same bits.  One launch each, no
+ *   workspace, nothing read back.
+ * D3D_ERR_BAD_ARG: a negative size, c < 1, a corner count other than 1 or 8, a missing pointer, batch without position_batch or the
+ *   reverse; D3D_ERR_UNSUPPORTED: another dtype, v or k * J (rows * j) above 2^31 - 1; D3D_ERR_WORKSPACE: workspace missing or smaller
+ *   than the query.  None of them launches anything.  rows == 0 (forward) and v == 0 (backward) return D3D_OK before any HIP call. */
+size_t d3d_voxel_corners_workspace_bytes(int64_t v);
+int d3d_voxel_corners(const int64_t *coords, const int64_t *batch, int64_t v, const void *positions, const int64_t *position_batch, int64_t k,
+                      int32_t dtype, int32_t corners, int32_t normalize, int32_t *table, void *weights, int64_t *counts, void *workspace,
+                      size_t workspace_bytes, void *stream);
+int d3d_table_interp_forward(const void *feat, int64_t v, int32_t c, int32_t dtype, const int32_t *table, const void *weights, int64_t rows,
+                             int32_t j, void *out, void *stream);
+int d3d_table_interp_backward(const void *grad, int64_t rows, int32_t c, int32_t dtype, const int32_t *order, const int64_t *offsets,
+                              const void *weights, int32_t j, int64_t v, void *grad_feat, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
