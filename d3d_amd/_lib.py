@@ -170,6 +170,12 @@ SIGNATURES = {
     "d3d_voxel_corners": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d3d_table_interp_forward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp]),
     "d3d_table_interp_backward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _vp]),
+    # (shape, origin: host int64[3]; axes: host int32[3])
+    "d3d_vdense_tile_cells": (_i32, []),
+    "d3d_vdense_sparse_cells": (_i32, []),
+    "d3d_vdense_map": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "d3d_vdense_scatter": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _i64, ctypes.c_double, _vp, _vp]),
+    "d3d_vdense_gather": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _i64, _vp, _vp]),
 }
 
 _lib = None

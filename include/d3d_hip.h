@@ -1155,6 +1155,48 @@ int d3d_table_interp_forward(const void *feat, int64_t v, int32_t c, int32_t dty
 int d3d_table_interp_backward(const void *grad, int64_t rows, int32_t c, int32_t dtype, const int32_t *order, const int64_t *offsets,
                               const void *weights, int32_t j, int64_t v, void *grad_feat, void *stream);
 
+/* ------------------------------------------------------------------ sparse voxel rows <-> a dense channels-first grid (BEV map) */
+
+/* The exit of a sparse backbone (csrc/vdense.hip): voxel rows [v, c] scattered into a dense grid [n, c, A, B, D] -- spconv's .dense();
+ * viewed [n, c * A, B, D] it is the BEV map the 2D heads take -- and the reverse, the values of a dense tensor at the active sites.
+ * Each is the other's gradient.  No float atomics, no workspace, nothing waits on another workgroup.  The reference has no counterpart.
+ *
+ * d3d_vdense_map: coords[v, 3] int64 and batch[v] int64 (may be NULL: every row in sample 0); HOST arrays shape[3] (>= 1) and
+ *   origin[3] int64 in coordinate-COLUMN order and axes[3] int32, a permutation of 0, 1, 2: dense axis k walks column axes[k], its
+ *   size is shape[axes[k]].  With (A, B, D) those three sizes and (a, b, d) = coords[axes[k]] - origin[axes[k]]:
+ *     cell[i] int64 = ((batch[i] * A + a) * B + b) * D + d, or -1 for a row that lies outside: a column outside [origin, origin +
+ *       shape) -- tested as (uint64) coord - (uint64) origin < (uint64) shape, so any int64 values are legal -- or a batch value
+ *       outside [0, batch_size);
+ *     index[batch_size * A * B * D] int32 = the row at every cell, -1 for none: filled with -1 first, then every inside row claims
+ *       its cell with an integer compare-and-swap -1 -> i;
+ *     counts[2] int64 (zeroed first): [0] the outside rows, [1] the rows whose claim failed (an earlier row holds the cell: a
+ *       repeated (batch, coordinate)).  With counts[1] != 0 WHICH of the rows holds a cell depends on the run: refuse the map.
+ *   Two fills and one launch (one lane per row; v == 0: the fills alone).
+ * d3d_vdense_scatter: feat[v, c] in `dtype`, index[n * cells_per_sample] (a map's, trusted: entries in [-1, v)) -> out[n, c,
+ *   cells_per_sample]: out[s, ch, p] = feat[index[s, p], ch] bit for bit where index[s, p] >= 0, else `fill` rounded once (to nearest
+ *   even) to the dtype.  EVERY element of out is written exactly once by this one launch: no memset before it.
+ * d3d_vdense_gather: dense[n, c, cells_per_sample], index -> out[v, c]: out[index[s, p], ch] = dense[s, ch, p] bit for bit for every
+ *   index[s, p] >= 0; rows that no cell names are left untouched (a map without outside rows names every row once).
+ * d3d_vdense_tile_cells: the cells of ONE sample a workgroup of the two kernels owns (a stretch; the last one of a sample is
+ *   partial).  A stretch without a present cell is filled (scatter) or skipped (gather) without staging anything.
+ * d3d_vdense_sparse_cells: a stretch with at most this many present cells moves them element by element instead of through the LDS
+ *   tile (the threshold between the two paths of the kernels: the tests put stretches on both sides of it).
+ * dtype: D3D_F32, D3D_F64, D3D_F16 or D3D_BF16; elements move as integers of their size (NaN payloads, infinities, -0.0 are kept).
+ *   Rows move as 16-byte vectors when c is a multiple of 4 (f32) / 2 (f64) / 8 (f16, bf16) and the row pointer is 16-byte aligned;
+ *   planes when cells_per_sample is such a multiple and the grid pointer is 16-byte aligned; element by element otherwise: the same
+ *   bits on every path and every run.  All offsets are 64-bit: n * c * cells_per_sample may pass 2^31.
+ * D3D_ERR_BAD_ARG: a negative size, batch_size < 1, a shape below 1, axes that are no permutation, a missing pointer with work to do;
+ *   D3D_ERR_UNSUPPORTED: another dtype, v above 2^31 - 1, n * cells_per_sample of 2^39 and more.  None of them launches anything.
+ *   c == 0, n == 0 or cells_per_sample == 0 (gather: v == 0 as well) return D3D_OK before any HIP call. */
+int32_t d3d_vdense_tile_cells(void);
+int32_t d3d_vdense_sparse_cells(void);
+int d3d_vdense_map(const int64_t *coords, const int64_t *batch, int64_t v, const int64_t *shape, const int64_t *origin, const int32_t *axes,
+                   int64_t batch_size, int64_t *cell, int32_t *index, int64_t *counts, void *stream);
+int d3d_vdense_scatter(const void *feat, int64_t v, int32_t c, int32_t dtype, const int32_t *index, int64_t n, int64_t cells_per_sample,
+                       double fill, void *out, void *stream);
+int d3d_vdense_gather(const void *dense, int64_t n, int32_t c, int32_t dtype, const int32_t *index, int64_t cells_per_sample, int64_t v,
+                      void *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
