@@ -176,7 +176,13 @@ SIGNATURES = {
     "d3d_vdense_map": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "d3d_vdense_scatter": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _i64, ctypes.c_double, _vp, _vp]),
     "d3d_vdense_gather": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _i64, _vp, _vp]),
+    # (point_offsets, sample_offsets, center_offsets: DEVICE int64 arrays)
+    "d3d_fps_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "d3d_fps_plan": (ctypes.c_int, [_i64, _i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "d3d_furthest_point_sample": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "d3d_ball_query": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _i64, ctypes.c_double, _i32, _i32, _vp, _vp, _vp]),
 }
+FPS_ROUTE_LDS, FPS_ROUTE_STREAM = 3, 4
 
 _lib = None
 

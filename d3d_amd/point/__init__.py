@@ -98,5 +98,7 @@ def aligned_scatter(coordinates, feature_map, method="drop"):
     return AlignedScatter.apply(feature_map, coordinates, align_type)
 
 
+from .sample import ball_query, fps_plan, furthest_point_sample      # noqa: E402
+
 __all__ = ["aligned_scatter", "AlignedScatter", "AlignType", "aligned_scatter_forward", "aligned_scatter_backward",
-           "cuda_available"]
+           "cuda_available", "furthest_point_sample", "ball_query", "fps_plan"]

@@ -1197,6 +1197,55 @@ int d3d_vdense_scatter(const void *feat, int64_t v, int32_t c, int32_t dtype, co
 int d3d_vdense_gather(const void *dense, int64_t n, int32_t c, int32_t dtype, const int32_t *index, int64_t cells_per_sample, int64_t v,
                       void *out, void *stream);
 
+/* ------------------------------------------------------------------ the point branch: furthest point sampling and ball query */
+
+/* Pick M well-spread rows of a cloud, then group the rows inside a radius of each (csrc/psample.hip): the first two steps of a
+ * PointNet++ set abstraction, PV-RCNN's keypoints, 3DSSD, Voxel R-CNN.  Both return indices only; no atomics, no sort, nothing waits
+ * on another workgroup, every run gives the same bits.  The reference has no counterpart.
+ *
+ * Both read columns 0 .. 2 of rows of `row_stride` (point_stride, center_stride) >= 3 ELEMENTS in `dtype` (D3D_F32 / D3D_F64); the
+ * base needs the alignment of one element only.  Every operation below is one rounding in the dtype (the build does not contract):
+ *     q(i, c) = ((dx * dx) + (dy * dy)) + (dz * dz),  dx = x_i - x_c, dy = y_i - y_c, dz = z_i - z_c.
+ *
+ * d3d_furthest_point_sample: segment b holds the rows point_offsets[b] .. point_offsets[b + 1] and gets M_b = sample_offsets[b + 1] -
+ *   sample_offsets[b] samples at indices[sample_offsets[b] ..] (int64, GLOBAL row numbers) and, where distances is not NULL, at
+ *   distances[sample_offsets[b] ..] in `dtype`.  Both offset arrays are DEVICE int64[segments + 1], nondecreasing from 0 (to n, and to
+ *   the number of samples), and TRUSTED: the caller has checked them (every segment at most 2^31 - 1 rows; no segment with 0 rows and
+ *   M_b > 0 -- such a segment would get indices -1 and NaN distances).  The rule, per segment:
+ *     a row is EXCLUDED when one of its three coordinates is not finite; every other row starts with d_i = +inf;
+ *     step s = 0 .. M_b - 1: c_s = the non-excluded row with the largest d, the LOWEST such row on a tie; indices[s] = c_s and
+ *       distances[s] = d_{c_s} as it is BEFORE the update (distances[0] = +inf, then the non-increasing coverage radius squared);
+ *       then, for every non-excluded row i, q = q(i, c_s) and d_i = q if q < d_i;
+ *     M_b above the segment's rows is legal: once every d is 0 the lowest row repeats;
+ *     a segment whose rows are all excluded returns its first row M_b times, with NaN distances;
+ *     squared distances in the subnormal range follow the device's denormal mode.
+ *   One launch, one workgroup per segment.  A segment's ROUTE follows from its rows (d3d_fps_plan): routes 0 .. 2 keep coordinates and
+ *   d in registers (three sizes), D3D_FPS_ROUTE_LDS adds LDS planes, D3D_FPS_ROUTE_STREAM (any size) reads the coordinates from global
+ *   memory every step and keeps d in the workspace.  One launch may hold segments of every route; the bits do not depend on the route.
+ *   Workspace: d3d_fps_workspace_bytes(n, segments, dtype).
+ * d3d_fps_plan (pure host): the route a segment of segment_rows rows takes and the rows that route holds (2^31 - 1 for streaming).
+ * d3d_ball_query: table[m, nsample] int32 and counts[m] int32.  point_offsets / center_offsets: DEVICE int64[segments + 1] as above
+ *   (to n and to m), both or neither (NULL, NULL: one segment, `segments` ignored); a centre sees the points of its own segment only.
+ *   The rule: r2 = r * r with r = radius rounded to the dtype; row i is inside iff q(i, c) < r2 -- strict, and false for NaN, so rows
+ *   and centres that are not finite match nothing; the entries of a centre are the first nsample inside rows in ascending i (global
+ *   row numbers), counts their number (at most nsample); the remaining slots are -1, or with pad_first != 0 the first entry again
+ *   (pointnet2's convention; an empty ball stays -1 with count 0).  A table with -1 is what d3d_neighbor_gather and
+ *   d3d_table_pool_forward read.  One launch, a wavefront per centre, O(m n) per segment; no workspace.
+ * D3D_ERR_BAD_ARG: a negative size, a stride below 3, a missing pointer with work to do, nsample outside 1 .. 1024, a radius that is
+ *   not a finite positive number, one offset array without the other; D3D_ERR_UNSUPPORTED: another dtype, n, m or segments above
+ *   2^31 - 1; D3D_ERR_WORKSPACE: workspace missing or smaller than the query.  None of them launches anything.  segments == 0
+ *   (sampling) and m == 0 (ball query) return D3D_OK before any HIP call. */
+#define D3D_FPS_ROUTE_LDS 3
+#define D3D_FPS_ROUTE_STREAM 4
+size_t d3d_fps_workspace_bytes(int64_t n, int64_t segments, int32_t dtype);
+int d3d_fps_plan(int64_t segment_rows, int32_t dtype, int32_t *route, int32_t *capacity);
+int d3d_furthest_point_sample(const void *points, int64_t n, int32_t row_stride, int32_t dtype, const int64_t *point_offsets,
+                              const int64_t *sample_offsets, int64_t segments, int64_t *indices, void *distances, void *workspace,
+                              size_t workspace_bytes, void *stream);
+int d3d_ball_query(const void *points, int64_t n, int32_t point_stride, const void *centers, int64_t m, int32_t center_stride, int32_t dtype,
+                   const int64_t *point_offsets, const int64_t *center_offsets, int64_t segments, double radius, int32_t nsample,
+                   int32_t pad_first, int32_t *table, int32_t *counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
