@@ -43,7 +43,7 @@ def _as_tensor(x):
 
 
 def _host_array(t, ctype, count):
-    if isinstance(t, ctypes.Array):          # already marshalled (VoxelGenerator caches its grid description)
+    if isinstance(t, ctypes.Array):          # already marshalled (_CallState keeps a generator's grid description)
         return t
     vals = t.tolist() if isinstance(t, torch.Tensor) else list(t)
     return (ctype * count)(*vals[:count])
@@ -463,27 +463,6 @@ def _spare_put(key, n, make):
     _spare.set = (key, cap, make(cap))
 
 
-# The output pools of the dense generators: per host thread, generator -> ({(device, stream, columns): _OutputPool}, route
-# counters).  Kept here and not on the generator (which stays a plain, copyable object); an entry goes with its generator.
-_pool_local = threading.local()
-
-
-def _pool_states():
-    m = getattr(_pool_local, "gens", None)
-    if m is None:
-        m = _pool_local.gens = weakref.WeakKeyDictionary()
-    return m
-
-
-def release_cached_buffers():
-    """drop what the CALLING thread keeps for later calls: the spare output set of its next sparse VoxelGenerator call (~100
-    bytes per point) and the pooled `voxels` buffers it holds for every dense VoxelGenerator (results still alive keep their own
-    memory).  Buffers that other threads hold are theirs to release: each thread calls this for itself."""
-    _spare.set = None
-    for pools, _ in list(_pool_states().values()):
-        pools.clear()
-
-
 class _SparseFilterCall(ctypes.Structure):
     """include/d3d_hip.h: D3DSparseFilterCall"""
     _fields_ = [("points", ctypes.c_void_p), ("n", ctypes.c_int64), ("c", ctypes.c_int32), ("min_points", ctypes.c_int32),
@@ -508,26 +487,39 @@ class _LazyCounts:
         return self.ws[:2 * _lib.NUM_COUNTS * 8].view(torch.int64).view(2, _lib.NUM_COUNTS).cpu()
 
 
-class _SparsePlan:
-    """what VoxelGenerator keeps for its sparse + filter calls (round 6): the argument block of d3d_voxelize_3d_sparse_filter_call,
-    filled once, and the buffer layouts per frame size.  Per frame the host sets three pointers and a size, makes ONE allocation
-    (the outputs, from the spare set) and one ctypes call with one argument -- 26 arguments, six allocations and twelve data_ptr()
-    calls before (VERDICT r05 weak #1: 14 us of every 68 were host)."""
+class _CallState:
+    """Everything ONE host thread keeps for ONE VoxelGenerator from call to call.  The generator itself stays a plain object of
+    tensors, numbers and enums that copies and pickles; a copy starts without any of this, and two threads never share it.
+      * shape_h, bounds_h, size_h: the grid description marshalled for the C ABI; offset_dev: the `offset` tensor per device;
+      * args, ref, layouts, frozen: the argument block of d3d_voxelize_3d_sparse_filter_call, its byref, the buffer layouts per
+        frame size, the settings the block was filled from.  Per frame the host sets three pointers and a size, makes ONE
+        allocation (the outputs, from the spare set) and one ctypes call with one argument -- 26 arguments, six allocations and
+        twelve data_ptr() calls before round 6 (14 us of every 68 were host);
+      * pools, stats: the dense output pools {(device, stream, columns): _OutputPool} and the dense calls by route;
+      * resident_buf: the DenseOutputBuffer of resident=True."""
 
-    def __init__(self, size_h, bound_h, min_points, max_points, max_voxels, pf, vf, offset_h):
+    def __init__(self, gen):
+        # the grid (_bounds, _shape and what __init__ derived from them) is read here and never again: fixed at construction, on both routes
+        self.shape_h = _host_array(gen._shape, ctypes.c_int32, 3)
+        self.bounds_h = _host_array(gen._bounds, ctypes.c_float, 6)
+        self.size_h = _host_array(gen._size, ctypes.c_float, 3)
+        self.offset_dev = {}
         a = self.args = _SparseFilterCall()
-        a.min_points, a.max_points, a.max_voxels = int(min_points or 0), int(max_points or 0), int(max_voxels or 0)
-        a.max_points_filter, a.max_voxels_filter = int(pf), int(vf)
-        for k in range(3):
-            a.voxel_size[k] = size_h[k]
-        for k in range(6):
-            a.coords_bound[k] = bound_h[k]
-        a.has_coord_offset = 0 if offset_h is None else 1
-        if offset_h is not None:
-            for k in range(3):
-                a.coord_offset[k] = offset_h[k]
+        a.voxel_size[:] = self.size_h[:]
+        a.coords_bound[:] = gen._vbounds.reshape(-1).tolist()
+        a.coord_offset[:], a.has_coord_offset = gen._offset.tolist(), 1     # (the offset of :103 is subtracted where the coords are written)
         self.ref = ctypes.byref(a)
         self.layouts = {}
+        self.frozen = None
+        self.pools, self.stats = {}, dict(pooled=0, second=0, fresh=0)
+        self.resident_buf = None
+
+    def freeze(self, gen, settings):
+        """the generator's settings into the block, after the reference's checks of them"""
+        a, (min_points, max_points, max_voxels, pf, vf) = self.args, settings
+        gen._check_sparse_args(int(pf), int(vf))
+        a.min_points, a.max_points, a.max_voxels = int(min_points or 0), int(max_points or 0), int(max_voxels or 0)
+        a.max_points_filter, a.max_voxels_filter, self.frozen = int(pf), int(vf), settings
 
     def layout(self, lib, n, c):
         got = self.layouts.get((n, c))
@@ -540,21 +532,50 @@ class _SparsePlan:
         return got
 
 
-def _sparse_filter_planned(plan, points, flags=None):
-    """VoxelGenerator.__call__'s sparse branch through the prepared argument block -> dict, or raises _NotFused"""
+# per host thread: generator -> _CallState.  An entry goes with its thread, as the workspace arenas do, and with its generator.
+_states = threading.local()
+
+
+def _call_state(gen):
+    """the calling thread's _CallState of `gen`, built on first use; a sparse generator's argument block follows its settings"""
+    m = getattr(_states, "gens", None)
+    if m is None:
+        m = _states.gens = weakref.WeakKeyDictionary()
+    st = m.get(gen)
+    if st is None:
+        st = m[gen] = _CallState(gen)
+    if not gen._dense:
+        settings = (gen._min_points, gen._max_points, gen._max_voxels, gen._max_points_filter, gen._max_voxels_filter)
+        if settings != st.frozen:
+            st.freeze(gen, settings)
+    return st
+
+
+def release_cached_buffers():
+    """drop what the CALLING thread keeps for later calls: the spare output set of its next sparse VoxelGenerator call (~100
+    bytes per point) and, of every VoxelGenerator, the pooled `voxels` buffers and the resident buffer (results still alive keep
+    their own memory).  Buffers that other threads hold are theirs to release: each thread calls this for itself."""
+    _spare.set = None
+    for st in list(getattr(_states, "gens", {}).values()):
+        st.pools.clear()
+        st.resident_buf = None
+
+
+def _sparse_filter_planned(st, points, flags=None):
+    """VoxelGenerator.__call__'s sparse branch through the prepared argument block of st, a _CallState -> dict, or raises _NotFused"""
     lib = _lib.load()
     pts, odev, dev = _stage(points)
     n, c = pts.shape
     if c < 3:
         raise RuntimeError("points need at least 3 columns (x, y, z)")
-    a = plan.args
+    a = st.args
     with _device_ctx(dev):
-        nbytes, off, ws_bytes = plan.layout(lib, n, c)
+        nbytes, off, ws_bytes = st.layout(lib, n, c)
         stream = _lib.stream_raw()
         key = (dev, c, stream, "planned")
 
         def make(m):
-            return torch.empty((plan.layout(lib, m, c)[0],), dtype=torch.uint8, device=dev)
+            return torch.empty((st.layout(lib, m, c)[0],), dtype=torch.uint8, device=dev)
         _, buf = _spare_take(key, n, make)
         ws = _lib.workspace(ws_bytes, dev)
         note = _lib.NotifyBuffer.get()
@@ -567,7 +588,7 @@ def _sparse_filter_planned(plan, points, flags=None):
         def run(fl):
             note.arm()
             a.flags = fl
-            rc = lib.d3d_voxelize_3d_sparse_filter_call(plan.ref)
+            rc = lib.d3d_voxelize_3d_sparse_filter_call(st.ref)
             if rc == _lib.ERR_UNSUPPORTED and a.max_voxels_filter == MaxVoxelsFilterType.DESCENDING:
                 raise _NotFused()
             _lib.check(rc, "voxelize_3d_sparse + voxelize_3d_filter")
@@ -594,6 +615,9 @@ def _lookup(enum_cls, name, message):
     return enum_cls[key]
 
 
+_POOL_MAX_KEYS = 4          # (device, stream, columns) combinations a thread keeps pools for
+
+
 class VoxelGenerator:
     """Convert point cloud to voxels -- same constructor, call signature and results as the
     reference's d3d.voxel.VoxelGenerator (voxel/__init__.py:12-104)."""
@@ -601,21 +625,21 @@ class VoxelGenerator:
     def __init__(self, bounds, shape, min_points=0, max_points=30, max_voxels=20000,
                  max_points_filter=None, max_voxels_filter=None, reduction=None, dense=False, resident=None):
         # resident (beyond the reference; dense only).  True: `voxels` is returned as a view of ONE buffer the generator keeps on
-        # the device (DenseOutputBuffer) -- same values, valid until the generator's next call, not to be written.  None (the
+        # the device PER CALLING THREAD (DenseOutputBuffer) -- same values, valid until the calling thread's next call, not to be written.  None (the
         # default): the same route through a pool of two such buffers, each reused only when no result that views it is alive
         # and nobody wrote it (_OutputPool) -- to the caller the result is a tensor of its own, as the reference's; otherwise,
         # and under the poison test hook, a fresh tensor per frame.  False: always a fresh tensor.
         # The derived grid quantities are tiny fp32 host tensors computed with the same torch
         # ops as the reference so that `size` is bit-identical (it feeds the coordinate division).
+        # Attributes are tensors, numbers, bools, None and the three enums only: what a call keeps lives in _CallState.
         self._bounds = torch.tensor(bounds, dtype=torch.float)
         self._shape = torch.tensor(shape, dtype=torch.int32)
         self._min_points, self._max_points, self._max_voxels, self._dense = min_points, max_points, max_voxels, dense
         if resident and not dense:
             raise ValueError("resident output is for dense voxelization")
-        self._resident, self._resident_buf = (None if resident is None else bool(resident)), None
+        self._resident = None if resident is None else bool(resident)
         # (the grid's cells must fit the binned index's 32-bit keys for the resident route, and with it the pooled output)
         self._cells_fit_u32 = float(shape[0]) * float(shape[1]) * float(shape[2]) < 4294967295.0
-        self._sparse_plan = None             # the prepared argument block of the sparse + filter call (_SparsePlan), made on first use
 
         lohi = self._bounds.reshape(3, 2)
         self._size = (lohi[:, 1] - lohi[:, 0]) / self._shape                                  # :41
@@ -625,12 +649,6 @@ class VoxelGenerator:
                              "which could lead to unexpected behavior!")
         self._offset = torch.round(origin_cells).int()                                        # :45
         self._vbounds = torch.round(lohi / self._size.reshape(3, 1)).long()                   # :46
-        self._shape_h = _host_array(self._shape, ctypes.c_int32, 3)      # marshalled once for the C ABI
-        self._offset_dev = {}
-        self._bounds_h = _host_array(self._bounds, ctypes.c_float, 6)
-        self._size_h = _host_array(self._size, ctypes.c_float, 3)
-        self._offset_h = (ctypes.c_int64 * 3)(*[int(v) for v in self._offset.tolist()])
-        self._vbounds_h = (ctypes.c_int64 * 6)(*[int(v) for v in self._vbounds.reshape(-1).tolist()])
 
         red = (reduction or "NONE").upper()
         if red != "NONE" and not dense:
@@ -670,109 +688,90 @@ class VoxelGenerator:
         odev = points.device
         if not points.is_cuda:
             points = points.to(_lib.require_gpu())    # stage once; results go back to the caller's device
+        st = _call_state(self)      # the one lookup of a call: everything below takes what it keeps from `st`
         if self._dense:
             buf = how = None
             if self._resident is None and points.dim() == 2 and points.shape[0] > 0:
-                buf, how, pool = self._pooled_buffer(points, poison, flags)
+                buf, how, pool = self._pooled_buffer(points, poison, flags, st)
             if self._resident and points.shape[0] > 0:
                 need = min(int(points.shape[0]), int(self._max_voxels))
-                buf = self._resident_buf
+                buf = st.resident_buf
                 if buf is None or buf.capacity < need or buf.device != points.device or buf.columns != int(points.shape[1]):
                     grow = need if buf is None else max(need, buf.capacity + buf.capacity // 4)
-                    buf = self._resident_buf = DenseOutputBuffer(min(grow, int(self._max_voxels)), self._max_points, points.device,
-                                                                 columns=int(points.shape[1]))
-            ret = Dict(voxelize_3d_dense(points, self._shape_h, self._bounds_h, self._max_points,
+                    buf = st.resident_buf = DenseOutputBuffer(min(grow, int(self._max_voxels)), self._max_points, points.device,
+                                                              columns=int(points.shape[1]))
+            ret = Dict(voxelize_3d_dense(points, st.shape_h, st.bounds_h, self._max_points,
                                          self._max_voxels, self._reduction, flags=flags, poison=poison, resident=buf))
             if how is not None:
-                self._pool_stats[how if buf is not None and buf.used else "fresh"] += 1
+                st.stats[how if buf is not None and buf.used else "fresh"] += 1
                 if buf is not None and buf.refused:
                     pool.refuse(buf)
         else:
-            pf, vf = int(self._max_points_filter), int(self._max_voxels_filter)
             ret = None
             if points.shape[0] > 0:
-                try:    # (the offset of :103 is subtracted inside the call, where the coords are written)
-                    if self._sparse_plan is None:
-                        self._check_sparse_args(pf, vf)
-                        self._sparse_plan = _SparsePlan(self._size_h, self._vbounds_h, self._min_points, self._max_points,
-                                                        self._max_voxels, pf, vf, self._offset_h)
-                    ret = Dict(_sparse_filter_planned(self._sparse_plan, points, flags=flags))
+                try:
+                    ret = Dict(_sparse_filter_planned(st, points, flags=flags))
                 except _NotFused:
                     pass
             if ret is None:
                 # (an empty cloud; DESCENDING off the binned index: its sort needs the voxel count on the host) the two calls
                 # of the reference, two read-backs
-                sparse = voxelize_3d_sparse(points, self._size_h, 3, flags=flags)
+                sparse = voxelize_3d_sparse(points, st.size_h, 3, flags=flags)
                 ret = Dict(voxelize_3d_filter(points, sparse["points_mapping"], sparse["coords"],
                                               sparse["voxel_npoints"], self._vbounds, self._min_points,
                                               self._max_points, self._max_voxels, self._max_points_filter,
                                               self._max_voxels_filter))
-                off = self._offset_dev.get(ret.coords.device)
+                off = st.offset_dev.get(ret.coords.device)
                 if off is None:
-                    off = self._offset_dev[ret.coords.device] = self._offset.to(ret.coords.device)
+                    off = st.offset_dev[ret.coords.device] = self._offset.to(ret.coords.device)
                 ret.coords = ret.coords - off                                                 # :103
         if odev != points.device:
             ret = Dict(_lib.to_caller(dict(ret), odev, points.device))
         return ret
 
+    def _pooled_buffer(self, points, poison, flags=None, st=None):
+        """-> (DenseOutputBuffer of this thread's pool | None, "pooled" | "second" | "fresh", the pool | None) for a frame already on
+        its device (st: the calling thread's _CallState, where __call__ has it at hand)"""
+        P, mv, n, c = int(self._max_points), int(self._max_voxels), int(points.shape[0]), int(points.shape[1])
+        opts = options.current()
+        if (opts.poison if poison is None else poison) or P <= 0 or mv <= 0 or not points.is_cuda:
+            return None, "fresh", None      # (poison fills would break a buffer whose zero padding is an invariant)
+        # what d3d_voxelize_3d_dense_resident takes -- a buffer is built only for frames that will use it: rows of 3 .. 8 floats, up
+        # to 256 rows per voxel (whole 16-byte units when the rows are not), frames of up to 8 M points on the binned index without
+        # the two-launch output, 16-byte aligned contiguous float32 rows, a grid whose cells fit 32 bits.  (Whatever else the
+        # route may refuse: _OutputPool.refuse.)
+        fl = opts.voxel_flags if flags is None else int(flags)
+        if not (3 <= c <= 8 and P <= 256 and (c == 4 or (P * c) % 4 == 0) and n <= (8 << 20) and points.dtype == torch.float32 and
+                not (fl & (_lib.VOXEL_PATH_HASH | _lib.VOXEL_SPLIT_FILL)) and self._cells_fit_u32 and points.is_contiguous() and
+                points.data_ptr() % 16 == 0):
+            return None, "fresh", None
+        dev = points.device
+        pools = (_call_state(self) if st is None else st).pools
+        key = (dev.index, _lib.stream_raw(dev.index), c)
+        pool = pools.get(key)
+        if pool is None:
+            def make(cap):
+                with _device_ctx(dev):
+                    return DenseOutputBuffer(cap, P, dev, columns=c, pooled=True)
+            pool = pools[key] = _OutputPool(make)
+            while len(pools) > _POOL_MAX_KEYS:      # (the oldest combination goes)
+                pools.pop(next(iter(pools)))
+        return pool.take(min(n, mv), lambda need: min(_spare_cap(need), mv)) + (pool,)
 
-_POOL_MAX_KEYS = 4          # (device, stream, columns) combinations a thread keeps pools for
+    def _check_sparse_args(self, pf, vf):
+        if vf != 0 and self._max_voxels is None:
+            raise ValueError("Must specify maximum voxel count to filter voxels!")            # voxelize.cpp:359
+        if pf != 0 and self._max_points is None:
+            raise ValueError("Must specify maximum points per voxel to filter points!")       # voxelize.cpp:362
+        if pf == MaxPointsFilterType.FARTHEST_SAMPLING:
+            raise ValueError("Farthest Sampling not implemented!")                            # voxelize.cpp:470
 
-
-def _vg_pool_state(self):
-    m = _pool_states()
-    st = m.get(self)
-    if st is None:
-        st = m[self] = ({}, dict(pooled=0, second=0, fresh=0))
-    return st
-
-
-def _vg_pooled_buffer(self, points, poison, flags=None):
-    """-> (DenseOutputBuffer of this thread's pool | None, "pooled" | "second" | "fresh", the pool | None) for a frame already on
-    its device"""
-    P, mv, n, c = int(self._max_points), int(self._max_voxels), int(points.shape[0]), int(points.shape[1])
-    opts = options.current()
-    if (opts.poison if poison is None else poison) or P <= 0 or mv <= 0 or not points.is_cuda:
-        return None, "fresh", None      # (poison fills would break a buffer whose zero padding is an invariant)
-    # what d3d_voxelize_3d_dense_resident takes -- a buffer is built only for frames that will use it: rows of 3 .. 8 floats, up
-    # to 256 rows per voxel (whole 16-byte units when the rows are not), frames of up to 8 M points on the binned index without
-    # the two-launch output, 16-byte aligned contiguous float32 rows, a grid whose cells fit 32 bits.  (Whatever else the
-    # route may refuse: _OutputPool.refuse.)
-    fl = opts.voxel_flags if flags is None else int(flags)
-    if not (3 <= c <= 8 and P <= 256 and (c == 4 or (P * c) % 4 == 0) and n <= (8 << 20) and points.dtype == torch.float32 and
-            not (fl & (_lib.VOXEL_PATH_HASH | _lib.VOXEL_SPLIT_FILL)) and self._cells_fit_u32 and points.is_contiguous() and
-            points.data_ptr() % 16 == 0):
-        return None, "fresh", None
-    dev = points.device
-    pools = _vg_pool_state(self)[0]
-    key = (dev.index, _lib.stream_raw(dev.index), c)
-    pool = pools.get(key)
-    if pool is None:
-        def make(cap):
-            with _device_ctx(dev):
-                return DenseOutputBuffer(cap, P, dev, columns=c, pooled=True)
-        pool = pools[key] = _OutputPool(make)
-        while len(pools) > _POOL_MAX_KEYS:      # (the oldest combination goes)
-            pools.pop(next(iter(pools)))
-    return pool.take(min(n, mv), lambda need: min(_spare_cap(need), mv)) + (pool,)
-
-
-VoxelGenerator._pooled_buffer = _vg_pooled_buffer
-VoxelGenerator._pool_map = property(lambda self: _vg_pool_state(self)[0], doc="the calling thread's {(device, stream, columns): _OutputPool}")
-VoxelGenerator._pool_stats = property(lambda self: _vg_pool_state(self)[1], doc="the calling thread's dense calls by route: views "
-                                      "of the pool's first free buffer, of one while another is still held outside, fresh tensors")
-
-
-def _vg_check_sparse_args(self, pf, vf):
-    if vf != 0 and self._max_voxels is None:
-        raise ValueError("Must specify maximum voxel count to filter voxels!")            # voxelize.cpp:359
-    if pf != 0 and self._max_points is None:
-        raise ValueError("Must specify maximum points per voxel to filter points!")       # voxelize.cpp:362
-    if pf == MaxPointsFilterType.FARTHEST_SAMPLING:
-        raise ValueError("Farthest Sampling not implemented!")                            # voxelize.cpp:470
-
-
-VoxelGenerator._check_sparse_args = _vg_check_sparse_args
+    # views of the calling thread's _CallState
+    _pool_map = property(lambda self: _call_state(self).pools, doc="the calling thread's {(device, stream, columns): _OutputPool}")
+    _pool_stats = property(lambda self: _call_state(self).stats, doc="the calling thread's dense calls by route: views of the pool's "
+                           "first free buffer, of one while another is still held outside, fresh tensors")
+    _resident_buf = property(lambda self: _call_state(self).resident_buf, doc="the calling thread's buffer of resident=True, or None")
+    _size_h = property(lambda self: _call_state(self).size_h, doc="`_size` as the calling thread marshalled it for the C ABI")
 
 
 class _FrameSlot:
@@ -793,6 +792,7 @@ def _stream_frames(gen, frames, flags, poison):
     poison = options.current().poison if poison is None else poison
     red = int(gen._reduction)
     P, mv = int(gen._max_points), int(gen._max_voxels)
+    st = _call_state(gen)
     slots = [_FrameSlot(), _FrameSlot()]
     s_idx = s_out = None
     pending = None          # (slot, outputs, frame) of the frame whose output launch is in flight
@@ -839,7 +839,7 @@ def _stream_frames(gen, frames, flags, poison):
                 need = _workspace_bytes(lib, n)
                 if slot.ws is None or slot.ws.numel() < need:
                     slot.ws = torch.empty(int(need * 1.25), dtype=torch.uint8, device=dev)
-                args = _dense_args(pts, gen._shape_h, gen._bounds_h, P, mv, red, out, slot.ws)
+                args = _dense_args(pts, st.shape_h, st.bounds_h, P, mv, red, out, slot.ws)
                 s_idx.wait_stream(cur)                                   # the frame (and the poison fills) are ready
                 if slot.used:
                     s_idx.wait_event(slot.out_done)                      # this slot's scratch: its last frame's output has read it

@@ -1,5 +1,6 @@
 """CPU: the ownership logic of the dense VoxelGenerator's output pool (d3d_amd.voxel._OutputPool) on host tensors -- when a
 buffer may serve again without the caller being able to tell that its `voxels` was not a tensor of its own.  No kernel runs."""
+import pytest
 import torch
 
 from d3d_amd.voxel import DenseOutputBuffer, _OutputPool, _spare_cap
@@ -135,14 +136,141 @@ def test_a_pool_whose_buffer_the_native_route_refused_keeps_nothing():
     assert not pool.slots and pool.take(10, 16) == (None, "fresh") and len(built) == 1
 
 
-def test_generators_stay_plain_copyable_objects_with_pools_of_their_own():
+# ---- what a generator keeps from call to call lives beside it, per host thread (d3d_amd.voxel._CallState); no kernel runs
+
+GENERATOR_KW = (dict(), dict(max_points=4, max_points_filter="trim", max_voxels=50, max_voxels_filter="descending"),
+                dict(dense=True), dict(dense=True, resident=True))
+
+
+def generators(more=()):
+    from d3d_amd.voxel import VoxelGenerator
+    return [VoxelGenerator([0, 1, 0, 1, 0, 1], [10, 10, 10], **kw) for kw in GENERATOR_KW + tuple(more)]
+
+
+def twins(gen):
     import copy
-    from d3d_amd.voxel import VoxelGenerator, release_cached_buffers
-    for kw in (dict(dense=True, max_points=4), dict()):
-        gen = VoxelGenerator([0, 1, 0, 1, 0, 1], [10, 10, 10], **kw)
-        twin = copy.deepcopy(gen)
-        assert twin is not gen and twin._resident is None and twin._pool_stats is not gen._pool_stats
-        assert twin._pool_map is not gen._pool_map
+    import pickle
+    return [pickle.loads(pickle.dumps(gen)), copy.deepcopy(gen), copy.copy(gen)]
+
+
+def assert_plain(gen):
+    from d3d_amd.voxel import MaxPointsFilterType, MaxVoxelsFilterType, ReductionType
+    for name, value in vars(gen).items():
+        assert type(value) in (torch.Tensor, int, float, bool, type(None), ReductionType, MaxPointsFilterType,
+                               MaxVoxelsFilterType), (name, type(value))
+
+
+def assert_same_vars(twin, gen):
+    assert twin is not gen and type(twin) is type(gen) and set(vars(twin)) == set(vars(gen))
+    for name, value in vars(gen).items():
+        other = vars(twin)[name]
+        assert type(other) is type(value), name
+        if isinstance(value, torch.Tensor):
+            assert other.dtype == value.dtype and torch.equal(other, value), name
+        else:
+            assert other == value, name
+
+
+def test_generators_stay_plain_copyable_objects_with_pools_of_their_own():
+    from d3d_amd.voxel import release_cached_buffers
+    for gen in generators(more=(dict(dense=True, max_points=4),)):
+        assert_plain(gen)
+        for twin in twins(gen):                                     # a fresh generator: pickle, deepcopy, copy
+            assert_same_vars(twin, gen)
+            assert_plain(twin)
+            assert twin._resident is gen._resident and twin._pool_stats is not gen._pool_stats
+            assert twin._pool_map is not gen._pool_map
+        assert_plain(gen)                                           # (the pools looked at above are not kept on it)
     gen._pool_map["key"] = "pool"
     release_cached_buffers()                                        # (the calling thread's pools, of every generator)
     assert not gen._pool_map
+
+
+def test_a_used_generator_is_as_plain_and_its_copies_start_with_state_of_their_own():
+    import ctypes
+    from d3d_amd.voxel import _call_state
+    for gen in generators():
+        before = dict(vars(gen))
+        st = _call_state(gen)                                       # what __call__ fetches: arrays marshalled, block filled
+        assert _call_state(gen) is st and gen._size_h is st.size_h
+        assert list(st.shape_h) == [10, 10, 10] and list(st.bounds_h) == [0, 1, 0, 1, 0, 1] and list(st.size_h) == gen._size.tolist()
+        assert list(st.args.coords_bound) == [0, 10, 0, 10, 0, 10] and list(st.args.coord_offset) == [0, 0, 0]
+        assert set(vars(gen)) == set(before) and all(vars(gen)[k] is v for k, v in before.items())
+        assert_plain(gen)
+        states = [st]
+        for twin in twins(gen):
+            assert_same_vars(twin, gen)
+            states.append(_call_state(twin))
+            assert_plain(twin)
+        assert len({id(s) for s in states}) == 4 and len({ctypes.addressof(s.args) for s in states}) == 4
+        assert len({id(s.pools) for s in states}) == 4 and all(s.resident_buf is None and s.stats == states[0].stats for s in states)
+
+
+def test_each_host_thread_has_state_of_its_own_that_goes_with_the_thread():
+    import ctypes
+    import gc
+    import threading
+    import weakref
+    from d3d_amd.voxel import _call_state
+    for gen in generators():
+        mine = _call_state(gen)
+        seen = {}
+
+        def work():
+            st = _call_state(gen)
+            seen.update(ref=weakref.ref(st), again=_call_state(gen) is st, other=st is not mine, block=ctypes.addressof(st.args),
+                        pools=id(st.pools))
+
+        thread = threading.Thread(target=work)
+        thread.start()
+        thread.join()
+        assert seen["again"] and seen["other"] and seen["block"] != ctypes.addressof(mine.args) and seen["pools"] != id(mine.pools)
+        assert _call_state(gen) is mine
+        gc.collect()
+        assert seen["ref"]() is None, "a thread's state must end with the thread"
+    ref = weakref.ref(mine)
+    del mine, gen
+    gc.collect()
+    assert ref() is None, "a generator's state must end with the generator"
+
+
+def test_the_sparse_argument_block_follows_the_settings_it_was_filled_from():
+    from d3d_amd.voxel import MaxPointsFilterType, MaxVoxelsFilterType, VoxelGenerator, _call_state
+    gen = VoxelGenerator([0, 1, 0, 1, 0, 1], [10, 10, 10], max_points=4, max_points_filter="trim", min_points=1, max_voxels=50,
+                         max_voxels_filter="trim")
+
+    def block():
+        a = _call_state(gen).args
+        return a.min_points, a.max_points, a.max_voxels, a.max_points_filter, a.max_voxels_filter
+
+    st = _call_state(gen)
+    assert block() == (1, 4, 50, 1, 1)
+    gen._max_points = 2
+    assert block() == (1, 2, 50, 1, 1) and _call_state(gen) is st
+    gen._min_points, gen._max_voxels_filter = 3, MaxVoxelsFilterType.DESCENDING
+    assert block() == (3, 2, 50, 1, 2)
+    # the reference's checks (voxelize.cpp:359-362, :470) run again for a setting changed after first use, and keep failing
+    gen._max_points_filter = MaxPointsFilterType.FARTHEST_SAMPLING
+    for _ in range(2):
+        with pytest.raises(ValueError, match="Farthest Sampling not implemented!"):
+            _call_state(gen)
+    gen._max_points_filter, gen._max_voxels = MaxPointsFilterType.TRIM, None
+    with pytest.raises(ValueError, match="Must specify maximum voxel count to filter voxels!"):
+        _call_state(gen)
+    gen._max_voxels, gen._max_points = 50, None
+    with pytest.raises(ValueError, match="Must specify maximum points per voxel to filter points!"):
+        _call_state(gen)
+    gen._max_points, gen._max_voxels_filter, gen._max_voxels = 7, MaxVoxelsFilterType.NONE, None
+    assert block() == (3, 7, 0, 1, 0) and _call_state(gen) is st
+
+
+def test_release_cached_buffers_drops_every_generators_pools_and_resident_buffer():
+    from d3d_amd.voxel import _call_state, release_cached_buffers
+    gens = generators()
+    for gen in gens:
+        gen._pool_map["key"] = "pool"
+        _call_state(gen).resident_buf = DenseOutputBuffer(4, 4, "cpu")
+        assert gen._pool_map and gen._resident_buf is not None
+    release_cached_buffers()
+    for gen in gens:
+        assert not gen._pool_map and gen._resident_buf is None
