@@ -181,7 +181,12 @@ SIGNATURES = {
     "d3d_fps_plan": (ctypes.c_int, [_i64, _i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "d3d_furthest_point_sample": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "d3d_ball_query": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _i64, ctypes.c_double, _i32, _i32, _vp, _vp, _vp]),
+    "d3d_knn_query": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "d3d_knn_weights": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, ctypes.c_double, _vp, _vp]),
+    "d3d_knn_interp_forward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "d3d_knn_interp_backward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _vp]),
 }
+KNN_MAX = 64                        # D3D_KNN_MAX
 FPS_ROUTE_LDS, FPS_ROUTE_STREAM = 3, 4
 
 _lib = None

@@ -26,6 +26,12 @@
 // k_ball_query: one wavefront per centre walks its segment 4 x 64 rows at a time (four tiles loaded before the first is judged);
 // q < r2, a ballot, the count of the lower lanes' bits is the slot: every slot is written once, in order, without a sort.  The walk
 // ends (wave-uniform) once nsample rows are found; the same wave writes the padding.  O(m n) per segment by design: see DESIGN.md.
+//
+// And the way back up, what a feature-propagation layer starts with:
+//   d3d_knn_query              points, centres, k -> table[m, k] int32 (ascending (q, row); -1: none), dist2[m, k]
+//   d3d_knn_weights            table, dist2 -> the normalised inverse-distance weights[m, k] (three_nn's 1 / (dist + eps))
+// k_knn_query: the same walk, a wavefront per centre; the k best so far are kept sorted across the lanes (see the kernel).  The fold
+// that uses table and weights is vinterp.hip's (d3d_knn_interp_forward / _backward).
 #include "common.hpp"
 
 #include <cmath>
@@ -382,6 +388,121 @@ __global__ __launch_bounds__(kBqThreads) void k_ball_query(const T *__restrict__
     if (lane == 0) counts[c] = count;
 }
 
+// ---------------------------------------------------------------- k nearest rows
+// The order-keeping key of a candidate: q >= +0 always, so its bits order as unsigned integers; the row breaks ties (the lower row
+// first).  fp32: one 64-bit word {q bits : 32 | row : 32}; fp64: the 64 bits of q and the row beside them.  All ones = "no entry":
+// above every candidate (its q bits would be a NaN's, and a NaN q is no candidate).
+struct KnnKey64 {
+    uint64_t d;
+    uint32_t row;
+};
+template <typename T> struct KnnKeyOf;
+template <> struct KnnKeyOf<float> { typedef uint64_t type; };
+template <> struct KnnKeyOf<double> { typedef KnnKey64 type; };
+
+__device__ __forceinline__ uint64_t knn_make(float q, uint32_t row) { return ((uint64_t)__float_as_uint(q) << 32) | row; }
+__device__ __forceinline__ KnnKey64 knn_make(double q, uint32_t row) { return KnnKey64{(uint64_t)__double_as_longlong(q), row}; }
+__device__ __forceinline__ void knn_clear(uint64_t &k) { k = ~0ull; }
+__device__ __forceinline__ void knn_clear(KnnKey64 &k) { k.d = ~0ull, k.row = ~0u; }
+__device__ __forceinline__ bool knn_lt(uint64_t a, uint64_t b) { return a < b; }
+__device__ __forceinline__ bool knn_lt(const KnnKey64 &a, const KnnKey64 &b) { return a.d < b.d || (a.d == b.d && a.row < b.row); }
+__device__ __forceinline__ bool knn_none(uint64_t k) { return k == ~0ull; }
+__device__ __forceinline__ bool knn_none(const KnnKey64 &k) { return k.d == ~0ull; }
+__device__ __forceinline__ uint32_t knn_row(uint64_t k) { return (uint32_t)k; }
+__device__ __forceinline__ uint32_t knn_row(const KnnKey64 &k) { return k.row; }
+__device__ __forceinline__ float knn_dist(uint64_t k, float) { return __uint_as_float((uint32_t)(k >> 32)); }
+__device__ __forceinline__ double knn_dist(const KnnKey64 &k, double) { return __longlong_as_double((long long)k.d); }
+__device__ __forceinline__ uint64_t knn_readlane(uint64_t k, int lane) { return ps_readlane(k, lane); }
+__device__ __forceinline__ KnnKey64 knn_readlane(const KnnKey64 &k, int lane) { return KnnKey64{ps_readlane(k.d, lane), ps_readlane(k.row, lane)}; }
+// lane l reads lane l - 1 over the whole wavefront (wave_shr:1); lane 0 reads 0 and is never asked
+__device__ __forceinline__ uint64_t knn_up(uint64_t k) { return d3d_dpp_u64<0x138, 0xf>(k); }
+__device__ __forceinline__ KnnKey64 knn_up(const KnnKey64 &k) { return KnnKey64{d3d_dpp_u64<0x138, 0xf>(k.d), d3d_dpp_u32<0x138, 0xf>(k.row)}; }
+
+// One wavefront per centre.  The wave holds its best rows so far SORTED ACROSS LANES: lane l the l-th smallest key (all ones while
+// fewer than l + 1 candidates were seen); tau = lane k - 1's key, wave-uniform, is what a row has to beat.  The segment is walked
+// 4 x 64 rows at a time, as k_ball_query walks it; per tile key < tau and a ballot -- zero for most tiles of an unordered cloud once
+// the first few are in, then the tile costs the compare alone.  Every set bit, in ascending lane, is inserted wave-uniformly: the
+// key is broadcast, its position is the number of held keys below it, the lanes above take their lower neighbour's key (one wave
+// shift), the lane at the position takes the new key, tau is read again and the ballot is taken again over the lanes above.  No LDS,
+// no atomics, no workspace; the lanes k .. 63 hold the next best keys, which costs nothing and is never read.
+template <typename T>
+__global__ __launch_bounds__(kBqThreads) void k_knn_query(const T *__restrict__ points, int64_t n, int32_t pstride, const T *__restrict__ centers,
+                                                          int64_t m, int32_t cstride, const int64_t *__restrict__ point_offsets,
+                                                          const int64_t *__restrict__ center_offsets, int64_t segments, int32_t k,
+                                                          int32_t *__restrict__ table, T *__restrict__ dist2)
+{
+    typedef typename KnnKeyOf<T>::type K;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t c = (int64_t)blockIdx.x * kBqWaves + threadIdx.x / kWave;
+    if (c >= m) return;
+    int64_t p0 = 0, p1 = n;
+    if (center_offsets) {                      // the segment b of the centre: center_offsets[b] <= c < center_offsets[b + 1]
+        int64_t lo = 0, hi = segments;
+        while (hi - lo > 1) {
+            const int64_t mid = lo + (hi - lo) / 2;
+            if (center_offsets[mid] <= c) lo = mid;
+            else hi = mid;
+        }
+        p0 = point_offsets[lo], p1 = point_offsets[lo + 1];
+    }
+    const T *const q0 = centers + c * cstride;
+    const T cx = q0[0], cy = q0[1], cz = q0[2];
+    K held, tau;
+    knn_clear(held), knn_clear(tau);
+    for (int64_t base = p0; base < p1; base += kBqAhead * kWave) {
+        K key[kBqAhead];
+#pragma unroll
+        for (int u = 0; u < kBqAhead; u++) {
+            const int64_t i = base + u * kWave + lane;
+            knn_clear(key[u]);
+            if (i < p1) {
+                const T *p = points + i * pstride;
+                const T dx = p[0] - cx, dy = p[1] - cy, dz = p[2] - cz;
+                const T q = ((dx * dx) + (dy * dy)) + (dz * dz);
+                if (q == q) key[u] = knn_make(q, (uint32_t)i);                  // (a NaN q: no candidate)
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kBqAhead; u++) {
+            unsigned long long vote = __ballot(knn_lt(key[u], tau));
+            while (vote) {                     // (wave-uniform)
+                const int src = __ffsll((long long)vote) - 1;
+                const K nk = knn_readlane(key[u], src);
+                const int pos = __popcll(__ballot(knn_lt(held, nk)));           // held is sorted: the lanes 0 .. pos - 1
+                const K up = knn_up(held);
+                if (lane > pos) held = up;
+                else if (lane == pos) held = nk;
+                tau = knn_readlane(held, k - 1);
+                // the lanes above src that still beat tau, which has come down: of a tile's 64 rows only a few are ever inserted
+                vote = __ballot(knn_lt(key[u], tau)) & (~1ull << src);
+            }
+        }
+    }
+    if (lane < k) {
+        const bool none = knn_none(held);
+        table[c * k + lane] = none ? -1 : (int32_t)knn_row(held);
+        if (dist2) dist2[c * k + lane] = none ? std::numeric_limits<T>::infinity() : knn_dist(held, (T)0);
+    }
+}
+
+// one lane per table row: the inverse-distance weights of its present entries, normalised by their sum in ascending column
+template <typename T>
+__global__ __launch_bounds__(kBqThreads) void k_knn_weights(const int32_t *__restrict__ table, const T *__restrict__ dist2, int64_t m, int32_t k,
+                                                            int32_t power, T eps, T *__restrict__ weights)
+{
+    const int64_t r = (int64_t)blockIdx.x * kBqThreads + threadIdx.x;
+    if (r >= m) return;
+    const int32_t *const t = table + r * k;
+    const T *const q = dist2 + r * k;
+    T *const w = weights + r * k;
+    auto u_of = [&](int j) { return (T)1 / ((power == 1 ? sqrt(q[j]) : q[j]) + eps); };
+    T s = (T)0;
+    for (int j = 0; j < k; j++)
+        if (t[j] >= 0) s = s + u_of(j);
+    const bool ok = s > (T)0 && s < std::numeric_limits<T>::infinity();          // false for NaN
+    for (int j = 0; j < k; j++) w[j] = (ok && t[j] >= 0) ? u_of(j) / s : (T)0;
+}
+
 bool ps_dtype_ok(int32_t dtype) { return dtype == D3D_F32 || dtype == D3D_F64; }
 
 // the one layout of the FPS workspace: d of every row, for the segments on the streaming route
@@ -457,6 +578,49 @@ extern "C" int d3d_ball_query(const void *points, int64_t n, int32_t point_strid
         const float r = (float)radius;
         D3D_LAUNCH("k_ball_query<f32>", k_ball_query<float>, grid, dim3(kBqThreads), 0, st, (const float *)points, n, point_stride,
                    (const float *)centers, m, center_stride, point_offsets, center_offsets, segments, r * r, nsample, pad_first, table, counts);
+    }
+    return D3D_OK;
+}
+
+extern "C" int d3d_knn_query(const void *points, int64_t n, int32_t point_stride, const void *centers, int64_t m, int32_t center_stride,
+                             int32_t dtype, const int64_t *point_offsets, const int64_t *center_offsets, int64_t segments, int32_t k,
+                             int32_t *table, void *dist2, void *stream)
+{
+    if (n < 0 || m < 0 || segments < 0 || point_stride < 3 || center_stride < 3 || k < 1) return D3D_ERR_BAD_ARG;
+    if ((point_offsets == nullptr) != (center_offsets == nullptr)) return D3D_ERR_BAD_ARG;
+    if (point_offsets && segments < 1 && m > 0) return D3D_ERR_BAD_ARG;
+    if (!ps_dtype_ok(dtype) || n > kPsRowMax || m > kPsRowMax || segments > kPsRowMax || k > D3D_KNN_MAX) return D3D_ERR_UNSUPPORTED;
+    if (m == 0) return D3D_OK;
+    if (!centers || !table || (n > 0 && !points)) return D3D_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)d3d_divup(m, kBqWaves));
+    if (dtype == D3D_F64) {
+        D3D_LAUNCH("k_knn_query<f64>", k_knn_query<double>, grid, dim3(kBqThreads), 0, st, (const double *)points, n, point_stride,
+                   (const double *)centers, m, center_stride, point_offsets, center_offsets, segments, k, table, (double *)dist2);
+    } else {
+        D3D_LAUNCH("k_knn_query<f32>", k_knn_query<float>, grid, dim3(kBqThreads), 0, st, (const float *)points, n, point_stride,
+                   (const float *)centers, m, center_stride, point_offsets, center_offsets, segments, k, table, (float *)dist2);
+    }
+    return D3D_OK;
+}
+
+extern "C" int d3d_knn_weights(const int32_t *table, const void *dist2, int64_t m, int32_t k, int32_t dtype, int32_t power, double eps,
+                               void *weights, void *stream)
+{
+    if (m < 0 || k < 1 || (power != 1 && power != 2)) return D3D_ERR_BAD_ARG;
+    if (!ps_dtype_ok(dtype) || k > D3D_KNN_MAX || m > kPsRowMax / k) return D3D_ERR_UNSUPPORTED;
+    const double e = dtype == D3D_F64 ? eps : (double)(float)eps;               // eps as the kernel adds it
+    if (!(e >= 0) || !std::isfinite(e)) return D3D_ERR_BAD_ARG;
+    if (m == 0) return D3D_OK;
+    if (!table || !dist2 || !weights) return D3D_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)d3d_divup(m, kBqThreads));
+    if (dtype == D3D_F64) {
+        D3D_LAUNCH("k_knn_weights<f64>", k_knn_weights<double>, grid, dim3(kBqThreads), 0, st, table, (const double *)dist2, m, k, power, e,
+                   (double *)weights);
+    } else {
+        D3D_LAUNCH("k_knn_weights<f32>", k_knn_weights<float>, grid, dim3(kBqThreads), 0, st, table, (const float *)dist2, m, k, power, (float)e,
+                   (float *)weights);
     }
     return D3D_OK;
 }

@@ -5,6 +5,8 @@
 //
 //   d3d_table_interp_forward   feat[V, C], table[R, J], weights[R, J]            -> out[R, C]       = sum_j w[r, j] feat[table[r, j]]
 //   d3d_table_interp_backward  grad[R, C], order, offsets, weights[R * J]        -> grad_feat[V, C] = sum_e w[e] grad[e / J]
+//   d3d_knn_interp_forward / _backward: the same two for a table of ANY width 1 .. D3D_KNN_MAX (a kNN or ball-query table with its
+//     weights: three_interpolate and its gradient) -- the same kernel through InterpRowsAny / SplatRowsAny, J a run-time value
 //
 // Both are ONE kernel, k_wfold: a weighted fold of source rows, one launch, no workspace, no read-back, no float atomics.  What differs
 // is where an output row finds its entries (InterpRows: the J entries of its table row; SplatRows: its slice of the inverted index
@@ -48,6 +50,22 @@ template <int J> struct SplatRows {           // voxel v: order[offsets[v] .. of
     const int64_t *offsets;
     __device__ void range(int64_t r, int64_t &beg, int64_t &end) const { beg = offsets[r], end = offsets[r + 1]; }
     __device__ void entry(int64_t i, int64_t &e, int64_t &src) const { e = order[i], src = e / J; }
+};
+// their siblings with the width taken at run time (d3d_knn_interp_*: any j in 1 .. D3D_KNN_MAX), four rows in flight
+struct InterpRowsAny {
+    static constexpr int kAhead = kWfSplatAhead;
+    const int32_t *table;
+    int32_t j;
+    __device__ void range(int64_t r, int64_t &beg, int64_t &end) const { beg = r * j, end = beg + j; }
+    __device__ void entry(int64_t i, int64_t &e, int64_t &src) const { e = i, src = table[i]; }
+};
+struct SplatRowsAny {
+    static constexpr int kAhead = kWfSplatAhead;
+    const int32_t *order;
+    const int64_t *offsets;
+    int32_t j;
+    __device__ void range(int64_t r, int64_t &beg, int64_t &end) const { beg = offsets[r], end = offsets[r + 1]; }
+    __device__ void entry(int64_t i, int64_t &e, int64_t &src) const { e = order[i], src = e / j; }
 };
 
 // Lane g of the group on the VEC channels from g * VEC, then from (g + group) * VEC, ... (a C the group does not cover in one pass;
@@ -101,28 +119,25 @@ __global__ __launch_bounds__(kWfThreads) void k_wfold(const T *__restrict__ src,
     }
 }
 
-// what both entries refuse: D3D_OK to go on
-int wf_check(int64_t src_rows, int64_t rows, int64_t v, int32_t c, int32_t dtype, int32_t j)
+// what the entries refuse: D3D_OK to go on.  any_width: j in 1 .. D3D_KNN_MAX (the d3d_knn_interp_* entries) instead of 1 or 8
+int wf_check(int64_t src_rows, int64_t rows, int64_t v, int32_t c, int32_t dtype, int32_t j, bool any_width = false)
 {
-    if (src_rows < 0 || rows < 0 || v < 0 || c < 1 || (j != 1 && j != 8)) return D3D_ERR_BAD_ARG;
+    if (src_rows < 0 || rows < 0 || v < 0 || c < 1 || (any_width ? j < 1 : (j != 1 && j != 8))) return D3D_ERR_BAD_ARG;
     if (dtype != D3D_F32 && dtype != D3D_F64 && dtype != D3D_F16 && dtype != D3D_BF16) return D3D_ERR_UNSUPPORTED;
-    if (v > kRowMax || rows > kRowMax / j) return D3D_ERR_UNSUPPORTED;
+    if (j > D3D_KNN_MAX || v > kRowMax || rows > kRowMax / j) return D3D_ERR_UNSUPPORTED;
     return D3D_OK;
 }
 
-// the one launch site: `n` output rows of c channels in `dtype`, their entries by make(J) (InterpRows<J> or SplatRows<J>)
-template <class Make>
-int wf_launch(const char *name, const void *src, const void *weights, int64_t n, int32_t c, int32_t dtype, int32_t j, void *out, hipStream_t st,
-              Make &&make)
+// the one launch site: `n` output rows of c channels in `dtype`, their entries by `rows` (one of the four Rows structs)
+template <class Rows>
+int wf_launch(const char *name, const void *src, const void *weights, int64_t n, int32_t c, int32_t dtype, void *out, hipStream_t st,
+              const Rows &rows)
 {
     return row_dispatch<D3D_F32, D3D_F64, D3D_F16, D3D_BF16>(dtype, c, row_aligned16(src) && row_aligned16(out), [&](auto p, auto vec, int gl) {
         typedef typename decltype(p)::T T;
-        return dispatch_int<1, 8>(j, [&](auto jj) {
-            const auto rows = make(jj);
-            D3D_LAUNCH(name, (k_wfold<T, decltype(vec)::value, std::decay_t<decltype(rows)>>), dim3((unsigned)d3d_divup(n << gl, kWfThreads)),
-                       dim3(kWfThreads), 0, st, (const T *)src, rows, (const typename RowAcc<T>::type *)weights, n, c, gl, (T *)out);
-            return D3D_OK;
-        });
+        D3D_LAUNCH(name, (k_wfold<T, decltype(vec)::value, Rows>), dim3((unsigned)d3d_divup(n << gl, kWfThreads)), dim3(kWfThreads), 0, st,
+                   (const T *)src, rows, (const typename RowAcc<T>::type *)weights, n, c, gl, (T *)out);
+        return D3D_OK;
     });
 }
 
@@ -134,8 +149,9 @@ extern "C" int d3d_table_interp_forward(const void *feat, int64_t v, int32_t c, 
     if (const int rc = wf_check(v, rows, v, c, dtype, j); rc != D3D_OK) return rc;
     if (rows == 0) return D3D_OK;
     if (!table || !weights || !out || (v > 0 && !feat)) return D3D_ERR_BAD_ARG;
-    return wf_launch("k_wfold<interp>", feat, weights, rows, c, dtype, j, out, (hipStream_t)stream,
-                     [&](auto jj) { return InterpRows<decltype(jj)::value>{table}; });
+    return dispatch_int<1, 8>(j, [&](auto jj) {
+        return wf_launch("k_wfold<interp>", feat, weights, rows, c, dtype, out, (hipStream_t)stream, InterpRows<decltype(jj)::value>{table});
+    });
 }
 
 extern "C" int d3d_table_interp_backward(const void *grad, int64_t rows, int32_t c, int32_t dtype, const int32_t *order, const int64_t *offsets,
@@ -144,6 +160,26 @@ extern "C" int d3d_table_interp_backward(const void *grad, int64_t rows, int32_t
     if (const int rc = wf_check(rows, rows, v, c, dtype, j); rc != D3D_OK) return rc;
     if (v == 0) return D3D_OK;
     if (!offsets || !grad_feat || (rows > 0 && (!grad || !order || !weights))) return D3D_ERR_BAD_ARG;
-    return wf_launch("k_wfold<splat>", grad, weights, v, c, dtype, j, grad_feat, (hipStream_t)stream,
-                     [&](auto jj) { return SplatRows<decltype(jj)::value>{order, offsets}; });
+    return dispatch_int<1, 8>(j, [&](auto jj) {
+        return wf_launch("k_wfold<splat>", grad, weights, v, c, dtype, grad_feat, (hipStream_t)stream,
+                         SplatRows<decltype(jj)::value>{order, offsets});
+    });
+}
+
+extern "C" int d3d_knn_interp_forward(const void *feat, int64_t v, int32_t c, int32_t dtype, const int32_t *table, const void *weights,
+                                      int64_t rows, int32_t j, void *out, void *stream)
+{
+    if (const int rc = wf_check(v, rows, v, c, dtype, j, true); rc != D3D_OK) return rc;
+    if (rows == 0) return D3D_OK;
+    if (!table || !weights || !out || (v > 0 && !feat)) return D3D_ERR_BAD_ARG;
+    return wf_launch("k_wfold<knn interp>", feat, weights, rows, c, dtype, out, (hipStream_t)stream, InterpRowsAny{table, j});
+}
+
+extern "C" int d3d_knn_interp_backward(const void *grad, int64_t rows, int32_t c, int32_t dtype, const int32_t *order, const int64_t *offsets,
+                                       const void *weights, int32_t j, int64_t v, void *grad_feat, void *stream)
+{
+    if (const int rc = wf_check(rows, rows, v, c, dtype, j, true); rc != D3D_OK) return rc;
+    if (v == 0) return D3D_OK;
+    if (!offsets || !grad_feat || (rows > 0 && (!grad || !order || !weights))) return D3D_ERR_BAD_ARG;
+    return wf_launch("k_wfold<knn splat>", grad, weights, v, c, dtype, grad_feat, (hipStream_t)stream, SplatRowsAny{order, offsets, j});
 }

@@ -99,6 +99,7 @@ def aligned_scatter(coordinates, feature_map, method="drop"):
 
 
 from .sample import ball_query, fps_plan, furthest_point_sample      # noqa: E402
+from .knn import PointInterp, knn_query, point_interpolate           # noqa: E402
 
 __all__ = ["aligned_scatter", "AlignedScatter", "AlignType", "aligned_scatter_forward", "aligned_scatter_backward",
-           "cuda_available", "furthest_point_sample", "ball_query", "fps_plan"]
+           "cuda_available", "furthest_point_sample", "ball_query", "fps_plan", "knn_query", "PointInterp", "point_interpolate"]

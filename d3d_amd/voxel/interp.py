@@ -45,6 +45,8 @@ class VoxelInterp:
     ValueError on duplicates and when the product of the coordinate (and batch) spans exceeds 2^62, as VoxelNeighbors.  Nothing here
     is differentiable: positions and weights get no gradient."""
 
+    _entries = ("d3d_table_interp_forward", "d3d_table_interp_backward")     # the pair of C entries _interp / _splat fold through
+
     def __init__(self, coords, positions, batch_index=None, position_batch=None, mode="linear", normalize=False):
         coords, batch_index, v = _check_coords(coords, batch_index)
         positions, _ = _as_tensor(positions, "positions")
@@ -116,14 +118,15 @@ class VoxelInterp:
 
 
 def _interp(feat, itp):
-    """feat [V, C] on itp.device -> [K, C]; one launch"""
+    """feat [V, C] on itp.device -> [K, C]; one launch.  itp: a VoxelInterp, or any object with its fields and its own `_entries`
+    (d3d_amd.point.PointInterp)"""
     k, c = itp.num_points, feat.shape[1]
     with torch.cuda.device(itp.device):
         if k == 0 or c == 0 or itp.num_entries == 0:
             return feat.new_zeros((k, c))
         out = torch.empty((k, c), dtype=feat.dtype, device=itp.device)
-        rc = _lib.load().d3d_table_interp_forward(_lib.ptr(feat), itp.num_voxels, c, _CODES[feat.dtype], _lib.ptr(itp.table),
-                                                  _lib.ptr(itp.weights_as(feat.dtype)), k, itp.num_corners, _lib.ptr(out), _lib.stream_ptr())
+        rc = getattr(_lib.load(), itp._entries[0])(_lib.ptr(feat), itp.num_voxels, c, _CODES[feat.dtype], _lib.ptr(itp.table),
+                                                   _lib.ptr(itp.weights_as(feat.dtype)), k, itp.num_corners, _lib.ptr(out), _lib.stream_ptr())
     _lib.check(rc, "table_interp")
     return out
 
@@ -136,7 +139,7 @@ def _splat(rows, itp):
             return rows.new_zeros((v, c))
         idx = itp.transpose()
         out = torch.empty((v, c), dtype=rows.dtype, device=itp.device)
-        rc = _lib.load().d3d_table_interp_backward(_lib.ptr(rows), itp.num_points, c, _CODES[rows.dtype], _lib.ptr(idx.order),
+        rc = getattr(_lib.load(), itp._entries[1])(_lib.ptr(rows), itp.num_points, c, _CODES[rows.dtype], _lib.ptr(idx.order),
                                                    _lib.ptr(idx.offsets), _lib.ptr(itp.weights_as(rows.dtype)), itp.num_corners, v,
                                                    _lib.ptr(out), _lib.stream_ptr())
     _lib.check(rc, "table_interp backward")

@@ -1246,6 +1246,50 @@ int d3d_ball_query(const void *points, int64_t n, int32_t point_stride, const vo
                    const int64_t *point_offsets, const int64_t *center_offsets, int64_t segments, double radius, int32_t nsample,
                    int32_t pad_first, int32_t *table, int32_t *counts, void *stream);
 
+/* The way back up (csrc/psample.hip, csrc/vinterp.hip): the k nearest known rows of every query row, their inverse-distance weights
+ * and the weighted sum of their features -- three_nn / three_interpolate of pointnet2, the feature propagation of PointNet++, 3DSSD,
+ * PV-RCNN's point heads; with a wider k the neighbourhoods of DGCNN and Point Transformer.  No atomics, no LDS, no workspace, nothing
+ * waits on another wavefront, every run gives the same bits.  The reference has no counterpart.
+ *
+ * d3d_knn_query: d3d_ball_query's arguments with k in place of radius / nsample / pad: table[m, k] int32 and, where dist2 is not
+ *   NULL, dist2[m, k] in `dtype`.  The rule, exact, with q(i, c) as above (every operation one rounding, no contraction):
+ *     row i of the centre's own segment is a CANDIDATE iff q(i, c) is not NaN: rows and centres that are not finite by a NaN drop
+ *       out (inf - inf is NaN as well); a q that overflows to +inf is a candidate and sorts last;
+ *     the entries of a centre are its candidates in ascending (q, i): equal q resolves to the lower row first; entries are GLOBAL
+ *       row numbers, dist2 holds the bits of their q;
+ *     with fewer than k candidates the remaining slots are -1 / +inf; a NaN centre and an empty segment give -1 throughout;
+ *     q in the subnormal range follows the device's denormal mode, as in d3d_furthest_point_sample.
+ *   k in 1 .. D3D_KNN_MAX (the wave-sorted maximum: one held entry per lane).  One launch, a wavefront per centre, O(m n) per
+ *   segment -- pointnet2's own cost, made for keypoint counts; no workspace.
+ * d3d_knn_weights: table[m, k], dist2[m, k] (what d3d_knn_query wrote) -> weights[m, k] in `dtype`, power 1 or 2, eps >= 0 finite
+ *   (rounded to the dtype first).  Per row, over the PRESENT entries (table >= 0) in ascending column:
+ *     u_j = 1 / (sqrt(q_j) + eps) for power 1 (pointnet2's 1 / (dist + 1e-8)), u_j = 1 / (q_j + eps) for power 2;
+ *     s = 0 + u_0 + u_1 + ..., w_j = u_j / s; absent entries get 0;
+ *     all weights of the row are 0 when s == 0 or s is not finite -- that covers an exact hit with eps == 0 (u = +inf): give eps > 0
+ *       where query rows may coincide with known rows.
+ *   Every operation is one correctly rounded operation in the dtype (the build passes no fast-math flag; divide and sqrt are the
+ *   correctly rounded ones).  One launch, one lane per row.
+ * d3d_knn_interp_forward / d3d_knn_interp_backward: the signatures, rules and bits of d3d_table_interp_forward / _backward (above:
+ *   out row = 0, then + (w * x) per present entry in ascending entry order, product and sum rounded separately, half types in fp32
+ *   with one rounding at the store; backward through order / offsets of d3d_voxel_index over the flattened table) with the width j
+ *   ANY value in 1 .. D3D_KNN_MAX, taken at run time -- the same kernel, its entries found through a run-time j.  For j == 1 and
+ *   j == 8 the bits are those of d3d_table_interp_*.  feat[v, c]: the known rows; rows: the query rows.
+ * D3D_ERR_BAD_ARG: a negative size, a stride below 3, k (j) < 1, c < 1, one offset array without the other, a power other than 1 or
+ *   2, an eps that is negative or not finite, a missing pointer with work to do; D3D_ERR_UNSUPPORTED: another dtype (query and
+ *   weights: D3D_F32 / D3D_F64; the folds also D3D_F16 / D3D_BF16), n, m, v or segments above 2^31 - 1, m * k (rows * j) above
+ *   2^31 - 1 for the weights and the folds, k (j) above D3D_KNN_MAX.  None of them launches anything.  m == 0 (query, weights),
+ *   rows == 0 (forward) and v == 0 (backward) return D3D_OK before any HIP call. */
+#define D3D_KNN_MAX 64
+int d3d_knn_query(const void *points, int64_t n, int32_t point_stride, const void *centers, int64_t m, int32_t center_stride, int32_t dtype,
+                  const int64_t *point_offsets, const int64_t *center_offsets, int64_t segments, int32_t k, int32_t *table, void *dist2,
+                  void *stream);
+int d3d_knn_weights(const int32_t *table, const void *dist2, int64_t m, int32_t k, int32_t dtype, int32_t power, double eps, void *weights,
+                    void *stream);
+int d3d_knn_interp_forward(const void *feat, int64_t v, int32_t c, int32_t dtype, const int32_t *table, const void *weights, int64_t rows,
+                           int32_t j, void *out, void *stream);
+int d3d_knn_interp_backward(const void *grad, int64_t rows, int32_t c, int32_t dtype, const int32_t *order, const int64_t *offsets,
+                            const void *weights, int32_t j, int64_t v, void *grad_feat, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
