@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._rows import device_of
 
 
 def _ingress(boxes, cloud):
@@ -34,7 +35,7 @@ def _ingress(boxes, cloud):
         raise ValueError("boxes should be [M,7] (x,y,z,lx,ly,lz,rz) or [M,9] (label,score,x,y,z,lx,ly,lz,yaw)")
     if pts.dim() != 2 or pts.shape[1] < 3:
         raise ValueError("cloud should be [N,>=3] (x, y, z first)")
-    dev = pts.device if pts.is_cuda else (bx.device if bx.is_cuda else _lib.require_gpu())
+    dev = device_of(pts, bx)
     odev = pts.device
     bx = bx.to(dev, torch.float32).contiguous()       # the reference's memoryviews are float32 (abstraction.pyx:310)
     pts = pts.to(dev, torch.float32).contiguous()
@@ -143,7 +144,7 @@ def _ingress_points(points):
     if not torch.is_tensor(pts) or pts.dim() != 2 or pts.shape[1] < 3:
         raise ValueError("points should be [N,>=3] (x, y, z first)")
     odev = pts.device
-    dev = odev if pts.is_cuda else _lib.require_gpu()
+    dev = device_of(pts)
     if pts.dtype not in (torch.float32, torch.float64):
         pts = pts.to(torch.float32)
     return pts.to(dev).contiguous(), dev, odev, convert

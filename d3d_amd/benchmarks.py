@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._rows import device_of
 from .tracking.matcher import DistanceTypes, ReferenceAssociation, prepare_boxes, score_match
 from .utils import Dict
 
@@ -374,7 +375,7 @@ class DetectionEvaluator:
             np.cumsum(np.diff(go)[good], out=go2[1:])
             np.cumsum(np.diff(do)[good], out=do2[1:])
             h = self._batch_prepare(gt[gsel], dt[dsel], go2, do2) if len(good) else None
-        pending = self._batch_launch(h, _seg_device(gt_boxes, dt_boxes)) if len(good) else None
+        pending = self._batch_launch(h, device_of(gt_boxes, dt_boxes)) if len(good) else None
         for f in np.nonzero(fallback)[0]:
             stats[f] = self.calc_stats(gt[go[f]:go[f + 1]], dt[do[f]:do[f + 1]])
         if pending is not None:
@@ -593,13 +594,6 @@ def _is_u16(x):
     return x.dtype == torch.uint16 if torch.is_tensor(x) else np.asarray(x).dtype == np.uint16
 
 
-def _seg_device(*tensors):
-    for t in tensors:
-        if torch.is_tensor(t) and t.device.type == "cuda":
-            return t.device
-    return _lib.require_gpu()
-
-
 def _seg_array(x, dtype, tdtype, dev, what):
     """a contiguous 1-D device tensor of x (numpy array or torch tensor) without changing its values"""
     if torch.is_tensor(x):
@@ -688,7 +682,7 @@ class SegmentationEvaluator:
             raise ValueError("labels and ids must have one entry per point")
         if frames == 0:
             return []
-        dev = _seg_device(gt_labels, pred_labels, gt_ids, pred_ids)
+        dev = device_of(gt_labels, pred_labels, gt_ids, pred_ids)
         gl = _seg_array(gt_labels, np.uint8, torch.uint8, dev, "gt_labels")
         pl = _seg_array(pred_labels, np.uint8, torch.uint8, dev, "pred_labels")
         gi = _seg_array(gt_ids, np.uint16, torch.uint16, dev, "gt_ids") if pano else None
@@ -971,7 +965,7 @@ class TrackingEvaluator(DetectionEvaluator):
         gt = _host_rows(gt_boxes, np.float32, 9)
         dt = _host_rows(dt_boxes, np.float32, 9)
         h = self._prepare_host(gt, dt, _host_tids(gt_tids, "gt_tids"), _host_tids(dt_tids, "dt_tids"))
-        return self._run([h], _seg_device(gt_boxes, dt_boxes, gt_tids, dt_tids))[0]
+        return self._run([h], device_of(gt_boxes, dt_boxes, gt_tids, dt_tids))[0]
 
     def calc_stats_sequence(self, gt_boxes, dt_boxes, gt_tids, dt_tids, gt_frame_offsets, dt_frame_offsets):
         """Extension (not in the reference): F frames stacked, frame f = gt rows gt_frame_offsets[f] .. gt_frame_offsets[f + 1]
@@ -992,7 +986,7 @@ class TrackingEvaluator(DetectionEvaluator):
             raise ValueError("gt_frame_offsets and dt_frame_offsets must describe the same frames")
         hs = [self._prepare_host(gt[go[f]:go[f + 1]], dt[do[f]:do[f + 1]], gtid[go[f]:go[f + 1]], dtid[do[f]:do[f + 1]])
               for f in range(len(go) - 1)]
-        return self._run(hs, _seg_device(gt_boxes, dt_boxes, gt_tids, dt_tids)) if hs else []
+        return self._run(hs, device_of(gt_boxes, dt_boxes, gt_tids, dt_tids)) if hs else []
 
     def calc_stats_batch(self, *args, **kwargs):
         """not for tracking: the frames of a sequence depend on each other and need track ids"""

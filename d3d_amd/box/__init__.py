@@ -15,6 +15,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from .. import _lib, options
+from .._rows import device_of
 
 
 class IouType(enum.IntEnum):            # box/common.h:5-9
@@ -47,13 +48,7 @@ def _dtype_code(t):
 
 
 def _to_device(*ts):
-    dev = None
-    for t in ts:
-        if t.is_cuda:
-            dev = t.device
-            break
-    if dev is None:
-        dev = _lib.require_gpu()
+    dev = device_of(*ts)
     return [t.to(dev).contiguous() for t in ts], dev
 
 

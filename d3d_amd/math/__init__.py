@@ -4,20 +4,17 @@ the reference's bits (bessel.hip), and the autograd function I0Exp behind i0e.""
 import torch
 
 from .. import _lib
+from .._rows import FLOAT_CODES, device_of
 
 cuda_available = True
-
-_CODES = {torch.float32: _lib.F32, torch.float64: _lib.F64}
 
 
 def _prepare(x, name):
     if not torch.is_tensor(x):
         raise TypeError("%s(): argument must be a Tensor, not %s" % (name, type(x).__name__))
-    if x.dtype not in _CODES:                         # AT_DISPATCH_FLOATING_TYPES (impl.cpp:21, 42)
+    if x.dtype not in FLOAT_CODES:                         # AT_DISPATCH_FLOATING_TYPES (impl.cpp:21, 42)
         raise RuntimeError('"%s" not implemented for \'%s\'' % (name, str(x.dtype).replace("torch.", "")))
-    odev = x.device
-    dev = odev if x.is_cuda else _lib.require_gpu()
-    return odev, dev
+    return x.device, device_of(x)
 
 
 def _bessel_e(order, x):
@@ -27,7 +24,7 @@ def _bessel_e(order, x):
     xs = x.detach().to(dev).contiguous()
     with torch.cuda.device(dev):
         out = torch.empty(xs.shape, dtype=xs.dtype, device=dev)
-        _lib.check(_lib.load().d3d_bessel_e(order, _lib.ptr(xs), xs.numel(), _CODES[xs.dtype], _lib.ptr(out), _lib.stream_ptr()), name)
+        _lib.check(_lib.load().d3d_bessel_e(order, _lib.ptr(xs), xs.numel(), FLOAT_CODES[xs.dtype], _lib.ptr(out), _lib.stream_ptr()), name)
     return _lib.to_caller(out, odev, dev)
 
 
@@ -50,7 +47,7 @@ def _i0e_backward(x, grad):
     xs, gs = x.detach().to(dev).contiguous(), grad.detach().to(dev).contiguous()
     with torch.cuda.device(dev):
         out = torch.empty(xs.shape, dtype=xs.dtype, device=dev)
-        _lib.check(_lib.load().d3d_i0e_backward(_lib.ptr(xs), _lib.ptr(gs), xs.numel(), _CODES[xs.dtype], _lib.ptr(out),
+        _lib.check(_lib.load().d3d_i0e_backward(_lib.ptr(xs), _lib.ptr(gs), xs.numel(), FLOAT_CODES[xs.dtype], _lib.ptr(out),
                                                 _lib.stream_ptr()), "i0e_backward")
     return _lib.to_caller(out, odev, dev)
 

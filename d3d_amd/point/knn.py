@@ -16,9 +16,9 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..voxel.interp import _Fold
-from ..voxel.pool import _CODES as _FEATURE_CODES, VoxelIndex, _on
-from .sample import _CODES, _ROW_MAX, _as_tensor, _check_rows, _device_of, _host_offsets, _rows_on
+from .._rows import FEATURE_CODES, FLOAT_CODES, ROW_MAX, as_tensor, back_to_caller, check_rows, device_of, host_offsets, rows_on
+from ..voxel.interp import WeightedTable, table_fold
+from .sample import check_xyz_rows
 
 _K_MAX = _lib.KNN_MAX
 
@@ -33,21 +33,21 @@ def _check_k(k, what="k"):
 
 def _check_pair(points, centers, k, point_offsets, center_offsets, names=("points", "centers")):
     """every host-side refusal of a query -> (points, centers, k, poffs + coffs or None, segments, points came as numpy)"""
-    points, was_numpy = _as_tensor(points, names[0])
-    centers, _ = _as_tensor(centers, names[1])
-    _check_rows(points, names[0])
-    _check_rows(centers, names[1])
+    points, was_numpy = as_tensor(points, names[0])
+    centers, _ = as_tensor(centers, names[1])
+    check_xyz_rows(points, names[0])
+    check_xyz_rows(centers, names[1])
     if points.dtype != centers.dtype:
         raise ValueError("%s (%s) and %s (%s) must share a dtype" % (names[0], points.dtype, names[1], centers.dtype))
     k = _check_k(k)
     if (point_offsets is None) != (center_offsets is None):
         raise ValueError("%s_offsets and %s_offsets go together: give both or neither" % (names[0].rstrip("s"), names[1].rstrip("s")))
     n, m = points.shape[0], centers.shape[0]
-    if n > _ROW_MAX or m * k > _ROW_MAX:
+    if n > ROW_MAX or m * k > ROW_MAX:
         raise ValueError("a kNN query takes at most 2^31 - 1 points and table entries (centres x k)")
     offs, segments = None, 0
     if point_offsets is not None:
-        poffs, coffs = _host_offsets(point_offsets, n, "point_offsets"), _host_offsets(center_offsets, m, "center_offsets")
+        poffs, coffs = host_offsets(point_offsets, n, "point_offsets"), host_offsets(center_offsets, m, "center_offsets")
         if len(poffs) != len(coffs):
             raise ValueError("point_offsets names %d segments, center_offsets %d" % (len(poffs) - 1, len(coffs) - 1))
         offs, segments = poffs + coffs, len(poffs) - 1
@@ -57,13 +57,13 @@ def _check_pair(points, centers, k, point_offsets, center_offsets, names=("point
 def _query(points, centers, k, offs, segments, dev, want_dist):
     """-> (table [M, k] int32, dist2 [M, k] or None) on dev; M > 0"""
     n, m = points.shape[0], centers.shape[0]
-    pts, pstride = _rows_on(points, dev)
-    ctr, cstride = _rows_on(centers, dev)
+    pts, pstride = rows_on(points, dev)
+    ctr, cstride = rows_on(centers, dev)
     with torch.cuda.device(dev):
         both = torch.from_numpy(np.asarray(offs, np.int64)).to(dev) if segments else None
         table = torch.empty((m, k), dtype=torch.int32, device=dev)
         dist2 = torch.empty((m, k), dtype=pts.dtype, device=dev) if want_dist else None
-        rc = _lib.load().d3d_knn_query(_lib.ptr(pts), n, pstride, _lib.ptr(ctr), m, cstride, _CODES[pts.dtype],
+        rc = _lib.load().d3d_knn_query(_lib.ptr(pts), n, pstride, _lib.ptr(ctr), m, cstride, FLOAT_CODES[pts.dtype],
                                        _lib.ptr(both[:segments + 1]) if segments else None,
                                        _lib.ptr(both[segments + 1:]) if segments else None, segments, k, _lib.ptr(table), _lib.ptr(dist2),
                                        _lib.stream_ptr())
@@ -93,7 +93,7 @@ def knn_query(points, centers, k, point_offsets=None, center_offsets=None, retur
     if m == 0:
         table, dist2 = torch.empty((0, k), dtype=torch.int32, device=odev), torch.empty((0, k), dtype=points.dtype, device=odev)
     else:
-        dev = _device_of(points, centers)
+        dev = device_of(points, centers)
         table, dist2 = _query(points, centers, k, offs, segments, dev, return_distances)
         if return_distances:
             table, dist2 = _lib.to_caller((table, dist2), odev, dev)
@@ -104,7 +104,7 @@ def knn_query(points, centers, k, point_offsets=None, center_offsets=None, retur
     return (table, dist2) if return_distances else table
 
 
-class PointInterp:
+class PointInterp(WeightedTable):
     """The neighbour table of one frame and layer: for every unknown (query) row its k nearest known rows and their weights.
 
     :param known: [Nk, D], D >= 3: the rows that carry features (the keypoints of the coarser level), and
@@ -130,7 +130,7 @@ class PointInterp:
         eps = float(eps)
         if known.dtype == torch.float32 and eps > float(np.finfo(np.float32).max):
             raise ValueError("eps = %r is not finite in float32" % (eps,))
-        dev = _device_of(known, unknown)
+        dev = device_of(known, unknown)
         m = unknown.shape[0]
         with torch.cuda.device(dev):
             if m == 0:
@@ -140,17 +140,15 @@ class PointInterp:
             else:
                 table, dist2 = _query(known, unknown, k, offs, segments, dev, True)
                 weights = torch.empty((m, k), dtype=dist2.dtype, device=dev)
-                rc = _lib.load().d3d_knn_weights(_lib.ptr(table), _lib.ptr(dist2), m, k, _CODES[dist2.dtype], int(power), eps,
+                rc = _lib.load().d3d_knn_weights(_lib.ptr(table), _lib.ptr(dist2), m, k, FLOAT_CODES[dist2.dtype], int(power), eps,
                                                  _lib.ptr(weights), _lib.stream_ptr())
                 _lib.check(rc, "knn_weights")
         self._set(dev, table, dist2, weights, known.shape[0])
         self.power, self.eps = int(power), eps
 
     def _set(self, dev, table, dist2, weights, num_known):
-        self.device, self.table, self.dist2, self.weights = dev, table, dist2, weights
-        self.num_known, self.num_points, self.k = int(num_known), table.shape[0], table.shape[1]
-        self._index = None
-        self._cast = {weights.dtype: weights}
+        self._set_table(dev, table, weights, num_known, table.numel())       # (the slots: absent ones are skipped by the kernel)
+        self.dist2, self.num_known, self.k = dist2, int(num_known), table.shape[1]
 
     @classmethod
     def from_table(cls, table, weights, num_known):
@@ -161,49 +159,27 @@ class PointInterp:
         :param num_known: the rows of the feature matrix the table names
         The table is checked once (ValueError for an entry outside [-1, num_known)): one number read back when it lives on the GPU.
         `dist2` is None."""
-        table, _ = _as_tensor(table, "table")
-        weights, _ = _as_tensor(weights, "weights")
+        table, _ = as_tensor(table, "table")
+        weights, _ = as_tensor(weights, "weights")
         if table.dim() != 2 or table.dtype != torch.int32:
             raise ValueError("table must be a [M, J] int32 tensor")
         if not 1 <= table.shape[1] <= _K_MAX:
             raise ValueError("the width of the table must be in 1 .. %d, not %d" % (_K_MAX, table.shape[1]))
         if weights.shape != table.shape:
             raise ValueError("weights must have the shape of the table %s, not %s" % (tuple(table.shape), tuple(weights.shape)))
-        if weights.dtype not in _CODES:
+        if weights.dtype not in FLOAT_CODES:
             raise ValueError("weights must be float32 or float64, not %s" % weights.dtype)
-        if isinstance(num_known, bool) or not isinstance(num_known, (int, np.integer)) or not 0 <= num_known <= _ROW_MAX:
+        if isinstance(num_known, bool) or not isinstance(num_known, (int, np.integer)) or not 0 <= num_known <= ROW_MAX:
             raise ValueError("num_known must be an int in 0 .. 2^31 - 1, not %r" % (num_known,))
-        if table.numel() > _ROW_MAX:
+        if table.numel() > ROW_MAX:
             raise ValueError("a table takes at most 2^31 - 1 entries")
         if table.numel() and bool(((table < -1) | (table >= int(num_known))).any()):
             raise ValueError("table holds rows outside [-1, %d)" % int(num_known))
-        dev = _device_of(table, weights)
+        dev = device_of(table, weights)
         self = cls.__new__(cls)
         self._set(dev, table.detach().to(dev).contiguous(), None, weights.detach().to(dev).contiguous(), num_known)
         self.power = self.eps = None
         return self
-
-    # what the fold of d3d_amd.voxel.interp reads of its interp object
-    num_voxels = property(lambda self: self.num_known)
-    num_corners = property(lambda self: self.k)
-    num_entries = property(lambda self: self.table.numel())      # (the slots: absent ones are skipped by the kernel)
-
-    def transpose(self):
-        """The inverted table: a VoxelIndex over the flattened table [Mu * k] taken as a mapping -- per known row the entries that
-        name it, in ascending entry number.  Built on the first call (VoxelIndex's one read-back) and kept: what the gradient of
-        point_interpolate walks."""
-        if self._index is None:
-            with torch.cuda.device(self.device):
-                self._index = VoxelIndex(self.table.view(-1), self.num_known, keep_mapping=False)
-        return self._index
-
-    def weights_as(self, dtype):
-        """the weights a fold in `dtype` multiplies by: float64 for float64 features, float32 otherwise; cast once and kept"""
-        want = torch.float64 if dtype == torch.float64 else torch.float32
-        w = self._cast.get(want)
-        if w is None:
-            w = self._cast[want] = self.weights.to(want)
-        return w
 
 
 def point_interpolate(known_features, interp):
@@ -220,16 +196,9 @@ def point_interpolate(known_features, interp):
     """
     if not isinstance(interp, PointInterp):
         raise TypeError("interp must be a PointInterp")
-    rows, was_numpy = _as_tensor(known_features, "known_features")
-    if rows.dim() != 2:
-        raise ValueError("known_features must be a 2-D tensor of one row per known point")
-    if rows.dtype not in _FEATURE_CODES:
-        raise ValueError("known_features must be float32, float64, float16 or bfloat16, not %s" % rows.dtype)
-    if rows.shape[0] != interp.num_known:
-        raise ValueError("known_features has %d rows where the PointInterp expects %d" % (rows.shape[0], interp.num_known))
-    _on(interp, rows)
-    out = _Fold.apply(rows, interp, False)
-    return out.detach().numpy() if was_numpy else out
+    rows, was_numpy = as_tensor(known_features, "known_features")
+    check_rows(rows, "known_features", "known point", "known_features", FEATURE_CODES, interp, interp.num_known)
+    return back_to_caller(table_fold(rows, interp), was_numpy)
 
 
 __all__ = ["knn_query", "PointInterp", "point_interpolate"]

@@ -15,70 +15,25 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._rows import FLOAT_CODES, ROW_MAX, as_tensor, device_of, host_offsets, rows_on
 
-_CODES = {torch.float32: _lib.F32, torch.float64: _lib.F64}
-_ROW_MAX = 2 ** 31 - 1
 _NSAMPLE_MAX = 1024
 
 
-def _as_tensor(x, what):
-    if isinstance(x, np.ndarray):
-        return torch.from_numpy(x), True
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("%s must be a torch.Tensor or numpy array" % what)
-    return x, False
-
-
-def _check_rows(t, what):
+def check_xyz_rows(t, what):
     if t.dim() != 2 or t.shape[1] < 3:
         raise ValueError("%s must be [N, D] with D >= 3 (columns 0..2 are the coordinates), not %s" % (what, tuple(t.shape)))
-    if t.dtype not in _CODES:
+    if t.dtype not in FLOAT_CODES:
         raise ValueError("%s must be float32 or float64, not %s" % (what, t.dtype))
-
-
-def _host_offsets(offsets, total, what):
-    """offsets -> a list of ints [B + 1], checked: 1-D, from 0 to `total`, nondecreasing.  None: one segment.  Offsets belong on the
-    host; a GPU tensor is read back (one blocking copy) for the checks."""
-    if offsets is None:
-        offsets = [0, int(total)]
-    if isinstance(offsets, torch.Tensor):
-        if offsets.dim() != 1 or offsets.dtype not in (torch.int64, torch.int32):
-            raise ValueError("%s must be a 1-D int64 or int32 tensor" % what)
-        offs = offsets.cpu().tolist()                    # (a GPU tensor: the read-back)
-    else:
-        arr = np.asarray(offsets)
-        if arr.ndim != 1 or (arr.size and not np.issubdtype(arr.dtype, np.integer)):
-            raise ValueError("%s must be a 1-D sequence of integers" % what)
-        offs = [int(v) for v in arr.tolist()]
-    if len(offs) < 1 or offs[0] != 0 or offs[-1] != int(total) or any(b < a for a, b in zip(offs, offs[1:])):
-        raise ValueError("%s must run nondecreasing from 0 to %d (the number of rows)" % (what, int(total)))
-    if any(b - a > _ROW_MAX for a, b in zip(offs, offs[1:])):
-        raise ValueError("a segment of %s holds more than 2^31 - 1 rows" % what)
-    return offs
-
-
-def _rows_on(t, dev):
-    """-> (tensor on dev with unit column stride, its row stride in elements)"""
-    t = t.detach().to(dev)
-    if t.shape[0] > 1 and t.stride(1) == 1 and t.shape[1] <= t.stride(0) <= _ROW_MAX:      # a column slice of wider rows: as it lies
-        return t, int(t.stride(0))
-    return t.contiguous(), int(t.shape[1])
-
-
-def _device_of(*tensors):
-    for t in tensors:
-        if t.is_cuda:
-            return t.device
-    return _lib.require_gpu()
 
 
 def fps_plan(segment_rows, dtype=torch.float32):
     """-> (route, capacity): the route a segment of that many rows takes (0 .. 2 registers, _lib.FPS_ROUTE_LDS, _lib.FPS_ROUTE_STREAM)
     and the rows that route holds.  Pure host arithmetic."""
-    if dtype not in _CODES:
+    if dtype not in FLOAT_CODES:
         raise ValueError("dtype must be float32 or float64, not %s" % dtype)
     route, cap = ctypes.c_int32(), ctypes.c_int32()
-    _lib.check(_lib.load().d3d_fps_plan(int(segment_rows), _CODES[dtype], ctypes.byref(route), ctypes.byref(cap)), "fps_plan")
+    _lib.check(_lib.load().d3d_fps_plan(int(segment_rows), FLOAT_CODES[dtype], ctypes.byref(route), ctypes.byref(cap)), "fps_plan")
     return route.value, cap.value
 
 
@@ -102,10 +57,10 @@ def furthest_point_sample(points, num_samples, offsets=None, return_distances=Fa
     first row M times with NaN distances.  Raises ValueError before any GPU work for malformed offsets, a segment of 0 rows with
     M > 0, a segment above 2^31 - 1 rows, a wrong dtype or shape, a negative num_samples.
     """
-    points, was_numpy = _as_tensor(points, "points")
-    _check_rows(points, "points")
+    points, was_numpy = as_tensor(points, "points")
+    check_xyz_rows(points, "points")
     n = points.shape[0]
-    offs = _host_offsets(offsets, n, "offsets")
+    offs = host_offsets(offsets, n, "offsets")
     b = len(offs) - 1
     if isinstance(num_samples, (torch.Tensor, np.ndarray)):
         num_samples = num_samples.tolist()
@@ -125,10 +80,10 @@ def furthest_point_sample(points, num_samples, offsets=None, return_distances=Fa
     if total == 0:                                       # nothing to launch
         idx, dist = torch.empty((0,), dtype=torch.int64, device=odev), torch.empty((0,), dtype=points.dtype, device=odev)
     else:
-        dev = _device_of(points)
-        pts, stride = _rows_on(points, dev)
+        dev = device_of(points)
+        pts, stride = rows_on(points, dev)
         lib = _lib.load()
-        code = _CODES[pts.dtype]
+        code = FLOAT_CODES[pts.dtype]
         with torch.cuda.device(dev):
             soffs = np.concatenate([[0], np.cumsum(ms)]).astype(np.int64)
             both = torch.from_numpy(np.concatenate([np.asarray(offs, np.int64), soffs])).to(dev)
@@ -164,10 +119,10 @@ def ball_query(points, centers, radius, nsample, point_offsets=None, center_offs
     The rule (exact): r2 = r * r with r rounded to the dtype; row i is inside iff q < r2 (strict; false for NaN, so rows and centres
     that are not finite match nothing), q as in furthest_point_sample.  O(M N) per segment: made for keypoint counts.
     """
-    points, was_numpy = _as_tensor(points, "points")
-    centers, _ = _as_tensor(centers, "centers")
-    _check_rows(points, "points")
-    _check_rows(centers, "centers")
+    points, was_numpy = as_tensor(points, "points")
+    centers, _ = as_tensor(centers, "centers")
+    check_xyz_rows(points, "points")
+    check_xyz_rows(centers, "centers")
     if points.dtype != centers.dtype:
         raise ValueError("points (%s) and centers (%s) must share a dtype" % (points.dtype, centers.dtype))
     if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not np.isfinite(radius) or not radius > 0:
@@ -180,11 +135,11 @@ def ball_query(points, centers, radius, nsample, point_offsets=None, center_offs
     if (point_offsets is None) != (center_offsets is None):
         raise ValueError("point_offsets and center_offsets go together: give both or neither")
     n, m = points.shape[0], centers.shape[0]
-    if n > _ROW_MAX or m > _ROW_MAX:
+    if n > ROW_MAX or m > ROW_MAX:
         raise ValueError("ball_query takes at most 2^31 - 1 points and centres")
     segments = 0
     if point_offsets is not None:
-        poffs, coffs = _host_offsets(point_offsets, n, "point_offsets"), _host_offsets(center_offsets, m, "center_offsets")
+        poffs, coffs = host_offsets(point_offsets, n, "point_offsets"), host_offsets(center_offsets, m, "center_offsets")
         if len(poffs) != len(coffs):
             raise ValueError("point_offsets names %d segments, center_offsets %d" % (len(poffs) - 1, len(coffs) - 1))
         segments = len(poffs) - 1
@@ -192,14 +147,14 @@ def ball_query(points, centers, radius, nsample, point_offsets=None, center_offs
     if m == 0:
         table, counts = (torch.empty((0, nsample), dtype=torch.int32, device=odev), torch.empty((0,), dtype=torch.int32, device=odev))
     else:
-        dev = _device_of(points, centers)
-        pts, pstride = _rows_on(points, dev)
-        ctr, cstride = _rows_on(centers, dev)
+        dev = device_of(points, centers)
+        pts, pstride = rows_on(points, dev)
+        ctr, cstride = rows_on(centers, dev)
         with torch.cuda.device(dev):
             both = torch.from_numpy(np.asarray(poffs + coffs, np.int64)).to(dev) if segments else None
             table = torch.empty((m, nsample), dtype=torch.int32, device=dev)
             counts = torch.empty((m,), dtype=torch.int32, device=dev)
-            rc = _lib.load().d3d_ball_query(_lib.ptr(pts), n, pstride, _lib.ptr(ctr), m, cstride, _CODES[pts.dtype],
+            rc = _lib.load().d3d_ball_query(_lib.ptr(pts), n, pstride, _lib.ptr(ctr), m, cstride, FLOAT_CODES[pts.dtype],
                                             _lib.ptr(both[:segments + 1]) if segments else None,
                                             _lib.ptr(both[segments + 1:]) if segments else None, segments, float(radius), nsample,
                                             int(pad.lower() == "first"), _lib.ptr(table), _lib.ptr(counts), _lib.stream_ptr())

@@ -16,58 +16,23 @@ library's own (kernels and the exact rules: csrc/vnbr.hip, include/d3d_hip.h; th
 method="fused" (the only route of fp16 and bf16) runs the convolution and its gradients as MFMA kernels that gather the rows straight
 into LDS: no [V, K * C] buffer exists (csrc/vconv.hip).
 
-Everything that convolves through a table lives here, once, for subm_conv3d and for sparse_conv.py's two operators: a _TableView per
-table, _conv_front (the argument checks and the choice of the route), and one autograd.Function per route, TableConv (gather) and
+Everything that convolves through a table lives here, once, for subm_conv3d and for sparse_conv.py's two operators: a TableView per
+table, conv_front (the argument checks and the choice of the route), and one autograd.Function per route, TableConv (gather) and
 FusedTableConv, over a forward and a backward view: out[r] = sum_k features[fwd.table[r, k]] @ weight[k] (+ bias).
 """
-import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
-from .pool import _as_tensor, _dtype_code, _on
+from .._rows import FEATURE_CODES, FLOAT_CODES, ROW_MAX, as_tensor, back_to_caller, check_rows, device_of, dtype_code, on_owner, to_owner
+from ._coords import _check_coords, _host_spans_fit, _triple
 
-_MAX_VOXELS = 2 ** 31 - 1
-_SPAN_LIMIT = 2 ** 62
 _GATHER_BYTES = 1 << 30           # what the default chunk_rows lets one gathered buffer take
 _GEMM_TILE_BYTES = 1 << 28        # the gathered rows of one GEMM call
 _GEMM_TILE_ROWS = (1024, 65536)
 
 
-def _triple(x, what):
-    t = tuple(x) if isinstance(x, (tuple, list)) else (x, x, x)
-    if len(t) != 3 or any(isinstance(a, bool) or not isinstance(a, (int, np.integer)) for a in t):
-        raise ValueError("%s must be an int or three ints, not %r" % (what, x))
-    return tuple(int(a) for a in t)
-
-
-def _host_spans_fit(coords, batch):
-    """host inputs: the span product the device would measure, before anything is copied"""
-    span = 1
-    for col in ([coords[:, a] for a in range(3)] + ([batch] if batch is not None else [])):
-        span *= int(col.max()) - int(col.min()) + 1
-    return span <= _SPAN_LIMIT
-
-
-def _check_coords(coords, batch_index):
-    """coords [V, 3] and batch_index [V] or None, int64 or int32, as given to a VoxelNeighbors or a SparseConvMap
-    -> (coords, batch_index, V) as tensors where they are; nothing here needs a GPU"""
-    coords, _ = _as_tensor(coords, "coords")
-    if coords.dim() != 2 or coords.shape[1] != 3:
-        raise ValueError("coords must be a [V, 3] tensor of voxel coordinates")
-    if coords.dtype not in (torch.int64, torch.int32):
-        raise ValueError("coords must be int64 or int32, not %s" % coords.dtype)
-    v = coords.shape[0]
-    if batch_index is not None:
-        batch_index, _ = _as_tensor(batch_index, "batch_index")
-        if batch_index.dim() != 1 or batch_index.shape[0] != v:
-            raise ValueError("batch_index must be a [V] tensor, one value per row of coords")
-        if batch_index.dtype not in (torch.int64, torch.int32):
-            raise ValueError("batch_index must be int64 or int32, not %s" % batch_index.dtype)
-    return coords, batch_index, v
-
-
-class _TableView:
+class TableView:
     """what the gathers, the fused launchers and _chunk_rows read of a table [num_voxels, K] whose entries point into src_rows feature
     rows: the one table of a VoxelNeighbors (src_rows = num_voxels), the two of a SparseConvMap"""
 
@@ -96,12 +61,12 @@ class VoxelNeighbors:
             raise ValueError("kernel_size must be odd and in 1 .. 7, not %r" % (kernel_size,))
         if any(d < 1 or d >= 2 ** 31 for d in dil):
             raise ValueError("dilation must be at least 1, not %r" % (dilation,))
-        if v > _MAX_VOXELS:
+        if v > ROW_MAX:
             raise ValueError("VoxelNeighbors takes at most 2^31 - 1 voxels")
         overflow = "the spans of the coordinates (and batch values) multiply to more than 2^62"
         if v and not coords.is_cuda and not _host_spans_fit(coords, None if batch_index is None or batch_index.is_cuda else batch_index):
             raise ValueError(overflow)
-        dev = coords.device if coords.is_cuda else _lib.require_gpu()
+        dev = device_of(coords)
         k = ks[0] * ks[1] * ks[2]
         self.device, self.num_voxels, self.kernel_size, self.dilation, self.kernel_volume = dev, v, ks, dil, k
         coords = coords.to(device=dev, dtype=torch.int64).contiguous()
@@ -122,12 +87,12 @@ class VoxelNeighbors:
         if dups:
             raise ValueError("coords holds %d rows whose (batch, coordinate) an earlier row already has" % dups)
         self.num_entries = entries
-        self._view = _TableView(self.table, v, k, dev)           # the voxels read the voxels: forward as it is, backward mirrored
+        self._view = TableView(self.table, v, k, dev)           # the voxels read the voxels: forward as it is, backward mirrored
 
 
 def _gather(feat, nbrs, mirrored, v0=0, rows=None, feat_cols=1, out=None):
     """feat [V, C] (or [V, K, C] with feat_cols = K) on nbrs.device -> [rows, K, C] for the rows v0 .. v0 + rows of the table (into
-    `out`, contiguous and of that many elements, when given); one launch, every output row written once.  nbrs: a _TableView
+    `out`, contiguous and of that many elements, when given); one launch, every output row written once.  nbrs: a TableView
     (V = nbrs.src_rows, the table has nbrs.num_voxels rows)"""
     k, c = nbrs.kernel_volume, feat.shape[-1]
     rows = nbrs.num_voxels - v0 if rows is None else rows
@@ -136,31 +101,36 @@ def _gather(feat, nbrs, mirrored, v0=0, rows=None, feat_cols=1, out=None):
             return feat.new_zeros((rows, k, c)) if out is None else out
         if out is None:
             out = torch.empty((rows, k, c), dtype=feat.dtype, device=nbrs.device)
-        rc = _lib.load().d3d_neighbor_gather(_lib.ptr(feat), nbrs.src_rows, c, _dtype_code(feat), feat_cols, _lib.ptr(nbrs.table[v0:]),
+        code = dtype_code(feat, FLOAT_CODES, "voxel features")
+        rc = _lib.load().d3d_neighbor_gather(_lib.ptr(feat), nbrs.src_rows, c, code, feat_cols, _lib.ptr(nbrs.table[v0:]),
                                              rows, k, int(mirrored), _lib.ptr(out), _lib.stream_ptr())
     _lib.check(rc, "neighbor_gather")
     return out
 
 
+def _gather_sum(grad, nbrs):
+    """grad [V, K, C] on nbrs.device -> [V, C]: the mirrored gather of it (row [table[u, K-1-k], k] for every (u, k)), then the sum
+    over k in ascending k"""
+    g = _gather(grad, nbrs, True, feat_cols=nbrs.kernel_volume)
+    acc = g[:, 0].clone()
+    for k in range(1, nbrs.kernel_volume):                       # a fixed left fold: the same bits on every run
+        acc += g[:, k]
+    return acc
+
+
 class NeighborGather(torch.autograd.Function):
     """neighbor_gather: (features [V, C], the view of a VoxelNeighbors) -> [V, K, C], one launch.  backward: the mirrored gather of
-    the gradient (row [table[u, K-1-k], k] of it for every (u, k)), then the sum over k in ascending k.  Differentiable once."""
+    the gradient, summed over k (_gather_sum).  Differentiable once."""
 
     @staticmethod
     def forward(ctx, features, nbrs):
         ctx.nbrs, ctx.odev = nbrs, features.device
-        out = _gather(features.detach().to(nbrs.device).contiguous(), nbrs, False)
-        return _lib.to_caller(out, ctx.odev, nbrs.device)
+        return on_owner(_gather, features, nbrs, ctx.odev, False)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad):
-        nbrs = ctx.nbrs
-        g = _gather(grad.to(nbrs.device).contiguous(), nbrs, True, feat_cols=nbrs.kernel_volume)
-        acc = g[:, 0].clone()
-        for k in range(1, nbrs.kernel_volume):                   # a fixed left fold: the same bits on every run
-            acc += g[:, k]
-        return _lib.to_caller(acc, ctx.odev, nbrs.device), None
+        return on_owner(_gather_sum, grad, ctx.nbrs, ctx.odev), None
 
 
 def _chunks(v, chunk_rows):
@@ -211,9 +181,8 @@ def _chunk_rows(chunk_rows, nbrs, cin, cout, itemsize):
 def _conv_enter(ctx, features, fwd, bwd, bwd_mirrored, weight, bias):
     """what both routes' forward begins with: -> (features, weight, bias or None) detached, contiguous and on the tables' device;
     on ctx the two views, the two of them saved, and the device each of the three came from"""
-    dev = fwd.device
-    f, w = features.detach().to(dev).contiguous(), weight.detach().to(dev).contiguous()
-    b = None if bias is None else bias.detach().to(dev).contiguous()
+    f, w = to_owner(features, fwd), to_owner(weight, fwd)
+    b = None if bias is None else to_owner(bias, fwd)
     ctx.fwd, ctx.bwd, ctx.bwd_mirrored = fwd, bwd, bwd_mirrored
     ctx.devs = (features.device, weight.device, None if bias is None else bias.device)
     ctx.save_for_backward(f, w)
@@ -255,7 +224,7 @@ class TableConv(torch.autograd.Function):
         f, w = ctx.saved_tensors
         fwd, bwd = ctx.fwd, ctx.bwd
         k, cin, cout = w.shape
-        g = grad.to(fwd.device).contiguous()
+        g = to_owner(grad, fwd)
         need_f, _, _, _, need_w, need_b, _, _ = ctx.needs_input_grad
         gf = gw = gb = None
         with torch.cuda.device(fwd.device):
@@ -274,14 +243,13 @@ class TableConv(torch.autograd.Function):
         return _conv_grads(ctx, gf, gw, gb) + (None, None)
 
 
-_FUSED_CODES = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
+_FUSED_CODES = {d: code for d, code in FEATURE_CODES.items() if d != torch.float64}
 _METHODS = (None, "gather", "fused")
 
 
 def _conv_dtype(t):
-    """the dtypes a convolution takes (neighbor_gather and voxel_pool keep to pool._dtype_code)"""
-    if t.dtype not in _FUSED_CODES and t.dtype != torch.float64:
-        raise ValueError("voxel features must be float32, float64, float16 or bfloat16, not %s" % t.dtype)
+    """the dtypes a convolution takes (neighbor_gather and voxel_pool keep to float32 and float64)"""
+    dtype_code(t, FEATURE_CODES, "voxel features")
 
 
 def _conv_route(features, weight, method):
@@ -342,7 +310,7 @@ class FusedTableConv(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad):
         f, w = ctx.saved_tensors
-        g = grad.to(ctx.fwd.device).contiguous()
+        g = to_owner(grad, ctx.fwd)
         need_f, _, _, _, need_w, need_b = ctx.needs_input_grad
         gf = gw = gb = None
         with torch.cuda.device(ctx.fwd.device):
@@ -355,30 +323,20 @@ class FusedTableConv(torch.autograd.Function):
         return _conv_grads(ctx, gf, gw, gb)
 
 
-def _check_rows(t, owner, rows, check_dtype):
-    """features of a gather or a convolution through a table of `owner` whose entries point into `rows` feature rows"""
-    if t.dim() != 2:
-        raise ValueError("features must be a 2-D tensor of one row per voxel")
-    check_dtype(t)
-    if t.shape[0] != rows:
-        raise ValueError("features has %d rows where the %s expects %d" % (t.shape[0], type(owner).__name__, rows))
-    _on(owner, t)
-
-
-def _conv_front(features, owner, fwd, bwd, bwd_mirrored, weight, bias, chunk_rows, method):
+def conv_front(features, owner, fwd, bwd, bwd_mirrored, weight, bias, chunk_rows, method):
     """What subm_conv3d, sparse_conv3d and sparse_inverse_conv3d do once each has checked its owner's type and picked the forward and
     the backward view of it: numpy in and out, every check of the arguments (shapes first, then what the route refuses), the route,
     the chunk sizes of the gather route, and the call of that route's Function"""
-    features, was_numpy = _as_tensor(features, "features")
-    weight, _ = _as_tensor(weight, "weight")
-    _check_rows(features, owner, fwd.src_rows, _conv_dtype)
+    features, was_numpy = as_tensor(features, "features")
+    weight, _ = as_tensor(weight, "weight")
+    check_rows(features, "features", "voxel", "voxel features", FEATURE_CODES, owner, fwd.src_rows)
     if weight.dim() != 3 or weight.shape[0] != fwd.kernel_volume or weight.shape[1] != features.shape[1]:
         raise ValueError("weight must be [K, Cin, Cout] = [%d, %d, Cout], not %s" % (fwd.kernel_volume, features.shape[1], tuple(weight.shape)))
     if weight.dtype != features.dtype:
         raise ValueError("weight is %s, features %s" % (weight.dtype, features.dtype))
     cin, cout, size = weight.shape[1], weight.shape[2], features.element_size()
     if bias is not None:
-        bias, _ = _as_tensor(bias, "bias")
+        bias, _ = as_tensor(bias, "bias")
         if bias.dim() != 1 or bias.shape[0] != cout or bias.dtype != features.dtype:
             raise ValueError("bias must be [Cout] = [%d] in %s, the dtype of features" % (cout, features.dtype))
     if chunk_rows is not None:
@@ -390,7 +348,7 @@ def _conv_front(features, owner, fwd, bwd, bwd_mirrored, weight, bias, chunk_row
     else:
         out = TableConv.apply(features, fwd, bwd, bwd_mirrored, weight, bias, _chunk_rows(chunk_rows, fwd, cin, cout, size),
                               _chunk_rows(chunk_rows, bwd, cin, cout, size))
-    return out.detach().numpy() if was_numpy else out
+    return back_to_caller(out, was_numpy)
 
 
 def neighbor_gather(features, nbrs):
@@ -403,10 +361,10 @@ def neighbor_gather(features, nbrs):
     """
     if not isinstance(nbrs, VoxelNeighbors):
         raise TypeError("nbrs must be a VoxelNeighbors")
-    features, was_numpy = _as_tensor(features, "features")
-    _check_rows(features, nbrs, nbrs.num_voxels, _dtype_code)
+    features, was_numpy = as_tensor(features, "features")
+    check_rows(features, "features", "voxel", "voxel features", FLOAT_CODES, nbrs, nbrs.num_voxels)
     out = NeighborGather.apply(features, nbrs._view)
-    return out.numpy() if was_numpy else out
+    return back_to_caller(out, was_numpy)
 
 
 def subm_conv3d(features, nbrs, weight, bias=None, chunk_rows=None, method=None):
@@ -431,7 +389,7 @@ def subm_conv3d(features, nbrs, weight, bias=None, chunk_rows=None, method=None)
     """
     if not isinstance(nbrs, VoxelNeighbors):
         raise TypeError("nbrs must be a VoxelNeighbors")
-    return _conv_front(features, nbrs, nbrs._view, nbrs._view, True, weight, bias, chunk_rows, method)
+    return conv_front(features, nbrs, nbrs._view, nbrs._view, True, weight, bias, chunk_rows, method)
 
 
 __all__ = ["VoxelNeighbors", "neighbor_gather", "subm_conv3d", "NeighborGather", "TableConv", "FusedTableConv"]

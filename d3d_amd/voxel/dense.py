@@ -16,14 +16,14 @@ Out of scope: layouts other than channels-first (there is no channels-last outpu
 arbitrary dense tensor (there is no `from_dense` that finds nonzeros: voxel_from_dense reads at the sites of a map).
 """
 import ctypes
+from functools import partial
 
 import numpy as np
 import torch
-from torch.autograd.function import once_differentiable
 
 from .. import _lib
-from .conv import _MAX_VOXELS, _check_coords, _triple
-from .pool import _CODES, _as_tensor, _on
+from .._rows import FEATURE_CODES, ROW_MAX, TransposePair, as_tensor, back_to_caller, check_owner_device, device_of, dtype_code
+from ._coords import _check_coords, _triple
 
 _MAX_CELLS = 2 ** 39 - 1             # N * A * B * D: the launch numbers stretches of cells in 31 bits
 
@@ -69,13 +69,13 @@ class VoxelDenseMap:
         if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
             raise ValueError("batch_size must be an int >= 1, not %r" % (batch_size,))
         batch_size = int(batch_size)
-        if v > _MAX_VOXELS:
+        if v > ROW_MAX:
             raise ValueError("VoxelDenseMap takes at most 2^31 - 1 voxels")
         dense_shape = tuple(shape[a] for a in axes)
         cells = batch_size * shape[0] * shape[1] * shape[2]
         if cells > _MAX_CELLS:
             raise ValueError("VoxelDenseMap takes at most 2^39 - 1 cells (batch_size * A * B * D), not %d" % cells)
-        dev = coords.device if coords.is_cuda else _lib.require_gpu()
+        dev = device_of(coords)
         self.device, self.num_voxels, self.batch_size = dev, v, batch_size
         self.spatial_shape, self.dense_shape, self.origin, self.axes = shape, dense_shape, origin, axes
         self.cells_per_sample = cells // batch_size
@@ -101,12 +101,12 @@ class VoxelDenseMap:
         return (self.batch_size, c) + self.dense_shape
 
 
-def _scatter(feat, dmap, fill):
+def _scatter(feat, dmap, fill=0.0):
     """feat [V, C] on dmap.device -> [N, C, A, B, D]; one launch writes every element"""
     c = feat.shape[1]
     with torch.cuda.device(dmap.device):
         out = torch.empty(dmap.grid_shape(c), dtype=feat.dtype, device=dmap.device)
-        rc = _lib.load().d3d_vdense_scatter(_lib.ptr(feat), dmap.num_voxels, c, _CODES[feat.dtype], _lib.ptr(dmap.index), dmap.batch_size,
+        rc = _lib.load().d3d_vdense_scatter(_lib.ptr(feat), dmap.num_voxels, c, FEATURE_CODES[feat.dtype], _lib.ptr(dmap.index), dmap.batch_size,
                                             dmap.cells_per_sample, fill, _lib.ptr(out), _lib.stream_ptr())
     _lib.check(rc, "vdense_scatter")
     return out
@@ -117,37 +117,17 @@ def _gather(dense, dmap):
     c = dense.shape[1]
     with torch.cuda.device(dmap.device):
         out = torch.empty((dmap.num_voxels, c), dtype=dense.dtype, device=dmap.device)
-        rc = _lib.load().d3d_vdense_gather(_lib.ptr(dense), dmap.batch_size, c, _CODES[dense.dtype], _lib.ptr(dmap.index),
+        rc = _lib.load().d3d_vdense_gather(_lib.ptr(dense), dmap.batch_size, c, FEATURE_CODES[dense.dtype], _lib.ptr(dmap.index),
                                            dmap.cells_per_sample, dmap.num_voxels, _lib.ptr(out), _lib.stream_ptr())
     _lib.check(rc, "vdense_gather")
     return out
 
 
-class _Dense(torch.autograd.Function):
-    """(tensor, VoxelDenseMap, fill or None) -> _scatter (fill given) or _gather of it; backward is the other one, its fill 0.
-    Differentiable once, in the tensor only."""
-
-    @staticmethod
-    def forward(ctx, x, dmap, fill):
-        ctx.dmap, ctx.scatter, ctx.odev = dmap, fill is not None, x.device
-        x = x.detach().to(dmap.device).contiguous()
-        out = _gather(x, dmap) if fill is None else _scatter(x, dmap, fill)
-        return _lib.to_caller(out, ctx.odev, dmap.device)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad):
-        grad = grad.to(ctx.dmap.device).contiguous()
-        g = _gather(grad, ctx.dmap) if ctx.scatter else _scatter(grad, ctx.dmap, 0.0)
-        return _lib.to_caller(g, ctx.odev, ctx.dmap.device), None, None
-
-
 def _front(x, what, dmap, fill, scatter):
     if not isinstance(dmap, VoxelDenseMap):
         raise TypeError("dmap must be a VoxelDenseMap")
-    x, was_numpy = _as_tensor(x, what)
-    if x.dtype not in _CODES:
-        raise ValueError("%s must be float32, float64, float16 or bfloat16, not %s" % (what, x.dtype))
+    x, was_numpy = as_tensor(x, what)
+    dtype_code(x, FEATURE_CODES, what)                       # (the dtype first, then the fill, then the shape: this front's own order)
     if scatter:
         if isinstance(fill, bool) or not isinstance(fill, (int, float)):
             raise TypeError("fill_value must be a number, not %r" % (fill,))
@@ -159,9 +139,9 @@ def _front(x, what, dmap, fill, scatter):
     elif x.dim() != 5 or tuple(x.shape) != dmap.grid_shape(x.shape[1]):
         raise ValueError("%s has the shape %r where the VoxelDenseMap expects (%d, C, %d, %d, %d)"
                          % ((what, tuple(x.shape), dmap.batch_size) + dmap.dense_shape))
-    _on(dmap, x)
-    out = _Dense.apply(x, dmap, fill)
-    return out.detach().numpy() if was_numpy else out
+    check_owner_device(dmap, x)
+    ops = (partial(_scatter, fill=fill), _gather) if scatter else (_gather, _scatter)      # each the other's gradient, its fill 0
+    return back_to_caller(TransposePair.apply(x, dmap, *ops), was_numpy)
 
 
 def voxel_to_dense(features, dmap, fill_value=0):

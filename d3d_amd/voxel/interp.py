@@ -16,17 +16,50 @@ built once (`VoxelInterp.transpose()`), so the results are the same bits on ever
 csrc/vinterp.hip, include/d3d_hip.h).  Positions and weights get NO gradient.
 """
 import torch
-from torch.autograd.function import once_differentiable
 
 from .. import _lib
-from .conv import _MAX_VOXELS, _check_coords, _host_spans_fit
-from .pool import _CODES, VoxelIndex, _as_tensor, _on
+from .._rows import FEATURE_CODES, FLOAT_CODES, ROW_MAX, TransposePair, as_tensor, back_to_caller, check_rows, device_of
+from ._coords import _check_coords, _host_spans_fit
+from .pool import VoxelIndex
 
 _MODES = {"linear": 8, "nearest": 1}
-_POS_CODES = {torch.float32: _lib.F32, torch.float64: _lib.F64}
 
 
-class VoxelInterp:
+class WeightedTable:
+    """A table with weights, as table_fold reads it: `table` [num_points, width] int32 names rows of a source of `src_rows` feature
+    rows (-1: none), `weights` [num_points, width] float32 or float64 belong to its entries, both on `device`; `num_entries` is what
+    makes a fold worth a launch (0: the result is zero).  A subclass names the pair of C entries (interpolate, splat) that fold
+    through it in `_entries` and calls _set_table once its table is made: VoxelInterp here, d3d_amd.point.PointInterp."""
+
+    _entries = None
+
+    def _set_table(self, device, table, weights, src_rows, num_entries):
+        self.device, self.table, self.weights = device, table, weights
+        self.src_rows, self.num_points, self.width, self.num_entries = int(src_rows), table.shape[0], table.shape[1], num_entries
+        self._index = None
+        self._cast = {weights.dtype: weights}
+
+    def transpose(self):
+        """The inverted table: a VoxelIndex over the flattened table [num_points * width] taken as a mapping -- per source row the
+        entries that name it, in ascending entry number.  Built on the first call (VoxelIndex's one read-back) and kept: what a splat
+        and the gradient of an interpolation walk.  It holds `order` and `offsets` only: its `mapping` is None (the table is the
+        mapping)."""
+        if self._index is None:
+            with torch.cuda.device(self.device):
+                self._index = VoxelIndex(self.table.view(-1), self.src_rows, keep_mapping=False)
+        return self._index
+
+    def weights_as(self, dtype):
+        """the weights a fold in `dtype` multiplies by: float64 for float64 features, float32 otherwise.  Weights of the other width
+        are cast once -- ONE more rounding when fp64 positions meet narrower features -- and kept"""
+        want = torch.float64 if dtype == torch.float64 else torch.float32
+        w = self._cast.get(want)
+        if w is None:
+            w = self._cast[want] = self.weights.to(want)
+        return w
+
+
+class VoxelInterp(WeightedTable):
     """The corner table of one frame: for every position the rows of the voxels around it and their weights.
 
     :param coords: [V, 3] int64 (int32 is widened) voxel coordinates, any values; torch tensor (GPU or host) or numpy array.
@@ -45,20 +78,20 @@ class VoxelInterp:
     ValueError on duplicates and when the product of the coordinate (and batch) spans exceeds 2^62, as VoxelNeighbors.  Nothing here
     is differentiable: positions and weights get no gradient."""
 
-    _entries = ("d3d_table_interp_forward", "d3d_table_interp_backward")     # the pair of C entries _interp / _splat fold through
+    _entries = ("d3d_table_interp_forward", "d3d_table_interp_backward")
 
     def __init__(self, coords, positions, batch_index=None, position_batch=None, mode="linear", normalize=False):
         coords, batch_index, v = _check_coords(coords, batch_index)
-        positions, _ = _as_tensor(positions, "positions")
+        positions, _ = as_tensor(positions, "positions")
         if positions.dim() != 2 or positions.shape[1] != 3:
             raise ValueError("positions must be a [K, 3] tensor in voxel units")
-        if positions.dtype not in _POS_CODES:
+        if positions.dtype not in FLOAT_CODES:
             raise ValueError("positions must be float32 or float64, not %s" % positions.dtype)
         k = positions.shape[0]
         if (batch_index is None) != (position_batch is None):
             raise ValueError("position_batch is required exactly when batch_index is given")
         if position_batch is not None:
-            position_batch, _ = _as_tensor(position_batch, "position_batch")
+            position_batch, _ = as_tensor(position_batch, "position_batch")
             if position_batch.dim() != 1 or position_batch.shape[0] != k:
                 raise ValueError("position_batch must be a [K] tensor, one value per row of positions")
             if position_batch.dtype not in (torch.int64, torch.int32):
@@ -66,27 +99,27 @@ class VoxelInterp:
         if not isinstance(mode, str) or mode not in _MODES:
             raise ValueError("mode must be \"linear\" or \"nearest\", not %r" % (mode,))
         j = _MODES[mode]
-        if v > _MAX_VOXELS or k * j > _MAX_VOXELS:
+        if v > ROW_MAX or k * j > ROW_MAX:
             raise ValueError("VoxelInterp takes at most 2^31 - 1 voxels and table entries (points x corners)")
         overflow = "the spans of the coordinates (and batch values) multiply to more than 2^62"
         if v and not coords.is_cuda and not _host_spans_fit(coords, None if batch_index is None or batch_index.is_cuda else batch_index):
             raise ValueError(overflow)
-        dev = coords.device if coords.is_cuda else positions.device if positions.is_cuda else _lib.require_gpu()
-        self.device, self.num_voxels, self.num_points, self.num_corners, self.mode, self.normalize = dev, v, k, j, mode, bool(normalize)
+        dev = device_of(coords, positions)
+        self.num_voxels, self.num_corners, self.mode, self.normalize = v, j, mode, bool(normalize)
         coords = coords.to(device=dev, dtype=torch.int64).contiguous()
         positions = positions.detach().to(device=dev).contiguous()
         batch = None if batch_index is None else batch_index.to(device=dev, dtype=torch.int64).contiguous()
         pbatch = None if position_batch is None else position_batch.to(device=dev, dtype=torch.int64).contiguous()
         with torch.cuda.device(dev):
-            self.table = torch.empty((k, j), dtype=torch.int32, device=dev)
-            self.weights = torch.empty((k, j), dtype=positions.dtype, device=dev)
+            table = torch.empty((k, j), dtype=torch.int32, device=dev)
+            weights = torch.empty((k, j), dtype=positions.dtype, device=dev)
             entries = dups = over = 0
             if v or k:
                 lib = _lib.load()
                 counts = torch.empty((3,), dtype=torch.int64, device=dev)
                 ws = _lib.workspace(lib.d3d_voxel_corners_workspace_bytes(v), dev)
                 rc = lib.d3d_voxel_corners(_lib.ptr(coords), _lib.ptr(batch), v, _lib.ptr(positions), _lib.ptr(pbatch), k,
-                                           _POS_CODES[positions.dtype], j, int(self.normalize), _lib.ptr(self.table), _lib.ptr(self.weights),
+                                           FLOAT_CODES[positions.dtype], j, int(self.normalize), _lib.ptr(table), _lib.ptr(weights),
                                            _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
                 _lib.check(rc, "voxel_corners")
                 entries, dups, over = counts.tolist()            # the one read-back of a frame's table
@@ -94,88 +127,49 @@ class VoxelInterp:
             raise ValueError(overflow)
         if dups:
             raise ValueError("coords holds %d rows whose (batch, coordinate) an earlier row already has" % dups)
-        self.num_entries = entries
-        self._index = None
-        self._cast = {self.weights.dtype: self.weights}
-
-    def transpose(self):
-        """The inverted table: a VoxelIndex over the flattened table [K * J] taken as a mapping -- per voxel the entries that name it,
-        in ascending entry number.  Built on the first call (VoxelIndex's one read-back) and kept: what voxel_splat and the gradient of
-        voxel_interpolate walk.  It holds `order` and `offsets` only: its `mapping` is None (the table is the mapping)."""
-        if self._index is None:
-            with torch.cuda.device(self.device):
-                self._index = VoxelIndex(self.table.view(-1), self.num_voxels, keep_mapping=False)
-        return self._index
-
-    def weights_as(self, dtype):
-        """the weights a fold in `dtype` multiplies by: float64 for float64 features, float32 otherwise.  Weights of the other width
-        are cast once -- ONE more rounding when fp64 positions meet narrower features -- and kept"""
-        want = torch.float64 if dtype == torch.float64 else torch.float32
-        w = self._cast.get(want)
-        if w is None:
-            w = self._cast[want] = self.weights.to(want)
-        return w
+        self._set_table(dev, table, weights, v, entries)
 
 
 def _interp(feat, itp):
-    """feat [V, C] on itp.device -> [K, C]; one launch.  itp: a VoxelInterp, or any object with its fields and its own `_entries`
-    (d3d_amd.point.PointInterp)"""
+    """feat [src_rows, C] on itp.device -> [num_points, C]; one launch.  itp: a WeightedTable"""
     k, c = itp.num_points, feat.shape[1]
     with torch.cuda.device(itp.device):
         if k == 0 or c == 0 or itp.num_entries == 0:
             return feat.new_zeros((k, c))
         out = torch.empty((k, c), dtype=feat.dtype, device=itp.device)
-        rc = getattr(_lib.load(), itp._entries[0])(_lib.ptr(feat), itp.num_voxels, c, _CODES[feat.dtype], _lib.ptr(itp.table),
-                                                   _lib.ptr(itp.weights_as(feat.dtype)), k, itp.num_corners, _lib.ptr(out), _lib.stream_ptr())
+        rc = getattr(_lib.load(), itp._entries[0])(_lib.ptr(feat), itp.src_rows, c, FEATURE_CODES[feat.dtype], _lib.ptr(itp.table),
+                                                   _lib.ptr(itp.weights_as(feat.dtype)), k, itp.width, _lib.ptr(out), _lib.stream_ptr())
     _lib.check(rc, "table_interp")
     return out
 
 
 def _splat(rows, itp):
-    """rows [K, C] on itp.device -> [V, C] through the inverted table; one launch, every voxel row written once"""
-    v, c = itp.num_voxels, rows.shape[1]
+    """rows [num_points, C] on itp.device -> [src_rows, C] through the inverted table; one launch, every source row written once"""
+    v, c = itp.src_rows, rows.shape[1]
     with torch.cuda.device(itp.device):
         if v == 0 or c == 0 or itp.num_entries == 0:
             return rows.new_zeros((v, c))
         idx = itp.transpose()
         out = torch.empty((v, c), dtype=rows.dtype, device=itp.device)
-        rc = getattr(_lib.load(), itp._entries[1])(_lib.ptr(rows), itp.num_points, c, _CODES[rows.dtype], _lib.ptr(idx.order),
-                                                   _lib.ptr(idx.offsets), _lib.ptr(itp.weights_as(rows.dtype)), itp.num_corners, v,
+        rc = getattr(_lib.load(), itp._entries[1])(_lib.ptr(rows), itp.num_points, c, FEATURE_CODES[rows.dtype], _lib.ptr(idx.order),
+                                                   _lib.ptr(idx.offsets), _lib.ptr(itp.weights_as(rows.dtype)), itp.width, v,
                                                    _lib.ptr(out), _lib.stream_ptr())
     _lib.check(rc, "table_interp backward")
     return out
 
 
-class _Fold(torch.autograd.Function):
-    """(rows, VoxelInterp, splat?) -> _splat or _interp of them; backward is the other one.  Differentiable once, in the rows only."""
-
-    @staticmethod
-    def forward(ctx, rows, itp, splat):
-        ctx.itp, ctx.splat, ctx.odev = itp, splat, rows.device
-        out = (_splat if splat else _interp)(rows.detach().to(itp.device).contiguous(), itp)
-        return _lib.to_caller(out, ctx.odev, itp.device)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad):
-        g = (_interp if ctx.splat else _splat)(grad.to(ctx.itp.device).contiguous(), ctx.itp)
-        return _lib.to_caller(g, ctx.odev, ctx.itp.device), None, None
+def table_fold(rows, itp, splat=False):
+    """The interpolation of source rows [src_rows, C] through a WeightedTable -> [num_points, C], or with `splat` its transpose, the
+    splat of point rows; each is the other's gradient.  Rows as a tensor anywhere, already checked; differentiable once, in the rows."""
+    return TransposePair.apply(rows, itp, *((_splat, _interp) if splat else (_interp, _splat)))
 
 
 def _front(rows, what, itp, splat):
     if not isinstance(itp, VoxelInterp):
         raise TypeError("interp must be a VoxelInterp")
-    want_rows = itp.num_points if splat else itp.num_voxels
-    rows, was_numpy = _as_tensor(rows, what)
-    if rows.dim() != 2:
-        raise ValueError("%s must be a 2-D tensor of one row per %s" % (what, "point" if splat else "voxel"))
-    if rows.dtype not in _CODES:
-        raise ValueError("%s must be float32, float64, float16 or bfloat16, not %s" % (what, rows.dtype))
-    if rows.shape[0] != want_rows:
-        raise ValueError("%s has %d rows where the VoxelInterp expects %d" % (what, rows.shape[0], want_rows))
-    _on(itp, rows)
-    out = _Fold.apply(rows, itp, splat)
-    return out.detach().numpy() if was_numpy else out
+    rows, was_numpy = as_tensor(rows, what)
+    check_rows(rows, what, "point" if splat else "voxel", what, FEATURE_CODES, itp, itp.num_points if splat else itp.num_voxels)
+    return back_to_caller(table_fold(rows, itp, splat), was_numpy)
 
 
 def voxel_interpolate(voxel_features, interp):
@@ -216,17 +210,17 @@ def voxel_positions(points, voxel_size, voxel_offset=0, dtype=None):
     :param voxel_offset: a number or three, in cells (VoxelGenerator's `_offset`)
     :param dtype: the dtype of the result (default: that of points); float64 keeps positions of large grids exact to more digits
     """
-    points, was_numpy = _as_tensor(points, "points")
+    points, was_numpy = as_tensor(points, "points")
     if points.dim() != 2 or points.shape[1] < 3:
         raise ValueError("points must be a [K, >= 3] tensor")
     dtype = points.dtype if dtype is None else dtype
-    if dtype not in _POS_CODES:
+    if dtype not in FLOAT_CODES:
         raise ValueError("positions are float32 or float64, not %s" % (dtype,))
     xyz = points[:, :3].to(dtype)
     size = torch.as_tensor(voxel_size, dtype=dtype, device=xyz.device)
     off = torch.as_tensor(voxel_offset, dtype=dtype, device=xyz.device)
     out = xyz / size - off - 0.5
-    return out.numpy() if was_numpy else out
+    return back_to_caller(out, was_numpy)
 
 
 __all__ = ["VoxelInterp", "voxel_interpolate", "voxel_splat", "voxel_positions"]

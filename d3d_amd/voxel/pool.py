@@ -10,36 +10,18 @@ An extension (the reference reduces the raw input columns inside its voxelizer o
 No float atomics: the index groups the points by voxel (stable, in point order) and the kernels fold a voxel's rows strictly in
 that order, so the results are the same bits on every run (kernels and the exact rules: csrc/vpool.hip, include/d3d_hip.h).
 """
-import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
+from .._rows import FLOAT_CODES, ROW_MAX, as_tensor, back_to_caller, check_owner_device, check_rows, device_of, dtype_code, on_owner
 
-_REDUCTIONS = {"sum": _lib.REDUCE_SUM, "mean": _lib.REDUCE_MEAN, "max": _lib.REDUCE_MAX, "min": _lib.REDUCE_MIN}
-_EXTREME = (_lib.REDUCE_MAX, _lib.REDUCE_MIN)
-_CODES = {torch.float32: _lib.F32, torch.float64: _lib.F64, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}   # (half: sparse_pool)
-_MAX_POINTS = 2 ** 31 - 1
-
-
-def _as_tensor(x, what):
-    if isinstance(x, np.ndarray):
-        return torch.from_numpy(x), True
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("%s must be a torch.Tensor or numpy array" % what)
-    return x, False
-
-
-def _on(owner, t):
-    """a tensor already on a GPU must be on the one its owner (a VoxelIndex, VoxelNeighbors or SparseConvMap) was built on"""
-    if t.is_cuda and t.device != owner.device:
-        raise ValueError("features live on %s, the %s on %s" % (t.device, type(owner).__name__, owner.device))
+REDUCTIONS = {"sum": _lib.REDUCE_SUM, "mean": _lib.REDUCE_MEAN, "max": _lib.REDUCE_MAX, "min": _lib.REDUCE_MIN}     # (sparse_pool's too)
+EXTREME = (_lib.REDUCE_MAX, _lib.REDUCE_MIN)
 
 
 def _dtype_code(t):
-    if t.dtype not in (torch.float32, torch.float64):
-        raise ValueError("voxel features must be float32 or float64, not %s" % t.dtype)
-    return _CODES[t.dtype]
+    return dtype_code(t, FLOAT_CODES, "voxel features")
 
 
 class VoxelIndex:
@@ -57,7 +39,7 @@ class VoxelIndex:
     ids outside [-1, V): ValueError if that is not 0); no pooling call reads anything back."""
 
     def __init__(self, mapping, num_voxels, keep_mapping=True):
-        mapping, _ = _as_tensor(mapping, "mapping")
+        mapping, _ = as_tensor(mapping, "mapping")
         if mapping.dim() != 1:
             raise ValueError("mapping must be a [K] tensor of voxel ids")
         if mapping.dtype not in (torch.int64, torch.int32):
@@ -65,9 +47,9 @@ class VoxelIndex:
         v, k = int(num_voxels), mapping.shape[0]
         if v < 0:
             raise ValueError("num_voxels must not be negative")
-        if k > _MAX_POINTS or v > _MAX_POINTS:
+        if k > ROW_MAX or v > ROW_MAX:
             raise ValueError("voxel_pool takes at most 2^31 - 1 points and voxels")
-        dev = mapping.device if mapping.is_cuda else _lib.require_gpu()
+        dev = device_of(mapping)
         self.device, self.num_voxels, self.num_points = dev, v, k
         self.mapping = mapping.to(device=dev, dtype=torch.int64).contiguous()
         with torch.cuda.device(dev):
@@ -105,7 +87,7 @@ def _index_of(index_or_mapping, num_voxels):
 
 def _beside(mapping, features):
     """a bare mapping goes to the GPU the features live on (host features: the current device, as everywhere)"""
-    mapping, _ = _as_tensor(mapping, "mapping")
+    mapping, _ = as_tensor(mapping, "mapping")
     return mapping.to(features.device) if features.is_cuda else mapping
 
 
@@ -146,20 +128,18 @@ class VoxelPool(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, features, idx, red):
-        odev = features.device
         need = ctx.needs_input_grad[0]
-        out, arg = _forward(features.detach().to(idx.device).contiguous(), idx, red, need and red in _EXTREME)
+        out, arg = on_owner(_forward, features, idx, features.device, red, need and red in EXTREME)
         if need:
-            ctx.idx, ctx.red, ctx.odev = idx, red, odev
+            ctx.idx, ctx.red, ctx.odev = idx, red, features.device
             ctx.save_for_backward(*([arg] if arg is not None else []))
-        return _lib.to_caller(out, odev, idx.device)
+        return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad):
         arg = ctx.saved_tensors[0] if ctx.saved_tensors else None
-        g = _backward(grad.to(ctx.idx.device).contiguous(), ctx.idx, ctx.red, arg)
-        return _lib.to_caller(g, ctx.odev, ctx.idx.device), None, None
+        return on_owner(_backward, grad, ctx.idx, ctx.odev, ctx.red, arg), None, None
 
 
 class VoxelUnpool(torch.autograd.Function):
@@ -168,22 +148,13 @@ class VoxelUnpool(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, voxel_features, idx):
-        odev = voxel_features.device
-        ctx.idx, ctx.odev = idx, odev
-        out = _backward(voxel_features.detach().to(idx.device).contiguous(), idx, _lib.REDUCE_SUM, None)
-        return _lib.to_caller(out, odev, idx.device)
+        ctx.idx, ctx.odev = idx, voxel_features.device
+        return on_owner(_backward, voxel_features, idx, ctx.odev, _lib.REDUCE_SUM, None)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad):
-        g, _ = _forward(grad.to(ctx.idx.device).contiguous(), ctx.idx, _lib.REDUCE_SUM, False)
-        return _lib.to_caller(g, ctx.odev, ctx.idx.device), None
-
-
-def _check_features(t, what):
-    if t.dim() != 2:
-        raise ValueError("%s must be a 2-D tensor of one row per %s" % (what, "voxel" if "voxel" in what else "point"))
-    _dtype_code(t)
+        return on_owner(_forward, grad, ctx.idx, ctx.odev, _lib.REDUCE_SUM, False)[0], None
 
 
 def voxel_pool(features, index_or_mapping, num_voxels=None, reduction="max"):
@@ -197,20 +168,20 @@ def voxel_pool(features, index_or_mapping, num_voxels=None, reduction="max"):
         index, in the dtype (np.add.at's bits); mean: that sum / count; max / min: the first strict winner in point order, NaN
         propagates (the first one wins); a voxel without points gives 0
     """
-    if not isinstance(reduction, str) or reduction.lower() not in _REDUCTIONS:
+    if not isinstance(reduction, str) or reduction.lower() not in REDUCTIONS:
         raise ValueError("Unsupported reduction %r in voxel_pool: sum, mean, max or min" % (reduction,))
-    red = _REDUCTIONS[reduction.lower()]
-    features, was_numpy = _as_tensor(features, "features")
-    _check_features(features, "features")
+    red = REDUCTIONS[reduction.lower()]
+    features, was_numpy = as_tensor(features, "features")
+    check_rows(features, "features", "point", "voxel features", FLOAT_CODES)
     mapping, idx = _index_of(index_or_mapping, num_voxels)
     k = idx.num_points if idx is not None else len(mapping)
     if features.shape[0] != k:
         raise ValueError("features has %d rows, the mapping %d points" % (features.shape[0], k))
     if idx is None:
         idx = VoxelIndex(_beside(mapping, features), num_voxels)
-    _on(idx, features)
+    check_owner_device(idx, features)
     out = VoxelPool.apply(features, idx, red)
-    return out.numpy() if was_numpy else out
+    return back_to_caller(out, was_numpy)
 
 
 def voxel_unpool(voxel_features, index_or_mapping, num_voxels=None):
@@ -220,16 +191,16 @@ def voxel_unpool(voxel_features, index_or_mapping, num_voxels=None):
     :param index_or_mapping: a VoxelIndex, or the [K] mapping itself
     :return: [K, C] on the caller's device
     """
-    voxel_features, was_numpy = _as_tensor(voxel_features, "voxel_features")
-    _check_features(voxel_features, "voxel_features")
+    voxel_features, was_numpy = as_tensor(voxel_features, "voxel_features")
+    check_rows(voxel_features, "voxel_features", "voxel", "voxel features", FLOAT_CODES)
     mapping, idx = _index_of(index_or_mapping, voxel_features.shape[0] if num_voxels is None else num_voxels)
     if idx is None:
         idx = VoxelIndex(_beside(mapping, voxel_features), voxel_features.shape[0])
     if voxel_features.shape[0] != idx.num_voxels:
         raise ValueError("voxel_features has %d rows, the index %d voxels" % (voxel_features.shape[0], idx.num_voxels))
-    _on(idx, voxel_features)
+    check_owner_device(idx, voxel_features)
     out = VoxelUnpool.apply(voxel_features, idx)
-    return out.numpy() if was_numpy else out
+    return back_to_caller(out, was_numpy)
 
 
 __all__ = ["VoxelIndex", "voxel_pool", "voxel_unpool", "VoxelPool", "VoxelUnpool"]

@@ -13,7 +13,7 @@ of them and GEMMs: nothing is scattered, no float atomics of the library's own (
 include/d3d_hip.h; the gather is csrc/vnbr.hip's, the GEMMs are torch's).  method="fused" -- the only route of fp16 and bf16 -- runs
 all of it on the MFMA kernels of csrc/vconv.hip instead, without the gathered buffer (see conv.subm_conv3d).
 
-This module builds the map and its two views; the convolution through them is conv.py's (_conv_front, TableConv, FusedTableConv):
+This module builds the map and its two views; the convolution through them is conv.py's (conv_front, TableConv, FusedTableConv):
 sparse_conv3d reads `_down` and goes back through `_up`, sparse_inverse_conv3d the other way round.
 """
 import ctypes
@@ -22,9 +22,10 @@ from math import gcd
 import torch
 
 from .. import _lib
-from .conv import _TableView, _check_coords, _conv_front, _triple
+from .._rows import ROW_MAX, device_of
+from ._coords import _check_coords, _triple
+from .conv import TableView, conv_front
 
-_MAX_ROWS = 2 ** 31 - 1
 _MAX_STEP = 2 ** 24
 _OVERFLOW = "the spans of the output box (and batch values) multiply to more than 2^62"
 
@@ -85,13 +86,13 @@ class SparseConvMap:
             if isinstance(spatial_shape, (int, float)):
                 raise ValueError("spatial_shape must be three ints, not %r" % (spatial_shape,))
             shape = _triple(spatial_shape, "spatial_shape")
-            if any(s < 1 or s > _MAX_ROWS for s in shape):
+            if any(s < 1 or s > ROW_MAX for s in shape):
                 raise ValueError("spatial_shape must be in 1 .. 2^31 - 1 per axis, not %r" % (spatial_shape,))
             if any(s + 2 * p - d * (k - 1) - 1 < 0 for s, p, d, k in zip(shape, pad, dil, ks)):
                 raise ValueError("a dense convolution of a %r grid with this kernel has no output" % (shape,))
-        if v * _fanout(ks, st, dil) > _MAX_ROWS:
+        if v * _fanout(ks, st, dil) > ROW_MAX:
             raise ValueError("SparseConvMap takes at most 2^31 - 1 candidates V * P (P = %d here)" % _fanout(ks, st, dil))
-        dev = coords.device if coords.is_cuda else _lib.require_gpu()
+        dev = device_of(coords)
         k = ks[0] * ks[1] * ks[2]
         self.device, self.num_voxels, self.kernel_volume = dev, v, k
         self.kernel_size, self.stride, self.padding, self.dilation, self.spatial_shape = ks, st, pad, dil, shape
@@ -124,8 +125,8 @@ class SparseConvMap:
         if dups:
             raise ValueError("coords holds rows whose (batch, coordinate) another row already has (%d contested table entries)" % dups)
         self.num_out, self.num_entries = vout, entries
-        self._down = _TableView(self.table_out, v, k, dev)               # output rows read input rows
-        self._up = _TableView(self.table_in, vout, k, dev)               # input rows read output rows
+        self._down = TableView(self.table_out, v, k, dev)               # output rows read input rows
+        self._up = TableView(self.table_in, vout, k, dev)               # input rows read output rows
 
 
 def sparse_conv3d(features, cmap, weight, bias=None, chunk_rows=None, method=None):
@@ -147,7 +148,7 @@ def sparse_conv3d(features, cmap, weight, bias=None, chunk_rows=None, method=Non
     """
     if not isinstance(cmap, SparseConvMap):
         raise TypeError("cmap must be a SparseConvMap")
-    return _conv_front(features, cmap, cmap._down, cmap._up, False, weight, bias, chunk_rows, method)
+    return conv_front(features, cmap, cmap._down, cmap._up, False, weight, bias, chunk_rows, method)
 
 
 def sparse_inverse_conv3d(features, cmap, weight, bias=None, chunk_rows=None, method=None):
@@ -165,7 +166,7 @@ def sparse_inverse_conv3d(features, cmap, weight, bias=None, chunk_rows=None, me
     """
     if not isinstance(cmap, SparseConvMap):
         raise TypeError("cmap must be a SparseConvMap")
-    return _conv_front(features, cmap, cmap._up, cmap._down, False, weight, bias, chunk_rows, method)
+    return conv_front(features, cmap, cmap._up, cmap._down, False, weight, bias, chunk_rows, method)
 
 
 __all__ = ["SparseConvMap", "sparse_conv3d", "sparse_inverse_conv3d"]

@@ -15,8 +15,9 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
+from .._rows import FEATURE_CODES, as_tensor, back_to_caller, check_rows, on_owner
 from .conv import VoxelNeighbors
-from .pool import _CODES, _EXTREME, _REDUCTIONS, _as_tensor, _on
+from .pool import EXTREME, REDUCTIONS
 from .sparse_conv import SparseConvMap
 
 
@@ -28,7 +29,7 @@ def _pool_forward(feat, view, red, need_arg, need_count):
         arg = torch.empty((rows, c), dtype=torch.int16, device=view.device) if need_arg else None
         count = torch.empty((rows,), dtype=torch.int32, device=view.device) if need_count else None
         if rows and c:
-            rc = _lib.load().d3d_table_pool_forward(_lib.ptr(feat), view.src_rows, c, _CODES[feat.dtype], _lib.ptr(view.table), rows,
+            rc = _lib.load().d3d_table_pool_forward(_lib.ptr(feat), view.src_rows, c, FEATURE_CODES[feat.dtype], _lib.ptr(view.table), rows,
                                                     view.kernel_volume, red, _lib.ptr(out), _lib.ptr(arg), _lib.ptr(count), _lib.stream_ptr())
             _lib.check(rc, "table_pool")
     return out, arg, count
@@ -41,7 +42,7 @@ def _pool_backward(grad, view, mirrored, red, arg, count):
         if rows == 0 or c == 0 or view.src_rows == 0:
             return grad.new_zeros((rows, c))
         out = torch.empty((rows, c), dtype=grad.dtype, device=view.device)
-        rc = _lib.load().d3d_table_pool_backward(_lib.ptr(grad), view.src_rows, c, _CODES[grad.dtype], _lib.ptr(view.table), rows,
+        rc = _lib.load().d3d_table_pool_backward(_lib.ptr(grad), view.src_rows, c, FEATURE_CODES[grad.dtype], _lib.ptr(view.table), rows,
                                                  view.kernel_volume, int(mirrored), red, _lib.ptr(arg), _lib.ptr(count), _lib.ptr(out),
                                                  _lib.stream_ptr())
     _lib.check(rc, "table_pool backward")
@@ -56,20 +57,19 @@ class TablePool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, features, fwd, bwd, bwd_mirrored, red):
         need = ctx.needs_input_grad[0]
-        out, arg, count = _pool_forward(features.detach().to(fwd.device).contiguous(), fwd, red, need and red in _EXTREME,
-                                        need and red == _lib.REDUCE_MEAN)
+        out, arg, count = on_owner(_pool_forward, features, fwd, features.device, red, need and red in EXTREME,
+                                   need and red == _lib.REDUCE_MEAN)
         if need:
             ctx.bwd, ctx.bwd_mirrored, ctx.red, ctx.odev = bwd, bwd_mirrored, red, features.device
             ctx.save_for_backward(*[t for t in (arg, count) if t is not None])
-        return _lib.to_caller(out, features.device, fwd.device)
+        return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad):
         saved = ctx.saved_tensors[0] if ctx.saved_tensors else None
-        arg, count = (saved, None) if ctx.red in _EXTREME else (None, saved)
-        g = _pool_backward(grad.to(ctx.bwd.device).contiguous(), ctx.bwd, ctx.bwd_mirrored, ctx.red, arg, count)
-        return _lib.to_caller(g, ctx.odev, ctx.bwd.device), None, None, None, None
+        arg, count = (saved, None) if ctx.red in EXTREME else (None, saved)
+        return on_owner(_pool_backward, grad, ctx.bwd, ctx.odev, ctx.bwd_mirrored, ctx.red, arg, count), None, None, None, None
 
 
 def sparse_pool3d(features, where, reduction="max"):
@@ -93,18 +93,12 @@ def sparse_pool3d(features, where, reduction="max"):
         fwd, bwd, mirrored = where._view, where._view, True
     else:
         raise TypeError("where must be a SparseConvMap or a VoxelNeighbors")
-    if not isinstance(reduction, str) or reduction.lower() not in _REDUCTIONS:
+    if not isinstance(reduction, str) or reduction.lower() not in REDUCTIONS:
         raise ValueError("Unsupported reduction %r in sparse_pool3d: sum, mean, max or min" % (reduction,))
-    features, was_numpy = _as_tensor(features, "features")
-    if features.dim() != 2:
-        raise ValueError("features must be a 2-D tensor of one row per voxel")
-    if features.dtype not in _CODES:
-        raise ValueError("voxel features must be float32, float64, float16 or bfloat16, not %s" % features.dtype)
-    if features.shape[0] != fwd.src_rows:
-        raise ValueError("features has %d rows where the %s expects %d" % (features.shape[0], type(where).__name__, fwd.src_rows))
-    _on(where, features)
-    out = TablePool.apply(features, fwd, bwd, mirrored, _REDUCTIONS[reduction.lower()])
-    return out.detach().numpy() if was_numpy else out
+    features, was_numpy = as_tensor(features, "features")
+    check_rows(features, "features", "voxel", "voxel features", FEATURE_CODES, where, fwd.src_rows)
+    out = TablePool.apply(features, fwd, bwd, mirrored, REDUCTIONS[reduction.lower()])
+    return back_to_caller(out, was_numpy)
 
 
 def sparse_max_pool3d(features, where):

@@ -274,7 +274,7 @@ def test_width_8_gives_the_bits_of_the_fixed_width_entries(dtype):
     table = cuda(random_table(rng, rows, j, v))
     w = cuda(rng.uniform(0.0, 1.0, (rows, j)).astype(acc_dtype(dtype)))
     from d3d_amd.voxel import VoxelIndex
-    from d3d_amd.voxel.pool import _CODES
+    from d3d_amd._rows import FEATURE_CODES as _CODES
     idx = VoxelIndex(table.view(-1), v, keep_mapping=False)
     for c in (5, 16):
         feat = torch.from_numpy(rng.normal(size=(v, c))).to(dtype).cuda()

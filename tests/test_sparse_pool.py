@@ -184,7 +184,7 @@ def test_large_kernel_scene_has_a_winner_beyond_column_255():
 
 def _fake_neighbors(v=6, k=27):
     """a VoxelNeighbors that was never built (building one needs a GPU): what the argument checks read of it"""
-    from d3d_amd.voxel.conv import VoxelNeighbors, _TableView
+    from d3d_amd.voxel.conv import TableView as _TableView, VoxelNeighbors
     nb = VoxelNeighbors.__new__(VoxelNeighbors)
     nb.device, nb.num_voxels, nb.kernel_volume = torch.device("cuda", 0), v, k
     nb._view = _TableView(torch.zeros((v, k), dtype=torch.int32), v, k, nb.device)
