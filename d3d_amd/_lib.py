@@ -8,6 +8,7 @@ import threading
 import time
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -305,6 +306,39 @@ def to_caller(results, odev, dev):
             torch.cuda.current_stream(dev).synchronize()
         out = tuple(out)
     return out[0] if single else out
+
+
+_TORCH_DTYPES = {np.dtype(name): getattr(torch, name)
+                 for name in ("bool", "uint8", "int8", "int16", "int32", "int64", "float16", "float32", "float64")}
+
+
+_PAD = np.zeros((8,), np.uint8)
+
+
+def ship(dev, *arrays):
+    """Several small host arrays (numpy: any dtype torch knows, any shape, empty ones too) to the GPU `dev` in ONE copy -> one device
+    tensor per array, with the array's dtype and shape.  Every piece starts at a multiple of 8 bytes of the one buffer, so each view
+    is aligned for its dtype whatever stands in front of it."""
+    arrays = [np.ascontiguousarray(a) for a in arrays]
+    parts, starts, total = [], [], 0
+    for a in arrays:
+        starts.append(total)
+        parts.append(a.reshape(-1).view(np.uint8))
+        pad = -a.nbytes & 7
+        if pad:
+            parts.append(_PAD[:pad])
+        total += a.nbytes + pad
+    buf = torch.from_numpy(np.concatenate(parts) if parts else np.zeros((0,), np.uint8)).to(dev)
+    typed, views = {}, []               # the buffer seen as each dtype once (its length is a multiple of 8), then one slice per piece
+    for a, s in zip(arrays, starts):
+        dtype = _TORCH_DTYPES[a.dtype]
+        whole = typed.get(dtype)
+        if whole is None:
+            whole = typed[dtype] = buf.view(dtype)
+        first = s // a.itemsize
+        view = whole[first:first + a.size]
+        views.append(view if a.ndim == 1 else view.view(a.shape))
+    return tuple(views)
 
 
 class HostWord:

@@ -24,10 +24,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._rows import device_of
+from ._rows import back_to_caller, device_of
 
 
 def _ingress(boxes, cloud):
+    # (not _rows.as_tensor: what is neither array nor tensor goes on to the shape checks and fails there, as it always has)
     convert = isinstance(cloud, np.ndarray)
     bx = torch.from_numpy(boxes) if isinstance(boxes, np.ndarray) else boxes
     pts = torch.from_numpy(cloud) if isinstance(cloud, np.ndarray) else cloud
@@ -52,10 +53,7 @@ def crop_points(boxes, cloud):
         rc = lib.d3d_crop_3dr(_lib.ptr(pts), n, pts.shape[1], _lib.ptr(bx), m, bx.shape[1], 0 if bx.shape[1] == 7 else 2,
                               _lib.ptr(out), _lib.stream_ptr())
     _lib.check(rc, "crop_3dr")
-    out = out.view(torch.bool)
-    if odev != dev:
-        out = out.to(odev)
-    return out.numpy() if convert else out
+    return _egress(out.view(torch.bool), odev, dev, convert, False)
 
 
 def paint_label(boxes, cloud, semantics, labels=None):
@@ -140,7 +138,7 @@ def _ingress_points(points):
     convert = isinstance(points, np.ndarray)
     if convert and any(st < 0 for st in points.strides):
         points = np.ascontiguousarray(points)
-    pts = torch.from_numpy(points) if convert else points
+    pts = torch.from_numpy(points) if convert else points      # (not _rows.as_tensor: no tensor is this front's ValueError below)
     if not torch.is_tensor(pts) or pts.dim() != 2 or pts.shape[1] < 3:
         raise ValueError("points should be [N,>=3] (x, y, z first)")
     odev = pts.device
@@ -152,11 +150,9 @@ def _ingress_points(points):
 
 def _egress(t, odev, dev, convert, sliced):
     """a result on the caller's side; `sliced`: t is the head of an upper-bound buffer, which a copy lets go"""
-    if convert:
-        return t.cpu().numpy()
-    if odev != dev:
-        return t.to(odev)
-    return t.clone() if sliced else t
+    if sliced and odev == dev:      # (this front's own: _lib.to_caller copies nothing for a caller on the GPU itself)
+        t = t.clone()
+    return back_to_caller(_lib.to_caller(t, odev, dev), convert)
 
 
 class TransformSet:

@@ -39,17 +39,76 @@ cuda_available = True   # box/impl.cpp:9-13: this build always has its device pa
 # (per-call options -- flags=, poison= -- or the calling context's: d3d_amd.options)
 
 
-def _dtype_code(t):
+def _dtype_code(t, wide32=False):
+    """the library's code of t's dtype; wide32 (`_wide32`): D3D_F32_WIDE for the fp32 tensors it stands for"""
     if t.dtype == torch.float64:
         return _lib.F64
     if t.dtype == torch.float32:
-        return _lib.F32
+        return _lib.F32_WIDE if wide32 else _lib.F32
     raise RuntimeError("boxes must be float32 or float64")   # AT_DISPATCH_FLOATING_TYPES (iou.cpp:132)
 
 
-def _to_device(*ts):
-    dev = device_of(*ts)
-    return [t.to(dev).contiguous() for t in ts], dev
+class _Staged:
+    """The frame of every call into the library: `with _Staged(x, y) as call:` has the inputs contiguous on one GPU in `call.inputs`
+    -- `call.dev`: that of the first CUDA tensor among them, else the current GPU -- and that GPU current inside the block;
+    `call.back(results)` brings a tensor, tuple or dict of results to the device the first input came from (`_lib.to_caller`)."""
+    __slots__ = ("odev", "dev", "inputs", "_previous")
+
+    def __init__(self, *ts):
+        self.odev = ts[0].device
+        self.dev = dev = device_of(*ts)
+        self.inputs = [t.to(dev).contiguous() for t in ts]
+
+    def __enter__(self):        # (the two calls `with torch.cuda.device(dev)` makes, without building that object per call)
+        self._previous = torch.cuda._exchange_device(self.dev.index)
+        return self
+
+    def __exit__(self, *exc):
+        torch.cuda._maybe_exchange_device(self._previous)
+        return False
+
+    def back(self, results):
+        return _lib.to_caller(results, self.odev, self.dev)
+
+
+_NX2 = "Input of rbox_2d_iou should be Nx2 tensors!"       # (sic: reference box/__init__.py:206-207)
+_FIELDS = {5: "Input boxes should have 5 fields: x, y, w, h, r", 7: "Input boxes should have 7 fields: x, y, z, lx, ly, lz, rz"}
+
+
+def _check_fields(cols, *boxes, flat=None):
+    """every tensor of `boxes` is [*, cols]: ValueError with the reference's message for that width (box/__init__.py:208-209).  A
+    tensor that is not 2-D answers with `flat` first where the front has such a message of its own, else with the width's."""
+    for b in boxes:
+        if len(b.shape) != 2:
+            raise ValueError(flat or _FIELDS[cols])
+    for b in boxes:
+        if b.shape[1] != cols:
+            raise ValueError(_FIELDS[cols])
+
+
+def _wide32(precise, a, b):
+    """precise on two fp32 tensors: they go in as they are and the kernels widen them where they load them -- fp64 arithmetic
+    without .double() copies; `_dtype_code(a, True)` is the code for it (D3D_F32_WIDE)"""
+    return precise and a.dtype == torch.float32 and b.dtype == torch.float32
+
+
+def _promote(precise, a, b):
+    """The `precise` rule of box2d_iou (reference box/__init__.py:204-205, 224) for the two tensors of a front -> (a, b, wide32):
+    fp32 pairs as they are (`_wide32`), anything else as .double() copies; the result is cast back to the dtype that came in."""
+    wide32 = _wide32(precise, a, b)
+    if precise and not wide32:
+        a, b = a.double(), b.double()
+    return a, b, wide32
+
+
+def _mixed_code(boxes, iou_type, matrix32, wide32):
+    """the dtype code d3d_iou2d_forward / _backward take: the boxes' own, or a mixed form for the box / rbox methods"""
+    code = _dtype_code(boxes)
+    if matrix32 or wide32:
+        if code != (_lib.F32 if wide32 else _lib.F64) or int(iou_type) not in (IouType.BOX, IouType.RBOX):
+            raise ValueError("matrix32 takes fp64 boxes, wide32 fp32 boxes, both the box / rbox methods")
+        code = _lib.F32_WIDE if wide32 else _lib.F64_M32
+    return code
 
 
 _MAX_ROWS = 65535 * 64      # rows of boxes1 per d3d_iou2d_forward launch (grid.y limit x 64-row tiles)
@@ -59,21 +118,16 @@ def _iou_forward(boxes1, boxes2, iou_type, flags=None, matrix32=False, wide32=Fa
     """matrix32 (fp64 boxes, BOX / RBOX): the arithmetic in fp64, `ious` stored as fp32 (D3D_F64_M32);
     wide32 (fp32 boxes, BOX / RBOX): the same with the boxes widened where the kernels load them (D3D_F32_WIDE)"""
     lib = _lib.load()
-    odev = boxes1.device
     if boxes1.dtype != boxes2.dtype:
         raise RuntimeError("boxes1 and boxes2 must have the same dtype")
-    (b1, b2), dev = _to_device(boxes1, boxes2)
-    n, m = b1.shape[0], b2.shape[0]
     fl = options.current().iou_flags if flags is None else int(flags)
-    with torch.cuda.device(dev):
+    with _Staged(boxes1, boxes2) as call:
+        (b1, b2), dev = call.inputs, call.dev
+        n, m = b1.shape[0], b2.shape[0]
         ious = torch.empty((n, m), dtype=torch.float32 if matrix32 else b1.dtype, device=dev)
         if options.current().poison:
             ious.fill_(float("nan"))
-        code = _dtype_code(b1)
-        if matrix32 or wide32:
-            if code != (_lib.F32 if wide32 else _lib.F64) or int(iou_type) not in (IouType.BOX, IouType.RBOX):
-                raise ValueError("matrix32 takes fp64 boxes, wide32 fp32 boxes, both the box / rbox methods")
-            code = _lib.F32_WIDE if wide32 else _lib.F64_M32
+        code = _mixed_code(b1, iou_type, matrix32, wide32)
         # one launch covers 65535 tiles of 64 rows; taller inputs go in row blocks into the same output
         for r0 in range(0, max(n, 1), _MAX_ROWS):
             r1 = min(n, r0 + _MAX_ROWS)
@@ -81,7 +135,7 @@ def _iou_forward(boxes1, boxes2, iou_type, flags=None, matrix32=False, wide32=Fa
             rc = lib.d3d_iou2d_forward(_lib.ptr(b1[r0:r1]), r1 - r0, _lib.ptr(b2), m, int(iou_type), code, _lib.ptr(ious[r0:r1]),
                                        _lib.ptr(ws), ws.numel() if ws is not None else 0, _lib.stream_ptr(), fl)
             _lib.check(rc, "iou2d_forward")
-    return _lib.to_caller(ious, odev, dev)
+    return call.back(ious)
 
 
 def iou2d_forward(boxes1, boxes2):
@@ -109,46 +163,37 @@ def iou2dr_flags(boxes1, boxes2, which=("nx", "xflags")):
     """the autograd bookkeeping of the rotated IoU family (include/d3d_hip.h: d3d_iou2dr_flags) -> dict of uint8 tensors:
     nx[N,M], xflags[N,M,8] (iou.cpp:125-141), nm[N,M], mflags[N,M,8] (giou, iou.cpp:243-258), far[N,M,2] (diou, :352-367)"""
     lib = _lib.load()
-    odev = boxes1.device
     if boxes1.dtype != boxes2.dtype:
         raise RuntimeError("boxes1 and boxes2 must have the same dtype")
-    (b1, b2), dev = _to_device(boxes1.detach(), boxes2.detach())
-    n, m = b1.shape[0], b2.shape[0]
-    shapes = dict(nx=(n, m), xflags=(n, m, 8), nm=(n, m), mflags=(n, m, 8), far=(n, m, 2))
-    with torch.cuda.device(dev):
-        out = {k: torch.empty(shapes[k], dtype=torch.uint8, device=dev) for k in which}
+    with _Staged(boxes1.detach(), boxes2.detach()) as call:
+        b1, b2 = call.inputs
+        n, m = b1.shape[0], b2.shape[0]
+        shapes = dict(nx=(n, m), xflags=(n, m, 8), nm=(n, m), mflags=(n, m, 8), far=(n, m, 2))
+        out = {k: torch.empty(shapes[k], dtype=torch.uint8, device=call.dev) for k in which}
         rc = lib.d3d_iou2dr_flags(_lib.ptr(b1), n, _lib.ptr(b2), m, _dtype_code(b1), _lib.ptr(out.get("nx")),
                                   _lib.ptr(out.get("xflags")), _lib.ptr(out.get("nm")), _lib.ptr(out.get("mflags")),
                                   _lib.ptr(out.get("far")), _lib.stream_ptr())
     _lib.check(rc, "iou2dr_flags")
-    return {k: (v.to(odev) if odev != dev else v) for k, v in out.items()}
+    return call.back(out)
 
 
 def _iou_backward(boxes1, boxes2, grad, iou_type, matrix32=False, wide32=False):
     """matrix32 (fp64 boxes, BOX / RBOX): `grad` is read as fp32 and widened in the kernels (D3D_F64_M32);
     wide32 (fp32 boxes, BOX / RBOX): the boxes too (D3D_F32_WIDE) -- the sums are kept in fp64 and come back rounded to fp32"""
     lib = _lib.load()
-    odev = boxes1.device
-    mixed = matrix32 or wide32
-    (b1, b2, g), dev = _to_device(boxes1.detach(), boxes2.detach(), grad.to(torch.float32 if mixed else boxes1.dtype))
-    n, m = b1.shape[0], b2.shape[0]
-    code = _dtype_code(b1)
-    if mixed:
-        if code != (_lib.F32 if wide32 else _lib.F64) or int(iou_type) not in (IouType.BOX, IouType.RBOX):
-            raise ValueError("matrix32 takes fp64 boxes, wide32 fp32 boxes, both the box / rbox methods")
-        code = _lib.F32_WIDE if wide32 else _lib.F64_M32
-    with torch.cuda.device(dev):
+    with _Staged(boxes1.detach(), boxes2.detach(), grad.to(torch.float32 if matrix32 or wide32 else boxes1.dtype)) as call:
+        (b1, b2, g), dev = call.inputs, call.dev
+        n, m = b1.shape[0], b2.shape[0]
+        code = _mixed_code(b1, iou_type, matrix32, wide32)
         # both results in ONE buffer: the library then clears them with one launch, and the wide form rounds them with one
         gg = torch.empty((n + m, 5), dtype=torch.float64 if wide32 else b1.dtype, device=dev)
-        g1, g2 = gg[:n], gg[n:]
         ws = _lib.workspace(lib.d3d_iou2d_workspace_bytes(n, m, code), dev)
-        rc = lib.d3d_iou2d_backward(_lib.ptr(b1), n, _lib.ptr(b2), m, _lib.ptr(g), int(iou_type), code, _lib.ptr(g1),
-                                    _lib.ptr(g2), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+        rc = lib.d3d_iou2d_backward(_lib.ptr(b1), n, _lib.ptr(b2), m, _lib.ptr(g), int(iou_type), code, _lib.ptr(gg[:n]),
+                                    _lib.ptr(gg[n:]), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
         _lib.check(rc, "iou2d_backward")
         if wide32:
             gg = gg.to(torch.float32)
-            g1, g2 = gg[:n], gg[n:]
-    return (g1.to(odev), g2.to(odev)) if odev != dev else (g1, g2)
+    return call.back((gg[:n], gg[n:]))
 
 
 def iou2d_backward(boxes1, boxes2, grad):
@@ -172,60 +217,36 @@ def diou2dr_backward(boxes1, boxes2, grad, nxd=None, xflags=None):
     return _iou_backward(boxes1, boxes2, grad, IouType.DRBOX)
 
 
-class Iou2D(torch.autograd.Function):
+def _iou_function(iou_type):
+    """the autograd function of one method of the IoU family: forward saves the boxes, backward recomputes from them"""
+    class IouFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, boxes1, boxes2):
+            ctx.save_for_backward(boxes1, boxes2)
+            return _iou_forward(boxes1, boxes2, iou_type)
+
+        @staticmethod
+        def backward(ctx, grad):
+            boxes1, boxes2 = ctx.saved_tensors
+            return _iou_backward(boxes1, boxes2, grad.contiguous(), iou_type)
+
+    return IouFunction
+
+
+class Iou2D(_iou_function(IouType.BOX)):
     """Differentiable axis aligned IoU function for 2D boxes -- reference box/__init__.py:41-61"""
 
-    @staticmethod
-    def forward(ctx, boxes1, boxes2):
-        ctx.save_for_backward(boxes1, boxes2)
-        return iou2d_forward(boxes1, boxes2)
 
-    @staticmethod
-    def backward(ctx, grad):
-        boxes1, boxes2 = ctx.saved_tensors
-        return iou2d_backward(boxes1, boxes2, grad.contiguous())
-
-
-class Iou2DR(torch.autograd.Function):
+class Iou2DR(_iou_function(IouType.RBOX)):
     """Differentiable rotated IoU function for 2D boxes -- reference box/__init__.py:63-84"""
 
-    @staticmethod
-    def forward(ctx, boxes1, boxes2):
-        ctx.save_for_backward(boxes1, boxes2)
-        return iou2dr_forward(boxes1, boxes2)
 
-    @staticmethod
-    def backward(ctx, grad):
-        boxes1, boxes2 = ctx.saved_tensors
-        return iou2dr_backward(boxes1, boxes2, grad.contiguous())
-
-
-class GIou2DR(torch.autograd.Function):
+class GIou2DR(_iou_function(IouType.GRBOX)):
     """Differentiable rotated GIoU function for 2D boxes -- reference box/__init__.py:86-107"""
 
-    @staticmethod
-    def forward(ctx, boxes1, boxes2):
-        ctx.save_for_backward(boxes1, boxes2)
-        return giou2dr_forward(boxes1, boxes2)
 
-    @staticmethod
-    def backward(ctx, grad):
-        boxes1, boxes2 = ctx.saved_tensors
-        return giou2dr_backward(boxes1, boxes2, grad.contiguous())
-
-
-class DIou2DR(torch.autograd.Function):
+class DIou2DR(_iou_function(IouType.DRBOX)):
     """Differentiable rotated DIoU function for 2D boxes -- reference box/__init__.py:109-130"""
-
-    @staticmethod
-    def forward(ctx, boxes1, boxes2):
-        ctx.save_for_backward(boxes1, boxes2)
-        return diou2dr_forward(boxes1, boxes2)
-
-    @staticmethod
-    def backward(ctx, grad):
-        boxes1, boxes2 = ctx.saved_tensors
-        return diou2dr_backward(boxes1, boxes2, grad.contiguous())
 
 
 class _IouPrecise32(torch.autograd.Function):
@@ -272,15 +293,10 @@ def box2d_iou(boxes1, boxes2, method="box", precise=True):
     :param precise: compute in float64 and cast back to the input dtype
     """
     (boxes1, boxes2), was_numpy = _ingress(boxes1, boxes2)
-    dtype_in = boxes1.dtype
     # fp32 boxes, precise: the fp64 arithmetic with an fp32 matrix (_IouPrecise32) instead of .double() ... .to(float32) around it
-    fused32 = precise and dtype_in == torch.float32 and boxes2.dtype == torch.float32
-    if precise and not fused32:
-        boxes1, boxes2 = boxes1.double(), boxes2.double()
-    if boxes1.dim() != 2 or boxes2.dim() != 2:
-        raise ValueError("Input of rbox_2d_iou should be Nx2 tensors!")
-    if boxes1.shape[1] != 5 or boxes2.shape[1] != 5:
-        raise ValueError("Input boxes should have 5 fields: x, y, w, h, r")
+    dtype_in = boxes1.dtype
+    boxes1, boxes2, fused32 = _promote(precise, boxes1, boxes2)
+    _check_fields(5, boxes1, boxes2, flat=_NX2)
     iou_type = getattr(IouType, method.upper())                   # AttributeError for unknown names, like the reference
     fn = _IOU_FUNCTIONS.get(iou_type)
     if fn is None:
@@ -297,15 +313,14 @@ def argsort_desc(scores):
     """stable descending argsort on the device (nms.cpp:103 uses torch's unstable argsort)."""
     lib = _lib.load()
     n = scores.numel()
-    dev = scores.device
-    order = torch.empty((n,), dtype=torch.int64, device=dev)
     code = _dtype_code(scores)
-    with torch.cuda.device(dev):
-        ws = _lib.workspace(lib.d3d_argsort_desc_workspace_bytes(n, code), dev)
-        rc = lib.d3d_argsort_desc(_lib.ptr(scores), n, code, _lib.ptr(order), _lib.ptr(ws), ws.numel(),
+    with _Staged(scores) as call:
+        order = torch.empty((n,), dtype=torch.int64, device=call.dev)
+        ws = _lib.workspace(lib.d3d_argsort_desc_workspace_bytes(n, code), call.dev)
+        rc = lib.d3d_argsort_desc(_lib.ptr(call.inputs[0]), n, code, _lib.ptr(order), _lib.ptr(ws), ws.numel(),
                                   _lib.stream_ptr())
     _lib.check(rc, "argsort_desc")
-    return order
+    return call.back(order)
 
 
 NMS_STATUS_DENSE_PATH, NMS_STATUS_SCAN_GAVE_UP = 1, 2
@@ -326,17 +341,14 @@ def nms2d(boxes, scores, iou_type, supression_type, iou_threshold, score_thresho
         raise ValueError("Unsupported iou type!")                   # common.h:25
     if supression_type not in (0, 1, 2):
         raise ValueError("Unsupported supression type!")            # common.h:40
-    odev = boxes.device
     if boxes.dtype != scores.dtype:
         raise RuntimeError("boxes and scores must have the same dtype")
-    (b, s), dev = _to_device(boxes, scores)
-    n = b.shape[0]
-    code = _dtype_code(b)
-    if wide32:
-        if code != _lib.F32:
+    with _Staged(boxes, scores) as call:
+        (b, s), dev = call.inputs, call.dev
+        n = b.shape[0]
+        code = _dtype_code(b, wide32)
+        if wide32 and code != _lib.F32_WIDE:
             raise ValueError("wide32 takes fp32 boxes and scores")
-        code = _lib.F32_WIDE
-    with torch.cuda.device(dev):
         # order = None: the library sorts the scores itself (inside the first kernel for up to 4096 boxes)
         order = None
         if sort_keys is not None and sort_keys.dtype == torch.float32 and sort_keys.numel() == n and s.dtype != torch.float32 and n > 4096:
@@ -354,8 +366,7 @@ def nms2d(boxes, scores, iou_type, supression_type, iou_threshold, score_thresho
         status = ctypes.c_uint32(0)
         if return_status and n > 0:
             _lib.check(lib.d3d_nms2d_status(_lib.ptr(ws), supression_type, _lib.stream_ptr(), ctypes.byref(status)), "nms2d_status")
-    sup = sup.view(torch.bool)
-    sup = _lib.to_caller(sup, odev, dev)
+    sup = call.back(sup.view(torch.bool))
     return (sup, int(status.value)) if return_status else sup
 
 
@@ -370,9 +381,7 @@ def box2d_nms(boxes, scores, iou_method="box", supression_method="hard",
     # (the order of fp32 scores survives the promotion -- fp32 -> fp64 is monotone and injective -- so the sort may use the narrow keys)
     keys = scores if scores.dtype == torch.float32 else None
     # fp32 boxes AND scores, precise: fp64 arithmetic on values widened inside the kernels (D3D_F32_WIDE) instead of .double() copies
-    wide32 = precise and boxes.dtype == torch.float32 and scores.dtype == torch.float32
-    if precise and not wide32:
-        boxes, scores = boxes.double(), scores.double()
+    boxes, scores, wide32 = _promote(precise, boxes, scores)
     if len(boxes) != len(scores):
         raise ValueError("Numbers of boxes and scores are inconsistent!")
     if scores.dim() == 2:
@@ -419,9 +428,7 @@ def box2d_nms_batched(boxes, scores, groups, iou_method="box", supression_method
     through nms2d on its own.  Only supression_method="hard": soft-NMS is sequential per set and stays with box2d_nms.
     """
     (boxes, scores), was_numpy = _ingress(boxes, scores)
-    wide32 = precise and boxes.dtype == torch.float32 and scores.dtype == torch.float32
-    if precise and not wide32:
-        boxes, scores = boxes.double(), scores.double()
+    boxes, scores, wide32 = _promote(precise, boxes, scores)
     if len(boxes) != len(scores):
         raise ValueError("Numbers of boxes and scores are inconsistent!")
     groups = _group_ids(groups)
@@ -438,13 +445,12 @@ def box2d_nms_batched(boxes, scores, groups, iou_method="box", supression_method
         raise ValueError("Unsupported iou type!")                   # common.h:25
     if boxes.dtype != scores.dtype:
         raise RuntimeError("boxes and scores must have the same dtype")
-    code = _lib.F32_WIDE if wide32 else _dtype_code(boxes)
+    code = _dtype_code(boxes, wide32)
     # everything above is host-side: nothing has touched the library or a device
     lib = _lib.load()
-    odev = boxes.device
-    (b, s), dev = _to_device(boxes, scores)
-    n = b.shape[0]
-    with torch.cuda.device(dev):
+    with _Staged(boxes, scores) as call:
+        (b, s), dev = call.inputs, call.dev
+        n = b.shape[0]
         # stable: the rows of a segment stay in ascending row order, the order ties in score keep
         ids, perm = torch.sort(groups.to(dev), stable=True)
         counts = torch.unique_consecutive(ids, return_counts=True)[1]
@@ -468,7 +474,7 @@ def box2d_nms_batched(boxes, scores, groups, iou_method="box", supression_method
                                    float(iou_threshold), float(score_threshold), _lib.ptr(keep), _lib.ptr(ws), ws.numel(),
                                    _lib.stream_ptr(), _lib.NMS_KEEP_MASK)
         _lib.check(rc, "nms2d_grouped")
-    return _egress(_lib.to_caller(keep.view(torch.bool), odev, dev), was_numpy)
+    return _egress(call.back(keep.view(torch.bool)), was_numpy)
 
 
 def iou3d(boxes1, boxes2, method="rbox"):
@@ -477,20 +483,14 @@ def iou3d(boxes1, boxes2, method="rbox"):
     (reference d3d/dgal_wrap.h:45-91; the pair loop of BaseMatcher.prepare_boxes,
     d3d/tracking/matcher.pyx:57-80, stores 1 - this value)."""
     lib = _lib.load()
-    convert_numpy = False
-    if isinstance(boxes1, np.ndarray):
-        assert isinstance(boxes2, np.ndarray), "Input should be both numpy tensor or pytorch tensor!"
-        boxes1, boxes2 = torch.from_numpy(boxes1), torch.from_numpy(boxes2)
-        convert_numpy = True
+    (boxes1, boxes2), was_numpy = _ingress(boxes1, boxes2)
     key = method.upper()
     if key not in ("RBOX", "BOX"):
         raise ValueError("Unrecognized iou type!")
-    if len(boxes1.shape) != 2 or len(boxes2.shape) != 2 or boxes1.shape[1] != 7 or boxes2.shape[1] != 7:
-        raise ValueError("Input boxes should have 7 fields: x, y, z, lx, ly, lz, rz")
-    odev = boxes1.device
-    (b1, b2), dev = _to_device(boxes1.to(torch.float32), boxes2.to(torch.float32))
-    n, m = b1.shape[0], b2.shape[0]
-    with torch.cuda.device(dev):
+    _check_fields(7, boxes1, boxes2)
+    with _Staged(boxes1.to(torch.float32), boxes2.to(torch.float32)) as call:
+        (b1, b2), dev = call.inputs, call.dev
+        n, m = b1.shape[0], b2.shape[0]
         out = torch.empty((n, m), dtype=torch.float32, device=dev)
         if options.current().poison:
             out.fill_(float("nan"))
@@ -498,18 +498,16 @@ def iou3d(boxes1, boxes2, method="rbox"):
         rc = lib.d3d_iou3d_forward(_lib.ptr(b1), n, _lib.ptr(b2), m, 1 if key == "RBOX" else 0, _lib.ptr(out),
                                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
     _lib.check(rc, "iou3d_forward")
-    out = _lib.to_caller(out, odev, dev)
-    return out.numpy() if convert_numpy else out
+    return _egress(call.back(out), was_numpy)
 
 
 def _iou_paired(boxes1, boxes2, cols, kind, code, need_jac):
     """one launch of d3d_iou2d_paired (cols 5) / d3d_iou3d_paired (cols 7) -> (ious[N] on the caller's device, jac[N, 2 cols] on the GPU
     or None).  jac is in the arithmetic's dtype: fp64 unless `code` is D3D_F32."""
     lib = _lib.load()
-    odev = boxes1.device
-    (b1, b2), dev = _to_device(boxes1.detach(), boxes2.detach())
-    n = b1.shape[0]
-    with torch.cuda.device(dev):
+    with _Staged(boxes1.detach(), boxes2.detach()) as call:
+        (b1, b2), dev = call.inputs, call.dev
+        n = b1.shape[0]
         ious = torch.empty((n,), dtype=b1.dtype, device=dev)
         jac = torch.empty((n, 2 * cols), dtype=torch.float32 if code == _lib.F32 else torch.float64, device=dev) if need_jac else None
         if options.current().poison:
@@ -519,7 +517,7 @@ def _iou_paired(boxes1, boxes2, cols, kind, code, need_jac):
         fn = lib.d3d_iou2d_paired if cols == 5 else lib.d3d_iou3d_paired
         rc = fn(_lib.ptr(b1), _lib.ptr(b2), n, int(kind), code, _lib.ptr(ious), _lib.ptr(jac), _lib.stream_ptr())
     _lib.check(rc, "iou2d_paired" if cols == 5 else "iou3d_paired")
-    return _lib.to_caller(ious, odev, dev), jac
+    return call.back(ious), jac
 
 
 def _paired_forward(ctx, cols, boxes1, boxes2, kind, code):
@@ -570,12 +568,10 @@ def _paired(fn, boxes1, boxes2, kind, precise, was_numpy):
     """dtype handling of box2d_iou for the paired operators: precise = fp64 arithmetic, the result cast back; on fp32 boxes the
     widening happens where the kernel loads them (D3D_F32_WIDE) -- no .double() copies, no cast launch"""
     dtype_in = boxes1.dtype
-    wide32 = precise and dtype_in == torch.float32 and boxes2.dtype == torch.float32
-    if precise and not wide32:
-        boxes1, boxes2 = boxes1.double(), boxes2.double()
+    boxes1, boxes2, wide32 = _promote(precise, boxes1, boxes2)
     if boxes1.dtype != boxes2.dtype:
         raise RuntimeError("boxes1 and boxes2 must have the same dtype")
-    code = _lib.F32_WIDE if wide32 else _dtype_code(boxes1)
+    code = _dtype_code(boxes1, wide32)
     if len(boxes1) == 0:                                            # nothing to launch (and nothing to differentiate)
         return _egress(boxes1[:, 0].to(dtype_in), was_numpy)
     ious = fn.apply(boxes1, boxes2, kind, code)
@@ -594,10 +590,7 @@ def box2d_iou_paired(boxes1, boxes2, method="rbox", precise=True):
     :return: [N]; 0 (and a zero gradient) for a rectangle without area ('rbox', 'grbox', 'drbox') and for pairs apart ('box', 'rbox')
     """
     (boxes1, boxes2), was_numpy = _ingress(boxes1, boxes2)
-    if boxes1.dim() != 2 or boxes2.dim() != 2:
-        raise ValueError("Input of rbox_2d_iou should be Nx2 tensors!")
-    if boxes1.shape[1] != 5 or boxes2.shape[1] != 5:
-        raise ValueError("Input boxes should have 5 fields: x, y, w, h, r")
+    _check_fields(5, boxes1, boxes2, flat=_NX2)
     if len(boxes1) != len(boxes2):
         raise ValueError("Paired boxes should come in equal numbers: %d and %d" % (len(boxes1), len(boxes2)))
     iou_type = getattr(IouType, method.upper())                   # AttributeError for unknown names, like box2d_iou
@@ -621,8 +614,7 @@ def box3d_iou_paired(boxes1, boxes2, method="rbox", precise=True):
     key = method.upper()
     if key not in ("RBOX", "BOX"):
         raise ValueError("Unrecognized iou type!")
-    if boxes1.dim() != 2 or boxes2.dim() != 2 or boxes1.shape[1] != 7 or boxes2.shape[1] != 7:
-        raise ValueError("Input boxes should have 7 fields: x, y, z, lx, ly, lz, rz")
+    _check_fields(7, boxes1, boxes2)
     if len(boxes1) != len(boxes2):
         raise ValueError("Paired boxes should come in equal numbers: %d and %d" % (len(boxes1), len(boxes2)))
     return _paired(IouPaired3D, boxes1, boxes2, 1 if key == "RBOX" else 0, precise, was_numpy)
@@ -648,8 +640,8 @@ def _iou_sparse(boxes1, boxes2, cols, iou_type, code, threshold, return_offsets,
                torch.zeros((n + 1,), dtype=torch.int64, device=odev))
     else:
         lib = _lib.load()
-        (b1, b2), dev = _to_device(boxes1.detach(), boxes2.detach())
-        with torch.cuda.device(dev):
+        with _Staged(boxes1.detach(), boxes2.detach()) as call:
+            (b1, b2), dev = call.inputs, call.dev
             offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev)
             ws = _lib.workspace(lib.d3d_iou_sparse_workspace_bytes(n, m), dev)
             inputs = (_lib.ptr(b1), n, _lib.ptr(b2), m, cols, int(iou_type), code, threshold)
@@ -660,7 +652,7 @@ def _iou_sparse(boxes1, boxes2, cols, iou_type, code, threshold, return_offsets,
             if k > 0:
                 _lib.check(lib.d3d_iou_sparse_emit(*inputs, _lib.ptr(offsets), k, _lib.ptr(pairs), _lib.ptr(values), _lib.ptr(ws), ws.numel(),
                                                    _lib.stream_ptr()), "iou_sparse_emit")
-        res = _lib.to_caller((pairs, values, offsets), odev, dev)
+        res = call.back((pairs, values, offsets))
     res = tuple(_egress(t, was_numpy) for t in res)
     return res if return_offsets else res[:2]
 
@@ -686,18 +678,15 @@ def box2d_iou_sparse(boxes1, boxes2, method="rbox", threshold=0.0, precise=True,
     """
     (boxes1, boxes2), was_numpy = _ingress(boxes1, boxes2)
     threshold = _sparse_threshold(threshold)
-    if boxes1.dim() != 2 or boxes2.dim() != 2:
-        raise ValueError("Input of rbox_2d_iou should be Nx2 tensors!")
-    if boxes1.shape[1] != 5 or boxes2.shape[1] != 5:
-        raise ValueError("Input boxes should have 5 fields: x, y, w, h, r")
+    _check_fields(5, boxes1, boxes2, flat=_NX2)
     iou_type = getattr(IouType, method.upper())                   # AttributeError for unknown names, like box2d_iou
     if iou_type not in (IouType.BOX, IouType.RBOX):
         raise ValueError("Unsupported iou type!")
     if boxes1.dtype != boxes2.dtype:
         raise RuntimeError("boxes1 and boxes2 must have the same dtype")
-    # box2d_iou's promotion: fp32 boxes, precise -- fp64 arithmetic on rows widened inside the kernels, the value rounded to fp32
-    code = _lib.F32_WIDE if precise and boxes1.dtype == torch.float32 else _dtype_code(boxes1)
-    return _iou_sparse(boxes1, boxes2, 5, iou_type, code, threshold, return_offsets, was_numpy)
+    # box2d_iou's promotion: fp32 boxes, precise -- fp64 arithmetic on rows widened inside the kernels, the value rounded to fp32;
+    # the values stay in the boxes' dtype, so nothing is copied to fp64 and another dtype is refused
+    return _iou_sparse(boxes1, boxes2, 5, iou_type, _dtype_code(boxes1, _wide32(precise, boxes1, boxes2)), threshold, return_offsets, was_numpy)
 
 
 def iou3d_sparse(boxes1, boxes2, method="rbox", threshold=0.0, return_offsets=False):
@@ -710,29 +699,30 @@ def iou3d_sparse(boxes1, boxes2, method="rbox", threshold=0.0, return_offsets=Fa
     key = method.upper()
     if key not in ("RBOX", "BOX"):
         raise ValueError("Unsupported iou type!" if hasattr(IouType, key) else "Unrecognized iou type!")
-    if len(boxes1.shape) != 2 or len(boxes2.shape) != 2 or boxes1.shape[1] != 7 or boxes2.shape[1] != 7:
-        raise ValueError("Input boxes should have 7 fields: x, y, z, lx, ly, lz, rz")
+    _check_fields(7, boxes1, boxes2)
     return _iou_sparse(boxes1.to(torch.float32), boxes2.to(torch.float32), 7, getattr(IouType, key), _lib.F32, threshold, return_offsets,
                        was_numpy)
+
+
+def _check_points_boxes(points, boxes):
+    if len(points.shape) != 2 or points.shape[1] != 2 or len(boxes.shape) != 2 or boxes.shape[1] != 5:
+        raise ValueError("points should be Nx2 and boxes Mx5")
+    if points.dtype != boxes.dtype:
+        raise RuntimeError("points and boxes must have the same dtype")
 
 
 def crop_2dr(points, boxes):
     """crop_2dr of the reference (utils.cpp:38-47; box_impl.crop_2dr): bool[M,N] indicators, [i,j] = point j is
     inside rotated box i.  points [N,2], boxes [M,5], same floating dtype."""
     lib = _lib.load()
-    if len(points.shape) != 2 or points.shape[1] != 2 or len(boxes.shape) != 2 or boxes.shape[1] != 5:
-        raise ValueError("points should be Nx2 and boxes Mx5")
-    if points.dtype != boxes.dtype:
-        raise RuntimeError("points and boxes must have the same dtype")
-    odev = points.device
-    (p, b), dev = _to_device(points, boxes)
-    n, m = p.shape[0], b.shape[0]
-    with torch.cuda.device(dev):
-        out = torch.empty((m, n), dtype=torch.uint8, device=dev)
+    _check_points_boxes(points, boxes)
+    with _Staged(points, boxes) as call:
+        p, b = call.inputs
+        n, m = p.shape[0], b.shape[0]
+        out = torch.empty((m, n), dtype=torch.uint8, device=call.dev)
         rc = lib.d3d_crop_2dr(_lib.ptr(p), n, _lib.ptr(b), m, _dtype_code(p), _lib.ptr(out), _lib.stream_ptr())
     _lib.check(rc, "crop_2dr")
-    out = out.view(torch.bool)
-    return _lib.to_caller(out, odev, dev)
+    return call.back(out.view(torch.bool))
 
 
 def box2dr_crop(points, boxes):
@@ -741,34 +731,31 @@ def box2dr_crop(points, boxes):
     return crop_2dr(points, boxes)
 
 
+def _project(points, boxes, axis):
+    """[N,3] points and [M,7] boxes seen along `axis` -> (points [N,2], boxes [M,5]: x, y, w, h, r in the plane of the two other axes)"""
+    if axis not in (0, 1, 2):
+        raise ValueError("The projection axis can only be 0-x, 1-y and 2-z!")
+    u, v = (a for a in (0, 1, 2) if a != axis)
+    return points[:, [u, v]], boxes[:, [u, v, 3 + u, 3 + v, 6]]
+
+
 def box3dp_crop(points, boxes, project_axis=2):
     """Crop points [N,3] by boxes [M,7] projected along `project_axis` -- reference box/__init__.py:289-315.  fp32, along z, a cloud
     of 4096 points and more against up to 4096 boxes: ONE launch (d3d_crop_3dp: the same tests on the same float expressions);
     anything else: the reference's composition around crop_2dr."""
-    if project_axis not in (0, 1, 2):
-        raise ValueError("The projection axis can only be 0-x, 1-y and 2-z!")
     if (project_axis == 2 and torch.is_tensor(points) and torch.is_tensor(boxes) and points.dtype == torch.float32 and
             boxes.dtype == torch.float32 and points.dim() == 2 and boxes.dim() == 2 and points.shape[1] >= 3 and boxes.shape[1] == 7
             and points.shape[0] >= 4096 and 0 < boxes.shape[0] <= 4096):
         lib = _lib.load()
-        odev = points.device
-        (p, b), dev = _to_device(points.detach(), boxes.detach())
-        n, m = p.shape[0], b.shape[0]
-        with torch.cuda.device(dev):
-            out = torch.empty((m, n), dtype=torch.uint8, device=dev)
+        with _Staged(points.detach(), boxes.detach()) as call:
+            p, b = call.inputs
+            n, m = p.shape[0], b.shape[0]
+            out = torch.empty((m, n), dtype=torch.uint8, device=call.dev)
             rc = lib.d3d_crop_3dp(_lib.ptr(p), n, p.shape[1], _lib.ptr(b), m, 7, 2, _lib.ptr(out), _lib.stream_ptr())
         if rc != _lib.ERR_UNSUPPORTED:
             _lib.check(rc, "crop_3dp")
-            return _lib.to_caller(out.view(torch.bool), odev, dev)
-    if project_axis == 0:
-        points_2d, boxes_2d = points[:, [1, 2]], boxes[:, [1, 2, 4, 5, 6]]
-    elif project_axis == 1:
-        points_2d, boxes_2d = points[:, [0, 2]], boxes[:, [0, 2, 3, 5, 6]]
-    elif project_axis == 2:
-        points_2d, boxes_2d = points[:, [0, 1]], boxes[:, [0, 1, 3, 4, 6]]
-    else:
-        raise ValueError("The projection axis can only be 0-x, 1-y and 2-z!")
-    mask_2d = crop_2dr(points_2d, boxes_2d)
+            return call.back(out.view(torch.bool))
+    mask_2d = crop_2dr(*_project(points, boxes, project_axis))
     points_p = points[:, [project_axis]].t()
     boxes_p = boxes[:, [project_axis]]
     boxes_pd = boxes[:, [3 + project_axis]] / 2
@@ -780,36 +767,31 @@ def pdist2dr_forward(points, boxes):
     """pdist2dr_forward[_cuda] (dist.h:7-9; dist.cpp:36-52): (distance[M,N], iedge[M,N] uint8) for points[N,2], boxes[M,5];
     signed distance to the box boundary, positive inside"""
     lib = _lib.load()
-    if len(points.shape) != 2 or points.shape[1] != 2 or len(boxes.shape) != 2 or boxes.shape[1] != 5:
-        raise ValueError("points should be Nx2 and boxes Mx5")
-    if points.dtype != boxes.dtype:
-        raise RuntimeError("points and boxes must have the same dtype")
-    odev = points.device
-    (p, b), dev = _to_device(points.detach(), boxes.detach())
-    n, m = p.shape[0], b.shape[0]
-    with torch.cuda.device(dev):
-        dist = torch.empty((m, n), dtype=p.dtype, device=dev)
-        iedge = torch.empty((m, n), dtype=torch.uint8, device=dev)
+    _check_points_boxes(points, boxes)
+    with _Staged(points.detach(), boxes.detach()) as call:
+        p, b = call.inputs
+        n, m = p.shape[0], b.shape[0]
+        dist = torch.empty((m, n), dtype=p.dtype, device=call.dev)
+        iedge = torch.empty((m, n), dtype=torch.uint8, device=call.dev)
         rc = lib.d3d_pdist2dr_forward(_lib.ptr(p), n, _lib.ptr(b), m, _dtype_code(p), _lib.ptr(dist), _lib.ptr(iedge),
                                       _lib.stream_ptr())
     _lib.check(rc, "pdist2dr_forward")
-    return (dist.to(odev), iedge.to(odev)) if odev != dev else (dist, iedge)
+    return call.back((dist, iedge))
 
 
 def pdist2dr_backward(points, boxes, grad, iedge=None):
     """pdist2dr_backward[_cuda] (dist.h:10-13; dist.cpp:90-110): (grad_boxes[M,5], grad_points[N,2]); `iedge` is accepted
     for signature compatibility and ignored (the nearest feature is recomputed)"""
     lib = _lib.load()
-    odev = points.device
-    (p, b, g), dev = _to_device(points.detach(), boxes.detach(), grad.to(points.dtype))
-    n, m = p.shape[0], b.shape[0]
-    with torch.cuda.device(dev):
-        gb = torch.empty((m, 5), dtype=p.dtype, device=dev)
-        gp = torch.empty((n, 2), dtype=p.dtype, device=dev)
+    with _Staged(points.detach(), boxes.detach(), grad.to(points.dtype)) as call:
+        p, b, g = call.inputs
+        n, m = p.shape[0], b.shape[0]
+        gb = torch.empty((m, 5), dtype=p.dtype, device=call.dev)
+        gp = torch.empty((n, 2), dtype=p.dtype, device=call.dev)
         rc = lib.d3d_pdist2dr_backward(_lib.ptr(p), n, _lib.ptr(b), m, _lib.ptr(g), _dtype_code(p), _lib.ptr(gb), _lib.ptr(gp),
                                        _lib.stream_ptr())
     _lib.check(rc, "pdist2dr_backward")
-    return (gb.to(odev), gp.to(odev)) if odev != dev else (gb, gp)
+    return call.back((gb, gp))
 
 
 class PDist2DR(torch.autograd.Function):
@@ -853,10 +835,7 @@ def seg1d_pdist(points, segs):
 
 def box2dr_pdist(points, boxes, method="rbox"):
     """Signed distance from points [N,2] to rotated 2D boxes [M,5] -> [M,N] -- reference box/__init__.py:333-349"""
-    if len(boxes.shape) != 2:
-        raise ValueError("Input boxes should be Nx2 tensors!")
-    if boxes.shape[1] != 5:
-        raise ValueError("Input boxes should have 5 fields: x, y, w, h, r")
+    _check_fields(5, boxes, flat="Input boxes should be Nx2 tensors!")
     if method != "rbox":
         raise ValueError("Only supported rotated boxes by now!")
     return PDist2DR.apply(points, boxes)
@@ -866,14 +845,7 @@ def box3dr_pdist(points, boxes, project_axis=2):
     """Signed distance from points [N,3] to 3D boxes [M,7] (surfaces) -> [M,N] -- reference box/__init__.py:351-381.
     (The reference combines a [M,N] planar distance with a [N,M] axial one, which only broadcasts for N == M; here the
     axial distance is laid out [M,N] as well.)"""
-    if project_axis == 0:
-        points_2d, boxes_2d = points[:, [1, 2]], boxes[:, [1, 2, 4, 5, 6]]
-    elif project_axis == 1:
-        points_2d, boxes_2d = points[:, [0, 2]], boxes[:, [0, 2, 3, 5, 6]]
-    elif project_axis == 2:
-        points_2d, boxes_2d = points[:, [0, 1]], boxes[:, [0, 1, 3, 4, 6]]
-    else:
-        raise ValueError("The projection axis can only be 0-x, 1-y and 2-z!")
+    points_2d, boxes_2d = _project(points, boxes, project_axis)
     dist_2d = box2dr_pdist(points_2d.contiguous(), boxes_2d.contiguous())
     dist_p = seg1d_pdist(points[:, [project_axis]], boxes[:, [project_axis, 3 + project_axis]]).t()
     return torch.where(

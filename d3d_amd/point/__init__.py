@@ -6,6 +6,7 @@ import enum
 import torch
 
 from .. import _lib
+from .._rows import device_of
 
 
 class AlignType(enum.IntEnum):      # point/scatter.h:37
@@ -44,19 +45,17 @@ def _check(coord, feat):
 def aligned_scatter_forward(coord, image_feature, atype):
     """aligned_scatter_forward[_cuda] (scatter.h:39-41): [N, C] features"""
     _check(coord, image_feature)
-    odev = image_feature.device
-    dev = odev if image_feature.is_cuda else _lib.require_gpu()
+    odev, dev = image_feature.device, device_of(image_feature)          # (the feature map decides; the coordinates follow it)
     c, f = coord.to(dev).contiguous(), image_feature.detach().to(dev).contiguous()
     with torch.cuda.device(dev):
         out = torch.empty((c.shape[0], f.shape[1]), dtype=f.dtype, device=dev)
         _call("d3d_aligned_scatter_forward", c, f, atype, out, f.shape)
-    return out.to(odev) if odev != dev else out
+    return _lib.to_caller(out, odev, dev)
 
 
 def aligned_scatter_backward(coord, grad, atype, image_grad):
     """aligned_scatter_backward[_cuda] (scatter.h:42-45): accumulates into image_grad (in place)"""
-    odev = image_grad.device
-    dev = odev if image_grad.is_cuda else _lib.require_gpu()
+    odev, dev = image_grad.device, device_of(image_grad)
     c, g = coord.to(dev).contiguous(), grad.to(dev).contiguous()
     target = image_grad if (odev == dev and image_grad.is_contiguous()) else image_grad.to(dev).contiguous()
     with torch.cuda.device(dev):

@@ -10,12 +10,32 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._rows import device_of
 
 
 class DistanceTypes(enum.IntEnum):      # matcher.pxd:5-8
     IoU = 1
     RIoU = 2
     Position = 3
+
+
+def _host(a):
+    """tags, scores, flags: numpy arrays, lists, or tensors on any device -> numpy on the host"""
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def _threshold_of(distance_threshold, tags):
+    """unordered_map<int, float>::operator[] (matcher.pyx:112, :115, :227): the threshold of every tag as fp32, a tag missing from
+    the map reads as 0.0"""
+    thr = np.zeros((tags.size,), np.float32)
+    for tag in set(tags.tolist()):      # (a frame has a handful of classes: cheaper than np.unique's sort)
+        thr[tags == tag] = np.float32(float(distance_threshold.get(tag, 0.0)))
+    return thr
+
+
+def _unmatched(dev, n, m, batch=()):
+    """(src_match[*batch, n], dst_match[*batch, m]) int32 on the device, every box unmatched (-1)"""
+    return tuple(torch.full(tuple(batch) + (k,), -1, dtype=torch.int32, device=dev) for k in (n, m))
 
 
 def _boxes(a, what):
@@ -32,7 +52,7 @@ def prepare_boxes(src_arr, dst_arr, distance_metric):
     lib = _lib.load()
     metric = DistanceTypes(int(distance_metric))
     src, dst = _boxes(src_arr, "src_boxes"), _boxes(dst_arr, "dst_boxes")
-    dev = src.device if src.is_cuda else (dst.device if dst.is_cuda else _lib.require_gpu())
+    dev = device_of(src, dst)
     src, dst = src.to(dev).contiguous(), dst.to(dev).contiguous()
     n, m = src.shape[0], dst.shape[0]
     with torch.cuda.device(dev):
@@ -57,12 +77,10 @@ def score_match(distance, src_scores, src_tags, dst_tags, distance_threshold):
     lib = _lib.load()
     dev = distance.device
     n, m = distance.shape
-    def host(a):                       # tags / scores: numpy arrays, lists, or tensors on any device
-        return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
     # host-side preparation in numpy (a frame has a few hundred boxes: tensor ops would each cost more than the arithmetic),
-    # shipped to the device as ONE buffer: [src scores f32 | src tags i32 | dst tags i32 | dst thresholds f32]
-    st = host(src_tags).astype(np.int32, copy=True).reshape(-1)
-    dt = host(dst_tags).astype(np.int32, copy=True).reshape(-1)
+    # shipped to the device in ONE copy: src scores f32, src tags i32, dst tags i32, dst thresholds f32
+    st = _host(src_tags).astype(np.int32, copy=True).reshape(-1)
+    dt = _host(dst_tags).astype(np.int32, copy=True).reshape(-1)
     thr = np.full((m,), np.nan, np.float32)
     known = np.zeros((max(int(st.max()) if n else 0, int(dt.max()) if m else 0, 0) + 2,), bool)
     for tag, v in distance_threshold.items():
@@ -73,13 +91,10 @@ def score_match(distance, src_scores, src_tags, dst_tags, distance_threshold):
     dt[(dt < 0) | ~known[np.clip(dt, 0, None)]] = -1
     # the score order: a stable descending sort ON THE DEVICE (equal scores in index order, as numpy's stable argsort of the
     # negated scores gives them; 20 k scores: 1 ms of numpy on the host against ~50 us) -- the scores ride in the one buffer
-    sc = host(src_scores).astype(np.float32).reshape(-1)
-    packed = torch.from_numpy(np.concatenate([sc.view(np.uint8), st.view(np.uint8), dt.view(np.uint8), thr.view(np.uint8)]))
+    sc = _host(src_scores).astype(np.float32).reshape(-1)
     with torch.cuda.device(dev):
-        packed = packed.to(dev)
-        order = torch.sort(packed[:4 * n].view(torch.float32), descending=True, stable=True).indices
-        st, dt = packed[4 * n:8 * n].view(torch.int32), packed[8 * n:8 * n + 4 * m].view(torch.int32)
-        thr = packed[8 * n + 4 * m:].view(torch.float32)
+        sc, st, dt, thr = _lib.ship(dev, sc, st, dt, thr)
+        order = torch.sort(sc, descending=True, stable=True).indices
         src_match = torch.empty((n,), dtype=torch.int32, device=dev)
         dst_match = torch.empty((m,), dtype=torch.int32, device=dev)
         status = torch.zeros((1,), dtype=torch.int32, device=dev)
@@ -125,20 +140,15 @@ class ReferenceAssociation:
     synchronises once, when it fetches the results."""
 
     def __init__(self, distance, src_scores, src_tags, dst_tags, distance_threshold, dst_subset):
-        def host(a):
-            return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
         self.dev = dev = distance.device
         self.n, self.m = distance.shape
-        self.scores = host(src_scores).astype(np.float32).reshape(-1)
-        stags, dtags = host(src_tags).astype(np.int64).reshape(-1), host(dst_tags).astype(np.int64).reshape(-1)
+        self.scores = _host(src_scores).astype(np.float32).reshape(-1)
+        stags, dtags = _host(src_tags).astype(np.int64).reshape(-1), _host(dst_tags).astype(np.int64).reshape(-1)
         self.dsub = dsub = _index_array(dst_subset)
         if dsub.size == 0 or self.n == 0:
             return
-        # a destination tag missing from `distance_threshold` gets 0.0, as unordered_map::operator[] hands out (matcher.pyx:112)
-        thr = np.zeros((dsub.size,), np.float32)
         dt_sub = dtags[dsub]
-        for tag in np.unique(dt_sub):
-            thr[dt_sub == tag] = np.float32(float(distance_threshold.get(int(tag), 0.0)))
+        thr = _threshold_of(distance_threshold, dt_sub)
         with torch.cuda.device(dev):
             self.dsub_t = torch.from_numpy(dsub).to(dev)
             self.cols = distance.index_select(1, self.dsub_t)                                   # [n, md]
@@ -153,8 +163,7 @@ class ReferenceAssociation:
     def match(self, src_subset):
         """-> (src_match[n], dst_match[m]) int32 tensors on the device, -1 = unmatched (nothing is read back here)"""
         dev, n, m = self.dev, self.n, self.m
-        src_match = torch.full((n,), -1, dtype=torch.int32, device=dev)
-        dst_match = torch.full((m,), -1, dtype=torch.int32, device=dev)
+        src_match, dst_match = _unmatched(dev, n, m)
         ssub = _index_array(src_subset)
         if ssub.size == 0 or self.dsub.size == 0:
             return src_match, dst_match
@@ -165,8 +174,7 @@ class ReferenceAssociation:
         lib = _lib.load()
         k, md = int(ssub.size), int(self.dsub.size)
         with torch.cuda.device(dev):
-            both = torch.from_numpy(np.concatenate([ssub, best])).to(dev)
-            ssub_t, best_t = both[:k], both[k:]
+            ssub_t, best_t = _lib.ship(dev, ssub, best)
             # P[k, j] = distance[subset row k, j] where (k-th best source, j) is acceptable, +inf elsewhere
             pref = torch.where(self.ok.index_select(0, best_t), self.cols.index_select(0, ssub_t), self._inf)
             sm = torch.empty((k,), dtype=torch.int32, device=dev)
@@ -191,8 +199,7 @@ class ReferenceAssociation:
         columns and its acceptable pairs from the k-th best source's row of the prepared mask, by index."""
         dev, n, m = self.dev, self.n, self.m
         T = len(src_subsets)
-        src_all = torch.full((T, n), -1, dtype=torch.int32, device=dev)
-        dst_all = torch.full((T, m), -1, dtype=torch.int32, device=dev)
+        src_all, dst_all = _unmatched(dev, n, m, batch=(T,))
         md = int(self.dsub.size)
         if md == 0 or n == 0:
             return src_all, dst_all
@@ -215,9 +222,7 @@ class ReferenceAssociation:
             local = np.concatenate([np.arange(k, dtype=np.int64) for k in sizes])
             bid = np.repeat(np.arange(B, dtype=np.int64), sizes)
             with torch.cuda.device(dev):
-                d = torch.from_numpy(np.concatenate([np.concatenate(subs[t0:t1]), np.concatenate(bests), off, local, bid])).to(dev)
-                ssub_t, best_t = d[:rows], d[rows:2 * rows]
-                off_t, order_t, bid_t = d[2 * rows:2 * rows + B + 1], d[2 * rows + B + 1:3 * rows + B + 1], d[3 * rows + B + 1:]
+                ssub_t, best_t, off_t, order_t, bid_t = _lib.ship(dev, np.concatenate(subs[t0:t1]), np.concatenate(bests), off, local, bid)
                 sm = torch.empty((rows,), dtype=torch.int32, device=dev)
                 dm = torch.empty((B, md), dtype=torch.int32, device=dev)
                 status = torch.zeros((1,), dtype=torch.int32, device=dev)
@@ -238,17 +243,13 @@ class ReferenceAssociation:
         return src_all, dst_all
 
 
-class ScoreMatcher:
-    """array-level ScoreMatcher (matcher.pyx:138-162): prepare_boxes, match on subsets, query_* -- same call sequence as the
-    reference's evaluator uses (benchmarks.pyx:188-238).  The default reproduces the reference's results: its pairing of the
-    k-th best source with the k-th subset row's distance order (matcher.pyx:155-158; INTEGRATION.md 5);
-    `reference_compat=False` pairs every source with its own nearest destinations (what the class docstring describes)."""
+class _BaseMatcher:
+    """BaseMatcher's array-level state (matcher.pyx:12-136): the boxes, their distance cache and the two assignment maps"""
 
-    def __init__(self, reference_compat=True):
+    def __init__(self):
         self._cache = None
         self._src = self._dst = None
         self._src_assignment, self._dst_assignment = {}, {}
-        self.reference_compat = bool(reference_compat)
 
     def clear_match(self):
         self._src_assignment, self._dst_assignment = {}, {}
@@ -264,6 +265,26 @@ class ScoreMatcher:
     @property
     def distance_cache(self):
         return self._cache
+
+    def query_src_match(self, src_idx):
+        return self._src_assignment.get(int(src_idx), -1)
+
+    def query_dst_match(self, dst_idx):
+        return self._dst_assignment.get(int(dst_idx), -1)
+
+    def num_of_matches(self):
+        return len(self._src_assignment)
+
+
+class ScoreMatcher(_BaseMatcher):
+    """array-level ScoreMatcher (matcher.pyx:138-162): prepare_boxes, match on subsets, query_* -- same call sequence as the
+    reference's evaluator uses (benchmarks.pyx:188-238).  The default reproduces the reference's results: its pairing of the
+    k-th best source with the k-th subset row's distance order (matcher.pyx:155-158; INTEGRATION.md 5);
+    `reference_compat=False` pairs every source with its own nearest destinations (what the class docstring describes)."""
+
+    def __init__(self, reference_compat=True):
+        super().__init__()
+        self.reference_compat = bool(reference_compat)
 
     def match(self, src_subset, dst_subset, distance_threshold):
         self.clear_match()
@@ -284,22 +305,9 @@ class ScoreMatcher:
         self._src_assignment = {int(i): int(j) for i, j in enumerate(sm) if j >= 0}
         self._dst_assignment = {int(j): int(i) for j, i in enumerate(dm) if i >= 0}
 
-    def query_src_match(self, src_idx):
-        return self._src_assignment.get(int(src_idx), -1)
-
-    def query_dst_match(self, dst_idx):
-        return self._dst_assignment.get(int(dst_idx), -1)
-
-    def num_of_matches(self):
-        return len(self._src_assignment)
-
 
 # ------------------------------------------------------------------------------------------ LSAP, Hungarian, nearest neighbour
 LSAP_INVALID, LSAP_INFEASIBLE, LSAP_TOO_BIG = 1, 2, 4          # status bits of d3d_lsap_batched (include/d3d_hip.h)
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
 
 def _lsap_launch(cost, ld, row_idx, col_idx, row_off, col_off, max_rows, max_cols, dev):
@@ -309,9 +317,7 @@ def _lsap_launch(cost, ld, row_idx, col_idx, row_off, col_off, max_rows, max_col
     B = row_off.size - 1
     nrt, nct = int(row_off[-1]), int(col_off[-1])
     with torch.cuda.device(dev):
-        d = torch.from_numpy(np.concatenate([row_idx, col_idx, row_off, col_off]).astype(np.int64)).to(dev)
-        ri, ci = d[:nrt], d[nrt:nrt + nct]
-        ro, co = d[nrt + nct:nrt + nct + B + 1], d[nrt + nct + B + 1:]
+        ri, ci, ro, co = _lib.ship(dev, row_idx, col_idx, row_off, col_off)
         row_match = torch.empty((nrt,), dtype=torch.int32, device=dev)
         col_match = torch.empty((nct,), dtype=torch.int32, device=dev)
         status = torch.zeros((1,), dtype=torch.int32, device=dev)
@@ -355,7 +361,7 @@ def linear_sum_assignment(cost):
     if B == 0 or k == 0:
         empty = torch.zeros((B, 0) if batched else (0,), dtype=torch.int64)
         return (empty.numpy(), empty.numpy()) if as_numpy else (empty.to(odev), empty.to(odev))
-    dev = odev if t.is_cuda else _lib.require_gpu()
+    dev = device_of(t)
     c = t.to(dev).contiguous().view(B * n, m)
     row_idx = np.arange(B * n, dtype=np.int64)
     col_idx = np.tile(np.arange(m, dtype=np.int64), B)
@@ -384,7 +390,7 @@ def _matrix_on_device(distance):
         raise ValueError("distance should be a [n, m] matrix")
     if t.dtype != torch.float32:
         t = t.to(torch.float32)
-    dev = t.device if t.is_cuda else _lib.require_gpu()
+    dev = device_of(t)
     return t.to(dev).contiguous(), dev
 
 
@@ -400,14 +406,6 @@ def _subset(subset, count, what):
     if s.size and (s.min() < 0 or s.max() >= count):
         raise ValueError("%s holds an index outside 0 .. %d" % (what, count - 1))
     return s
-
-
-def _threshold_of(distance_threshold, tags):
-    """unordered_map<int, float>::operator[] (matcher.pyx:115, :227): a tag missing from the map reads as 0.0"""
-    thr = np.zeros((tags.size,), np.float32)
-    for tag in np.unique(tags):
-        thr[tags == tag] = np.float32(float(distance_threshold.get(int(tag), 0.0)))
-    return thr
 
 
 def _hungarian_problems(stags, dtags, ssub, dsub):
@@ -433,9 +431,7 @@ def hungarian_match(distance, src_tags, dst_tags, distance_threshold, src_subset
     n, m = dist.shape
     stags, dtags = _tags(src_tags, n, "src_tags"), _tags(dst_tags, m, "dst_tags")
     ssub, dsub = _subset(src_subset, n, "src_subset"), _subset(dst_subset, m, "dst_subset")
-    with torch.cuda.device(dev):
-        src_match = torch.full((n,), -1, dtype=torch.int32, device=dev)
-        dst_match = torch.full((m,), -1, dtype=torch.int32, device=dev)
+    src_match, dst_match = _unmatched(dev, n, m)
     rows, cols, classes = _hungarian_problems(stags, dtags, ssub, dsub)
     if not rows:
         return src_match, dst_match
@@ -444,13 +440,10 @@ def hungarian_match(distance, src_tags, dst_tags, distance_threshold, src_subset
     row_off, col_off = np.zeros((len(rows) + 1,), np.int64), np.zeros((len(rows) + 1,), np.int64)
     row_off[1:], col_off[1:] = np.cumsum(nr), np.cumsum(nc)
     row_idx, col_idx = np.concatenate([np.asarray(r, np.int64) for r in rows]), np.concatenate([np.asarray(c, np.int64) for c in cols])
-    thr = np.repeat(np.array([np.float32(float(distance_threshold.get(int(c), 0.0))) for c in classes], np.float32), nr)
+    thr = np.repeat(_threshold_of(distance_threshold, np.asarray(classes, np.int64)), nr)        # (one class per problem)
     row_match, _, status = _lsap_launch(dist, m, row_idx, col_idx, row_off, col_off, int(nr.max()), int(nc.max()), dev)
     with torch.cuda.device(dev):
-        aux = torch.from_numpy(np.concatenate([row_idx, np.repeat(col_off[:-1], nr), thr.view(np.int32).astype(np.int64)])).to(dev)
-        R = row_idx.size
-        ri, cbase, thr_t = aux[:R], aux[R:2 * R], aux[2 * R:].to(torch.int32).view(torch.float32)
-        ci_all = torch.from_numpy(col_idx).to(dev)
+        ri, cbase, thr_t, ci_all = _lib.ship(dev, row_idx, np.repeat(col_off[:-1], nr), thr, col_idx)
         has = row_match >= 0
         cj = ci_all[(cbase + row_match.clamp_min(0).to(torch.int64))]
         ok = has & (dist[ri, cj] <= thr_t)
@@ -473,9 +466,7 @@ def nearest_neighbor_match(distance, src_tags, dst_tags, distance_threshold, src
     n, m = dist.shape
     stags, dtags = _tags(src_tags, n, "src_tags"), _tags(dst_tags, m, "dst_tags")
     ssub, dsub = _subset(src_subset, n, "src_subset"), _subset(dst_subset, m, "dst_subset")
-    with torch.cuda.device(dev):
-        src_match = torch.full((n,), -1, dtype=torch.int32, device=dev)
-        dst_match = torch.full((m,), -1, dtype=torch.int32, device=dev)
+    src_match, dst_match = _unmatched(dev, n, m)
     ns, nd = ssub.size, dsub.size
     if ns == 0 or nd == 0:
         return src_match, dst_match
@@ -484,20 +475,8 @@ def nearest_neighbor_match(distance, src_tags, dst_tags, distance_threshold, src
     thr = _threshold_of(distance_threshold, dt)
     sf = np.ones((ns,), np.uint8) if src_free is None else _host(src_free).reshape(-1).astype(bool)[ssub].astype(np.uint8)
     df = np.ones((nd,), np.uint8) if dst_free is None else _host(dst_free).reshape(-1).astype(bool)[dsub].astype(np.uint8)
-    # one buffer: [src subset i64 | dst subset i64 | src tags i32 | dst tags i32 | thresholds f32 | src free u8 | dst free u8]
-    packed = np.concatenate([ssub.view(np.uint8), dsub.view(np.uint8), st.view(np.uint8), dt.view(np.uint8), thr.view(np.uint8),
-                             sf, df])
     with torch.cuda.device(dev):
-        d = torch.from_numpy(packed).to(dev)
-        o = 0
-        def take(nbytes, dtype):
-            nonlocal o
-            t = d[o:o + nbytes].view(dtype)
-            o += nbytes
-            return t
-        si, di = take(8 * ns, torch.int64), take(8 * nd, torch.int64)
-        st_t, dt_t, thr_t = take(4 * ns, torch.int32), take(4 * nd, torch.int32), take(4 * nd, torch.float32)
-        sf_t, df_t = take(ns, torch.uint8), take(nd, torch.uint8)
+        si, di, st_t, dt_t, thr_t, sf_t, df_t = _lib.ship(dev, ssub, dsub, st, dt, thr, sf, df)      # (one copy)
         sm = torch.empty((ns,), dtype=torch.int32, device=dev)
         dm = torch.empty((nd,), dtype=torch.int32, device=dev)
         ws = _lib.workspace(lib.d3d_nn_match_workspace_bytes(ns, nd), dev)
@@ -510,43 +489,17 @@ def nearest_neighbor_match(distance, src_tags, dst_tags, distance_threshold, src
     return src_match, dst_match
 
 
-class _AssignmentMatcher:
-    """BaseMatcher's array-level state (matcher.pyx:12-136) for the two matchers below.  Unlike ScoreMatcher here, `match`
-    does not clear the assignment first -- as in the reference, a second `match` without clear_match / prepare_boxes adds to
-    it."""
-
-    def __init__(self):
-        self._cache = None
-        self._src = self._dst = None
-        self._src_assignment, self._dst_assignment = {}, {}
-
-    def clear_match(self):
-        self._src_assignment, self._dst_assignment = {}, {}
-
-    def prepare_boxes(self, src_arr, dst_arr, distance_metric):
-        self.clear_match()
-        self._src, self._dst = _boxes(src_arr, "src_boxes"), _boxes(dst_arr, "dst_boxes")
-        if len(self._src) == 0 or len(self._dst) == 0:
-            self._cache = torch.zeros((len(self._src), len(self._dst)), dtype=torch.float32)      # matcher.pyx:41-43
-            return
-        self._cache = prepare_boxes(self._src, self._dst, distance_metric)
-
-    @property
-    def distance_cache(self):
-        return self._cache
+class _AssignmentMatcher(_BaseMatcher):
+    """the base of the two matchers below.  Unlike ScoreMatcher here, `match` does not clear the assignment first -- as in the
+    reference, a second `match` without clear_match / prepare_boxes adds to it --, so the two maps are
+    checked against each other when they are counted."""
 
     def _tags(self):
         return self._src[:, 0].cpu().numpy().astype(np.int64), self._dst[:, 0].cpu().numpy().astype(np.int64)
 
-    def query_src_match(self, src_idx):
-        return self._src_assignment.get(int(src_idx), -1)
-
-    def query_dst_match(self, dst_idx):
-        return self._dst_assignment.get(int(dst_idx), -1)
-
     def num_of_matches(self):
         assert len(self._src_assignment) == len(self._dst_assignment)
-        return len(self._src_assignment)
+        return super().num_of_matches()
 
 
 class NearestNeighborMatcher(_AssignmentMatcher):
