@@ -38,16 +38,60 @@ one GPU at config 5's full size, and RCCL (backend "nccl") with one rank.  `tool
 (assumed link and latency constants) next to both single-GPU bases.
 """
 import ctypes
+from itertools import accumulate
 
 import torch
 
-from .. import _lib
+from . import DenseOutputBuffer
+from .. import _lib, options
 from ..utils import Dict
 
 _REDUCTIONS = {"MEAN": 1, "MAX": 2, "MIN": 3}
 _SUM = 4
-_I64_MAX = (1 << 63) - 1
 _MAX_OWNER_WORLD = 16      # kMaxOwnerWorld of grid.hip
+
+
+# ---- what the HipOps methods and the two exchanges share ----
+def _d3d(name):
+    return getattr(_lib.load(), "d3d_" + name)
+
+
+def _call(name, *args):
+    """d3d_<name>(*args); any status but OK raises under the label `name` (_lib.check)"""
+    _lib.check(_d3d(name)(*args), name)
+
+
+def _shape_host(shape):
+    """the grid's shape as the host int32[3] the C entry points read"""
+    return (ctypes.c_int32 * 3)(*[int(x) for x in shape])
+
+
+def _prefix(counts):
+    """[k0, k1, ...] -> [0, k0, k0 + k1, ..., total]"""
+    return list(accumulate((int(k) for k in counts), initial=0))
+
+
+def _status_of(words):
+    """the ranks' status words as they travel in a key slot (-1 - status bits each) -> the bits, OR-ed"""
+    status = 0
+    for w in words:
+        status |= -1 - int(w)
+    return status
+
+
+def _voxel_rows(nvox, c, dev, vid=False):
+    """-> uninitialised coords[nvox, 3] i64, cnt[nvox] i32, feats[nvox, c] f32 (, vid[nvox] i64)"""
+    out = (torch.empty((nvox, 3), dtype=torch.int64, device=dev), torch.empty((nvox,), dtype=torch.int32, device=dev),
+           torch.empty((nvox, c), dtype=torch.float32, device=dev))
+    return out + (torch.empty((nvox,), dtype=torch.int64, device=dev),) if vid else out
+
+
+def _redo_on_general_path(status):
+    """the one rule for the status bits of the local passes, OR-ed over the ranks: -> whether every rank repeats the call"""
+    if status & _lib.STATUS_TABLE_FULL:
+        raise RuntimeError("voxelize_3d_reduce: internal hash table overflow")
+    # a voxel outgrew the packed slot counter, or a bucket of the binned index its workgroup: redo on the general path
+    return bool(status & (_lib.STATUS_PACK_OVERFLOW | _lib.STATUS_BIN_OVERFLOW))
 
 
 class TorchComm:
@@ -135,11 +179,9 @@ class HipOps:
         """-> coords[n,3], cnt[n], agg[n,c], first[n], mapping[n], keys[n], counts[4] -- all on the device and all
         sized for n voxels; only the first counts[0] rows are meaningful.  keys has n + 1 entries: -1 beyond the
         voxels, and keys[n] = -1 - status bits (so the status reaches every rank with the key all-gather)."""
-        lib = _lib.load()
         pts = points.contiguous()
         dev = pts.device
         n, c = pts.shape
-        shape_h = (ctypes.c_int32 * 3)(*[int(x) for x in shape])
         bound_h = (ctypes.c_float * 6)(*[float(x) for x in bounds])
         with torch.cuda.device(dev):
             coords = torch.empty((n, 3), dtype=torch.int64, device=dev) if want_coords else None
@@ -152,17 +194,15 @@ class HipOps:
             seg = rows = None
             if max_points:     # dense contract: every voxel's first min(count, max_points) rows, in point order
                 seg = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
-                rows = torch.empty((lib.d3d_voxelize_reduce_rows(n), 4), dtype=torch.float32, device=dev)
-            ws = _lib.workspace(lib.d3d_voxelize_workspace_bytes(n, 0), dev)
-            from .. import options
+                rows = torch.empty((_d3d("voxelize_reduce_rows")(n), 4), dtype=torch.float32, device=dev)
+            ws = _lib.workspace(_d3d("voxelize_workspace_bytes")(n, 0), dev)
             flags = options.current().voxel_flags
             if plain:      # the retry after a status overflow: general slots in the hash table (no bucket capacity to outgrow)
                 flags |= _lib.VOXEL_PATH_HASH | _lib.VOXEL_PLAIN_SLOTS
-            rc = lib.d3d_voxelize_3d_reduce(
-                _lib.ptr(pts), n, c, ctypes.cast(shape_h, ctypes.c_void_p), ctypes.cast(bound_h, ctypes.c_void_p),
-                int(reduction), int(index_offset), _lib.ptr(coords), _lib.ptr(cnt), _lib.ptr(agg), _lib.ptr(first),
-                _lib.ptr(mapping), _lib.ptr(keys), int(max_points), _lib.ptr(seg), _lib.ptr(rows), _lib.ptr(counts), _lib.ptr(ws),
-                ws.numel(), _lib.stream_ptr(), flags)
+            rc = _d3d("voxelize_3d_reduce")(
+                _lib.ptr(pts), n, c, _shape_host(shape), bound_h, int(reduction), int(index_offset), _lib.ptr(coords),
+                _lib.ptr(cnt), _lib.ptr(agg), _lib.ptr(first), _lib.ptr(mapping), _lib.ptr(keys), int(max_points), _lib.ptr(seg),
+                _lib.ptr(rows), _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), flags)
             if rc == _lib.ERR_UNSUPPORTED and max_points:
                 raise ValueError("the sharded dense contract needs points[n, 4] float32, 16-byte aligned")
             _lib.check(rc, "voxelize_3d_reduce")
@@ -176,33 +216,26 @@ class HipOps:
         """-> (handle, number of distinct keys, status bits OR-ed over the ranks); handle feeds build_table.
         Negative keys are ignored; with status_stride, every status_stride-th key (the last of each rank's block)
         is a status row.  Reading the total is THE host synchronisation of a sharded call."""
-        lib = _lib.load()
         dev = keys.device
         keys = keys.contiguous()
         with torch.cuda.device(dev):
-            ws = torch.empty((lib.d3d_grid_compact_workspace_bytes(ncells),), dtype=torch.uint8, device=dev)
+            ws = torch.empty((_d3d("grid_compact_workspace_bytes")(ncells),), dtype=torch.uint8, device=dev)
             counts = torch.empty((_lib.NUM_COUNTS,), dtype=torch.int64, device=dev)
-            rc = lib.d3d_grid_compact_index(_lib.ptr(keys), keys.numel(), int(ncells), _lib.ptr(counts), _lib.ptr(ws),
-                                            ws.numel(), _lib.stream_ptr())
-            _lib.check(rc, "grid_compact_index")
+            _call("grid_compact_index", _lib.ptr(keys), keys.numel(), int(ncells), _lib.ptr(counts), _lib.ptr(ws), ws.numel(),
+                  _lib.stream_ptr())
             if status_stride:
                 host = torch.cat([counts[:1], keys[status_stride - 1::status_stride]]).tolist()
             else:
                 host = counts[:1].tolist()
-        status = 0
-        for flag in host[1:]:
-            status |= -1 - int(flag)
-        return (ws, int(ncells)), int(host[0]), status
+        return (ws, int(ncells)), int(host[0]), _status_of(host[1:])
 
     def bitmap_mark(self, keys, n, ncells):
         """this rank's occupancy bitmap as int64 words + one trailing status word (keys[n] = -1 - status bits)"""
-        lib = _lib.load()
         dev = keys.device
         nw = (int(ncells) + 63) // 64
         with torch.cuda.device(dev):
             part = torch.empty((nw + 1,), dtype=torch.int64, device=dev)
-            rc = lib.d3d_grid_bitmap_mark(_lib.ptr(keys), int(n), int(ncells), _lib.ptr(part), _lib.stream_ptr())
-            _lib.check(rc, "grid_bitmap_mark")
+            _call("grid_bitmap_mark", _lib.ptr(keys), int(n), int(ncells), _lib.ptr(part), _lib.stream_ptr())
             part[nw:] = keys[n:n + 1]
         return part
 
@@ -210,29 +243,22 @@ class HipOps:
         """-> (handle, number of occupied cells, status bits OR-ed over the ranks) from the all-gathered bitmaps;
         the host read-back of a sharded call in bitmap mode.  With `rank` the handle also carries the ownership
         bookkeeping (cells a lower rank has, cells owned per rank) that build_table_owned needs."""
-        lib = _lib.load()
         dev = parts_all.device
         nw = (int(ncells) + 63) // 64
         with torch.cuda.device(dev):
-            ws = torch.empty((lib.d3d_grid_compact_workspace_bytes(ncells),), dtype=torch.uint8, device=dev)
+            ws = torch.empty((_d3d("grid_compact_workspace_bytes")(ncells),), dtype=torch.uint8, device=dev)
             ows = None
             if rank is not None:
-                ows = torch.empty((lib.d3d_grid_owner_workspace_bytes(ncells),), dtype=torch.uint8, device=dev)
+                ows = torch.empty((_d3d("grid_owner_workspace_bytes")(ncells),), dtype=torch.uint8, device=dev)
             counts = torch.empty((_lib.NUM_COUNTS,), dtype=torch.int64, device=dev)
-            rc = lib.d3d_grid_compact_from_bitmaps(_lib.ptr(parts_all), nw + 1, int(world), int(ncells), _lib.ptr(counts),
-                                                   _lib.ptr(ws), ws.numel(), int(rank or 0), _lib.ptr(ows),
-                                                   ows.numel() if ows is not None else 0, _lib.stream_ptr())
-            _lib.check(rc, "grid_compact_from_bitmaps")
+            _call("grid_compact_from_bitmaps", _lib.ptr(parts_all), nw + 1, int(world), int(ncells), _lib.ptr(counts), _lib.ptr(ws),
+                  ws.numel(), int(rank or 0), _lib.ptr(ows), ows.numel() if ows is not None else 0, _lib.stream_ptr())
             host = torch.cat([counts[:1], parts_all[nw::nw + 1]]).tolist()
-        status = 0
-        for flag in host[1:]:
-            status |= -1 - int(flag)
-        return (ws, int(ncells), ows), int(host[0]), status
+        return (ws, int(ncells), ows), int(host[0]), _status_of(host[1:])
 
     def build_table_owned(self, handle, keys_local, n_local, nvox, c, reduction, agg, cnt, rank):
         """identity-filled all-reduce operand with this rank's partial rows in place and, for the voxels this rank owns,
         the global voxel id in the last column: -> table[nvox, c + 2 | c + 1], cnt_table[nvox] | None, slot_of_local"""
-        lib = _lib.load()
         ws, ncells, ows = handle
         dev = keys_local.device
         mean = int(reduction) == 1
@@ -241,43 +267,31 @@ class HipOps:
             cnt_t = None if mean else torch.empty((nvox,), dtype=torch.int32, device=dev)
             slot = torch.empty((n_local,), dtype=torch.int64, device=dev)
             sws = torch.empty(((n_local // 1024 + 2) * 8 + 1024,), dtype=torch.uint8, device=dev)
-            rc = lib.d3d_sharded_scatter_owned(_lib.ptr(keys_local), int(n_local), ncells, _lib.ptr(ws), ws.numel(),
-                                               _lib.ptr(ows), ows.numel(), int(rank), int(nvox), int(c), int(reduction),
-                                               _lib.ptr(agg), _lib.ptr(cnt), _lib.ptr(table), table.shape[1], _lib.ptr(cnt_t),
-                                               _lib.ptr(slot), _lib.ptr(sws), sws.numel(), _lib.stream_ptr())
-            _lib.check(rc, "sharded_scatter_owned")
+            _call("sharded_scatter_owned", _lib.ptr(keys_local), int(n_local), ncells, _lib.ptr(ws), ws.numel(), _lib.ptr(ows),
+                  ows.numel(), int(rank), int(nvox), int(c), int(reduction), _lib.ptr(agg), _lib.ptr(cnt), _lib.ptr(table),
+                  table.shape[1], _lib.ptr(cnt_t), _lib.ptr(slot), _lib.ptr(sws), sws.numel(), _lib.stream_ptr())
         return table, cnt_t, slot
 
     def finalize_owned(self, nvox, c, key_of_slot, table, mean, cnt_in, shape):
         """slot-ordered reduced table (id in the last column) -> voxel-id-ordered (coords, counts, features) + vid_of_slot"""
-        lib = _lib.load()
         dev = table.device
-        shape_h = (ctypes.c_int32 * 3)(*[int(x) for x in shape])
         with torch.cuda.device(dev):
-            coords = torch.empty((nvox, 3), dtype=torch.int64, device=dev)
-            cnt = torch.empty((nvox,), dtype=torch.int32, device=dev)
-            feats = torch.empty((nvox, c), dtype=torch.float32, device=dev)
-            vid = torch.empty((nvox,), dtype=torch.int64, device=dev)
-            rc = lib.d3d_sharded_finalize_owned(nvox, c, _lib.ptr(key_of_slot), _lib.ptr(table), table.shape[1],
-                                                1 if mean else 0, _lib.ptr(cnt_in), ctypes.cast(shape_h, ctypes.c_void_p),
-                                                _lib.ptr(vid), _lib.ptr(coords), _lib.ptr(cnt), _lib.ptr(feats),
-                                                _lib.stream_ptr())
-            _lib.check(rc, "sharded_finalize_owned")
+            coords, cnt, feats, vid = _voxel_rows(nvox, c, dev, vid=True)
+            _call("sharded_finalize_owned", nvox, c, _lib.ptr(key_of_slot), _lib.ptr(table), table.shape[1], 1 if mean else 0,
+                  _lib.ptr(cnt_in), _shape_host(shape), _lib.ptr(vid), _lib.ptr(coords), _lib.ptr(cnt), _lib.ptr(feats),
+                  _lib.stream_ptr())
         return coords, cnt, feats, vid
 
     def compact_keys(self, handle, nvox):
-        lib = _lib.load()
         ws, ncells = handle[0], handle[1]
         with torch.cuda.device(ws.device):
             key_of_slot = torch.empty((nvox,), dtype=torch.int64, device=ws.device)
-            rc = lib.d3d_grid_compact_keys(ncells, _lib.ptr(ws), ws.numel(), _lib.ptr(key_of_slot), _lib.stream_ptr())
-            _lib.check(rc, "grid_compact_keys")
+            _call("grid_compact_keys", ncells, _lib.ptr(ws), ws.numel(), _lib.ptr(key_of_slot), _lib.stream_ptr())
         return key_of_slot
 
     def build_table(self, handle, keys_all, begin, n_local, nvox, c, reduction, agg, cnt, first_local, want_keys=True):
         """identity-filled all-reduce operands with this rank's partial rows in place:
         -> table[nvox, c(+1)], cnt_table[nvox] (None for mean), first[nvox], key_of_slot[nvox], slot_of_local[n_local]"""
-        lib = _lib.load()
         ws, ncells = handle[0], handle[1]
         dev = keys_all.device
         mean = int(reduction) == 1
@@ -287,30 +301,22 @@ class HipOps:
             first = torch.empty((nvox,), dtype=torch.int64, device=dev)
             key_of_slot = torch.empty((nvox,), dtype=torch.int64, device=dev) if want_keys else None
             slot = torch.empty((n_local,), dtype=torch.int64, device=dev)
-            rc = lib.d3d_sharded_scatter(_lib.ptr(keys_all), keys_all.numel(), int(begin), int(n_local), ncells, _lib.ptr(ws),
-                                         ws.numel(), int(nvox), int(c), int(reduction), _lib.ptr(agg), _lib.ptr(cnt),
-                                         _lib.ptr(first_local), _lib.ptr(table), table.shape[1], _lib.ptr(cnt_t),
-                                         _lib.ptr(first), _lib.ptr(key_of_slot), _lib.ptr(slot), _lib.stream_ptr())
-            _lib.check(rc, "sharded_scatter")
+            _call("sharded_scatter", _lib.ptr(keys_all), keys_all.numel(), int(begin), int(n_local), ncells, _lib.ptr(ws),
+                  ws.numel(), int(nvox), int(c), int(reduction), _lib.ptr(agg), _lib.ptr(cnt), _lib.ptr(first_local),
+                  _lib.ptr(table), table.shape[1], _lib.ptr(cnt_t), _lib.ptr(first), _lib.ptr(key_of_slot), _lib.ptr(slot),
+                  _lib.stream_ptr())
         return table, cnt_t, first, key_of_slot, slot
 
     def finalize(self, nvox, c, first, n_total, key_of_slot, table, mean, cnt_in, shape):
         """slot-ordered reduced table -> voxel-id-ordered (coords, counts, features) + vid_of_slot"""
-        lib = _lib.load()
         dev = table.device
-        shape_h = (ctypes.c_int32 * 3)(*[int(x) for x in shape])
         with torch.cuda.device(dev):
-            coords = torch.empty((nvox, 3), dtype=torch.int64, device=dev)
-            cnt = torch.empty((nvox,), dtype=torch.int32, device=dev)
-            feats = torch.empty((nvox, c), dtype=torch.float32, device=dev)
-            vid = torch.empty((nvox,), dtype=torch.int64, device=dev)
+            coords, cnt, feats, vid = _voxel_rows(nvox, c, dev, vid=True)
             counts = torch.empty((_lib.NUM_COUNTS,), dtype=torch.int64, device=dev)
-            ws = torch.empty((lib.d3d_grid_compact_workspace_bytes(max(n_total, 1)),), dtype=torch.uint8, device=dev)
-            rc = lib.d3d_sharded_finalize(nvox, c, _lib.ptr(first), int(n_total), _lib.ptr(counts), _lib.ptr(ws), ws.numel(),
-                                          _lib.ptr(key_of_slot), _lib.ptr(table), table.shape[1], 1 if mean else 0,
-                                          _lib.ptr(cnt_in), ctypes.cast(shape_h, ctypes.c_void_p), _lib.ptr(vid),
-                                          _lib.ptr(coords), _lib.ptr(cnt), _lib.ptr(feats), _lib.stream_ptr())
-            _lib.check(rc, "sharded_finalize")
+            ws = torch.empty((_d3d("grid_compact_workspace_bytes")(max(n_total, 1)),), dtype=torch.uint8, device=dev)
+            _call("sharded_finalize", nvox, c, _lib.ptr(first), int(n_total), _lib.ptr(counts), _lib.ptr(ws), ws.numel(),
+                  _lib.ptr(key_of_slot), _lib.ptr(table), table.shape[1], 1 if mean else 0, _lib.ptr(cnt_in), _shape_host(shape),
+                  _lib.ptr(vid), _lib.ptr(coords), _lib.ptr(cnt), _lib.ptr(feats), _lib.stream_ptr())
         return coords, cnt, feats, vid
 
     # ---- owner-computes exchange (owner.hip) ----
@@ -318,9 +324,8 @@ class HipOps:
         """local voxels -> records grouped by owner rank: send[n, words] int32, perm[n] (send position -> local voxel),
         pos_of_local[n] (its inverse), send_rows[n, 4] | None (dense contract: the voxels' ranked rows, same grouping),
         send_counts[2 world + 2] (device: records per destination, status bits, rows per destination, points_in_shard)"""
-        lib = _lib.load()
         dev = keys.device
-        words = lib.d3d_owner_record_words(c)
+        words = _d3d("owner_record_words")(c)
         with torch.cuda.device(dev):
             send = torch.empty((n, words), dtype=torch.int32, device=dev)
             perm = torch.empty((n,), dtype=torch.int32, device=dev)
@@ -330,13 +335,12 @@ class HipOps:
             # that no separate size exchange is needed -- ShardedVoxelGenerator._run_owner)
             sc = torch.empty((2 * world + 2,), dtype=torch.int64, device=dev)
             sc[2 * world + 1:].fill_(int(points_in_shard) if points_in_shard is not None else -1)
-            ws = torch.empty((lib.d3d_owner_pack_workspace_bytes(n, world),), dtype=torch.uint8, device=dev)
+            ws = torch.empty((_d3d("owner_pack_workspace_bytes")(n, world),), dtype=torch.uint8, device=dev)
             src = rows if isinstance(rows, _RowSource) else _RowSource(rows, None, 0)
-            rc = lib.d3d_owner_pack(_lib.ptr(keys), _lib.ptr(cnt), _lib.ptr(agg), _lib.ptr(first), _lib.ptr(counts), n, c, world,
-                                    int(max_points), _lib.ptr(seg), _lib.ptr(src.buf), _lib.ptr(send), _lib.ptr(perm), _lib.ptr(pos),
-                                    _lib.ptr(send_rows), _lib.ptr(sc), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(),
-                                    _lib.ptr(src.points), int(src.index_offset))
-            _lib.check(rc, "owner_pack")
+            _call("owner_pack", _lib.ptr(keys), _lib.ptr(cnt), _lib.ptr(agg), _lib.ptr(first), _lib.ptr(counts), n, c, world,
+                  int(max_points), _lib.ptr(seg), _lib.ptr(src.buf), _lib.ptr(send), _lib.ptr(perm), _lib.ptr(pos),
+                  _lib.ptr(send_rows), _lib.ptr(sc), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), _lib.ptr(src.points),
+                  int(src.index_offset))
         return send, perm, pos, send_rows, sc
 
     def owner_merge(self, recv, recv_counts, world, c, reduction, shape, flags=0, point_off=None):
@@ -345,142 +349,102 @@ class HipOps:
         BIN_OVERFLOW asks for flags=OWNER_MERGE_CHAINS), and a handle (leader records + the cells' record lists) for
         owner_dense.  point_off (list of world ints, or None): the records carry point indices LOCAL to their source rank's shard;
         point_off[s] = global index of rank s's first point (added to the leader's index: first_o is global either way)"""
-        lib = _lib.load()
         dev = recv.device
         R = int(recv.shape[0])
-        off = [0]
-        for k in recv_counts:
-            off.append(off[-1] + int(k))
-        shape_h = (ctypes.c_int32 * 3)(*[int(x) for x in shape])
         with torch.cuda.device(dev):
             # record offsets and (optionally) point offsets of the sources: ONE small host -> device copy
-            both = torch.tensor(off + ([int(x) for x in point_off] if point_off is not None else []), dtype=torch.int64, device=dev)
+            both = torch.tensor(_prefix(recv_counts) + ([int(x) for x in point_off] if point_off is not None else []),
+                                dtype=torch.int64, device=dev)
             src_off = both[:world + 1]
             poff = both[world + 1:] if point_off is not None else None
             first_o = torch.empty((R,), dtype=torch.int64, device=dev)
-            coords = torch.empty((R, 3), dtype=torch.int64, device=dev)
-            npoints = torch.empty((R,), dtype=torch.int32, device=dev)
-            feats = torch.empty((R, c), dtype=torch.float32, device=dev)
+            coords, npoints, feats = _voxel_rows(R, c, dev)
             rec_owned = torch.empty((R,), dtype=torch.int32, device=dev)
             lead = torch.empty((R,), dtype=torch.int32, device=dev)
             counts = torch.empty((_lib.NUM_COUNTS,), dtype=torch.int64, device=dev)
-            ws = torch.empty((lib.d3d_owner_merge_workspace_bytes(R, world),), dtype=torch.uint8, device=dev)   # kept for owner_dense
-            rc = lib.d3d_owner_merge(_lib.ptr(recv), R, _lib.ptr(src_off), world, c, int(reduction),
-                                     ctypes.cast(shape_h, ctypes.c_void_p), _lib.ptr(first_o), _lib.ptr(coords), _lib.ptr(npoints),
-                                     _lib.ptr(feats), _lib.ptr(rec_owned), _lib.ptr(lead), _lib.ptr(counts), _lib.ptr(ws), ws.numel(),
-                                     _lib.stream_ptr(), int(flags), _lib.ptr(poff))
-            _lib.check(rc, "owner_merge")
+            ws = torch.empty((_d3d("owner_merge_workspace_bytes")(R, world),), dtype=torch.uint8, device=dev)   # kept for owner_dense
+            _call("owner_merge", _lib.ptr(recv), R, _lib.ptr(src_off), world, c, int(reduction), _shape_host(shape),
+                  _lib.ptr(first_o), _lib.ptr(coords), _lib.ptr(npoints), _lib.ptr(feats), _lib.ptr(rec_owned), _lib.ptr(lead),
+                  _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), int(flags), _lib.ptr(poff))
         return first_o, coords, npoints, feats, rec_owned, counts, (recv, lead, npoints, counts, ws, world, int(flags))
 
     def owner_dense(self, handle, recv_rows, recv_row_counts, max_points, resident=None):
         """the dense contract of the owned voxels (id order): voxels[R, max_points, 4], pmask[R, max_points] uint8.
         resident: a d3d_amd.voxel.DenseOutputBuffer of at least R voxels -- `voxels` is then that buffer"""
-        lib = _lib.load()
         recv, lead, npoints, counts, ws, world, flags = handle
         dev = recv.device
         R = int(recv.shape[0])
-        off = [0]
-        for k in recv_row_counts:
-            off.append(off[-1] + int(k))
         with torch.cuda.device(dev):
-            roff = torch.tensor(off, dtype=torch.int64, device=dev)
+            roff = torch.tensor(_prefix(recv_row_counts), dtype=torch.int64, device=dev)
             if resident is not None and (resident.capacity < R or resident.max_points != int(max_points) or resident.device != dev):
                 raise ValueError("resident output: capacity, max_points or device do not fit")
             voxels = resident.voxels if resident is not None else torch.empty((R, max_points, 4), dtype=torch.float32, device=dev)
             pmask = torch.empty((R, max_points), dtype=torch.uint8, device=dev)
-            rc = lib.d3d_owner_dense(_lib.ptr(recv), R, _lib.ptr(recv_rows), _lib.ptr(roff), world, int(max_points), _lib.ptr(lead),
-                                     _lib.ptr(npoints), _lib.ptr(counts), R, _lib.ptr(ws), ws.numel(), _lib.ptr(voxels),
-                                     _lib.ptr(pmask), _lib.stream_ptr(), flags,
-                                     _lib.ptr(resident.row_state) if resident is not None else None)
-            _lib.check(rc, "owner_dense")
+            _call("owner_dense", _lib.ptr(recv), R, _lib.ptr(recv_rows), _lib.ptr(roff), world, int(max_points), _lib.ptr(lead),
+                  _lib.ptr(npoints), _lib.ptr(counts), R, _lib.ptr(ws), ws.numel(), _lib.ptr(voxels), _lib.ptr(pmask),
+                  _lib.stream_ptr(), flags, _lib.ptr(resident.row_state) if resident is not None else None)
         return voxels, pmask
 
     def owner_mark_first(self, first_o, counts_o, n_total):
         """-> int64 words of the bitmap over the frame's point indices with this owner's first points set, + one word: this
         owner's merge has to be repeated (summed over the ranks by the same all-reduce)"""
-        lib = _lib.load()
         dev = first_o.device
         with torch.cuda.device(dev):
             bits = torch.empty(((max(n_total, 1) + 63) // 64 + 1,), dtype=torch.int64, device=dev)
-            rc = lib.d3d_owner_mark_first(_lib.ptr(first_o), _lib.ptr(counts_o), first_o.numel(), n_total, _lib.ptr(bits),
-                                          _lib.stream_ptr())
-            _lib.check(rc, "owner_mark_first")
+            _call("owner_mark_first", _lib.ptr(first_o), _lib.ptr(counts_o), first_o.numel(), n_total, _lib.ptr(bits),
+                  _lib.stream_ptr())
         return bits
 
     def owner_number(self, gbits, n_total, first_o, counts_o):
         """-> vids[R] (global id of every owned voxel), counts_out (device; [0] = voxels of the whole frame)"""
-        lib = _lib.load()
         dev = first_o.device
         R = int(first_o.numel())
         with torch.cuda.device(dev):
             vids = torch.empty((R,), dtype=torch.int64, device=dev)
             counts = torch.empty((_lib.NUM_COUNTS,), dtype=torch.int64, device=dev)
-            ws = _lib.workspace(lib.d3d_owner_number_workspace_bytes(n_total), dev)
-            rc = lib.d3d_owner_number(_lib.ptr(gbits), n_total, _lib.ptr(first_o), _lib.ptr(counts_o), R, _lib.ptr(vids),
-                                      _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
-            _lib.check(rc, "owner_number")
+            ws = _lib.workspace(_d3d("owner_number_workspace_bytes")(n_total), dev)
+            _call("owner_number", _lib.ptr(gbits), n_total, _lib.ptr(first_o), _lib.ptr(counts_o), R, _lib.ptr(vids),
+                  _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
         return vids, counts
 
     def owner_reply(self, rec_owned, vids):
-        lib = _lib.load()
         R = int(rec_owned.numel())
         with torch.cuda.device(rec_owned.device):
             reply = torch.empty((R,), dtype=torch.int64, device=rec_owned.device)
-            _lib.check(lib.d3d_owner_reply(R, _lib.ptr(rec_owned), _lib.ptr(vids), _lib.ptr(reply), _lib.stream_ptr()),
-                       "owner_reply")
+            _call("owner_reply", R, _lib.ptr(rec_owned), _lib.ptr(vids), _lib.ptr(reply), _lib.stream_ptr())
         return reply
 
     def owner_map(self, local_map, pos_of_local, back):
-        lib = _lib.load()
         dev = local_map.device
         n = int(local_map.numel())
         with torch.cuda.device(dev):
             gmap = torch.empty((n,), dtype=torch.int64, device=dev)
-            _lib.check(lib.d3d_owner_map(n, _lib.ptr(local_map), _lib.ptr(pos_of_local), _lib.ptr(back), _lib.ptr(gmap),
-                                         _lib.stream_ptr()), "owner_map")
+            _call("owner_map", n, _lib.ptr(local_map), _lib.ptr(pos_of_local), _lib.ptr(back), _lib.ptr(gmap), _lib.stream_ptr())
         return gmap
 
     def owner_replicate(self, nvox, vids, coords_in, cnt_in, feats_in, sizes=None):
         """rows of all owners -> voxel-id order.  sizes: rows per rank when the rows are the ranks' blocks in rank order, each
         ascending in id (the all-gather's layout): merged with coalesced accesses instead of scattered row by row"""
-        lib = _lib.load()
         dev = vids.device
         c = int(feats_in.shape[1])
         with torch.cuda.device(dev):
             src_off = ws = None
             if sizes is not None:
-                off = [0]
-                for k in sizes:
-                    off.append(off[-1] + int(k))
-                src_off = torch.tensor(off, dtype=torch.int64, device=dev)
+                src_off = torch.tensor(_prefix(sizes), dtype=torch.int64, device=dev)
                 ws = torch.empty(((nvox // 1024 + 2) * len(sizes),), dtype=torch.int64, device=dev)
-            coords = torch.empty((nvox, 3), dtype=torch.int64, device=dev)
-            cnt = torch.empty((nvox,), dtype=torch.int32, device=dev)
-            feats = torch.empty((nvox, c), dtype=torch.float32, device=dev)
-            _lib.check(lib.d3d_owner_replicate(nvox, _lib.ptr(vids), _lib.ptr(coords_in), _lib.ptr(cnt_in), _lib.ptr(feats_in), c,
-                                               _lib.ptr(coords), _lib.ptr(cnt), _lib.ptr(feats), _lib.stream_ptr(),
-                                               _lib.ptr(src_off), len(sizes) if sizes is not None else 0,
-                                               _lib.ptr(ws), ws.numel() * 8 if ws is not None else 0),
-                       "owner_replicate")
+            coords, cnt, feats = _voxel_rows(nvox, c, dev)
+            _call("owner_replicate", nvox, _lib.ptr(vids), _lib.ptr(coords_in), _lib.ptr(cnt_in), _lib.ptr(feats_in), c,
+                  _lib.ptr(coords), _lib.ptr(cnt), _lib.ptr(feats), _lib.stream_ptr(), _lib.ptr(src_off),
+                  len(sizes) if sizes is not None else 0, _lib.ptr(ws), ws.numel() * 8 if ws is not None else 0)
         return coords, cnt, feats
 
     def compose_map(self, local_map, slot_of_local, nvox, vid_of_slot):
-        lib = _lib.load()
         dev = local_map.device
         with torch.cuda.device(dev):
             gmap = torch.empty_like(local_map)
-            rc = lib.d3d_sharded_map(local_map.numel(), _lib.ptr(local_map), _lib.ptr(slot_of_local), nvox,
-                                     _lib.ptr(vid_of_slot), _lib.ptr(gmap), _lib.stream_ptr())
-            _lib.check(rc, "sharded_map")
+            _call("sharded_map", local_map.numel(), _lib.ptr(local_map), _lib.ptr(slot_of_local), nvox, _lib.ptr(vid_of_slot),
+                  _lib.ptr(gmap), _lib.stream_ptr())
         return gmap
-
-
-def _status_retry(counts_host):
-    status = int(counts_host[_lib.COUNT_STATUS])
-    if status & _lib.STATUS_TABLE_FULL:
-        raise RuntimeError("voxelize_3d_reduce: internal hash table overflow")
-    # a voxel outgrew the packed slot counter, or a bucket of the binned index its workgroup: redo on the general path
-    return bool(status & (_lib.STATUS_PACK_OVERFLOW | _lib.STATUS_BIN_OVERFLOW))
 
 
 def voxelize_reduce(points, shape, bounds, reduction="mean"):
@@ -489,7 +453,7 @@ def voxelize_reduce(points, shape, bounds, reduction="mean"):
     ops = HipOps()
     out = ops.voxelize_reduce(points, shape, bounds, red, 0)
     host = out[6].cpu()
-    if _status_retry(host):
+    if _redo_on_general_path(int(host[_lib.COUNT_STATUS])):
         out = ops.voxelize_reduce(points, shape, bounds, red, 0, plain=True)
         host = out[6].cpu()
     v = int(host[_lib.COUNT_VOXELS])
@@ -571,6 +535,14 @@ class ShardedVoxelGenerator:
                 return out
         raise RuntimeError("sharded voxelization failed")
 
+    def _local_pass(self, points, index_offset, plain, **kw):
+        """step 1 of either exchange: partial SUM (for mean) / MAX / MIN on this rank's shard; the ops see `plain` on the repeat
+        only"""
+        if plain:
+            kw["plain"] = True
+        return self._ops.voxelize_reduce(points, self._shape, self._bounds, _SUM if self._red == 1 else self._red, index_offset,
+                                         **kw)
+
     def _run_owner(self, points, plain):
         """owner-computes exchange (module docstring).  FOUR collectives (five with the dense contract's rows) and TWO host
         synchronisations per call: the count matrix -- which since round 5 also carries every shard's point count, so the local
@@ -579,53 +551,43 @@ class ShardedVoxelGenerator:
         dev = points.device
         n, c = points.shape
         W = comm.world
-        mean = self._red == 1
-        kw = {"plain": True} if plain else {}
         P = self._max_points
         if P and c != 4:
             raise ValueError("the sharded dense contract needs points[n, 4]")
-        out = ops.voxelize_reduce(points, self._shape, self._bounds, _SUM if mean else self._red, 0, want_coords=False,
-                                  max_points=P, **kw)                  # (first points as indices into THIS shard)
+        out = self._local_pass(points, 0, plain, want_coords=False, max_points=P)    # (first points as indices into THIS shard)
         _, cnt_r, agg_r, first_r, map_r, keys_r, counts_r = out[:7]
         seg_r, rows_r = out[7:] if P else (None, None)
         send, perm, pos_r, send_rows, sc_dev = ops.owner_pack(keys_r, cnt_r, agg_r, first_r, counts_r, n, c, W, P, seg_r, rows_r,
                                                               points_in_shard=n)
         # [src][dst] records, [src][W] status bits, [src][W+1+dst] rows, [src][2W+1] points of the shard -- host sync 1 of 2
-        mat = comm.exchange_counts(sc_dev)
-        shard = [int(row[2 * W + 1]) for row in mat]
-        if min(shard) < 0:
+        mat = [[int(x) for x in row] for row in comm.exchange_counts(sc_dev)]
+        mine, col = mat[comm.rank], [list(column) for column in zip(*mat)]       # what this rank sends / what it receives
+        if min(col[2 * W + 1]) < 0:
             raise RuntimeError("owner_pack of some rank did not report its shard size (an `ops` of the round-4 protocol?)")
-        point_off = [0] * W
-        for r in range(1, W):
-            point_off[r] = point_off[r - 1] + shard[r - 1]
-        n_total = point_off[-1] + shard[-1]
+        point_off = _prefix(col[2 * W + 1])       # [r] = global index of rank r's first point, [W] = points of the frame
+        n_total = point_off.pop()
         status = 0
-        for row in mat:
-            status |= int(row[W])
-        if status & _lib.STATUS_TABLE_FULL:
-            raise RuntimeError("voxelize_3d_reduce: internal hash table overflow")
-        if status & (_lib.STATUS_PACK_OVERFLOW | _lib.STATUS_BIN_OVERFLOW) and not plain:
+        for bits in col[W]:
+            status |= bits
+        if _redo_on_general_path(status) and not plain:
             return None        # some rank hit a capacity limit of the fast index (rare): all ranks redo on the general path
-        sc = [int(x) for x in mat[comm.rank][:W]]
-        rc = [int(mat[s][comm.rank]) for s in range(W)]
+        sc, rc = mine[:W], col[comm.rank]
         recv = comm.all_to_all(send[:sum(sc)], sc, rc)
         first_o, coords, npoints, feats, rec_owned, counts_o, handle = ops.owner_merge(
             recv, rc, W, c, self._red, self._shape, flags=self._merge_flags | (_lib.OWNER_MERGE_CHAINS if plain else 0),
             point_off=point_off)
         voxels = pmask = None
         if P:
-            rsc = [int(x) for x in mat[comm.rank][W + 1:2 * W + 1]]
-            rrc = [int(mat[s][W + 1 + comm.rank]) for s in range(W)]
+            rsc, rrc = mine[W + 1:2 * W + 1], col[W + 1 + comm.rank]
             recv_rows = comm.all_to_all(send_rows[:sum(rsc)], rsc, rrc)
+            into = {}          # (`resident` goes along only with a buffer: an `ops` written before round 6 has no such parameter)
             if self._resident:
-                from . import DenseOutputBuffer
                 buf, need = self._resident_buf, int(recv.shape[0])        # (rows are indexed by owned voxel id < records received)
                 if buf is None or buf.capacity < need or buf.device != recv.device:
                     grow = need if buf is None else max(need, buf.capacity + buf.capacity // 4)
                     buf = self._resident_buf = DenseOutputBuffer(grow, P, recv.device)
-                voxels, pmask = ops.owner_dense(handle, recv_rows, rrc, P, resident=buf)
-            else:
-                voxels, pmask = ops.owner_dense(handle, recv_rows, rrc, P)
+                into["resident"] = buf
+            voxels, pmask = ops.owner_dense(handle, recv_rows, rrc, P, **into)
         lbits = ops.owner_mark_first(first_o, counts_o, n_total)
         gbits = comm.all_reduce(lbits, "sum")                   # disjoint bit sets: their sum is their OR
         vids, counts_out = ops.owner_number(gbits, n_total, first_o, counts_o)
@@ -647,11 +609,11 @@ class ShardedVoxelGenerator:
             # all_reduce is not an int64 SUM (the lock-step redo rests on every rank reading the same word)
             if int(gbits.numel()) == (max(n_total, 1) + 63) // 64 + 1:       # (HipOps: one status word behind the bitmap)
                 assert 0 <= int(gbits[-1]) <= W, "all_reduce('sum') of the first-point bitmap did not add the ranks' status words"
-        if self._debug_checks and nown > 1:
-            fo = first_o[:nown]
-            assert bool((fo[1:] > fo[:-1]).all()), "owned voxels are not ordered by their first point"
-            assert bool((vids[1:] > vids[:-1]).all()), "global voxel ids of the owned voxels are not ascending"
-            assert 0 <= int(fo[0]) and int(fo[-1]) < n_total, "first-point index outside the frame"
+            if nown > 1:
+                fo = first_o[:nown]
+                assert bool((fo[1:] > fo[:-1]).all()), "owned voxels are not ordered by their first point"
+                assert bool((vids[1:] > vids[:-1]).all()), "global voxel ids of the owned voxels are not ascending"
+                assert 0 <= int(fo[0]) and int(fo[-1]) < n_total, "first-point index outside the frame"
         if P:
             voxels, pmask = voxels[:nown], pmask[:nown].view(torch.bool)
             self.last_stats["rows_all_to_all_bytes_sent"] = (sum(rsc) - rsc[comm.rank]) * 16
@@ -685,70 +647,59 @@ class ShardedVoxelGenerator:
         offset, n_total, cap = self._layout(n, dev)
         mean = self._red == 1
         # 1. local hash + partial reduction; nothing is read back: rows >= V_r carry key -1, row n the status
-        kw = {"plain": True} if plain else {}
-        _, cnt_r, agg_r, first_r, map_r, keys_r, _ = ops.voxelize_reduce(
-            points, self._shape, self._bounds, _SUM if mean else self._red, offset, **kw)
+        _, cnt_r, agg_r, first_r, map_r, keys_r, _ = self._local_pass(points, offset, plain)
         nw = (self._ncells + 63) // 64
         # auto: bitmaps when the grid's bitmap is not larger than a key list (KITTI-size grids), else key lists
         bitmap_mode = self._exchange == "bitmap" or (self._exchange == "auto" and nw <= cap + 1)
-        owned = False
+        by_owner = False       # numbering by ownership (bitmaps only) instead of by the voxels' first point indices
         if bitmap_mode:
             # 2b. all-gather the ranks' occupancy bitmaps (+ status word); 3b. OR them: a streaming pass instead of
             #     one atomic per gathered key, and the keys of the slots fall out of the merged bitmap
             part = ops.bitmap_mark(keys_r, n, self._ncells)
             parts_all = comm.all_gather_var(part, [nw + 1] * comm.world)
-            owned = comm.world <= _MAX_OWNER_WORLD
+            by_owner = comm.world <= _MAX_OWNER_WORLD
             handle, nvox, status = ops.compact_from_bitmaps(parts_all, comm.world, self._ncells,
-                                                            rank=comm.rank if owned else None)
-            owned = owned and nvox < (1 << 24)         # voxel ids travel in an fp32 column of the table
+                                                            rank=comm.rank if by_owner else None)
+            by_owner = by_owner and nvox < (1 << 24)         # voxel ids travel in an fp32 column of the table
         else:
             # 2. all-gather the occupied-cell keys (+ status row), padded to the largest shard
             pad = keys_r if n == cap else torch.cat([keys_r[:n], keys_r.new_full((cap - n,), -1), keys_r[n:]])
             keys_all = comm.all_gather_var(pad, [cap + 1] * comm.world)
             # 3. identical compact slots on every rank; the one host read-back: global voxel count + every rank's status
             handle, nvox, status = ops.compact_index(keys_all, self._ncells, status_stride=cap + 1)
-        if status & _lib.STATUS_TABLE_FULL:
-            raise RuntimeError("voxelize_3d_reduce: internal hash table overflow")
-        if status & (_lib.STATUS_PACK_OVERFLOW | _lib.STATUS_BIN_OVERFLOW) and not plain:
+        if _redo_on_general_path(status) and not plain:
             return None        # some rank hit a capacity limit of the fast index (rare): all ranks redo on the general path
         # what this call moves between the ranks (bytes each rank contributes / receives; bench.py reports them)
-        tcols = (c + 2 if bitmap_mode and owned else c + 1) if mean else (c + 1 if bitmap_mode and owned else c)
+        tcols = c + int(mean) + int(by_owner)
         self.last_stats = dict(
-            exchange="bitmap" if bitmap_mode else "keys", numbering="ownership" if bitmap_mode and owned else "first-index",
+            exchange="bitmap" if bitmap_mode else "keys", numbering="ownership" if by_owner else "first-index",
             voxels=nvox, ranks=comm.world,
             all_gather_bytes_per_rank=8 * ((nw + 1) if bitmap_mode else (cap + 1)),
-            all_reduce_bytes=nvox * (4 * tcols + (0 if mean else 4) + (0 if bitmap_mode and owned else 8)))
-        # 4. all-reduce the compact voxel table
-        if bitmap_mode and owned:
-            # numbering by ownership: the lowest rank that has a cell holds its first point, so the voxel ids follow from
-            # the bitmaps and every rank's local order; they ride in an extra column of the table -- no first-index exchange
-            key_of_slot = ops.compact_keys(handle, nvox)
+            all_reduce_bytes=nvox * (4 * tcols + (0 if mean else 4) + (0 if by_owner else 8)))
+        # 4. all-reduce the compact voxel table.  The cells of the slots come out of the marked bitmap in one streaming pass
+        key_of_slot = ops.compact_keys(handle, nvox)
+        first = None
+        if by_owner:
+            # the lowest rank that has a cell holds its first point, so the voxel ids follow from the bitmaps and every
+            # rank's local order; they ride in an extra column of the table -- no first-index exchange
             table, cnt_t, slot_r = ops.build_table_owned(handle, keys_r[:n], n, nvox, c, self._red, agg_r, cnt_r, comm.rank)
-            if nvox > 0:
-                comm.all_reduce(table, "sum" if mean else ("max" if self._red == 2 else "min"))
-                if cnt_t is not None:
-                    comm.all_reduce(cnt_t, "sum")
-            coords, out_cnt, out_feats, vid_of_slot = ops.finalize_owned(nvox, c, key_of_slot, table, mean, cnt_t, self._shape)
-            gmap = ops.compose_map(map_r, slot_r, nvox, vid_of_slot)
-            return Dict(coords=coords, voxel_npoints=out_cnt, aggregates=out_feats, points_mapping=gmap)
-        if bitmap_mode:
-            key_of_slot = ops.compact_keys(handle, nvox)
-            table, cnt_t, first, _, slot_r = ops.build_table(handle, keys_r[:n], 0, n, nvox, c, self._red, agg_r, cnt_r,
-                                                             first_r, want_keys=False)
         else:
-            # the cells of the slots come out of the marked bitmap in one streaming pass; only this rank's own voxels need
-            # the per-key lookup (looking all world x cap gathered keys up again cost 8 x the requests at world 8)
-            key_of_slot = ops.compact_keys(handle, nvox)
+            # only this rank's own voxels need the per-key lookup (looking all world x cap gathered keys up again cost 8 x the
+            # requests at world 8)
             table, cnt_t, first, _, slot_r = ops.build_table(handle, keys_r[:n], 0, n, nvox, c, self._red, agg_r, cnt_r,
                                                              first_r, want_keys=False)
         if nvox > 0:
             comm.all_reduce(table, "sum" if mean else ("max" if self._red == 2 else "min"))
             if cnt_t is not None:
                 comm.all_reduce(cnt_t, "sum")
-            comm.all_reduce(first, "min")
-        # 5. first-seen numbering: rank of each voxel's first point index among all first indices
-        coords, out_cnt, out_feats, vid_of_slot = ops.finalize(nvox, c, first, n_total, key_of_slot, table, mean, cnt_t,
-                                                               self._shape)
+            if first is not None:
+                comm.all_reduce(first, "min")
+        if by_owner:
+            coords, out_cnt, out_feats, vid_of_slot = ops.finalize_owned(nvox, c, key_of_slot, table, mean, cnt_t, self._shape)
+        else:
+            # 5. first-seen numbering: rank of each voxel's first point index among all first indices
+            coords, out_cnt, out_feats, vid_of_slot = ops.finalize(nvox, c, first, n_total, key_of_slot, table, mean, cnt_t,
+                                                                   self._shape)
         gmap = ops.compose_map(map_r, slot_r, nvox, vid_of_slot)
         return Dict(coords=coords, voxel_npoints=out_cnt, aggregates=out_feats, points_mapping=gmap)
 
