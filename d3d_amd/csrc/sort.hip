@@ -675,6 +675,8 @@ extern "C" size_t d3d_internal_argsort_i32_bytes(int64_t n) { return argsort_byt
 extern "C" int d3d_internal_argsort_desc_i32(const int32_t *keys, int64_t n, int32_t *order, void *ws, size_t ws_bytes,
                                              hipStream_t st)
 {
+    // (the query is the larger of two carves: the route that n takes may fit into less, and would run where the caller is short)
+    if (n > 0 && ws_bytes < d3d_internal_argsort_i32_bytes(n)) return D3D_ERR_WORKSPACE;
     return argsort_desc<int32_t, int32_t>(keys, n, order, ws, ws_bytes, st);
 }
 

@@ -705,7 +705,8 @@ int d3d_crop_3dp(const float *points, int64_t n, int32_t point_stride, const flo
 
 /* stable descending argsort (the role torch::argsort plays inside the reference's nms2d,
  * nms.cpp:103): keys[n] in `dtype` -> order[n] i64; ties keep ascending index.  The order is torch's:
- * by value (-0 == +0), NaN before every number.  8 k .. 128 k keys: a 4-launch sample sort; other sizes: rocPRIM. */
+ * by value (-0 == +0), NaN before every number.  Up to 2048 keys: one workgroup in LDS; 2049 .. 131072: a 4-launch
+ * sample sort; above: an LSD radix sort. */
 size_t d3d_argsort_desc_workspace_bytes(int64_t n, int32_t dtype);
 int d3d_argsort_desc(const void *keys, int64_t n, int32_t dtype, int64_t *order,
                      void *workspace, size_t workspace_bytes, void *stream);

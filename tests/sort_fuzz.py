@@ -1,23 +1,21 @@
 #!/usr/bin/env python3
-"""d3d_argsort_desc on random sizes across its three size ranges and on adversarial key distributions, against numpy's stable
-order (development aid, not collected by pytest): python tests/sort_fuzz.py [count]"""
+"""d3d_argsort_desc on random sizes across its three size ranges (one workgroup up to 2048 keys, the sample sort up to 131072,
+the radix sort above) and on adversarial key distributions, against expected_order() of tests/sort_reference.py
+(development aid, not collected by pytest): python tests/sort_fuzz.py [count]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np, torch
 from d3d_amd.box import argsort_desc
-
-
-def expected(s):
-    nan = np.isnan(s)
-    return np.lexsort((np.arange(len(s)), -np.where(nan, 0, s), ~nan))
+from sort_reference import SS_BUCKET_CAP, SS_MAX_N, expected_order as expected
 
 
 count = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 bad = 0
 for it in range(count):
     rng = np.random.default_rng(it)
-    n = int(rng.choice([rng.integers(1, 8192), rng.integers(8192, 131073), rng.integers(131073, 400000)], p=[0.2, 0.7, 0.1]))
+    n = int(rng.choice([rng.integers(1, SS_BUCKET_CAP + 1), rng.integers(SS_BUCKET_CAP + 1, SS_MAX_N + 1), rng.integers(SS_MAX_N + 1, 400000),
+                        rng.choice([SS_BUCKET_CAP, SS_MAX_N]) + rng.integers(-2, 3)], p=[0.2, 0.5, 0.1, 0.2]))
     kind = it % 8
     if kind == 0: s = rng.random(n)
     elif kind == 1: s = rng.integers(0, 3, n).astype(np.float64)                 # three distinct values

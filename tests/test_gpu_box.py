@@ -736,9 +736,10 @@ def _expected_order(s):
 @pytest.mark.parametrize("n", [8191, 8192, 8193, 50000, 131072, 131073, (1 << 20) + 3])
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_argsort_desc_bucket_path(n, dtype):
-    """the 8 k .. 128 k range takes the bucket (sample) sort, the sizes around it the library: same order on random keys with
-    ties, on constant / sorted / few-valued inputs (the splitters cut runs of equal keys by index), and on NaN, +-0, +-inf;
-    the library path at the same size agrees entry by entry"""
+    """2049 .. 131072 keys take the bucket (sample) sort (up to 2048: one workgroup in LDS; above: the radix sort): same order
+    on random keys with ties, on constant / sorted / few-valued inputs (the splitters cut runs of equal keys by index), and on
+    NaN, +-0, +-inf; the radix path at the same size agrees entry by entry.  (The routes' own size edges, the other key types
+    and the oversized buckets: tests/test_gpu_sort.py.)"""
     import ctypes
     from d3d_amd import _lib
     from d3d_amd.box import argsort_desc
