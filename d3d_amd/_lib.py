@@ -186,6 +186,12 @@ SIGNATURES = {
     "d3d_knn_weights": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, ctypes.c_double, _vp, _vp]),
     "d3d_knn_interp_forward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp]),
     "d3d_knn_interp_backward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _vp]),
+    # (out_size: host int32[3]; point_offsets, box_offsets: DEVICE int64 arrays)
+    "d3d_roi_grid_max_cells": (_i32, []),
+    "d3d_roi_grid_plan": (ctypes.c_int, [_i64, _i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                         ctypes.POINTER(ctypes.c_int32)]),
+    "d3d_roi_grid_table": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "d3d_table_pool_backward_index": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 KNN_MAX = 64                        # D3D_KNN_MAX
 FPS_ROUTE_LDS, FPS_ROUTE_STREAM = 3, 4

@@ -9,35 +9,7 @@ namespace {
 
 constexpr int kBoxTile = 64;        // boxes staged in LDS at a time
 
-struct Box3 {
-    BoxGeom<float> g;
-    float zlo, zhi;
-};
-
-// a box row is (x, y, z, lx, ly, lz, rz) at boxes + i * stride + offset  ([M,7] arrays: stride 7, offset 0; the [n,9] rows of
-// Target3DArray.to_numpy -- label, score, x, y, z, lx, ly, lz, yaw: stride 9, offset 2)
-__device__ __forceinline__ Box3 load_box3(const float *__restrict__ b)
-{
-    Box3 r;
-    r.g = make_geom<float>(b[0], b[1], b[3], b[4], b[6]);
-    r.zhi = b[2] + b[5] / 2;        // dgal_wrap.h:12, fp32
-    r.zlo = b[2] - b[5] / 2;
-    return r;
-}
-
-// the cheap part of the test: z interval and the rectangle's bounding box (a point that fails it is outside)
-__device__ __forceinline__ bool near3(const Box3 &b, float x, float y, float z)
-{
-    if (z > b.zhi || z < b.zlo) return false;                                   // dgal_wrap.h:12-13 (NaN z: inside, as there)
-    const BoxGeom<float> &g = b.g;
-    return x >= g.xmin && x <= g.xmax && y >= g.ymin && y <= g.ymax;             // :14-15
-}
-
-__device__ __forceinline__ bool contains3(const Box3 &b, float x, float y, float z)
-{
-    if (z > b.zhi || z < b.zlo) return false;                                   // dgal_wrap.h:12-13 (NaN z: inside, as there)
-    return quad_contains<float>(b.g, x, y);                                     // :14-17
-}
+// (Box3, load_box3, near3 and contains3 live in geom.hpp: roipool.hip bins the members of a box with the same test)
 
 // indicators[i, j] = box i contains point j.  Lane = 4 consecutive points -> one 32-bit store per box row.
 __global__ __launch_bounds__(256) void k_crop3dr(const float *__restrict__ points, int64_t n, int pstride,

@@ -4,6 +4,7 @@
 //
 //   d3d_table_pool_forward   feat[src_rows, C], table[rows, K]            -> out[rows, C] (+ arg[rows, C] int16, count[rows])
 //   d3d_table_pool_backward  grad_out[out_rows, C], back_table[rows, K]   -> grad_feat[rows, C]
+//   d3d_table_pool_backward_index  grad_out[rows, C], order, offsets      -> grad_feat[src_rows, C]   (a table without a transposed table)
 //
 // Both are a reduce-while-gathering, one launch each, no workspace, no float atomics: the tables are each other's transposed map
 // (table_out[r, k] == v <=> table_in[v, k] == r; a VoxelNeighbors' table against its own mirrored columns), so the gradient of "row r
@@ -173,6 +174,70 @@ __global__ __launch_bounds__(kTpThreads) void k_tpool_bwd(const T *__restrict__ 
     }
 }
 
+// ---------------------------------------------------------------- backward through an inverted index
+// For a table that has no fixed-width transposed table -- the cells of RoIs, a ball-query or kNN table: a source row is named by as
+// many entries as boxes overlap it.  Source row v walks order[offsets[v] .. offsets[v + 1]), the entries e = r * K + kk that hold v in
+// ascending e (d3d_knn_interp_backward's layout), four in flight, and adds what each owes it by k_tpool_bwd's rules.  No ballots:
+// the lanes of a group only share the row.
+constexpr int kTpIndexAhead = 4;
+template <typename T, int VEC, int RED>
+__global__ __launch_bounds__(kTpThreads) void k_tpool_bwd_index(const T *__restrict__ grad_out, const int32_t *__restrict__ order,
+                                                                const int64_t *__restrict__ offsets, int64_t src_rows, int32_t K, int32_t c,
+                                                                int gl, const int16_t *__restrict__ arg, const int32_t *__restrict__ count,
+                                                                T *__restrict__ grad_feat)
+{
+    typedef RowPack<T, VEC> P;
+    typedef RowPack<int16_t, VEC> W;
+    typedef typename RowAcc<T>::type A;
+    constexpr bool EXTREME = RED == D3D_REDUCE_MAX || RED == D3D_REDUCE_MIN;
+    constexpr int AH = kTpIndexAhead;
+    const int64_t t = (int64_t)blockIdx.x * kTpThreads + threadIdx.x, v = t >> gl;
+    if (v >= src_rows) return;
+    const int g = (int)(t & ((1 << gl) - 1)), step = VEC << gl;
+    const int64_t beg = offsets[v], end = offsets[v + 1];
+    for (int c0 = g * VEC; c0 < c; c0 += step) {
+        A acc[VEC];
+#pragma unroll
+        for (int q = 0; q < VEC; q++) acc[q] = 0;
+        for (int64_t i = beg; i < end; i += AH) {
+            int64_t r[AH];
+            int kk[AH];
+            P x[AH];
+            W w[AH];
+            A cnt[AH];
+#pragma unroll
+            for (int a = 0; a < AH; a++) {
+                r[a] = -1, kk[a] = 0, cnt[a] = 1;
+                if (i + a < end) {
+                    const int32_t e = order[i + a];
+                    r[a] = e / K, kk[a] = e - (int32_t)r[a] * K;
+                }
+            }
+#pragma unroll
+            for (int a = 0; a < AH; a++)
+                if (r[a] >= 0) {
+                    x[a] = *(const P *)(grad_out + r[a] * c + c0);
+                    if constexpr (EXTREME) w[a] = *(const W *)(arg + r[a] * c + c0);
+                    if constexpr (RED == D3D_REDUCE_MEAN) cnt[a] = (A)count[r[a]];
+                }
+#pragma unroll
+            for (int a = 0; a < AH; a++)
+                if (r[a] >= 0) {
+#pragma unroll
+                    for (int q = 0; q < VEC; q++) {
+                        if constexpr (EXTREME) acc[q] = (int)w[a].v[q] == kk[a] ? acc[q] + (A)x[a].v[q] : acc[q];
+                        else if constexpr (RED == D3D_REDUCE_MEAN) acc[q] += (A)x[a].v[q] / cnt[a];
+                        else acc[q] += (A)x[a].v[q];
+                    }
+                }
+        }
+        P o;
+#pragma unroll
+        for (int q = 0; q < VEC; q++) o.v[q] = (T)acc[q];
+        *(P *)(grad_feat + v * c + c0) = o;
+    }
+}
+
 bool tp_dtype_ok(int32_t d) { return d == D3D_F32 || d == D3D_F64 || d == D3D_F16 || d == D3D_BF16; }
 
 }  // namespace
@@ -216,6 +281,27 @@ extern "C" int d3d_table_pool_backward(const void *grad_out, int64_t out_rows, i
         typedef typename decltype(p)::T T;
         D3D_LAUNCH("k_tpool_bwd", (k_tpool_bwd<T, decltype(vec)::value, decltype(red)::value>), dim3((unsigned)d3d_divup(rows << gl, kTpThreads)),
                    dim3(kTpThreads), 0, st, (const T *)grad_out, back_table, rows, k, c, mirrored, gl, arg, count, (T *)grad_feat);
+        return D3D_OK;
+    });
+}
+
+extern "C" int d3d_table_pool_backward_index(const void *grad_out, int64_t rows, int32_t c, int32_t dtype, const int32_t *order,
+                                             const int64_t *offsets, int64_t src_rows, int32_t k, int32_t reduction, const int16_t *arg,
+                                             const int32_t *count, void *grad_feat, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (rows < 0 || src_rows < 0 || c < 1 || k < 1) return D3D_ERR_BAD_ARG;
+    if (!row_reduction_ok(reduction) || !tp_dtype_ok(dtype) || k > kTpMaxK || src_rows > kRowMax || rows > kRowMax / k) return D3D_ERR_UNSUPPORTED;
+    if (src_rows == 0) return D3D_OK;
+    const bool extreme = reduction == D3D_REDUCE_MAX || reduction == D3D_REDUCE_MIN;
+    if (!offsets || !grad_feat || (rows > 0 && (!grad_out || !order || (extreme && !arg) || (reduction == D3D_REDUCE_MEAN && !count))))
+        return D3D_ERR_BAD_ARG;
+    const bool aligned = row_aligned16(grad_out) && row_aligned16(grad_feat) && (!extreme || row_aligned16(arg));
+    return row_dispatch<D3D_F32, D3D_F64, D3D_F16, D3D_BF16>(dtype, c, aligned, reduction, [&](auto p, auto vec, auto red, int gl) {
+        typedef typename decltype(p)::T T;
+        D3D_LAUNCH("k_tpool_bwd_index", (k_tpool_bwd_index<T, decltype(vec)::value, decltype(red)::value>),
+                   dim3((unsigned)d3d_divup(src_rows << gl, kTpThreads)), dim3(kTpThreads), 0, st, (const T *)grad_out, order, offsets, src_rows,
+                   k, c, gl, arg, count, (T *)grad_feat);
         return D3D_OK;
     });
 }

@@ -43,11 +43,14 @@ class WeightedTable:
         """The inverted table: a VoxelIndex over the flattened table [num_points * width] taken as a mapping -- per source row the
         entries that name it, in ascending entry number.  Built on the first call (VoxelIndex's one read-back) and kept: what a splat
         and the gradient of an interpolation walk.  It holds `order` and `offsets` only: its `mapping` is None (the table is the
-        mapping)."""
+        mapping).  (A table that is mostly padding inverts its present entries only: _invert of d3d_amd.point.roi.)"""
         if self._index is None:
             with torch.cuda.device(self.device):
-                self._index = VoxelIndex(self.table.view(-1), self.src_rows, keep_mapping=False)
+                self._index = self._invert()
         return self._index
+
+    def _invert(self):
+        return VoxelIndex(self.table.view(-1), self.src_rows, keep_mapping=False)
 
     def weights_as(self, dtype):
         """the weights a fold in `dtype` multiplies by: float64 for float64 features, float32 otherwise.  Weights of the other width

@@ -1291,6 +1291,64 @@ int d3d_knn_interp_forward(const void *feat, int64_t v, int32_t c, int32_t dtype
 int d3d_knn_interp_backward(const void *grad, int64_t rows, int32_t c, int32_t dtype, const int32_t *order, const int64_t *offsets,
                             const void *weights, int32_t j, int64_t v, void *grad_feat, void *stream);
 
+/* ------------------------------------------------------------------ RoI pooling of points: the cell table of rotated boxes */
+
+/* The step where a two-stage detector turns a proposal box back into features (csrc/roipool.hip, csrc/vtpool.hip): the points inside
+ * every rotated box, binned into the cells of the box's own grid -- Part-A2's roiaware_pool3d (its pts_idx_of_voxels), and with one cell
+ * and the cyclic fill PointRCNN's roipoint_pool3d.  The table is a -1-padded int32 table like d3d_ball_query's: d3d_table_pool_forward
+ * folds it, d3d_table_pool_backward_index is that fold's gradient.  No float atomics, no [m, n] mask, no sort, no workspace; every
+ * run gives the same bits.  The reference has crop_points and nothing that bins.
+ *
+ * d3d_roi_grid_table: points[n, point_stride >= 3] and box row i = 7 floats (x, y, z, lx, ly, lz, rz; z the centre) at boxes + i *
+ *   box_stride + box_offset, exactly as d3d_crop_3dr reads them; dtype D3D_F32 only.  point_offsets / box_offsets: DEVICE
+ *   int64[segments + 1] as d3d_ball_query's (to n and to m), both or neither, trusted; a box sees the points of its own segment only.
+ *   out_size: HOST int32[3] = (ox, oy, oz), G = ox * oy * oz cells; max_points = P; pad 0 or 1.  ->
+ *     table[m, G, P] int32: GLOBAL point rows, -1 for none;  counts[m, G] int32: the kept entries (<= P);
+ *     inside[m] int32: all members of the box, uncapped.
+ *   The rule.  All arithmetic is fp32, every operation one rounding (the build does not contract).
+ *     MEMBER: point i belongs to box b iff its x, y and z are all finite AND the test of d3d_crop_3dr holds -- the same function on the
+ *       same expressions (contains3 of csrc/geom.hpp), so for finite points the result is d3d_crop_3dr's bits.  A NaN z, which
+ *       d3d_crop_3dr counts as inside, is excluded here: no cell can be computed for it.  A box row on which that test is false for
+ *       every point (NaN fields, degenerate extents) has no members.  ONE predicate decides membership; the cell never does.
+ *     CELL: with (s, c) = the sine and cosine d3d_crop_3dr takes of rz (the host's sinf / cosf), dx = x - bx, dy = y - by, dz = z - bz:
+ *         u = dx * c + dy * s,  v = dy * c - dx * s,
+ *         t_x = (u / lx + 0.5f) * ox,  t_y = (v / ly + 0.5f) * oy,  t_z = (dz / lz + 0.5f) * oz   (ox, oy, oz as floats),
+ *         i_a = 0 where !(t_a >= 0) -- a NaN t maps to cell 0 --, else min(trunc(t_a), o_a - 1), saturated BEFORE the conversion,
+ *         cell = (i_x * oy + i_y) * oz + i_z.
+ *       The cells are CLAMPED: a member on a face whose t lands at o_a, or a hair outside, falls into the border cell.
+ *     ENTRIES: a cell's entries are its first P members in ascending global row, counts is their number, the remaining slots are -1.
+ *       pad == 1 ("cycle", PointRCNN's fill): slot j >= count holds entry j % count; an empty cell stays -1 with count 0.
+ *   Nothing of this depends on the launch shape: d3d_roi_grid_plan's numbers say where the kernel's seams lie, not what it computes.
+ *   One launch, one workgroup per box, O(m n) per segment as d3d_ball_query; every slot of the table is written exactly once by that
+ *   launch (no memset).  P in 1 .. 1024; G <= d3d_roi_grid_max_cells(); m * G * P, n, m and segments at most 2^31 - 1.
+ * d3d_roi_grid_max_cells (pure host): the largest G, 4096 = 16^3.
+ * d3d_roi_grid_plan (pure host): for a segment of segment_rows rows and a grid of `cells` cells, what the launch uses: tile_rows,
+ *   the rows one ballot judges; slab_rows, the contiguous rows one wavefront judges at a time (slab k = rows [k * slab_rows, (k + 1) *
+ *   slab_rows) of the segment; its members wait in on-chip memory, which holds a whole slab); round_rows, the rows the workgroup
+ *   takes between two barriers, a whole number of slabs -- the members of a round are placed before the next round is loaded.
+ * d3d_table_pool_backward_index: the gradient of d3d_table_pool_forward for a table that has no fixed-width transposed table (a point
+ *   lies in as many boxes as overlap it).  grad_out[rows, c] in `dtype`, the forward's table [rows, k] given as its inverted index:
+ *   order[offsets[v] .. offsets[v + 1]) names, for source row v, the entries e = r * k + kk that hold v, in ascending e (DEVICE int32 /
+ *   int64[src_rows + 1], trusted: d3d_knn_interp_backward's layout) -> grad_feat[src_rows, c].  Entry e contributes grad_out[r] (SUM),
+ *   grad_out[r] / (T)count[r] (MEAN), grad_out[r, ch] where arg[r, ch] == kk and nothing elsewhere (MAX / MIN); the contributions are
+ *   added to 0 in ascending e.  D3D_F16 / D3D_BF16: contributions and sum in fp32, one rounding.  Every row of grad_feat is written
+ *   exactly once, zero where nothing names it.  arg [rows, c] int16 and count [rows] int32 as the forward wrote them (arg read for
+ *   MAX / MIN only, count for MEAN only).  16-byte row moves under d3d_table_pool_backward's conditions, the same bits on both paths.
+ *   dtype D3D_F32, D3D_F64, D3D_F16 or D3D_BF16; c >= 1; k in 1 .. 343; src_rows and rows * k at most 2^31 - 1.  One launch.
+ * D3D_ERR_BAD_ARG: a negative size, a stride below 3 (box_stride below box_offset + 7), a missing pointer with work to do, one offset
+ *   array without the other, an out_size component below 1, P outside 1 .. 1024, a pad other than 0 or 1, c < 1, k < 1;
+ *   D3D_ERR_UNSUPPORTED: the limits above, another dtype or reduction code.  None of them launches anything.  m == 0 (table) and
+ *   src_rows == 0 (backward) return D3D_OK before any HIP call. */
+int32_t d3d_roi_grid_max_cells(void);
+int d3d_roi_grid_plan(int64_t segment_rows, int32_t cells, int32_t *tile_rows, int32_t *slab_rows, int32_t *round_rows);
+int d3d_roi_grid_table(const void *points, int64_t n, int32_t point_stride, const void *boxes, int64_t m, int32_t box_stride,
+                       int32_t box_offset, int32_t dtype, const int64_t *point_offsets, const int64_t *box_offsets, int64_t segments,
+                       const int32_t *out_size, int32_t max_points, int32_t pad, int32_t *table, int32_t *counts, int32_t *inside,
+                       void *stream);
+int d3d_table_pool_backward_index(const void *grad_out, int64_t rows, int32_t c, int32_t dtype, const int32_t *order, const int64_t *offsets,
+                                  int64_t src_rows, int32_t k, int32_t reduction, const int16_t *arg, const int32_t *count,
+                                  void *grad_feat, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
