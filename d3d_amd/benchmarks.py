@@ -70,9 +70,9 @@ class DetectionEvaluator:
         """DetectionEvalStats.initialize (:66-78): counts 0, accuracies NaN"""
         T = self._pr_nsamples
         st = Dict(ngt={c: 0 for c in self._classes})
-        for k in ("ndt", "tp", "fp", "fn"):
+        for k in _COUNT_FIELDS:
             st[k] = {c: [0] * T for c in self._classes}
-        for k in _ACC_FIELDS:
+        for k in ("acc_angular", "acc_box", "acc_iou", "acc_dist", "acc_var"):    # _ACC_FIELDS in the order get_stats() lists them
             st[k] = {c: [math.nan] * T for c in self._classes}
         return st
 
@@ -93,7 +93,7 @@ class DetectionEvaluator:
             for name in _ACC_FIELDS:
                 mine = getattr(self._stats, name)
                 mine[k] = _wmean(mine[k], otp, getattr(stats, name)[k], ntp)
-            for name in ("ndt", "tp", "fp", "fn"):
+            for name in _COUNT_FIELDS:
                 mine, theirs = getattr(self._stats, name), getattr(stats, name)[k]
                 mine[k] = [int(mine[k][i]) + int(theirs[i]) for i in range(T)]
 
@@ -215,8 +215,7 @@ class DetectionEvaluator:
         gt_tag, dt_tag = gt[:, 0].astype(np.int64), dt[:, 0].astype(np.int64)
         dt_score = dt[:, 1]
         if self.reference_compat:
-            out = Dict(ngt={}, ndt={}, tp={}, fp={}, fn={}, acc_iou={}, acc_angular={}, acc_dist={}, acc_box={}, acc_var={})
-            return self._calc_stats_per_threshold(gt, dt, out)
+            return self._calc_stats_per_threshold(gt, dt)
         if len(gt) and len(dt):
             cache = prepare_boxes(dt, gt, DistanceTypes.RIoU)                                        # :188-189
             sm, dm = score_match(cache, dt_score, dt_tag, gt_tag, self._max_distance)
@@ -233,20 +232,16 @@ class DetectionEvaluator:
     def _stats_of_match(self, gt, dt, sm, dm, iou):
         """the stats of a frame from ONE association (reference_compat=False): sm[n] / dm[m] int64 partners or -1, iou[m] fp32
         = 1 - distance of a ground truth's pair, 0 without one.  calc_stats and calc_stats_batch share it."""
-        T, classes, thr = self._pr_nsamples, self._classes, self._pr_thresholds
+        classes, thr = self._classes, self._pr_thresholds
         gt_tag, dt_tag = gt[:, 0].astype(np.int64), dt[:, 0].astype(np.int64)
         dt_score = dt[:, 1]
-        out = Dict(ngt={}, ndt={}, tp={}, fp={}, fn={}, acc_iou={}, acc_angular={}, acc_dist={}, acc_box={}, acc_var={})
+        out = Dict((k, {}) for k in ("ngt",) + _COUNT_FIELDS + _ACC_FIELDS)
         matched = dm >= 0
         partner = np.where(matched, dm, 0)
         # a ground-truth box is a true positive at threshold t iff its detection is selected there (score >= t)  (:220-238)
         gscore = np.where(matched, dt_score[partner] if len(dt) else 0.0, -np.inf)
-        dist = np.linalg.norm(gt[:, 2:5] - dt[partner, 2:5], axis=1) if len(dt) else np.zeros(len(gt))          # :244
-        box = np.linalg.norm(gt[:, 5:8] - dt[partner, 5:8], axis=1) if len(dt) else np.zeros(len(gt))           # :245
-        dyaw = (gt[:, 8] - dt[partner, 8]) if len(dt) else np.zeros(len(gt))
-        ang = np.abs((dyaw + np.pi) % (2 * np.pi) - np.pi) / np.pi                                     # quatdiff of two yaw rotations / pi (:247-248)
         dmatched = sm >= 0
-        vals = np.stack([iou, ang, dist, box]).astype(np.float64)                                      # [4, m]
+        vals = np.stack(_pair_terms(gt, dt[partner], iou)).astype(np.float64) if len(dt) else np.zeros((4, len(gt)))   # [4, m]
 
         def at_least(scores):
             """#(scores >= t) for every threshold t: one sort instead of a [len, T] comparison (:224-225: `score < thres` is
@@ -270,26 +265,17 @@ class DetectionEvaluator:
             csum = np.concatenate([np.zeros((4, 1)), np.cumsum(vals[:, g][:, o], axis=1)], axis=1)      # [4, mc + 1]
             with np.errstate(invalid="ignore", divide="ignore"):
                 means = np.where(tp[None, :] > 0, csum[:, tp] / tp[None, :], np.nan).astype(np.float32)
-            out.acc_iou[c], out.acc_angular[c] = means[0].tolist(), means[1].tolist()
-            out.acc_dist[c], out.acc_box[c] = means[2].tolist(), means[3].tolist()
-            # no variances travel in the [n,9] arrays: orientation_var = 0 -> -inf per match (:250-258), NaN without one
-            out.acc_var[c] = np.where(tp > 0, -np.inf, np.nan).astype(np.float32).tolist()
+            for name, v in zip(_ACC_FIELDS, list(means) + [_acc_var(tp)]):
+                out[name][c] = v.tolist()
         return out
 
-
-    def _calc_stats_per_threshold(self, gt, dt, out):
+    def _calc_stats_per_threshold(self, gt, dt):
         """benchmarks.pyx:188-283 as written: select the detections of a threshold, associate (the literal pairing), count"""
-        T, classes, thr = self._pr_nsamples, self._classes, self._pr_thresholds
+        T, C, thr = self._pr_nsamples, len(self._classes), self._pr_thresholds
         gt_tag, dt_tag = gt[:, 0].astype(np.int64), dt[:, 0].astype(np.int64)
+        gslot, dslot = _class_slots(self._classes, gt), _class_slots(self._classes, dt)
         dt_score = dt[:, 1]
-        gt_idx = np.nonzero(np.isin(gt_tag, classes))[0]                                              # :205-212
-        dt_in = np.isin(dt_tag, classes)
-        for c in classes:
-            out.ngt[c] = int((gt_tag == c).sum())
-            for k in ("ndt", "tp", "fp", "fn"):
-                out[k][c] = [0] * T
-            for k in ("acc_iou", "acc_angular", "acc_dist", "acc_box", "acc_var"):
-                out[k][c] = [float("nan")] * T
+        gt_idx = np.nonzero(gslot >= 0)[0]                                                            # :205-212
         cache = prepare_boxes(dt, gt, DistanceTypes.RIoU) if len(gt) and len(dt) else None             # :188-189
         # the 40 associations share what does not depend on the threshold (the ground truths' columns of the cache, which pairs are
         # acceptable) and go to the device as batched calls (ReferenceAssociation.match_many: one for a frame, a few for config 4's
@@ -298,7 +284,7 @@ class DetectionEvaluator:
         if cache is not None and len(gt_idx):
             assoc = ReferenceAssociation(cache, dt_score, dt_tag, gt_tag, self._max_distance, gt_idx)
             gt_idx_t = torch.from_numpy(gt_idx).to(cache.device)
-        sel = dt_in[None, :] & ~(dt_score[None, :] < thr[:, None])                                   # [T, n]: :219-228 (`score < thres`: skip)
+        sel = (dslot >= 0)[None, :] & ~(dt_score[None, :] < thr[:, None])                            # [T, n]: :219-228 (`score < thres`: skip)
         dt_idxs = [np.nonzero(sel[t])[0] for t in range(T)]
         md = len(gt_idx)
         sm_all = np.full((T, len(dt)), -1, np.int32)
@@ -309,39 +295,17 @@ class DetectionEvaluator:
             dmg_t = dm_t.index_select(1, gt_idx_t)
             iou_t = 1 - cache[dmg_t.long().clamp_min(0), gt_idx_t[None, :]]                            # :243 (entries of the unmatched: unused)
             sm_all, dm_g, iou_all = sm_t.cpu().numpy(), dmg_t.cpu().numpy(), iou_t.cpu().numpy()
-        # the counts and means of :236-283 for all thresholds at once: the K matched (threshold, ground truth) pairs as flat arrays,
-        # per-threshold counts and float64 sums by bincount (the arithmetic of one pair is unchanged: float32 terms, their sum in
-        # float64, one division, rounded to float32)
+        # the counts and means of :236-283 for all thresholds at once: the K matched (threshold, ground truth) pairs as flat arrays
         tt, jj = np.nonzero(dm_g >= 0)
-        terms, gcls = {}, np.zeros((0,), np.int64)
-        if len(tt):
-            gi, d_of = gt_idx[jj], dm_g[tt, jj]
-            ga, da = gt[gi], dt[d_of]                                                                  # [K, 9]
-            dp, db = ga[:, 2:5] - da[:, 2:5], ga[:, 5:8] - da[:, 5:8]
-            dyaw = ga[:, 8] - da[:, 8]
-            terms = dict(acc_iou=iou_all[tt, jj],
-                         acc_angular=np.abs((dyaw + np.pi) % (2 * np.pi) - np.pi) / np.pi,              # :247-248
-                         # (np.linalg.norm(., axis=1) spelled out -- sqrt(add.reduce(x * x)) over three terms, the same bits)
-                         acc_dist=np.sqrt((dp[:, 0] * dp[:, 0] + dp[:, 1] * dp[:, 1]) + dp[:, 2] * dp[:, 2]),   # :244
-                         acc_box=np.sqrt((db[:, 0] * db[:, 0] + db[:, 1] * db[:, 1]) + db[:, 2] * db[:, 2]))    # :245
-            gcls = gt_tag[gi]
+        gi = gt_idx[jj]
+        tp, acc = _bin_means(gslot[gi].astype(np.int64) * T + tt, (C, T), _pair_terms(gt[gi], dt[dm_g[tt, jj]], iou_all[tt, jj]))
+        ngt = np.bincount(gslot[gt_idx], minlength=C)
+        ndt, fp = np.zeros((C, T), np.int64), np.zeros((C, T), np.int64)
         unmatched = sm_all < 0
-        for c in classes:
-            dc = sel & (dt_tag == c)[None, :]
-            of_c = gcls == c
-            tc = tt[of_c]
-            tp = np.bincount(tc, minlength=T)
-            out.ndt[c] = dc.sum(1).tolist()
-            out.tp[c] = tp.tolist()
-            out.fn[c] = (out.ngt[c] - tp).tolist()                                                     # :236-240
-            out.fp[c] = (dc & unmatched).sum(1).tolist()                                               # :262-265
-            for name, v in terms.items():                                                              # :150-174 (sum / count, fp32)
-                ssum = np.bincount(tc, weights=v[of_c].astype(np.float64), minlength=T)
-                with np.errstate(invalid="ignore", divide="ignore"):
-                    out[name][c] = np.where(tp > 0, (ssum / tp).astype(np.float32), np.float32(np.nan)).tolist()
-            # no variances travel in the [n,9] arrays: orientation_var = 0 -> -inf per match (:250-258), NaN without one
-            out.acc_var[c] = np.where(tp > 0, -np.inf, np.nan).tolist()
-        return out
+        for i in range(C):
+            dc = sel & (dslot == i)[None, :]
+            ndt[i], fp[i] = dc.sum(1), (dc & unmatched).sum(1)                                         # :262-265
+        return self._frame_dicts(ngt[None], [a[None] for a in [ndt, tp, fp, ngt[:, None] - tp] + acc])[0]   # (fn: :236-240)
 
     # ------------------------------------------------------------------ many frames per call
     def calc_stats_batch(self, gt_boxes, dt_boxes, gt_frame_offsets, dt_frame_offsets):
@@ -356,12 +320,8 @@ class DetectionEvaluator:
         orders every threshold's selection with numpy's unstable argsort, which only a run on the same subset reproduces);
         and every frame when the score thresholds do not rise."""
         gt, dt = _host_rows(gt_boxes, np.float32, 9), _host_rows(dt_boxes, np.float32, 9)
-        go, do = _host_rows(gt_frame_offsets, np.int64, 0), _host_rows(dt_frame_offsets, np.int64, 0)
-        for off, n in ((go, len(gt)), (do, len(dt))):
-            if len(off) < 1 or off[0] != 0 or off[-1] != n or np.any(np.diff(off) < 0):
-                raise ValueError("frame offsets must rise from 0 to the number of boxes")
-        if len(go) != len(do):
-            raise ValueError("gt_frame_offsets and dt_frame_offsets must describe the same frames")
+        go, do = _frame_offsets("frame offsets must rise from 0 to the number of boxes",
+                                (gt_frame_offsets, len(gt)), (dt_frame_offsets, len(dt)))
         F = len(go) - 1
         if F == 0:
             return []
@@ -391,13 +351,7 @@ class DetectionEvaluator:
         F = len(go) - 1
         nf, mf = np.diff(do), np.diff(go)
         fd, fg = np.repeat(np.arange(F), nf), np.repeat(np.arange(F), mf)
-        by_value = np.argsort(np.asarray(self._classes, np.int64), kind="stable")
-        values = np.asarray(self._classes, np.int64)[by_value]
-
-        def slots(tags):
-            at = np.minimum(np.searchsorted(values, tags), C - 1)
-            return np.where(values[at] == tags, by_value[at], -1).astype(np.int32)
-        gslot, dslot = slots(gt[:, 0].astype(np.int64)), slots(dt[:, 0].astype(np.int64))
+        gslot, dslot = _class_slots(self._classes, gt), _class_slots(self._classes, dt)
         score = dt[:, 1]
         nan, inc = np.isnan(score), dslot >= 0
         order = np.lexsort((np.where(nan, np.float32(0), -score), ~nan, ~inc, fd))
@@ -447,37 +401,29 @@ class DetectionEvaluator:
                 f1 += 1
             chunks.append((f0, f1))
             f0 = f1
-        parts, pos = [], 0
-
-        def put(a):
-            nonlocal pos
-            b = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-            at, pad = pos, _aligned(len(b)) - len(b)
-            parts.append(b)
-            if pad:
-                parts.append(np.zeros((pad,), np.uint8))
-            pos += len(b) + pad
-            return at
-        at = {k: put(v) for k, v in (("dt", h["dt"]), ("gt", h["gt"]), ("dslot", h["dslot"]), ("gslot", h["gslot"]),
-                                     ("perm", h["perm"]), ("rank", h["rank"]), ("slots", slots), ("maxd", maxd))}
-        offs = []
+        shared = {k: h[k] for k in ("dt", "gt", "dslot", "gslot", "perm", "rank")}
+        shared.update(slots=slots, maxd=maxd)
+        offs = []                                          # a chunk's offsets: detection rows, ground-truth rows, cache entries
         for f0, f1 in chunks:
             co = np.zeros((f1 - f0 + 1,), np.int64)
             np.cumsum(pairs[f0:f1], out=co[1:])
-            offs.append((put(do[f0:f1 + 1] - do[f0]), put(go[f0:f1 + 1] - go[f0]), put(co), int(co[-1])))
+            offs += [do[f0:f1 + 1] - do[f0], go[f0:f1 + 1] - go[f0], co]
+        npairs = [int(co[-1]) for co in offs[2::3]]
         with torch.cuda.device(dev):
-            blob = torch.from_numpy(np.concatenate(parts)).to(dev)
+            blob, addr = _upload(dev, list(shared.values()) + offs)
+            at, chunk_at = dict(zip(shared, addr)), addr[len(shared):]
             out = torch.empty((max(2 * P * M + (0 if literal else N), 1),), dtype=torch.int32, device=dev)
-            base, obase, stream = blob.data_ptr(), out.data_ptr(), _lib.stream_ptr()
-            ws = _lib.workspace(max(lib.d3d_deteval_batched_workspace_bytes(o[3], 0) for o in offs), dev)
-            for (f0, f1), (dof, gof, cof, npairs) in zip(chunks, offs):
+            obase, stream = out.data_ptr(), _lib.stream_ptr()
+            ws = _lib.workspace(max(lib.d3d_deteval_batched_workspace_bytes(k, 0) for k in npairs), dev)
+            for i, (f0, f1) in enumerate(chunks):
                 d0, g0 = int(do[f0]), int(go[f0])
+                dof, gof, cof = chunk_at[3 * i:3 * i + 3]
                 rc = lib.d3d_deteval_batched(
-                    ctypes.c_void_p(base + at["dt"] + 36 * d0), ctypes.c_void_p(base + at["gt"] + 36 * g0), ctypes.c_void_p(base + dof),
-                    ctypes.c_void_p(base + gof), ctypes.c_void_p(base + cof), f1 - f0, npairs, int(nf[f0:f1].max()), int(mf[f0:f1].max()),
-                    ctypes.c_void_p(base + at["dslot"] + 4 * d0), ctypes.c_void_p(base + at["gslot"] + 4 * g0),
-                    ctypes.c_void_p(base + at["perm"] + 4 * d0), ctypes.c_void_p(base + at["rank"] + 4 * d0),
-                    ctypes.c_void_p(base + at["slots"] + 4 * P * f0), T, ctypes.c_void_p(base + at["maxd"]), C, 1 if literal else 0,
+                    ctypes.c_void_p(at["dt"] + 36 * d0), ctypes.c_void_p(at["gt"] + 36 * g0), ctypes.c_void_p(dof),
+                    ctypes.c_void_p(gof), ctypes.c_void_p(cof), f1 - f0, npairs[i], int(nf[f0:f1].max()), int(mf[f0:f1].max()),
+                    ctypes.c_void_p(at["dslot"] + 4 * d0), ctypes.c_void_p(at["gslot"] + 4 * g0),
+                    ctypes.c_void_p(at["perm"] + 4 * d0), ctypes.c_void_p(at["rank"] + 4 * d0),
+                    ctypes.c_void_p(at["slots"] + 4 * P * f0), T, ctypes.c_void_p(at["maxd"]), C, 1 if literal else 0,
                     None, ctypes.c_void_p(obase + 4 * P * g0), ctypes.c_void_p(obase + 4 * (P * M + P * g0)),
                     None if literal else ctypes.c_void_p(obase + 4 * (2 * M + d0)), _lib.ptr(ws), ws.numel(), stream)
                 _lib.check(rc, "deteval_batched")
@@ -485,46 +431,33 @@ class DetectionEvaluator:
 
     def _batch_stats(self, h, res):
         """the frames' stats from the fetched results (_batch_launch's layout)"""
-        T, C, classes = self._pr_nsamples, len(self._classes), self._classes
+        T, C = self._pr_nsamples, len(self._classes)
         gt, dt, go, do, mf = h["gt"], h["dt"], h["go"], h["do"], h["mf"]
         F, N, M = len(mf), len(dt), len(gt)
         if not self.reference_compat:                      # one association per frame: calc_stats' own epilogue, frame by frame
             dm, iou, sm = res[:M].astype(np.int64), res[M:2 * M].view(np.float32), res[2 * M:2 * M + N].astype(np.int64)
             return [self._stats_of_match(gt[go[f]:go[f + 1]], dt[do[f]:do[f + 1]], sm[do[f]:do[f + 1]], dm[go[f]:go[f + 1]],
                                          iou[go[f]:go[f + 1]]) for f in range(F)]
-        # _calc_stats_per_threshold's epilogue over all frames at once: the K matched (frame, threshold, ground truth) triples in
-        # that order, counts and float64 sums by bincount over (frame, threshold, class) keys -- a bin receives its terms in
-        # ascending ground-truth order, as the per-frame bincount over thresholds does, so the sums have the same bits
+        # the K matched (frame, threshold, ground truth) triples in that order, binned by (frame, class, threshold): a bin receives
+        # its terms in ascending ground-truth order, as calc_stats' bins of one frame do, so the sums have the same bits
         gm, iou = res[:T * M], res[T * M:2 * T * M].view(np.float32)
         e = np.nonzero(gm >= 0)[0]
         fe = np.searchsorted(T * go[1:], e, side="right")             # frame f's [T, m_f] block starts at T * go[f]
         rem = e - T * go[fe]
         te = rem // np.maximum(mf[fe], 1)
         gi, di = go[fe] + (rem - te * mf[fe]), do[fe] + gm[e]
-        ga, da = gt[gi], dt[di]
-        dp, db = ga[:, 2:5] - da[:, 2:5], ga[:, 5:8] - da[:, 5:8]
-        dyaw = ga[:, 8] - da[:, 8]
-        terms = dict(acc_iou=iou[e],
-                     acc_angular=np.abs((dyaw + np.pi) % (2 * np.pi) - np.pi) / np.pi,
-                     acc_dist=np.sqrt((dp[:, 0] * dp[:, 0] + dp[:, 1] * dp[:, 1]) + dp[:, 2] * dp[:, 2]),
-                     acc_box=np.sqrt((db[:, 0] * db[:, 0] + db[:, 1] * db[:, 1]) + db[:, 2] * db[:, 2]))
-        key = (fe * T + te) * C + h["gslot"][gi]
-        tp = np.bincount(key, minlength=F * T * C).reshape(F, T, C).transpose(0, 2, 1)                 # [F, C, T]
+        tp, acc = _bin_means((fe * C + h["gslot"][gi]) * T + te, (F, C, T), _pair_terms(gt[gi], dt[di], iou[e]))
         ndt, ngt = h["ndt"], h["ngt"]
-        cols = dict(ndt=ndt.tolist(), tp=tp.tolist(), fp=(ndt - tp).tolist(), fn=(ngt[:, :, None] - tp).tolist(),
-                    acc_var=np.where(tp > 0, -np.inf, np.nan).tolist())
-        for name, v in terms.items():
-            ssum = np.bincount(key, weights=v.astype(np.float64), minlength=F * T * C).reshape(F, T, C).transpose(0, 2, 1)
-            with np.errstate(invalid="ignore", divide="ignore"):
-                cols[name] = np.where(tp > 0, (ssum / tp).astype(np.float32), np.float32(np.nan)).tolist()
-        ngt_l = ngt.tolist()
-        names = ("ndt", "tp", "fp", "fn", "acc_iou", "acc_angular", "acc_dist", "acc_box", "acc_var")
+        return self._frame_dicts(ngt, [ndt, tp, ndt - tp, ngt[:, :, None] - tp] + acc)
+
+    def _frame_dicts(self, ngt, cols):
+        """ngt [F, C] and the arrays [F, C, T] of _COUNT_FIELDS + _ACC_FIELDS, in that order -> the F frames' stats"""
+        ngt, cols = ngt.tolist(), [col.tolist() for col in cols]
         stats = []
-        for f in range(F):
-            st = Dict(ngt={c: ngt_l[f][i] for i, c in enumerate(classes)})
-            for name in names:
-                col = cols[name][f]
-                st[name] = {c: col[i] for i, c in enumerate(classes)}
+        for f in range(len(ngt)):
+            st = Dict(ngt=dict(zip(self._classes, ngt[f])))
+            for name, col in zip(_COUNT_FIELDS + _ACC_FIELDS, cols):
+                st[name] = dict(zip(self._classes, col[f]))
             stats.append(st)
         return stats
 
@@ -532,7 +465,79 @@ class DetectionEvaluator:
 _DET_MAX_FRAMES = 16384                # frames of one d3d_deteval_batched call (one wavefront per frame and threshold: 40
                                        # thresholds make 655 k workgroups, seconds of evaluator input to prepare and fetch at once)
 _DET_MAX_CACHE_BYTES = 256 << 20       # and the bytes of its ragged distance cache, which lives in the workspace arena
-_ACC_FIELDS =("acc_angular", "acc_box", "acc_iou", "acc_dist", "acc_var")
+# the fields of a frame's stats beside ngt, in the order calc_stats lists them: counts and accuracies per class and threshold
+_COUNT_FIELDS = ("ndt", "tp", "fp", "fn")
+_ACC_FIELDS = ("acc_iou", "acc_angular", "acc_dist", "acc_box", "acc_var")
+
+
+def _class_slots(classes, boxes):
+    """the position in `classes` of the class of every box [n, 9] (int32), -1 for a class that is not among them"""
+    tags, values = boxes[:, 0].astype(np.int64), np.asarray(classes, np.int64)
+    by_value = np.argsort(values, kind="stable")
+    at = np.minimum(np.searchsorted(values[by_value], tags), len(values) - 1)
+    return np.where(values[by_value[at]] == tags, by_value[at], -1).astype(np.int32)
+
+
+def _pair_terms(ga, da, iou):
+    """the accuracy terms of K matched pairs (benchmarks.pyx:252-257, 648-653) from the ground truths' rows ga [K, 9], their detections'
+    rows da [K, 9] and the pairs' IoUs -> fp32 [K] each, in _ACC_FIELDS' order: the IoU, the angular error (quatdiff of two yaw
+    rotations / pi), the distance of the centres and of the box sizes (np.linalg.norm(., axis=1) spelled out --
+    sqrt(add.reduce(x * x)) over three terms, the same bits)"""
+    dp, db = ga[:, 2:5] - da[:, 2:5], ga[:, 5:8] - da[:, 5:8]
+    dyaw = ga[:, 8] - da[:, 8]
+    return (iou, np.abs((dyaw + np.pi) % (2 * np.pi) - np.pi) / np.pi,
+            np.sqrt((dp[:, 0] * dp[:, 0] + dp[:, 1] * dp[:, 1]) + dp[:, 2] * dp[:, 2]),
+            np.sqrt((db[:, 0] * db[:, 0] + db[:, 1] * db[:, 1]) + db[:, 2] * db[:, 2]))
+
+
+def _acc_var(tp):
+    """no variances travel in the [n,9] arrays: orientation_var = 0 -> -inf per match (:259-267, 655-663), NaN without one"""
+    return np.where(tp > 0, -np.inf, np.nan)
+
+
+def _bin_means(key, shape, terms):
+    """the counts and means of benchmarks.pyx:150-174, 236-283 over bins (of frame, class and threshold): key[K] = the bin of every
+    matched pair, `shape` = the bins' (their number is its product), terms = _pair_terms' arrays [K] -> tp (int64) and the
+    arrays of _ACC_FIELDS, all of `shape`.  A mean is the float32 terms summed in float64 in the order of the pairs, one
+    division, one rounding to float32; NaN for a bin without a pair."""
+    nbins = math.prod(shape)
+    tp = np.bincount(key, minlength=nbins)
+    acc = []
+    for v in terms:
+        ssum = np.bincount(key, weights=v.astype(np.float64), minlength=nbins)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            acc.append(np.where(tp > 0, (ssum / tp).astype(np.float32), np.float32(np.nan)).reshape(shape))
+    return tp.reshape(shape), acc + [_acc_var(tp).reshape(shape)]
+
+
+def _frame_offsets(message, *sides):
+    """the frame offsets of stacked rows, checked -> one int64 array per side = (offsets, number of rows): F + 1 offsets that rise
+    from 0 to the number of rows (ValueError(message) otherwise), every side describing the same frames"""
+    offs = [_host_rows(offsets, np.int64, 0) for offsets, _ in sides]
+    for off, (_, n) in zip(offs, sides):
+        if len(off) < 1 or off[0] != 0 or off[-1] != n or np.any(np.diff(off) < 0):
+            raise ValueError(message)
+    if any(len(off) != len(offs[0]) for off in offs):
+        raise ValueError("gt_frame_offsets and dt_frame_offsets must describe the same frames")
+    return offs
+
+
+def _upload(dev, arrays):
+    """host arrays to the GPU `dev` in ONE copy -> (the device buffer, the device address of every array in it); every array
+    starts at a multiple of 256 bytes of the buffer.  _lib.ship's job for callers that step through the rows by bytes (a
+    chunk's first frame, `+ 36 * d0`), send uint64 ids and hand the C entry points an address for every array, an empty one
+    included; the caller holds the buffer until its launches are queued"""
+    parts, starts, pos = [], [], 0
+    for a in arrays:
+        b = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+        starts.append(pos)
+        parts.append(b)
+        pad = _aligned(len(b)) - len(b)
+        if pad:
+            parts.append(np.zeros((pad,), np.uint8))
+        pos += len(b) + pad
+    blob = torch.from_numpy(np.concatenate(parts)).to(dev)
+    return blob, [blob.data_ptr() + s for s in starts]
 
 
 def _wmean(a, wa, b, wb):
@@ -667,10 +672,7 @@ class SegmentationEvaluator:
         n = len(gt_labels)
         if frame_offsets is None:
             raise ValueError("frame_offsets is required")
-        off = frame_offsets.cpu().numpy() if torch.is_tensor(frame_offsets) else np.asarray(frame_offsets)
-        off = off.astype(np.int64).reshape(-1)
-        if len(off) < 1 or off[0] != 0 or off[-1] != n or np.any(np.diff(off) < 0):
-            raise ValueError("frame_offsets must rise from 0 to the number of points")
+        off, = _frame_offsets("frame_offsets must rise from 0 to the number of points", (frame_offsets, n))
         return self._calc(gt_labels, pred_labels, gt_ids, pred_ids, off)
 
     def _calc(self, gt_labels, pred_labels, gt_ids, pred_ids, off):
@@ -833,7 +835,7 @@ class TrackingEvalStats:
     def initialize(self, classes, nsamples):
         T = nsamples
         self.ngt = {c: 0 for c in classes}
-        for k in ("ndt", "tp", "fp", "fn", "id_switches", "fragments"):
+        for k in _COUNT_FIELDS + ("id_switches", "fragments"):
             setattr(self, k, {c: [0] * T for c in classes})
         for k in _ACC_FIELDS:
             setattr(self, k, {c: [math.nan] * T for c in classes})
@@ -851,13 +853,11 @@ class TrackingEvalStats:
             if counts.ndim == 1:
                 return [int(x) for x in tids[counts > 0]]
             return [[int(x) for x in tids[row > 0]] for row in counts]
-        return dict(ngt=dict(self.ngt), tp=dict(self.tp), fp=dict(self.fp), fn=dict(self.fn), ndt=dict(self.ndt),
-                    acc_iou=dict(self.acc_iou), acc_angular=dict(self.acc_angular), acc_dist=dict(self.acc_dist),
-                    acc_box=dict(self.acc_box), acc_var=dict(self.acc_var),
-                    id_switches=dict(self.id_switches), fragments=dict(self.fragments),
-                    ngt_ids={c: keys(v) for c, v in self.ngt_ids.items()},
-                    ngt_tracked={c: keys(v) for c, v in self.ngt_tracked.items()},
-                    ndt_ids={c: keys(v) for c, v in self.ndt_ids.items()})
+        plain = ("ngt",) + _COUNT_FIELDS[1:] + _COUNT_FIELDS[:1] + _ACC_FIELDS + ("id_switches", "fragments")   # (ndt after fn, :478)
+        obj = {k: dict(getattr(self, k)) for k in plain}
+        for k in ("ngt_ids", "ngt_tracked", "ndt_ids"):
+            obj[k] = {c: keys(v) for c, v in getattr(self, k).items()}
+        return obj
 
     def __repr__(self):
         return "TrackingEvalStats(%r)" % (self.as_object(),)
@@ -897,7 +897,6 @@ class TrackingEvaluator(DetectionEvaluator):
     def __init__(self, classes, min_overlaps, pr_sample_count=40, min_score=0, pr_sample_scale="log10"):
         super().__init__(classes, min_overlaps, pr_sample_count=pr_sample_count, min_score=min_score,
                          pr_sample_scale=pr_sample_scale)
-        self._slot = {c: i for i, c in enumerate(self._classes)}
         self._dev = None
         self._state = None              # two device buffers of d3d_track_state_bytes(self._cap, T), self._state[self._cur] current
         self._cap, self._cur = 0, 0
@@ -977,13 +976,8 @@ class TrackingEvaluator(DetectionEvaluator):
         gtid, dtid = _host_tids(gt_tids, "gt_tids"), _host_tids(dt_tids, "dt_tids")
         if len(gtid) != len(gt) or len(dtid) != len(dt):
             raise ValueError("one track id per box is required")
-        go = _host_rows(gt_frame_offsets, np.int64, 0)
-        do = _host_rows(dt_frame_offsets, np.int64, 0)
-        for off, n in ((go, len(gt)), (do, len(dt))):
-            if len(off) < 1 or off[0] != 0 or off[-1] != n or np.any(np.diff(off) < 0):
-                raise ValueError("frame offsets must rise from 0 to the number of boxes")
-        if len(go) != len(do):
-            raise ValueError("gt_frame_offsets and dt_frame_offsets must describe the same frames")
+        go, do = _frame_offsets("frame offsets must rise from 0 to the number of boxes",
+                                (gt_frame_offsets, len(gt)), (dt_frame_offsets, len(dt)))
         hs = [self._prepare_host(gt[go[f]:go[f + 1]], dt[do[f]:do[f + 1]], gtid[go[f]:go[f + 1]], dtid[do[f]:do[f + 1]])
               for f in range(len(go) - 1)]
         return self._run(hs, device_of(gt_boxes, dt_boxes, gt_tids, dt_tids)) if hs else []
@@ -999,11 +993,7 @@ class TrackingEvaluator(DetectionEvaluator):
             raise ValueError("one track id per box is required")
         if len(np.unique(gtid)) != len(gtid) or len(np.unique(dtid)) != len(dtid):
             raise ValueError("track ids must be unique among the boxes of a frame")
-        gslot, dslot = np.full((len(gt),), -1, np.int32), np.full((len(dt),), -1, np.int32)
-        gtag, dtag = gt[:, 0].astype(np.int64), dt[:, 0].astype(np.int64)
-        for c, i in self._slot.items():
-            gslot[gtag == c] = i
-            dslot[dtag == c] = i
+        gslot, dslot = _class_slots(self._classes, gt), _class_slots(self._classes, dt)
         score = dt[:, 1]
         sel = (dslot >= 0)[None, :] & ~(score[None, :] < self._pr_thresholds[:, None])          # [T, n]  (:588-593)
         if np.any(sel.any(0) & (dtid == 0)):
@@ -1019,23 +1009,13 @@ class TrackingEvaluator(DetectionEvaluator):
         """the device chain of every frame of `hs` (_prepare_host), queued in order; one fetch at the end"""
         lib = _lib.load()
         T, C = self._pr_nsamples, len(self._classes)
-        # everything the device reads, in one upload: per frame [dt boxes f32 | row_off i64 | 4 tid arrays u64 | 5 index arrays i32]
-        parts, layout, pos = [], [], 0
-
-        def put(a):
-            nonlocal pos
-            b = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-            at = pos
-            parts.append(b)
-            pad = _aligned(len(b)) - len(b)
-            if pad:
-                parts.append(np.zeros((pad,), np.uint8))
-            pos += len(b) + pad
-            return at
-        consts = (put(self._pr_thresholds), put(np.array([np.float32(self._max_distance[c]) for c in self._classes], np.float32)))
-        for h in hs:
-            layout.append({k: put(h[k]) for k in ("dt", "row_off", "dtid", "gtid", "dt_stid", "gt_stid", "dslot", "gslot",
-                                                  "dt_srow", "gt_srow", "perm")})
+        # everything the device reads, in one upload: the thresholds, the classes' distances, then per frame [dt boxes f32 |
+        # row_off i64 | 4 tid arrays u64 | 5 index arrays i32]
+        inputs = (("dt", "dt_boxes"), ("row_off", "row_off"), ("dtid", "dt_tid"), ("gtid", "gt_tid"), ("dt_stid", "dt_stid"),
+                  ("gt_stid", "gt_stid"), ("dslot", "dt_cls"), ("gslot", "gt_cls"), ("dt_srow", "dt_srow"), ("gt_srow", "gt_srow"),
+                  ("perm", "dt_perm"))                          # (_prepare_host's key, _TrackFrame's field)
+        pieces = [self._pr_thresholds, np.array([np.float32(self._max_distance[c]) for c in self._classes], np.float32)]
+        pieces += [h[k] for h in hs for k, _ in inputs]
         sizes = [(len(h["dt"]), len(h["gt"])) for h in hs]
         cache_at, out_at, cpos, opos = [], [], 0, 0
         for n, m in sizes:                                      # the caches; the outputs assign, iou [T, m] and counts [T, 3, C]
@@ -1044,7 +1024,7 @@ class TrackingEvaluator(DetectionEvaluator):
             out_at.append(opos)
             opos += 2 * T * m + 3 * T * C
         with torch.cuda.device(dev):
-            blob = torch.from_numpy(np.concatenate(parts)).to(dev)
+            blob, addr = _upload(dev, pieces)
             gts = [torch.from_numpy(h["gt"]) for h in hs]
             gt_dev = torch.cat(gts).to(dev) if sum(len(g) for g in gts) else None
             caches = torch.empty((max(cpos, 1),), dtype=torch.float32, device=dev)
@@ -1053,25 +1033,23 @@ class TrackingEvaluator(DetectionEvaluator):
             ws_bytes = max(max(lib.d3d_track_workspace_bytes(n, m, T, int(h["row_off"][-1])),
                                lib.d3d_iou3d_workspace_bytes(n, m)) for (n, m), h in zip(sizes, hs))
             ws = _lib.workspace(ws_bytes, dev)
-            base = blob.data_ptr()
             stream = _lib.stream_ptr()
             g0 = 0
             fr = _TrackFrame()
-            for (n, m), h, lay, ca, oa in zip(sizes, hs, layout, cache_at, out_at):
+            for i, ((n, m), h, ca, oa) in enumerate(zip(sizes, hs, cache_at, out_at)):
+                lay = addr[2 + len(inputs) * i:2 + len(inputs) * (i + 1)]
+                for (_, field), at in zip(inputs, lay):
+                    setattr(fr, field, at)
                 cache_ptr = caches.data_ptr() + 4 * ca
                 if n and m:
-                    rc = lib.d3d_match_distance(ctypes.c_void_p(base + lay["dt"]), n, ctypes.c_void_p(gt_dev.data_ptr() + 36 * g0), m,
+                    rc = lib.d3d_match_distance(ctypes.c_void_p(lay[0]), n, ctypes.c_void_p(gt_dev.data_ptr() + 36 * g0), m,
                                                 1, ctypes.c_void_p(cache_ptr), _lib.ptr(ws), ws.numel(), stream)
                     _lib.check(rc, "match_distance")
                 g0 += m
-                for k, f in (("dt", "dt_boxes"), ("dslot", "dt_cls"), ("gslot", "gt_cls"), ("dtid", "dt_tid"), ("gtid", "gt_tid"),
-                             ("dt_stid", "dt_stid"), ("dt_srow", "dt_srow"), ("gt_stid", "gt_stid"), ("gt_srow", "gt_srow"),
-                             ("perm", "dt_perm"), ("row_off", "row_off")):
-                    setattr(fr, f, base + lay[k])
                 fr.cache = cache_ptr if n and m else None
                 fr.n, fr.m, fr.n_total, fr.capacity = n, m, int(h["row_off"][-1]), self._cap
                 optr = out.data_ptr() + 4 * oa
-                rc = lib.d3d_track_frame(ctypes.addressof(fr), ctypes.c_void_p(base + consts[0]), T, ctypes.c_void_p(base + consts[1]),
+                rc = lib.d3d_track_frame(ctypes.addressof(fr), ctypes.c_void_p(addr[0]), T, ctypes.c_void_p(addr[1]),
                                          C, _lib.ptr(self._state[self._cur]), _lib.ptr(self._state[1 - self._cur]),
                                          ctypes.c_void_p(optr), ctypes.c_void_p(optr + 4 * T * m),
                                          ctypes.c_void_p(optr + 8 * T * m), _lib.ptr(ws), ws.numel(), stream)
@@ -1088,23 +1066,10 @@ class TrackingEvaluator(DetectionEvaluator):
         assign = res[:T * m].reshape(T, m)
         iou = res[T * m:2 * T * m].view(np.float32).reshape(T, m)
         counts = res[2 * T * m:].reshape(T, 3, C)
-        st = TrackingEvalStats()
+        st = TrackingEvalStats().initialize(classes, T)
         tracked = (assign >= 0) & (gslot >= 0)[None, :]
         tt, jj = np.nonzero(tracked)
-        terms, gcls = {}, gslot[jj]
-        if len(tt):
-            d_of = assign[tt, jj]
-            ga, da = gt[jj], dt[d_of]
-            dp, db = ga[:, 2:5] - da[:, 2:5], ga[:, 5:8] - da[:, 5:8]
-            dyaw = ga[:, 8] - da[:, 8]
-            terms = dict(acc_iou=iou[tt, jj],
-                         acc_angular=np.abs((dyaw + np.pi) % (2 * np.pi) - np.pi) / np.pi,              # :663-664
-                         acc_dist=np.sqrt((dp[:, 0] * dp[:, 0] + dp[:, 1] * dp[:, 1]) + dp[:, 2] * dp[:, 2]),
-                         acc_box=np.sqrt((db[:, 0] * db[:, 0] + db[:, 1] * db[:, 1]) + db[:, 2] * db[:, 2]))
-        st.ngt, st.ndt, st.tp, st.fp, st.fn, st.id_switches, st.fragments = {}, {}, {}, {}, {}, {}, {}
-        st.ngt_ids, st.ngt_tracked, st.ndt_ids = {}, {}, {}
-        for name in _ACC_FIELDS:
-            setattr(st, name, {})
+        tp, acc = _bin_means(gslot[jj].astype(np.int64) * T + tt, (C, T), _pair_terms(gt[jj], dt[assign[tt, jj]], iou[tt, jj]))
         for i, c in enumerate(classes):
             gi = np.nonzero(gslot == i)[0]
             gi = gi[np.argsort(h["gtid"][gi], kind="stable")]
@@ -1115,22 +1080,13 @@ class TrackingEvaluator(DetectionEvaluator):
             st.ngt_tracked[c] = (h["gtid"][gi], tracked[:, gi].astype(np.int64))
             st.ndt_ids[c] = (h["dtid"][di], sel[:, di].astype(np.int64))
             st.ndt[c] = sel[:, di].sum(1).tolist()
-            of_c = gcls == i
-            tp = np.bincount(tt[of_c], minlength=T)
-            st.tp[c] = tp.tolist()
-            st.fn[c] = (len(gi) - tp).tolist()
+            st.tp[c] = tp[i].tolist()
+            st.fn[c] = (len(gi) - tp[i]).tolist()
             st.fp[c] = counts[:, 0, i].tolist()
             st.id_switches[c] = counts[:, 1, i].tolist()
             st.fragments[c] = counts[:, 2, i].tolist()
-            for name in ("acc_iou", "acc_angular", "acc_dist", "acc_box"):
-                if name in terms:
-                    ssum = np.bincount(tt[of_c], weights=terms[name][of_c].astype(np.float64), minlength=T)
-                    with np.errstate(invalid="ignore", divide="ignore"):
-                        v = np.where(tp > 0, (ssum / tp).astype(np.float32), np.float32(np.nan))
-                else:
-                    v = np.full((T,), np.nan, np.float32)
-                getattr(st, name)[c] = v.tolist()
-            st.acc_var[c] = np.where(tp > 0, -np.inf, np.nan).tolist()      # orientation_var = 0 (:666-674)
+            for name, a in zip(_ACC_FIELDS, acc):
+                getattr(st, name)[c] = a[i].tolist()
         return st
 
     # ------------------------------------------------------------------ accumulation and metrics
