@@ -192,6 +192,13 @@ SIGNATURES = {
                                          ctypes.POINTER(ctypes.c_int32)]),
     "d3d_roi_grid_table": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "d3d_table_pool_backward_index": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    # (us, vs, ds, pre, post: DEVICE fp32 arrays; lo, size: host float[3]; shape: host int32[3])
+    "d3d_frustum_map_workspace_bytes": (_sz, [_i64, _i64]),
+    "d3d_frustum_map_count": (ctypes.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3d_frustum_map_emit": (ctypes.c_int, [_i32, _i32, _i32, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3d_lift_pool_forward": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
+    "d3d_lift_pool_backward_feat": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "d3d_lift_pool_backward_depth": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
 }
 KNN_MAX = 64                        # D3D_KNN_MAX
 FPS_ROUTE_LDS, FPS_ROUTE_STREAM = 3, 4

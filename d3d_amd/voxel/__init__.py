@@ -884,9 +884,10 @@ from .sparse_conv import SparseConvMap, sparse_conv3d, sparse_inverse_conv3d  # 
 from .sparse_pool import sparse_avg_pool3d, sparse_max_pool3d, sparse_pool3d  # noqa: E402  (pooling through the same tables: an extension)
 from .interp import VoxelInterp, voxel_interpolate, voxel_positions, voxel_splat  # noqa: E402  (voxels -> arbitrary points and back: an extension)
 from .dense import VoxelDenseMap, voxel_from_dense, voxel_to_bev, voxel_to_dense  # noqa: E402  (voxels -> a dense grid / BEV map and back: an extension)
+from .lift import FrustumMap, frustum_matrices, lift_splat, lift_splat_bev  # noqa: E402  (camera features -> voxel rows, "lift, splat": an extension)
 
 __all__ = ["VoxelGenerator", "voxelize_3d_dense", "voxelize_3d_sparse", "voxelize_3d_filter", "release_cached_buffers",
            "ReductionType", "MaxPointsFilterType", "MaxVoxelsFilterType", "VoxelIndex", "voxel_pool", "voxel_unpool",
            "VoxelNeighbors", "neighbor_gather", "subm_conv3d", "SparseConvMap", "sparse_conv3d", "sparse_inverse_conv3d",
            "sparse_pool3d", "sparse_max_pool3d", "sparse_avg_pool3d", "VoxelInterp", "voxel_interpolate", "voxel_splat", "voxel_positions",
-           "VoxelDenseMap", "voxel_to_dense", "voxel_to_bev", "voxel_from_dense"]
+           "VoxelDenseMap", "voxel_to_dense", "voxel_to_bev", "voxel_from_dense", "FrustumMap", "lift_splat", "lift_splat_bev", "frustum_matrices"]

@@ -1349,6 +1349,68 @@ int d3d_table_pool_backward_index(const void *grad_out, int64_t rows, int32_t c,
                                   int64_t src_rows, int32_t k, int32_t reduction, const int16_t *arg, const int32_t *count,
                                   void *grad_feat, void *stream);
 
+/* ------------------------------------------------------------------ camera features to voxel rows: the frustum map and lift-splat */
+
+/* The "lift, splat" view transform of LSS / BEVDet / BEVDepth / BEVFusion (bev_pool), csrc/vlift.hip: every pixel of S = B * N cameras
+ * carries a depth distribution over D bins and a context row of C channels; the K = S * D * H * W frustum points are placed in the ego
+ * grid and every cell gets the sum of depth[p] * feat[pixel(p)] over its points.  The result is voxel rows [V, C] with coords, as the
+ * voxelizer's: d3d_vdense_scatter is the dense exit, the sparse convolutions take the rows as they are.  No float atomics, the [K, C]
+ * product never exists, every run gives the same bits.  The reference has no counterpart.
+ *
+ * d3d_frustum_map_count: DEVICE fp32 arrays us[w] (pixel columns), vs[h] (pixel rows), ds[d] (depth bins) -- given explicitly, no
+ *   linspace rounding is part of the contract --, pre[s, 3, 4] and post[s, 3, 4] row-major; HOST arrays lo[3], size[3] fp32 and
+ *   shape[3] int32 in coordinate-column order (x, y, z) as the voxelizer's coords; cams_per_sample = N.
+ *   Point p = ((cam * D + d) * H + h) * W + w.  Every operation below is ONE rounding in fp32 (the build does not contract):
+ *     a   = (us[w], vs[h], ds[d])
+ *     q_i = ((pre[i,0] * a0 + pre[i,1] * a1) + pre[i,2] * a2) + pre[i,3]
+ *     e   = (q0 * q2, q1 * q2, q2)
+ *     x_i = ((post[i,0] * e0 + post[i,1] * e1) + post[i,2] * e2) + post[i,3]
+ *     t_i = (x_i - lo_i) / size_i
+ *   The point is a MEMBER iff t_i >= 0 && t_i < shape_i on all three axes (a NaN fails; -0.0 passes and lands in cell 0); its
+ *   coordinate is c_i = (int32) t_i, its sample b = cam / N.  Points with t in (-1, 0) are NOT members: the .long() truncation of
+ *   LSS's voxel_pooling rounds that band toward zero and folds it into cell 0 -- this rule does not, deliberately.
+ *   Present cells are numbered by ascending key ((b * n0 + c0) * n1 + c1) * n2 + c2: the numbering is a function of the input alone.
+ *   _count writes, into the workspace, the per-point key, the marks of the present cells (a bitmap, set with integer atomics) and
+ *   their scan; counts[2] int64 = {V, the members}.  The caller reads counts back, allocates and calls
+ * d3d_frustum_map_emit with the SAME workspace, untouched in between, and the same sizes: mapping[K] int64 (the row of every point, -1
+ *   for none), coords[v, 3] int64 (x, y, z) and batch_index[v] int64, rows in ascending key.  v is the V of _count (rows from v on are
+ *   not written).  The inverted index (order, offsets) of the folds is d3d_voxel_index(mapping, K, V), unchanged.
+ *   Launches: cells, the scan trio (count), rows, coords (emit); every dependency is a kernel boundary, nothing waits on another
+ *   workgroup.  Workspace: d3d_frustum_map_workspace_bytes(K, B * n0 * n1 * n2), caller-owned.
+ *   D3D_ERR_BAD_ARG: a size[i] that is not positive or not finite, a shape[i] below 1, cams_per_sample below 1, s % cams_per_sample
+ *   != 0, a negative size, v above the number of cells, a missing pointer; D3D_ERR_UNSUPPORTED: K or B * n0 * n1 * n2 above 2^31 - 1;
+ *   D3D_ERR_WORKSPACE: workspace missing or smaller than the query.  All refusals come before any HIP call.
+ *
+ * The folds.  depth[s, d, h, w] and feat[s, h, w, c] (channels-last) in ONE dtype: D3D_F32, D3D_F64, D3D_F16 or D3D_BF16; the half
+ *   types multiply and add in fp32 and round once, to nearest even, at the store.  pix(p) = (p / (D * H * W)) * H * W + p % (H * W).
+ *   Rows move as 16-byte vectors when c is a multiple of 4 (f32) / 2 (f64) / 8 (f16, bf16) and the row pointers are 16-byte aligned,
+ *   element by element otherwise: the same bits on both paths.  One launch each, no workspace, nothing read back.
+ * d3d_lift_pool_forward: out[r] is 0, then + (depth[p] * feat[pix(p)]) for p in order[offsets[r] .. offsets[r + 1]) in that order --
+ *   the product and the sum are two roundings.  out[v, c], every row written exactly once (a row without points: 0).  order / offsets
+ *   as d3d_voxel_index wrote them (trusted).  One lane group per row, eight feature rows in flight; a crowded cell is a long
+ *   sequential fold by contract.
+ * d3d_lift_pool_backward_feat: grad_feat[pixel] is 0, then + (depth[p] * grad[mapping[p]]) over d = 0 .. D - 1 ascending for the
+ *   points p of that pixel with mapping[p] in [0, v).  A gather: grad_feat[s, h, w, c], every row written exactly once; needs no index.
+ * d3d_lift_pool_backward_depth: grad_depth[p] = sum over ch of grad[mapping[p], ch] * feat[pix(p), ch], 0 where mapping[p] is not in
+ *   [0, v).  Products and sums in fp32 (fp64 for D3D_F64), every product rounded, reduced across the lane group; the ORDER of the sum
+ *   is the kernel's own: |result - exact| <= (c + 1) * u * sum |grad * feat| (u the unit roundoff of the accumulation type) plus the
+ *   one rounding of the store.  This is the one output that is not defined bit for bit; it is still the same bits on every run.
+ *   D3D_ERR_BAD_ARG: a negative size, c < 1, a missing pointer with work to do; D3D_ERR_UNSUPPORTED: another dtype, K, v (and for
+ *   _backward_feat s * h * w) above 2^31 - 1.  None of them launches anything.  v == 0 (forward), s * h * w == 0 (_backward_feat) and
+ *   K == 0 (_backward_depth) return D3D_OK before any HIP call. */
+size_t d3d_frustum_map_workspace_bytes(int64_t k, int64_t cells);
+int d3d_frustum_map_count(const float *us, int32_t w, const float *vs, int32_t h, const float *ds, int32_t d, const float *pre,
+                          const float *post, int64_t s, int32_t cams_per_sample, const float *lo, const float *size, const int32_t *shape,
+                          int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+int d3d_frustum_map_emit(int32_t w, int32_t h, int32_t d, int64_t s, int32_t cams_per_sample, const int32_t *shape, int64_t v,
+                         int64_t *mapping, int64_t *coords, int64_t *batch_index, void *workspace, size_t workspace_bytes, void *stream);
+int d3d_lift_pool_forward(const void *depth, const void *feat, int64_t s, int32_t d, int32_t h, int32_t w, int32_t c, int32_t dtype,
+                          const int32_t *order, const int64_t *offsets, int64_t v, void *out, void *stream);
+int d3d_lift_pool_backward_feat(const void *grad, int64_t v, const void *depth, const int64_t *mapping, int64_t s, int32_t d, int32_t h,
+                                int32_t w, int32_t c, int32_t dtype, void *grad_feat, void *stream);
+int d3d_lift_pool_backward_depth(const void *grad, int64_t v, const void *feat, const int64_t *mapping, int64_t s, int32_t d, int32_t h,
+                                 int32_t w, int32_t c, int32_t dtype, void *grad_depth, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
