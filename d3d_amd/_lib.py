@@ -186,6 +186,14 @@ SIGNATURES = {
     "d3d_knn_weights": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, ctypes.c_double, _vp, _vp]),
     "d3d_knn_interp_forward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp]),
     "d3d_knn_interp_backward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _vp]),
+    # (bounds, finite_rows, plan: DEVICE for _bounds / _build and the queries, HOST for _plan; plan: D3DPointGridSegment records)
+    "d3d_point_grid_bounds": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "d3d_point_grid_plan": (ctypes.c_int, [_vp, _vp, _i64, ctypes.c_double, ctypes.c_double, _vp, ctypes.POINTER(ctypes.c_int64)]),
+    "d3d_point_grid_workspace_bytes": (_sz, [_i64, _i64]),
+    "d3d_point_grid_build": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3d_ball_query_grid": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, _i32, _i32, _vp, _vp,
+                                           _vp]),
+    "d3d_knn_query_grid": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     # (out_size: host int32[3]; point_offsets, box_offsets: DEVICE int64 arrays)
     "d3d_roi_grid_max_cells": (_i32, []),
     "d3d_roi_grid_plan": (ctypes.c_int, [_i64, _i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),

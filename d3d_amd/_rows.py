@@ -63,6 +63,14 @@ def check_rows(t, name, row, subject, codes, owner=None, rows=None):
         check_owner_device(owner, t)
 
 
+def check_xyz_rows(t, what):
+    """coordinate rows of the point operators: [N, D] with D >= 3, float32 or float64"""
+    if t.dim() != 2 or t.shape[1] < 3:
+        raise ValueError("%s must be [N, D] with D >= 3 (columns 0..2 are the coordinates), not %s" % (what, tuple(t.shape)))
+    if t.dtype not in FLOAT_CODES:
+        raise ValueError("%s must be float32 or float64, not %s" % (what, t.dtype))
+
+
 def host_offsets(offsets, total, what):
     """offsets -> a list of ints [B + 1], checked: 1-D, from 0 to `total`, nondecreasing.  None: one segment.  Offsets belong on the
     host; a GPU tensor is read back (one blocking copy) for the checks."""

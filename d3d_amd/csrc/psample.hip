@@ -33,6 +33,7 @@
 // k_knn_query: the same walk, a wavefront per centre; the k best so far are kept sorted across the lanes (see the kernel).  The fold
 // that uses table and weights is vinterp.hip's (d3d_knn_interp_forward / _backward).
 #include "common.hpp"
+#include "pquery.hpp"
 
 #include <cmath>
 #include <limits>
@@ -106,17 +107,7 @@ template <int CTRL, int ROW_MASK> __device__ __forceinline__ FpsKey64 key_dpp(co
 {
     return FpsKey64{d3d_dpp_u64<CTRL, ROW_MASK>(k.d), d3d_dpp_u32<CTRL, ROW_MASK>(k.inv)};
 }
-__device__ __forceinline__ uint32_t ps_readlane(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
-__device__ __forceinline__ uint64_t ps_readlane(uint64_t v, int lane)
-{
-    return ((uint64_t)ps_readlane((uint32_t)(v >> 32), lane) << 32) | ps_readlane((uint32_t)v, lane);
-}
 __device__ __forceinline__ FpsKey64 ps_readlane(const FpsKey64 &k, int lane) { return FpsKey64{ps_readlane(k.d, lane), ps_readlane(k.inv, lane)}; }
-__device__ __forceinline__ float ps_readlane(float v, int lane) { return __uint_as_float(ps_readlane(__float_as_uint(v), lane)); }
-__device__ __forceinline__ double ps_readlane(double v, int lane)
-{
-    return __longlong_as_double((long long)ps_readlane((uint64_t)__double_as_longlong(v), lane));
-}
 
 #define D3D_KEY_STEP(CTRL, MASK)                   \
     {                                              \
@@ -142,12 +133,6 @@ template <typename T> struct FpsSlot {
     typename FpsKeyOf<T>::type key;
     T x, y, z;
 };
-
-template <typename T> __device__ __forceinline__ bool ps_finite3(T x, T y, T z)
-{
-    const T inf = std::numeric_limits<T>::infinity();
-    return fabs(x) < inf && fabs(y) < inf && fabs(z) < inf;         // false for NaN
-}
 
 // A lane's candidate of one step: the best of its rows so far.  d < 0: none yet.  row: the row MINUS the lane's number (a constant of
 // the unrolled loops: no register per row).
@@ -347,12 +332,7 @@ __global__ __launch_bounds__(kBqThreads) void k_ball_query(const T *__restrict__
     if (c >= m) return;
     int64_t p0 = 0, p1 = n;
     if (center_offsets) {                      // the segment b of the centre: center_offsets[b] <= c < center_offsets[b + 1]
-        int64_t lo = 0, hi = segments;
-        while (hi - lo > 1) {
-            const int64_t mid = lo + (hi - lo) / 2;
-            if (center_offsets[mid] <= c) lo = mid;
-            else hi = mid;
-        }
+        const int64_t lo = ps_segment_of(center_offsets, segments, c);
         p0 = point_offsets[lo], p1 = point_offsets[lo + 1];
     }
     const T *const q0 = centers + c * cstride;
@@ -368,8 +348,7 @@ __global__ __launch_bounds__(kBqThreads) void k_ball_query(const T *__restrict__
             in[u] = false;
             if (i < p1) {
                 const T *p = points + i * pstride;
-                const T dx = p[0] - cx, dy = p[1] - cy, dz = p[2] - cz;
-                in[u] = ((dx * dx) + (dy * dy)) + (dz * dz) < r2;               // false for NaN
+                in[u] = ps_q<T>(p[0], p[1], p[2], cx, cy, cz) < r2;              // false for NaN
             }
         }
 #pragma unroll
@@ -389,35 +368,7 @@ __global__ __launch_bounds__(kBqThreads) void k_ball_query(const T *__restrict__
 }
 
 // ---------------------------------------------------------------- k nearest rows
-// The order-keeping key of a candidate: q >= +0 always, so its bits order as unsigned integers; the row breaks ties (the lower row
-// first).  fp32: one 64-bit word {q bits : 32 | row : 32}; fp64: the 64 bits of q and the row beside them.  All ones = "no entry":
-// above every candidate (its q bits would be a NaN's, and a NaN q is no candidate).
-struct KnnKey64 {
-    uint64_t d;
-    uint32_t row;
-};
-template <typename T> struct KnnKeyOf;
-template <> struct KnnKeyOf<float> { typedef uint64_t type; };
-template <> struct KnnKeyOf<double> { typedef KnnKey64 type; };
-
-__device__ __forceinline__ uint64_t knn_make(float q, uint32_t row) { return ((uint64_t)__float_as_uint(q) << 32) | row; }
-__device__ __forceinline__ KnnKey64 knn_make(double q, uint32_t row) { return KnnKey64{(uint64_t)__double_as_longlong(q), row}; }
-__device__ __forceinline__ void knn_clear(uint64_t &k) { k = ~0ull; }
-__device__ __forceinline__ void knn_clear(KnnKey64 &k) { k.d = ~0ull, k.row = ~0u; }
-__device__ __forceinline__ bool knn_lt(uint64_t a, uint64_t b) { return a < b; }
-__device__ __forceinline__ bool knn_lt(const KnnKey64 &a, const KnnKey64 &b) { return a.d < b.d || (a.d == b.d && a.row < b.row); }
-__device__ __forceinline__ bool knn_none(uint64_t k) { return k == ~0ull; }
-__device__ __forceinline__ bool knn_none(const KnnKey64 &k) { return k.d == ~0ull; }
-__device__ __forceinline__ uint32_t knn_row(uint64_t k) { return (uint32_t)k; }
-__device__ __forceinline__ uint32_t knn_row(const KnnKey64 &k) { return k.row; }
-__device__ __forceinline__ float knn_dist(uint64_t k, float) { return __uint_as_float((uint32_t)(k >> 32)); }
-__device__ __forceinline__ double knn_dist(const KnnKey64 &k, double) { return __longlong_as_double((long long)k.d); }
-__device__ __forceinline__ uint64_t knn_readlane(uint64_t k, int lane) { return ps_readlane(k, lane); }
-__device__ __forceinline__ KnnKey64 knn_readlane(const KnnKey64 &k, int lane) { return KnnKey64{ps_readlane(k.d, lane), ps_readlane(k.row, lane)}; }
-// lane l reads lane l - 1 over the whole wavefront (wave_shr:1); lane 0 reads 0 and is never asked
-__device__ __forceinline__ uint64_t knn_up(uint64_t k) { return d3d_dpp_u64<0x138, 0xf>(k); }
-__device__ __forceinline__ KnnKey64 knn_up(const KnnKey64 &k) { return KnnKey64{d3d_dpp_u64<0x138, 0xf>(k.d), d3d_dpp_u32<0x138, 0xf>(k.row)}; }
-
+// (the order-keeping key of a candidate and its insertion: pquery.hpp, shared with the grid route of pgrid.hip)
 // One wavefront per centre.  The wave holds its best rows so far SORTED ACROSS LANES: lane l the l-th smallest key (all ones while
 // fewer than l + 1 candidates were seen); tau = lane k - 1's key, wave-uniform, is what a row has to beat.  The segment is walked
 // 4 x 64 rows at a time, as k_ball_query walks it; per tile key < tau and a ballot -- zero for most tiles of an unordered cloud once
@@ -437,12 +388,7 @@ __global__ __launch_bounds__(kBqThreads) void k_knn_query(const T *__restrict__ 
     if (c >= m) return;
     int64_t p0 = 0, p1 = n;
     if (center_offsets) {                      // the segment b of the centre: center_offsets[b] <= c < center_offsets[b + 1]
-        int64_t lo = 0, hi = segments;
-        while (hi - lo > 1) {
-            const int64_t mid = lo + (hi - lo) / 2;
-            if (center_offsets[mid] <= c) lo = mid;
-            else hi = mid;
-        }
+        const int64_t lo = ps_segment_of(center_offsets, segments, c);
         p0 = point_offsets[lo], p1 = point_offsets[lo + 1];
     }
     const T *const q0 = centers + c * cstride;
@@ -457,26 +403,12 @@ __global__ __launch_bounds__(kBqThreads) void k_knn_query(const T *__restrict__ 
             knn_clear(key[u]);
             if (i < p1) {
                 const T *p = points + i * pstride;
-                const T dx = p[0] - cx, dy = p[1] - cy, dz = p[2] - cz;
-                const T q = ((dx * dx) + (dy * dy)) + (dz * dz);
+                const T q = ps_q<T>(p[0], p[1], p[2], cx, cy, cz);
                 if (q == q) key[u] = knn_make(q, (uint32_t)i);                  // (a NaN q: no candidate)
             }
         }
 #pragma unroll
-        for (int u = 0; u < kBqAhead; u++) {
-            unsigned long long vote = __ballot(knn_lt(key[u], tau));
-            while (vote) {                     // (wave-uniform)
-                const int src = __ffsll((long long)vote) - 1;
-                const K nk = knn_readlane(key[u], src);
-                const int pos = __popcll(__ballot(knn_lt(held, nk)));           // held is sorted: the lanes 0 .. pos - 1
-                const K up = knn_up(held);
-                if (lane > pos) held = up;
-                else if (lane == pos) held = nk;
-                tau = knn_readlane(held, k - 1);
-                // the lanes above src that still beat tau, which has come down: of a tile's 64 rows only a few are ever inserted
-                vote = __ballot(knn_lt(key[u], tau)) & (~1ull << src);
-            }
-        }
+        for (int u = 0; u < kBqAhead; u++) knn_insert_tile(key[u], held, tau, lane, k);
     }
     if (lane < k) {
         const bool none = knn_none(held);

@@ -97,10 +97,11 @@ def aligned_scatter(coordinates, feature_map, method="drop"):
     return AlignedScatter.apply(feature_map, coordinates, align_type)
 
 
+from .grid import PointGrid, grid_plan                                 # noqa: E402
 from .sample import ball_query, fps_plan, furthest_point_sample      # noqa: E402
 from .knn import PointInterp, knn_query, point_interpolate           # noqa: E402
 from .roi import RoiGrid, group_pool, roi_grid_max_cells, roi_grid_plan, roiaware_pool3d, roipoint_pool3d      # noqa: E402
 
 __all__ = ["aligned_scatter", "AlignedScatter", "AlignType", "aligned_scatter_forward", "aligned_scatter_backward",
            "cuda_available", "furthest_point_sample", "ball_query", "fps_plan", "knn_query", "PointInterp", "point_interpolate",
-           "RoiGrid", "roiaware_pool3d", "group_pool", "roipoint_pool3d", "roi_grid_plan", "roi_grid_max_cells"]
+           "RoiGrid", "roiaware_pool3d", "group_pool", "roipoint_pool3d", "roi_grid_plan", "roi_grid_max_cells", "PointGrid", "grid_plan"]

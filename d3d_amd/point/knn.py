@@ -18,6 +18,7 @@ import torch
 from .. import _lib
 from .._rows import FEATURE_CODES, FLOAT_CODES, ROW_MAX, as_tensor, back_to_caller, check_rows, device_of, host_offsets, rows_on
 from ..voxel.interp import WeightedTable, table_fold
+from .grid import PointGrid
 from .sample import check_xyz_rows
 
 _K_MAX = _lib.KNN_MAX
@@ -32,14 +33,24 @@ def _check_k(k, what="k"):
 
 
 def _check_pair(points, centers, k, point_offsets, center_offsets, names=("points", "centers")):
-    """every host-side refusal of a query -> (points, centers, k, poffs + coffs or None, segments, points came as numpy)"""
-    points, was_numpy = as_tensor(points, names[0])
+    """every host-side refusal of a query -> (points, centers, k, poffs + coffs or None, segments, points came as numpy).  A
+    PointGrid in the place of the points comes back as it is, with the centre offsets alone (None: one segment)"""
+    grid = points if isinstance(points, PointGrid) else None
+    if grid is not None:
+        points, was_numpy = grid.points, grid._was_numpy
+    else:
+        points, was_numpy = as_tensor(points, names[0])
     centers, _ = as_tensor(centers, names[1])
     check_xyz_rows(points, names[0])
     check_xyz_rows(centers, names[1])
     if points.dtype != centers.dtype:
         raise ValueError("%s (%s) and %s (%s) must share a dtype" % (names[0], points.dtype, names[1], centers.dtype))
     k = _check_k(k)
+    if grid is not None:
+        if centers.shape[0] * k > ROW_MAX:
+            raise ValueError("a kNN query takes at most 2^31 - 1 points and table entries (centres x k)")
+        coffs = grid.check_query(centers, k, ("k", names[1].rstrip("s") + "_offsets"), point_offsets, center_offsets, "")
+        return grid, centers, k, coffs, grid.num_segments, was_numpy
     if (point_offsets is None) != (center_offsets is None):
         raise ValueError("%s_offsets and %s_offsets go together: give both or neither" % (names[0].rstrip("s"), names[1].rstrip("s")))
     n, m = points.shape[0], centers.shape[0]
@@ -56,6 +67,8 @@ def _check_pair(points, centers, k, point_offsets, center_offsets, names=("point
 
 def _query(points, centers, k, offs, segments, dev, want_dist):
     """-> (table [M, k] int32, dist2 [M, k] or None) on dev; M > 0"""
+    if isinstance(points, PointGrid):
+        return points.knn(centers, offs, k, want_dist)
     n, m = points.shape[0], centers.shape[0]
     pts, pstride = rows_on(points, dev)
     ctr, cstride = rows_on(centers, dev)
@@ -86,14 +99,19 @@ def knn_query(points, centers, k, point_offsets=None, center_offsets=None, retur
     The rule (exact): q as in furthest_point_sample; row i is a candidate iff q is not NaN (rows and centres that are not finite by a
     NaN drop out; a q that overflows to +inf is a candidate and sorts last); a centre's entries are its candidates in ascending
     (q, i), the lower row first where q is equal; dist2 holds their q.  O(M N) per segment: made for keypoint counts.
+
+    A PointGrid in the place of `points` takes the grid route: the same table and the same bits of dist2 from rings of cells around
+    every centre -- made for N = M = 10^5.  Its segments are the point offsets (point_offsets with it is a ValueError, center_offsets
+    is required iff the grid was built with offsets); the centres' dtype must be the grid's.
     """
     points, centers, k, offs, segments, was_numpy = _check_pair(points, centers, k, point_offsets, center_offsets)
     m = centers.shape[0]
-    odev = points.device
+    grid = points if isinstance(points, PointGrid) else None
+    odev = points.device if grid is None else grid._odev
     if m == 0:
         table, dist2 = torch.empty((0, k), dtype=torch.int32, device=odev), torch.empty((0, k), dtype=points.dtype, device=odev)
     else:
-        dev = device_of(points, centers)
+        dev = device_of(points, centers) if grid is None else grid.device
         table, dist2 = _query(points, centers, k, offs, segments, dev, return_distances)
         if return_distances:
             table, dist2 = _lib.to_caller((table, dist2), odev, dev)
@@ -107,7 +125,8 @@ def knn_query(points, centers, k, point_offsets=None, center_offsets=None, retur
 class PointInterp(WeightedTable):
     """The neighbour table of one frame and layer: for every unknown (query) row its k nearest known rows and their weights.
 
-    :param known: [Nk, D], D >= 3: the rows that carry features (the keypoints of the coarser level), and
+    :param known: [Nk, D], D >= 3: the rows that carry features (the keypoints of the coarser level), or a PointGrid over them (the
+        grid route of knn_query: the same table, dist2 and weights; known_offsets is then the grid's), and
     :param unknown: [Mu, D'], D' >= 3: the rows that want them, of the same dtype (float32 or float64); torch tensors or numpy arrays
     :param k: 1 .. 64 neighbours (3: pointnet2's three_nn)
     :param known_offsets, unknown_offsets: [B + 1] segment boundaries, both or neither, as knn_query's
@@ -130,7 +149,7 @@ class PointInterp(WeightedTable):
         eps = float(eps)
         if known.dtype == torch.float32 and eps > float(np.finfo(np.float32).max):
             raise ValueError("eps = %r is not finite in float32" % (eps,))
-        dev = device_of(known, unknown)
+        dev = known.device if isinstance(known, PointGrid) else device_of(known, unknown)
         m = unknown.shape[0]
         with torch.cuda.device(dev):
             if m == 0:
@@ -143,7 +162,7 @@ class PointInterp(WeightedTable):
                 rc = _lib.load().d3d_knn_weights(_lib.ptr(table), _lib.ptr(dist2), m, k, FLOAT_CODES[dist2.dtype], int(power), eps,
                                                  _lib.ptr(weights), _lib.stream_ptr())
                 _lib.check(rc, "knn_weights")
-        self._set(dev, table, dist2, weights, known.shape[0])
+        self._set(dev, table, dist2, weights, known.num_points if isinstance(known, PointGrid) else known.shape[0])
         self.power, self.eps = int(power), eps
 
     def _set(self, dev, table, dist2, weights, num_known):

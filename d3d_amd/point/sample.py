@@ -15,16 +15,10 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .._rows import FLOAT_CODES, ROW_MAX, as_tensor, device_of, host_offsets, rows_on
+from .._rows import FLOAT_CODES, ROW_MAX, as_tensor, check_xyz_rows, device_of, host_offsets, rows_on
+from .grid import PointGrid
 
 _NSAMPLE_MAX = 1024
-
-
-def check_xyz_rows(t, what):
-    if t.dim() != 2 or t.shape[1] < 3:
-        raise ValueError("%s must be [N, D] with D >= 3 (columns 0..2 are the coordinates), not %s" % (what, tuple(t.shape)))
-    if t.dtype not in FLOAT_CODES:
-        raise ValueError("%s must be float32 or float64, not %s" % (what, t.dtype))
 
 
 def fps_plan(segment_rows, dtype=torch.float32):
@@ -111,6 +105,9 @@ def ball_query(points, centers, radius, nsample, point_offsets=None, center_offs
     :param nsample: 1 .. 1024, the width of the table
     :param point_offsets, center_offsets: [B + 1] segment boundaries of the two arrays, both or neither; a centre sees the points of
         its own segment only.  On the host; a GPU tensor is read back once for the checks
+    A PointGrid in the place of `points` takes the grid route: the same table and counts, bit for bit, from the cells around every
+    centre alone -- made for N = M = 10^5.  Its segments are the point offsets (point_offsets with it is a ValueError, center_offsets
+    is required iff the grid was built with offsets), the centres' dtype must be the grid's, and nsample stops at 64 there
     :param pad: 'none': the slots after the last entry are -1; 'first' (pointnet2's convention): they repeat the first entry -- an
         empty ball stays all -1 with count 0
     :return: (table [M, nsample] int32, counts [M] int32) on the side `points` came from (numpy in, numpy out).  Table values are
@@ -119,7 +116,11 @@ def ball_query(points, centers, radius, nsample, point_offsets=None, center_offs
     The rule (exact): r2 = r * r with r rounded to the dtype; row i is inside iff q < r2 (strict; false for NaN, so rows and centres
     that are not finite match nothing), q as in furthest_point_sample.  O(M N) per segment: made for keypoint counts.
     """
-    points, was_numpy = as_tensor(points, "points")
+    grid = points if isinstance(points, PointGrid) else None
+    if grid is not None:
+        points, was_numpy = grid.points, grid._was_numpy
+    else:
+        points, was_numpy = as_tensor(points, "points")
     centers, _ = as_tensor(centers, "centers")
     check_xyz_rows(points, "points")
     check_xyz_rows(centers, "centers")
@@ -132,20 +133,24 @@ def ball_query(points, centers, radius, nsample, point_offsets=None, center_offs
         raise ValueError("nsample must be in 1 .. %d, not %d" % (_NSAMPLE_MAX, nsample))
     if not isinstance(pad, str) or pad.lower() not in ("none", "first"):
         raise ValueError("pad must be 'none' or 'first', not %r" % (pad,))
-    if (point_offsets is None) != (center_offsets is None):
+    if grid is None and (point_offsets is None) != (center_offsets is None):
         raise ValueError("point_offsets and center_offsets go together: give both or neither")
     n, m = points.shape[0], centers.shape[0]
     if n > ROW_MAX or m > ROW_MAX:
         raise ValueError("ball_query takes at most 2^31 - 1 points and centres")
     segments = 0
-    if point_offsets is not None:
+    if grid is not None:
+        coffs = grid.check_query(centers, nsample, ("nsample", "center_offsets"), point_offsets, center_offsets, " (nsample up to 1024)")
+    elif point_offsets is not None:
         poffs, coffs = host_offsets(point_offsets, n, "point_offsets"), host_offsets(center_offsets, m, "center_offsets")
         if len(poffs) != len(coffs):
             raise ValueError("point_offsets names %d segments, center_offsets %d" % (len(poffs) - 1, len(coffs) - 1))
         segments = len(poffs) - 1
-    odev = points.device
+    odev = points.device if grid is None else grid._odev
     if m == 0:
         table, counts = (torch.empty((0, nsample), dtype=torch.int32, device=odev), torch.empty((0,), dtype=torch.int32, device=odev))
+    elif grid is not None:
+        table, counts = _lib.to_caller(grid.ball(centers, coffs, radius, nsample, pad.lower() == "first"), odev, grid.device)
     else:
         dev = device_of(points, centers)
         pts, pstride = rows_on(points, dev)

@@ -1291,6 +1291,82 @@ int d3d_knn_interp_forward(const void *feat, int64_t v, int32_t c, int32_t dtype
 int d3d_knn_interp_backward(const void *grad, int64_t rows, int32_t c, int32_t dtype, const int32_t *order, const int64_t *offsets,
                             const void *weights, int32_t j, int64_t v, void *grad_feat, void *stream);
 
+/* ------------------------------------------------------------------ PointGrid: grid-accelerated ball query and kNN, the same bits */
+
+/* A uniform cell index of a cloud, built once per frame, and the two neighbour searches over it (csrc/pgrid.hip).  d3d_ball_query_grid
+ * and d3d_knn_query_grid return BIT FOR BIT what d3d_ball_query / d3d_knn_query return for the same points, centres and arguments --
+ * tables, counts, dist2, padding, -1 / +inf tails, GLOBAL row numbers -- and read only the cells a centre can reach (the proofs:
+ * DESIGN.md 8j).  No float atomics, no LDS; the queries take no workspace.  The reference has no counterpart.
+ *
+ * The grid, per SEGMENT (one cloud, or one slice of point_offsets):
+ *   a FINITE ROW has three finite coordinates.  lo_a / hi_a = the least / largest coordinate a over the segment's finite rows, as
+ *     doubles (exact for fp32); a segment without a finite row has lo = 0 and ONE cell;
+ *   cap = max(64, ceil(max_cells_per_point * finite rows)) as a double: a bound on memory (offsets: 8 bytes per cell), not a tuning
+ *     number, and what keeps a cloud with int32-sized or 1e19 coordinates legal;
+ *   h = the first of cell_size * 2^j, j = 0, 1, ..., with prod_a (floor((hi_a - lo_a) / h) + 1) <= cap, the quotients and the product
+ *     in fp64, compared BEFORE any conversion to an integer; inv_h = 1 / h in fp64; dim_a = floor((hi_a - lo_a) * inv_h) + 1;
+ *   the cell of a coordinate: cell_a(x) = clamp(floor((fp64(x) - lo_a) * inv_h), 0, dim_a - 1), clamped while still a double; a NaN
+ *     gives 0 (centres only).  Every step is monotone in x, so cell_a is: all that follows rests on that;
+ *   cell id = base_s + (z * dim_y + y) * dim_x + x: x is fastest, so the cells of an x range at fixed (y, z) are ONE contiguous run
+ *     of `order`;
+ *   a row with a NaN coordinate maps to -1 (it can be a candidate of neither query); a row without NaN but with an infinite
+ *     coordinate maps to the segment's OVERFLOW CELL base_s + dim_x * dim_y * dim_z (d3d_knn_query counts q = +inf as a candidate
+ *     that sorts last: these rows stay reachable); base_0 = 0, base_{s+1} = base_s + cells_s + 1; total_cells = the sum, at most
+ *     2^31 - 1;
+ *   order / offsets = d3d_voxel_index(mapping, n, total_cells), unchanged: rows grouped by cell, ascending row inside a cell;
+ *   packed[K', 3] in `dtype`: the coordinates of row order[j] at entry j, K' = counts[0] = the mapped rows.
+ *
+ * d3d_point_grid_bounds: points[n, row_stride >= 3] as d3d_ball_query reads them; point_offsets: DEVICE int64[segments + 1] or NULL
+ *   (one segment, `segments` ignored) -> DEVICE bounds[S, 6] = (lo_x, lo_y, lo_z, hi_x, hi_y, hi_z) as doubles and finite_rows[S]
+ *   int64, zeros for a segment without a finite row.  Integer atomic maxima on order-keeping keys and an integer sum: the same bits on
+ *   every run.  The caller reads both back (ONE host read-back per grid) for
+ * d3d_point_grid_plan (PURE HOST, no HIP call): HOST bounds, finite_rows -> HOST plan[S] and *total_cells.  cell_size and
+ *   max_cells_per_point: finite, > 0.  D3D_ERR_UNSUPPORTED: total_cells above 2^31 - 1, an extent hi - lo that is not finite.
+ * d3d_point_grid_build: DEVICE plan[S] -> mapping[n] int64, then order[n] int32, offsets[total_cells + 1] int64 and counts[2] int64
+ *   exactly as d3d_voxel_index writes them (its launches, its workspace: d3d_point_grid_workspace_bytes(n, total_cells)), then
+ *   packed.  point_offsets as above, TRUSTED.
+ * d3d_ball_query_grid / d3d_knn_query_grid: the centres, radius / nsample / pad_first or k, table, counts or dist2 of d3d_ball_query /
+ *   d3d_knn_query, and the grid in place of the points: n (its rows), plan, order, cell_offsets (= offsets), packed, all DEVICE and
+ *   TRUSTED.  center_offsets: DEVICE int64[segments + 1], required iff the grid was built with point_offsets (NULL: one segment); a
+ *   centre sees the cells of its own segment only.  One launch, a wavefront per centre.
+ *     ball: the box of cells of u_a - R .. u_a + R per axis, u_a = fp64(x_c) - lo_a, R = r (1 + 2^-20), every edge moved outward by
+ *       2^-50 of itself; the entries are the nsample LOWEST rows among the inside rows of the box -- the first nsample inside rows in
+ *       ascending row, as d3d_ball_query's.  The overflow cell is never read.
+ *     kNN: rings of cells around the centre's own clamped cell; after ring rho, d = the least distance of the centre to a face of
+ *       the walked box that is not on the grid's border (faces at j * h, the centre at u_a), dd = d (1 - 2^-20) - 2^-20 h; the
+ *       walk ends iff the k-th held key exists and fp64(q_k) < dd * dd * (1 - 2^-20), with dd > 0 and the right side at least four
+ *       times the smallest normal number of the dtype -- STRICT: an unexplored row with equal q and a lower row number would win the
+ *       tie.  When every face is on the border the grid is exhausted; the overflow cell is walked then unless the k-th key is
+ *       there with a finite q.
+ *   nsample and k are at most D3D_KNN_MAX here (one held entry per lane): above it D3D_ERR_UNSUPPORTED -- d3d_ball_query takes up to
+ *   1024.
+ * D3D_ERR_BAD_ARG: a negative size, a stride below 3, nsample / k below 1 (nsample above 1024), a radius, cell_size or
+ *   max_cells_per_point that is not a finite positive number, bounds that are not finite or not ordered, total_cells < 1, a missing
+ *   pointer with work to do; D3D_ERR_UNSUPPORTED: another dtype than D3D_F32 / D3D_F64, n, m, segments or total_cells above 2^31 - 1,
+ *   nsample / k above D3D_KNN_MAX; D3D_ERR_WORKSPACE: workspace missing or smaller than the query.  None of them launches anything.
+ *   m == 0 (queries) and S == 0 (bounds, plan) return D3D_OK before any HIP call. */
+typedef struct D3DPointGridSegment {
+    double lo[3];
+    double h, inv_h;
+    int64_t base;      /* the id of the segment's first cell; its overflow cell is base + dim[0] * dim[1] * dim[2] */
+    int32_t dim[3];
+    int32_t pad_;
+} D3DPointGridSegment; /* 64 bytes */
+int d3d_point_grid_bounds(const void *points, int64_t n, int32_t row_stride, int32_t dtype, const int64_t *point_offsets, int64_t segments,
+                          double *bounds, int64_t *finite_rows, void *stream);
+int d3d_point_grid_plan(const double *bounds, const int64_t *finite_rows, int64_t segments, double cell_size, double max_cells_per_point,
+                        D3DPointGridSegment *plan, int64_t *total_cells);
+size_t d3d_point_grid_workspace_bytes(int64_t n, int64_t total_cells);
+int d3d_point_grid_build(const void *points, int64_t n, int32_t row_stride, int32_t dtype, const int64_t *point_offsets, int64_t segments,
+                         const D3DPointGridSegment *plan, int64_t total_cells, int64_t *mapping, int32_t *order, int64_t *offsets,
+                         int64_t *counts, void *packed, void *workspace, size_t workspace_bytes, void *stream);
+int d3d_ball_query_grid(const void *centers, int64_t m, int32_t center_stride, int32_t dtype, const int64_t *center_offsets, int64_t segments,
+                        const D3DPointGridSegment *plan, const int32_t *order, const int64_t *cell_offsets, const void *packed, int64_t n,
+                        double radius, int32_t nsample, int32_t pad_first, int32_t *table, int32_t *counts, void *stream);
+int d3d_knn_query_grid(const void *centers, int64_t m, int32_t center_stride, int32_t dtype, const int64_t *center_offsets, int64_t segments,
+                       const D3DPointGridSegment *plan, const int32_t *order, const int64_t *cell_offsets, const void *packed, int64_t n,
+                       int32_t k, int32_t *table, void *dist2, void *stream);
+
 /* ------------------------------------------------------------------ RoI pooling of points: the cell table of rotated boxes */
 
 /* The step where a two-stage detector turns a proposal box back into features (csrc/roipool.hip, csrc/vtpool.hip): the points inside
