@@ -207,6 +207,13 @@ SIGNATURES = {
     "d3d_lift_pool_forward": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
     "d3d_lift_pool_backward_feat": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "d3d_lift_pool_backward_depth": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    # (perm, seg_offsets, offsets: DEVICE int64 arrays; centers / radii / classes of the drawing: DEVICE int32)
+    "d3d_heatmap_peaks_max": (_i32, []),
+    "d3d_heatmap_peaks_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i32]),
+    "d3d_heatmap_peaks": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3d_circle_nms_max": (_i32, []),
+    "d3d_circle_nms": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _i64, _i32, _i32, ctypes.c_double, _i32, _vp, _vp]),
+    "d3d_gaussian_heatmap": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
 }
 KNN_MAX = 64                        # D3D_KNN_MAX
 FPS_ROUTE_LDS, FPS_ROUTE_STREAM = 3, 4

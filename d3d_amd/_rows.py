@@ -92,6 +92,22 @@ def host_offsets(offsets, total, what):
     return offs
 
 
+def group_ids(groups):
+    """groups as an int64 torch tensor whose equal values are the caller's equal values (uint64 is reinterpreted: a bijection)"""
+    if isinstance(groups, np.ndarray):
+        if not np.issubdtype(groups.dtype, np.integer):
+            raise TypeError("groups must be an integer array, got %s" % groups.dtype)
+        groups = np.ascontiguousarray(groups)
+        return torch.from_numpy(groups.view(np.int64) if groups.dtype == np.uint64 else groups.astype(np.int64, copy=False))
+    if not torch.is_tensor(groups):
+        raise TypeError("groups must be a torch tensor or a numpy array of integers")
+    if groups.dtype == torch.bool or groups.is_floating_point() or groups.is_complex():
+        raise TypeError("groups must be an integer tensor, got %s" % groups.dtype)
+    if groups.dtype == getattr(torch, "uint64", None):
+        return groups.contiguous().view(torch.int64)
+    return groups.to(torch.int64)
+
+
 def rows_on(t, dev):
     """-> (tensor on dev with unit column stride, its row stride in elements)"""
     t = t.detach().to(dev)

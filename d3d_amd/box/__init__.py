@@ -15,7 +15,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from .. import _lib, options
-from .._rows import device_of
+from .._rows import device_of, group_ids
 
 
 class IouType(enum.IntEnum):            # box/common.h:5-9
@@ -395,20 +395,7 @@ def box2d_nms(boxes, scores, iou_method="box", supression_method="hard",
     return _egress(keep, was_numpy)
 
 
-def _group_ids(groups):
-    """groups as an int64 torch tensor whose equal values are the caller's equal values (uint64 is reinterpreted: a bijection)"""
-    if isinstance(groups, np.ndarray):
-        if not np.issubdtype(groups.dtype, np.integer):
-            raise TypeError("groups must be an integer array, got %s" % groups.dtype)
-        groups = np.ascontiguousarray(groups)
-        return torch.from_numpy(groups.view(np.int64) if groups.dtype == np.uint64 else groups.astype(np.int64, copy=False))
-    if not torch.is_tensor(groups):
-        raise TypeError("groups must be a torch tensor or a numpy array of integers")
-    if groups.dtype == torch.bool or groups.is_floating_point() or groups.is_complex():
-        raise TypeError("groups must be an integer tensor, got %s" % groups.dtype)
-    if groups.dtype == getattr(torch, "uint64", None):
-        return groups.contiguous().view(torch.int64)
-    return groups.to(torch.int64)
+_group_ids = group_ids               # (shared with circle_nms: d3d_amd._rows)
 
 
 def box2d_nms_batched(boxes, scores, groups, iou_method="box", supression_method="hard",
@@ -858,7 +845,12 @@ def box3dr_pdist(points, boxes, project_axis=2):
 iou2d = box2d_iou
 nms = box2d_nms
 
-__all__ = ["Iou2D", "Iou2DR", "GIou2DR", "DIou2DR", "PDist2DR", "iou2d_backward", "iou2dr_backward", "giou2dr_forward",
+from .center import (HeatmapPeaks, circle_nms, circle_nms_max, gather_at_peaks, gaussian_heatmap, gaussian_radius,  # noqa: E402
+                     heatmap_peaks, heatmap_peaks_max)
+
+__all__ = ["HeatmapPeaks", "heatmap_peaks", "heatmap_peaks_max", "gather_at_peaks", "circle_nms", "circle_nms_max", "gaussian_heatmap",
+           "gaussian_radius",
+           "Iou2D", "Iou2DR", "GIou2DR", "DIou2DR", "PDist2DR", "iou2d_backward", "iou2dr_backward", "giou2dr_forward",
            "giou2dr_backward", "diou2dr_forward", "diou2dr_backward", "iou2dr_flags", "pdist2dr_forward", "pdist2dr_backward",
            "box2dr_crop", "box3dp_crop", "box2dr_pdist", "box3dr_pdist", "seg1d_pdist", "seg1d_iou", "crop_2dr", "box2d_iou", "box2d_nms",
            "box2d_nms_batched", "box2d_iou_paired", "box3d_iou_paired", "IouPaired2D", "IouPaired3D", "box2d_iou_sparse", "iou3d_sparse",

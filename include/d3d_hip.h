@@ -1487,6 +1487,81 @@ int d3d_lift_pool_backward_feat(const void *grad, int64_t v, const void *depth, 
 int d3d_lift_pool_backward_depth(const void *grad, int64_t v, const void *feat, const int64_t *mapping, int64_t s, int32_t d, int32_t h,
                                  int32_t w, int32_t c, int32_t dtype, void *grad_depth, void *stream);
 
+/* ------------------------------------------------------------------ the centre head: peaks of a heat map, circle NMS, target drawing */
+
+/* The station between the BEV map and the boxes in CenterPoint, BEVFusion, BEVDet, PillarNet and OpenPCDet's CenterHead,
+ * csrc/center.hip.  The reference has no counterpart.  Every output is integers, copies of input bits or one rounded expression; no
+ * float atomics, the same bits on every run, nothing is read back to the host, and no launch waits on another workgroup.
+ *
+ * d3d_heatmap_peaks: CenterNet's _nms + _topk (max_pool2d(heat, kernel, 1, kernel / 2) == heat, multiply, topk over C * H * W;
+ *   OpenPCDet's centernet_utils._topk: two topk's) on heat[b, c, h, w], contiguous, D3D_F32, D3D_F16 or D3D_BF16, read only.
+ *   PEAK: cell (b, c, y, x) is a peak iff no value in its kernel x kernel window -- clipped to the plane, inside the cell's own class
+ *     plane -- is NaN and its value is >= every value of the window.  That is max_pool2d == heat exactly, NaN and +-inf included.
+ *     kernel 1: every cell that is not NaN.  -0.0 == +0.0.  Every cell of a plateau is a peak.
+ *   CANDIDATE: a peak whose value, widened to fp32 (exact for the half types), is > threshold (fp32; has_threshold == 0: every peak,
+ *     -inf included).
+ *   RANKING: by descending value in the order of csrc/lds_sort.hpp's KeyBits<float>::desc on the widened value, so equal values, and
+ *     -0 against +0, are ties; ties go to the lowest flat index (c * h + y) * w + x.  (torch.topk leaves the tie order open.)
+ *   -> scores[b, k] in heat's dtype: the INPUT'S OWN BITS of the k best candidates in ranking order (-0.0 comes back as -0.0),
+ *     -inf in the missing slots; classes, ys, xs [b, k] int32, -1 in the missing slots; counts[b] int32 = min(k, candidates).
+ *   No sigmoid inside: it is monotone, the caller applies it to the [b, k] scores; peaks and ties are those of the values passed in.
+ *   How: an exact radix select on the 32-bit key.  Three counting passes over the map (the top 12 key bits, the next 12 inside the
+ *   pivot bin, the last 8: per-workgroup histograms in on-chip memory, flushed with integer atomics), each followed by one workgroup
+ *   per sample that walks the histogram; then the k-th key and the number of candidates strictly above it are known.  A count pass,
+ *   a scan per sample and an emit pass compact the candidates above the pivot key and, of those equal to it, the `need` lowest flat
+ *   indices (a workgroup owns 1024 consecutive flat cells, so the order of the ties is a prefix sum).  One workgroup per sample
+ *   orders the <= k winners on (key, flat index), a unique composite.  Every pass recomputes the peak test from the map; no
+ *   [b, c, h, w] intermediate exists.  A constant map and any other map cost the same five passes.  Eleven launches and one memset.
+ *   Workspace: d3d_heatmap_peaks_workspace_bytes(b, c, h, w, k) = O(b * (3 * 4096 bins + c * h * w / 1024 tiles + k)) bytes.
+ *   Limits: c * h * w <= 2^31 - 1, b <= 65535, k in 1 .. d3d_heatmap_peaks_max() = 4096, kernel in {1, 3, 5, 7}.  Sample offsets
+ *   b * c * h * w are 64-bit.
+ *   D3D_ERR_BAD_ARG: a negative b, c, h or w below 1, k below 1, another kernel, has_threshold not 0 or 1, a missing pointer with
+ *   b > 0; D3D_ERR_UNSUPPORTED: another dtype, the limits above (the size query returns 0 for them); D3D_ERR_WORKSPACE: workspace
+ *   missing or smaller than the query.  All refusals come before any HIP call; b == 0 returns D3D_OK.
+ *
+ * d3d_circle_nms: det3d's circle_nms (core/utils/circle_nms_jit.py, a numba loop on the host; OpenPCDet copies to the host for it)
+ *   inside every segment of a batch and never across segments.  centers: rows of `stride` >= 2 elements, columns 0 and 1 = (x, y);
+ *   scores[n]; D3D_F32 or D3D_F64, both in one dtype.  Segment s is rows perm[seg_offsets[s] .. seg_offsets[s + 1]) (DEVICE int64
+ *   arrays, trusted; perm NULL: the rows seg_offsets[s] .. themselves).  max_segment: the longest segment, given by the caller.
+ *   Inside a segment the rows are visited in d3d_argsort_desc's order -- descending score, NaN first, ties in ascending position in
+ *   the segment (ascending row for a stable perm).  A visited row that is not suppressed is kept; a kept row i suppresses every
+ *   later row j with  d2 = (xi - xj) * (xi - xj) + (yi - yj) * (yi - yj) <= t,  every operation rounded once in the dtype (the build
+ *   does not contract), t = dist2_threshold rounded to the dtype -- the SQUARED distance (CenterPoint's configs pass their "radius"
+ *   straight into this slot).  A NaN d2 suppresses nothing; a suppressed row suppresses nothing.  max_keep (CenterPoint's
+ *   post_max_size): only the first max_keep kept rows of a segment, in visiting order, stay.  -> keep[n] u8, indexed by ROW: every
+ *   byte of a segment's rows is written exactly once, 1 = kept; rows of no segment and empty segments are not touched.
+ *   One launch, one workgroup per segment, everything on chip, no atomics: the segment is sorted (sort_lds), then swept in blocks
+ *   of 64 ranks -- one wavefront resolves a block (one ballot per open row), all wavefronts apply its kept rows to the later ranks.
+ *   D3D_ERR_BAD_ARG: a negative size, stride < 2, max_keep < 0, a missing pointer with work to do; D3D_ERR_UNSUPPORTED: another
+ *   dtype, max_segment above d3d_circle_nms_max() = 4096, n or segments above 2^31 - 1.  A segment longer than max_segment is
+ *   skipped by its workgroup untouched.  n == 0, segments == 0 and max_segment == 0 return D3D_OK before any HIP call.
+ *
+ * d3d_gaussian_heatmap: CenterNet's draw_umich_gaussian for every box of a batch (OpenPCDet: draw_gaussian_to_heatmap once per box
+ *   from a Python loop) -> out[b, c, h, w] fp32.  centers[m, 2] int32 = (x, y) = (column, row), anywhere, outside the map too;
+ *   radii[m] int32 in 0 .. 4095 and classes[m] int32 (trusted: the caller has checked them; a class outside [0, c) draws nothing);
+ *   offsets: DEVICE int64[b + 1], the boxes of every sample, or NULL with b == 1.
+ *     out[s, cl, y, x] = the maximum of 0 and, over the boxes i of sample s with classes[i] == cl, |x - cx| <= r and |y - cy| <= r, of
+ *         g(r, d2) = (float) exp( -(double)(18 * d2) / (double)((2 r + 1) * (2 r + 1)) ),   d2 = (x - cx)^2 + (y - cy)^2:
+ *   gaussian2D with sigma = (2 r + 1) / 6 over the SQUARE window, clipped at the borders.  The integers are exact; then one fp64
+ *   division, one fp64 exp (the device library's, within 1 ulp) and one rounding to fp32.  The centre cell is exactly 1.0.
+ *   CenterNet's `h < eps * max` mask never fires and is left out: d2 <= 2 r^2 keeps the exponent above -9, and e^-9 = 1.2e-4 is far
+ *   above fp32's eps.  One launch: a workgroup owns a 16 x 64 tile of one class plane and takes the sample's boxes through on-chip
+ *   memory 256 at a time, dropping by ballot those of another class or whose window misses the tile; every element of out is stored
+ *   exactly once, zeros included -- no memset, no atomics.
+ *   D3D_ERR_BAD_ARG: a negative size, offsets NULL with b > 1, a missing pointer with work to do; D3D_ERR_UNSUPPORTED: b or c above
+ *   65535, h or w above 2^30, m above 2^31 - 1.  An empty out returns D3D_OK before any HIP call. */
+int32_t d3d_heatmap_peaks_max(void);
+size_t d3d_heatmap_peaks_workspace_bytes(int64_t b, int64_t c, int64_t h, int64_t w, int32_t k);
+int d3d_heatmap_peaks(const void *heat, int64_t b, int64_t c, int64_t h, int64_t w, int32_t dtype, int32_t k, int32_t kernel,
+                      int32_t has_threshold, float threshold, void *scores, int32_t *classes, int32_t *ys, int32_t *xs, int32_t *counts,
+                      void *workspace, size_t workspace_bytes, void *stream);
+int32_t d3d_circle_nms_max(void);
+int d3d_circle_nms(const void *centers, int32_t stride, const void *scores, const int64_t *perm, const int64_t *seg_offsets, int64_t n,
+                   int64_t segments, int32_t max_segment, int32_t dtype, double dist2_threshold, int32_t max_keep, uint8_t *keep,
+                   void *stream);
+int d3d_gaussian_heatmap(const int32_t *centers, const int32_t *radii, const int32_t *classes, const int64_t *offsets, int64_t m,
+                         int64_t b, int64_t c, int64_t h, int64_t w, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
