@@ -819,19 +819,13 @@ static unsigned long long nms_cand_capacity(int64_t n)
 
 // Scan across the workgroups of ONE launch: every workgroup publishes its total with a ready bit (tot[] zeroed by an earlier
 // kernel) and adds up the totals of the workgroups before it, polling the ones not there yet.  "Before" is the order of
-// scan_ticket(), not blockIdx.x -- the dispatch order of workgroups is undefined: a workgroup holding ticket t only waits for
+// lookback_ticket() (common.hpp), not blockIdx.x -- the dispatch order of workgroups is undefined: a workgroup holding ticket t only waits for
 // tickets < t, whose holders are running (they took theirs first) and publish before they wait: always progress, wherever
 // and in whatever order the workgroups are placed.  Value and ready bit travel in one agent-scope 64-bit word.
 // Returns (in every thread) the sum of the totals of tickets 0 .. id - 1; both contain workgroup barriers.
 // The poll is bounded all the same (kChainSpins reads of one word, seconds): a predecessor that never publishes -- only a
 // defect elsewhere could cause that -- raises flags->need_sweep (the dense path then recomputes everything from the geometry)
 // instead of hanging the GPU.
-__device__ __forceinline__ unsigned int scan_ticket(unsigned int *ticket, unsigned int *sid)
-{
-    if (threadIdx.x == 0) *sid = atomicAdd(ticket, 1u);
-    __syncthreads();
-    return *sid;
-}
 // A predecessor holds a lower ticket, i.e. it is running and publishes within microseconds; kChainSpins polls (~0.1 s) without
 // its word turning up means something is wrong (a lost store, a preempted queue): the scan GIVES UP -- flags->need_sweep is
 // raised (the dense path then recomputes everything), flags->scan_gave_up counts it (d3d_nms2d_status reports both: a caller
@@ -1188,7 +1182,7 @@ __global__ __launch_bounds__(1024) void k_nms_gridscan(uint32_t *cellcur, uint32
     // (second registration: runs only when the levels did.  Workgroups of this launch raise the density and lower the entries
     // while others still test them -- both move the test further towards "on")
     if (gate && !nms_levels_on(*grid, gate)) return;
-    const int chunk = (int)scan_ticket(ticket, &sid);
+    const int chunk = (int)lookback_ticket(ticket, &sid);
     const int cells = grid->gx * grid->gy;                                      // entry `cells` = the total
     if (chunk * 1024 > cells) return;                                           // (nobody waits for a higher chunk)
     const int c = chunk * 1024 + threadIdx.x;
@@ -1670,30 +1664,21 @@ __global__ __launch_bounds__(256) void k_nms_incscan(const uint32_t *__restrict_
 {
     __shared__ unsigned long long smem[4], sbase;
     __shared__ unsigned int sid;
-    const unsigned int tile = scan_ticket(ticket, &sid);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t base = (int64_t)tile * kIncTile + (int64_t)w * 256 + lane;             // wavefront w: 4 rows of 64 boxes
-    unsigned long long ex[4], carry = 0;
+    const unsigned int tile = lookback_ticket(ticket, &sid);
+    const int64_t base = tile_item<256, kIncTile / 256>(tile);
+    unsigned long long v[kIncTile / 256], ex[kIncTile / 256], total;
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int64_t i = base + k * 64;
-        const unsigned long long v = i < n ? inc_cnt[i] : 0u;
-        const unsigned long long incl = wave_incl_scan_u64(v);
-        ex[k] = carry + incl - v;
-        carry += __shfl(incl, 63, 64);
+    for (int k = 0; k < kIncTile / 256; k++) {
+        const int64_t i = base + k * kWave;
+        v[k] = i < n ? inc_cnt[i] : 0u;
     }
-    if (lane == 0) smem[w] = carry;
-    __syncthreads();
-    unsigned long long woff = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { if (k < w) woff += smem[k]; total += smem[k]; }
+    tile_excl_scan_u64<256, kIncTile / 256>(v, ex, smem, &total);
     const unsigned long long before = chained_prefix(tile_tot, tile, total, &sbase, flags, withhold);
     if (before == kChainVoid) return;                       // gave up: nothing that depends on the prefix is stored
-    const unsigned long long off = before + woff;
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int64_t i = base + k * 64;
-        if (i < n) inc_off[i] = (uint32_t)(off + ex[k]);
+    for (int k = 0; k < kIncTile / 256; k++) {
+        const int64_t i = base + k * kWave;
+        if (i < n) inc_off[i] = (uint32_t)(before + ex[k]);
     }
 }
 
@@ -1925,17 +1910,12 @@ __global__ __launch_bounds__(1024) void k_nms_small_front(const B *__restrict__ 
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char small_lds[];
     typedef typename KeyBits<T>::U U;
-    uint32_t npad = kWave;
-    while (npad < n) npad <<= 1;
+    const uint32_t npad = (uint32_t)sort_lds_pad(n);
     U *d0 = reinterpret_cast<U *>(small_lds), *d1 = d0 + npad;
     uint32_t *i0 = reinterpret_cast<uint32_t *>(d1 + npad), *i1 = i0 + npad;
     uint32_t *ii = i0;
     if (!order_in) {
-        for (uint32_t e = threadIdx.x; e < npad; e += blockDim.x) {
-            d0[e] = e < n ? KeyBits<T>::desc((T)scores[e]) : ~(U)0;         // padding sorts behind every real entry and is unique
-            i0[e] = e < n ? e : 0x80000000u + e;
-        }
-        __syncthreads();
+        fill_desc_keys(d0, i0, (int)npad, (int)n, [&](int e) { return (T)scores[e]; });
         U *d;
         if (npad <= 1024) sort_lds<1>(d0, i0, d1, i1, (int)npad, &d, &ii);          // entries per thread: no idle slots
         else if (npad <= 2048) sort_lds<2>(d0, i0, d1, i1, (int)npad, &d, &ii);
@@ -2274,8 +2254,7 @@ int nms_typed(const B *boxes, const B *scores, const int64_t *order, int64_t n, 
     };
     if (nms_small_eligible(n, opts)) {
         typedef typename KeyBits<T>::U U;
-        uint32_t npad = kWave;
-        while ((int64_t)npad < n) npad <<= 1;
+        const uint32_t npad = (uint32_t)sort_lds_pad(n);
         const size_t lds = order ? 0 : (size_t)npad * (2 * sizeof(U) + 8);
         if (lds > 65536)
             D3D_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_nms_small_front<T, B>),
@@ -2465,16 +2444,10 @@ __global__ __launch_bounds__(THREADS) void k_nms_group(const B *__restrict__ box
     unsigned long long *tri = reinterpret_cast<unsigned long long *>(farea + THREADS);   // the chunk's triangle, a word per row
     unsigned long long *supw = tri + kWave;                                              // suppressed ranks, a word per chunk
     // ---- 1. sort
-    uint32_t npad = kWave;
-    while (npad < n) npad <<= 1;
+    const uint32_t npad = (uint32_t)sort_lds_pad(n);
     U *d0 = reinterpret_cast<U *>(group_lds), *d1 = d0 + npad;
     uint32_t *i0 = reinterpret_cast<uint32_t *>(d1 + npad), *i1 = i0 + npad, *ii;
-    if (threadIdx.x < npad) {
-        const uint32_t e = threadIdx.x;
-        d0[e] = e < n ? KeyBits<T>::desc((T)scores[perm ? perm[seg0 + e] : seg0 + e]) : ~(U)0;   // padding: last, unique
-        i0[e] = e < n ? e : 0x80000000u + e;
-    }
-    __syncthreads();
+    fill_desc_keys(d0, i0, (int)npad, (int)n, [&](int e) { return (T)scores[perm ? perm[seg0 + e] : seg0 + e]; });
     U *d;
     sort_lds<1>(d0, i0, d1, i1, (int)npad, &d, &ii);
     const uint32_t p = threadIdx.x;
@@ -2523,12 +2496,10 @@ __global__ __launch_bounds__(THREADS) void k_nms_group(const B *__restrict__ box
         // (b) greedy over the chunk's 64 ranks: rank r, unless suppressed by then, suppresses the columns of its row
         unsigned long long s = pre;
         {
-            const unsigned long long mine = tri[lane];
-            const int mlo = (int)(uint32_t)mine, mhi = (int)(uint32_t)(mine >> 32);
+            const uint64_t mine = tri[lane];
 #pragma unroll
             for (int r = 0; r < kWave; r++) {
-                const unsigned long long wr = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane(mhi, r) << 32) |
-                                              (uint32_t)__builtin_amdgcn_readlane(mlo, r);
+                const unsigned long long wr = wave_readlane(mine, r);
                 if (!((s >> r) & 1ull)) s |= wr;
             }
         }

@@ -170,78 +170,39 @@ __global__ __launch_bounds__(kSpThreads) void k_sp_sweep(const TIn *__restrict__
 }
 
 // ---------------------------------------------------------------- counts[n] -> offsets[n + 1], in place
-// item layout of a tile as in k_scan_count: wavefront w owns 256 consecutive rows, row k of it = 64 consecutive items
-__device__ __forceinline__ int64_t sp_tile_base(int lane, int w) { return (int64_t)blockIdx.x * kSpTile + (int64_t)w * (kSpTile / kSpWaves) + lane; }
+constexpr int kSpItems = kSpTile / kSpThreads;
 
 __global__ __launch_bounds__(kSpThreads) void k_sp_tile_sum(const int64_t *__restrict__ counts, int64_t n, unsigned long long *__restrict__ bsum)
 {
     __shared__ unsigned long long sm[kSpWaves];
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
-    const int64_t base = sp_tile_base(lane, w);
+    const int64_t base = tile_item<kSpThreads, kSpItems>(blockIdx.x);
     unsigned long long s = 0;
 #pragma unroll
-    for (int k = 0; k < kSpTile / kSpThreads; k++) {
+    for (int k = 0; k < kSpItems; k++) {
         const int64_t i = base + (int64_t)k * kWave;
         if (i < n) s += (unsigned long long)counts[i];
     }
-    s = wave_sum_u64(s);
-    if (lane == 0) sm[w] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-#pragma unroll
-        for (int k = 0; k < kSpWaves; k++) t += sm[k];
-        bsum[blockIdx.x] = t;
-    }
-}
-
-// one workgroup: exclusive scan of the nb tile sums in place; *total = K
-__global__ __launch_bounds__(1024) void k_sp_scan(unsigned long long *__restrict__ bsum, int64_t nb, int64_t *__restrict__ total)
-{
-    __shared__ unsigned long long smem[1024 / kWave];
-    unsigned long long carry = 0;
-    for (int64_t c0 = 0; c0 < nb; c0 += 4096) {
-        const int64_t i = c0 + (int64_t)threadIdx.x * 4;
-        unsigned long long v[4], mine = 0, tot;
-#pragma unroll
-        for (int k = 0; k < 4; k++) { v[k] = i + k < nb ? bsum[i + k] : 0ull; mine += v[k]; }
-        unsigned long long ex = carry + block_excl_scan_u64<1024>(mine, &tot, smem);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (i + k < nb) bsum[i + k] = ex;
-            ex += v[k];
-        }
-        carry += tot;
-    }
-    if (threadIdx.x == 0) *total = (int64_t)carry;
+    s = tile_sum_u64<kSpThreads>(s, sm);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = s;
 }
 
 // every thread reads its items before it writes them: in place
 __global__ __launch_bounds__(kSpThreads) void k_sp_offsets(int64_t *__restrict__ offsets, int64_t n, const unsigned long long *__restrict__ bsum_excl)
 {
     __shared__ unsigned long long sm[kSpWaves];
-    constexpr int kItems = kSpTile / kSpThreads;
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
-    const int64_t base = sp_tile_base(lane, w);
-    unsigned long long ex[kItems], carry = 0;
+    const int64_t base = tile_item<kSpThreads, kSpItems>(blockIdx.x);
+    unsigned long long v[kSpItems], ex[kSpItems], total;
 #pragma unroll
-    for (int k = 0; k < kItems; k++) {
+    for (int k = 0; k < kSpItems; k++) {
         const int64_t i = base + (int64_t)k * kWave;
-        const unsigned long long v = i < n ? (unsigned long long)offsets[i] : 0ull;
-        const unsigned long long incl = wave_incl_scan_u64(v);
-        ex[k] = carry + incl - v;
-        carry += __shfl(incl, kWave - 1, kWave);
+        v[k] = i < n ? (unsigned long long)offsets[i] : 0ull;
     }
-    if (lane == 0) sm[w] = carry;
-    __syncthreads();
-    unsigned long long woff = bsum_excl[blockIdx.x];
+    tile_excl_scan_u64<kSpThreads, kSpItems>(v, ex, sm, &total);
+    const unsigned long long before = bsum_excl[blockIdx.x];
 #pragma unroll
-    for (int k = 0; k < kSpWaves; k++)
-        if (k < w) woff += sm[k];
-#pragma unroll
-    for (int k = 0; k < kItems; k++) {
+    for (int k = 0; k < kSpItems; k++) {
         const int64_t i = base + (int64_t)k * kWave;
-        if (i < n) offsets[i] = (int64_t)(woff + ex[k]);
+        if (i < n) offsets[i] = (int64_t)(before + ex[k]);
     }
 }
 
@@ -324,7 +285,7 @@ extern "C" int d3d_iou_sparse_count(const void *boxes1, int64_t n, const void *b
         return rc;
     const int64_t nb = d3d_divup(n, kSpTile);
     D3D_LAUNCH("k_sp_tile_sum", k_sp_tile_sum, dim3((unsigned)nb), dim3(kSpThreads), 0, st, (const int64_t *)offsets, n, a.bsum);
-    D3D_LAUNCH("k_sp_scan", k_sp_scan, dim3(1), dim3(1024), 0, st, a.bsum, nb, offsets + n);
+    D3D_LAUNCH("k_scan_tile_sums", k_scan_tile_sums<kSumsWhole>, dim3(1), dim3(1024), 0, st, a.bsum, nb, offsets + n);      // offsets[n] = K, 64 bits
     D3D_LAUNCH("k_sp_offsets", k_sp_offsets, dim3((unsigned)nb), dim3(kSpThreads), 0, st, offsets, n, (const unsigned long long *)a.bsum);
     return D3D_OK;
 }

@@ -5,7 +5,7 @@
 // launch, fp64 arithmetic on fp32 / fp64 rows read in place, no contraction (-ffp-contract=off).
 //
 // The compaction keeps point order, so it needs a prefix sum over the cloud.  Three launches, none of which waits on another
-// workgroup: k_cam_count (flags per point, one packed count per workgroup and camera), k_cam_scan (one workgroup per camera
+// workgroup: k_cam_count (flags per point, one packed count per workgroup and camera), k_scan_tile_sums (one workgroup per camera
 // scans those counts and leaves K and Kd), k_cam_emit (the same flags again -- the same expressions give the same bits --
 // a scan inside the workgroup, the stores).  The flags are recomputed instead of stored: 12-16 bytes read again per point
 // against 16 bytes of uv per point and camera that a stored form would have to keep for the gather.
@@ -84,21 +84,15 @@ __device__ __forceinline__ unsigned long long project(const D3DCamera &c, double
     return (view ? kInView : 0ull) | (front ? kInFront : 0ull);
 }
 
-// item layout of a tile as in k_scan_count: wavefront w owns 256 consecutive points, row k of it = 64 consecutive points, one
-// per lane
-__device__ __forceinline__ int64_t tile_base(int lane, int w)
-{
-    return (int64_t)blockIdx.x * kCamTile + (int64_t)w * (kWave * kCamItems) + lane;
-}
-
-// bsum[c * nb + workgroup] = (points in view : 32 | points in front : 32) of the workgroup's tile for camera c
+// bsum[c * nb + workgroup] = (points in view : 32 | points in front : 32) of the workgroup's tile for camera c.  (Not
+// tile_sum_u64: with a slot per camera ONE barrier serves up to eight cameras.)
 template <class T>
 __global__ __launch_bounds__(kCamThreads) void k_cam_count(const T *__restrict__ points, int64_t n, int stride, int vec, CamSet cs,
                                                            int ncam, unsigned long long *__restrict__ bsum, int64_t nb)
 {
     __shared__ unsigned long long sm[kCamMax][kCamThreads / kWave];
     const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
-    const int64_t base = tile_base(lane, w);
+    const int64_t base = tile_item<kCamThreads, kCamItems>(blockIdx.x);
     double x[kCamItems], y[kCamItems], z[kCamItems];
 #pragma unroll
     for (int k = 0; k < kCamItems; k++) {
@@ -125,31 +119,6 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_count(const T *__restrict__
     }
 }
 
-// workgroup c: exclusive scan of camera c's nb counts in place; counts[2 c] = K, counts[2 c + 1] = Kd
-__global__ __launch_bounds__(1024) void k_cam_scan(unsigned long long *__restrict__ bsum, int64_t nb, int64_t *__restrict__ counts)
-{
-    __shared__ unsigned long long smem[1024 / kWave];
-    bsum += (int64_t)blockIdx.x * nb;
-    unsigned long long carry = 0;
-    for (int64_t c0 = 0; c0 < nb; c0 += 4096) {
-        const int64_t i = c0 + (int64_t)threadIdx.x * 4;
-        unsigned long long v[4], mine = 0, tot;
-#pragma unroll
-        for (int k = 0; k < 4; k++) { v[k] = i + k < nb ? bsum[i + k] : 0ull; mine += v[k]; }
-        unsigned long long ex = carry + block_excl_scan_u64<1024>(mine, &tot, smem);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (i + k < nb) bsum[i + k] = ex;
-            ex += v[k];
-        }
-        carry += tot;
-    }
-    if (threadIdx.x == 0) {
-        counts[2 * blockIdx.x] = (int64_t)(carry >> 32);
-        counts[2 * blockIdx.x + 1] = (int64_t)(carry & 0xffffffffull);
-    }
-}
-
 // Camera c writes into its own section of the outputs: uv + c * n * 2, mask + c * n, dmask + c * n.  ALL_UV: uv row i = point
 // i; else uv row j = the j-th point in view.  dmask may be NULL.
 template <class T, bool ALL_UV>
@@ -158,8 +127,7 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_emit(const T *__restrict__ 
                                                           double *__restrict__ uv, int64_t *__restrict__ mask, int64_t *__restrict__ dmask)
 {
     __shared__ unsigned long long sm[kCamMax][kCamThreads / kWave];
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
-    const int64_t base = tile_base(lane, w);
+    const int64_t base = tile_item<kCamThreads, kCamItems>(blockIdx.x);
     double x[kCamItems], y[kCamItems], z[kCamItems];
 #pragma unroll
     for (int k = 0; k < kCamItems; k++) {
@@ -169,28 +137,21 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_emit(const T *__restrict__ 
     }
     for (int c = 0; c < ncam; c++) {
         double u[kCamItems], v[kCamItems];
-        unsigned long long f[kCamItems], ex[kCamItems], carry = 0;
+        unsigned long long f[kCamItems], ex[kCamItems], total;
 #pragma unroll
         for (int k = 0; k < kCamItems; k++) {
             f[k] = 0;
             u[k] = v[k] = 0.0;
             if (base + (int64_t)k * kWave < n) f[k] = project(cs.cam[c], x[k], y[k], z[k], u[k], v[k]);
-            const unsigned long long incl = wave_incl_scan_u64(f[k]);
-            ex[k] = carry + incl - f[k];
-            carry += __shfl(incl, kWave - 1, kWave);        // row total
         }
-        if (lane == 0) sm[c][w] = carry;                     // (a slot per camera: one barrier per camera is enough)
-        __syncthreads();
-        unsigned long long woff = bsum_excl[(int64_t)c * nb + blockIdx.x];
-#pragma unroll
-        for (int k = 0; k < kCamThreads / kWave; k++)
-            if (k < w) woff += sm[c][k];
+        tile_excl_scan_u64<kCamThreads, kCamItems>(f, ex, sm[c], &total);      // (a slot per camera: its one barrier is enough)
+        const unsigned long long before = bsum_excl[(int64_t)c * nb + blockIdx.x];
         double2 *uvc = reinterpret_cast<double2 *>(uv) + (int64_t)c * n;
 #pragma unroll
         for (int k = 0; k < kCamItems; k++) {
             const int64_t i = base + (int64_t)k * kWave;
             if (i >= n) continue;
-            const unsigned long long off = woff + ex[k];     // (both fields < n: the sections hold n rows)
+            const unsigned long long off = before + ex[k];   // (both fields < n: the sections hold n rows)
             if (ALL_UV) uvc[i] = make_double2(u[k], v[k]);
             if (f[k] & kInView) {
                 mask[(int64_t)c * n + (int64_t)(off >> 32)] = i;
@@ -254,7 +215,7 @@ extern "C" int d3d_project_points(const void *points, int64_t n, int32_t stride,
             if (nb > 0)
                 D3D_LAUNCH("k_cam_count", k_cam_count<T>, dim3((unsigned)nb), dim3(kCamThreads), 0, st, (const T *)points, n, (int)stride, vec,
                            cs, nc, bs, nb);
-            D3D_LAUNCH("k_cam_scan", k_cam_scan, dim3((unsigned)nc), dim3(1024), 0, st, bs, nb, counts + 2 * c0);
+            D3D_LAUNCH("k_scan_tile_sums", k_scan_tile_sums<kSumsPacked>, dim3((unsigned)nc), dim3(1024), 0, st, bs, nb, counts + 2 * c0);
             if (nb == 0) return D3D_OK;
             return dispatch((flags & D3D_PROJECT_ALL_UV) != 0, [&](auto all) -> int {
                 D3D_LAUNCH("k_cam_emit", (k_cam_emit<T, all>), dim3((unsigned)nb), dim3(kCamThreads), 0, st, (const T *)points, n, (int)stride,

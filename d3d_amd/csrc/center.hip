@@ -86,12 +86,6 @@ __device__ __forceinline__ bool peak_candidate(const T *__restrict__ sample, con
     return ok;
 }
 
-// item layout of a tile as in k_cam_count: wavefront w owns 256 consecutive cells, row j of it = 64 consecutive cells
-__device__ __forceinline__ int64_t peak_tile_base(int lane, int w)
-{
-    return (int64_t)blockIdx.x * kPeakTile + (int64_t)w * (kWave * kPeakItems) + lane;
-}
-
 // level 0: bin = key >> 20; level 1: keys with the pivot's top 12 bits, bin = (key >> 8) & 4095; level 2: keys with its top 24
 // bits, bin = key & 255.  hist[(level * B + b) * kPeakBins + bin] += the candidates of the tile.
 template <class T, int KS>
@@ -99,7 +93,7 @@ __global__ __launch_bounds__(kPeakThreads) void k_peak_hist(const T *__restrict_
                                                             const uint32_t *__restrict__ state, uint32_t *__restrict__ hist)
 {
     __shared__ uint32_t sh[kPeakBins];
-    const int b = blockIdx.y, lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
+    const int b = blockIdx.y;
     const int bins = level == 2 ? 256 : kPeakBins;
     const uint32_t keep_mask = level == 0 ? 0u : level == 1 ? 0xfff00000u : 0xffffff00u;      // the key bits that must equal the pivot's
     const int bin_shift = level == 0 ? 20 : level == 1 ? 8 : 0;
@@ -108,7 +102,7 @@ __global__ __launch_bounds__(kPeakThreads) void k_peak_hist(const T *__restrict_
     for (int i = threadIdx.x; i < bins; i += kPeakThreads) sh[i] = 0;
     __syncthreads();
     const T *sample = heat + (int64_t)b * d.chw;
-    const int64_t base = peak_tile_base(lane, w);
+    const int64_t base = tile_item<kPeakThreads, kPeakItems>(blockIdx.x);
 #pragma unroll
     for (int j = 0; j < kPeakItems; j++) {
         const int64_t e = base + (int64_t)j * kWave;
@@ -181,46 +175,18 @@ __global__ __launch_bounds__(kPeakThreads) void k_peak_count(const T *__restrict
                                                              unsigned long long *__restrict__ bsum)
 {
     __shared__ unsigned long long sm[kPeakThreads / kWave];
-    const int b = blockIdx.y, lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
+    const int b = blockIdx.y;
     const uint32_t pivot = state[(int64_t)b * kStWords + kStPrefix];
     const T *sample = heat + (int64_t)b * d.chw;
-    const int64_t base = peak_tile_base(lane, w);
+    const int64_t base = tile_item<kPeakThreads, kPeakItems>(blockIdx.x);
     unsigned long long s = 0;
 #pragma unroll
     for (int j = 0; j < kPeakItems; j++) {
         uint32_t key;
         s += peak_flags<T, KS>(sample, d, base + (int64_t)j * kWave, pivot, key);
     }
-    s = wave_sum_u64(s);
-    if (lane == 0) sm[w] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-#pragma unroll
-        for (int j = 0; j < kPeakThreads / kWave; j++) t += sm[j];
-        bsum[(int64_t)b * gridDim.x + blockIdx.x] = t;
-    }
-}
-
-// workgroup b: exclusive scan of sample b's tile counts in place
-__global__ __launch_bounds__(1024) void k_peak_scan(unsigned long long *__restrict__ bsum, int64_t nb)
-{
-    __shared__ unsigned long long smem[1024 / kWave];
-    bsum += (int64_t)blockIdx.x * nb;
-    unsigned long long carry = 0;
-    for (int64_t c0 = 0; c0 < nb; c0 += 4096) {
-        const int64_t i = c0 + (int64_t)threadIdx.x * 4;
-        unsigned long long v[4], mine = 0, tot;
-#pragma unroll
-        for (int j = 0; j < 4; j++) { v[j] = i + j < nb ? bsum[i + j] : 0ull; mine += v[j]; }
-        unsigned long long ex = carry + block_excl_scan_u64<1024>(mine, &tot, smem);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (i + j < nb) bsum[i + j] = ex;
-            ex += v[j];
-        }
-        carry += tot;
-    }
+    s = tile_sum_u64<kPeakThreads>(s, sm);
+    if (threadIdx.x == 0) bsum[(int64_t)b * gridDim.x + blockIdx.x] = s;
 }
 
 // the same flags again (the same expressions on the same map), a scan inside the workgroup, and the winners' stores: a candidate
@@ -232,30 +198,21 @@ __global__ __launch_bounds__(kPeakThreads) void k_peak_emit(const T *__restrict_
                                                             uint32_t *__restrict__ wkey, uint32_t *__restrict__ widx)
 {
     __shared__ unsigned long long sm[kPeakThreads / kWave];
-    const int b = blockIdx.y, lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
+    const int b = blockIdx.y;
     const uint32_t *st = state + (int64_t)b * kStWords;
     const uint32_t pivot = st[kStPrefix], above = st[kStAbove], need = st[kStNeed];
     const T *sample = heat + (int64_t)b * d.chw;
-    const int64_t base = peak_tile_base(lane, w);
-    unsigned long long f[kPeakItems], ex[kPeakItems], carry = 0;
+    const int64_t base = tile_item<kPeakThreads, kPeakItems>(blockIdx.x);
+    unsigned long long f[kPeakItems], ex[kPeakItems], total;
     uint32_t key[kPeakItems];
 #pragma unroll
-    for (int j = 0; j < kPeakItems; j++) {
-        f[j] = peak_flags<T, KS>(sample, d, base + (int64_t)j * kWave, pivot, key[j]);
-        const unsigned long long incl = wave_incl_scan_u64(f[j]);
-        ex[j] = carry + incl - f[j];
-        carry += __shfl(incl, kWave - 1, kWave);
-    }
-    if (lane == 0) sm[w] = carry;
-    __syncthreads();
-    unsigned long long woff = bsum_excl[(int64_t)b * gridDim.x + blockIdx.x];
-#pragma unroll
-    for (int j = 0; j < kPeakThreads / kWave; j++)
-        if (j < w) woff += sm[j];
+    for (int j = 0; j < kPeakItems; j++) f[j] = peak_flags<T, KS>(sample, d, base + (int64_t)j * kWave, pivot, key[j]);
+    tile_excl_scan_u64<kPeakThreads, kPeakItems>(f, ex, sm, &total);
+    const unsigned long long before = bsum_excl[(int64_t)b * gridDim.x + blockIdx.x];
 #pragma unroll
     for (int j = 0; j < kPeakItems; j++) {
         if (!f[j]) continue;
-        const unsigned long long off = woff + ex[j];
+        const unsigned long long off = before + ex[j];
         const uint32_t lt = (uint32_t)(off >> 32), eq = (uint32_t)off;
         uint32_t slot;
         if (f[j] >> 32) slot = lt;
@@ -283,8 +240,8 @@ __global__ __launch_bounds__(kPeakSortThreads) void k_peak_sort(const BITS *__re
     uint32_t *d0 = reinterpret_cast<uint32_t *>(peak_lds), *d1 = d0 + npad, *i0 = d1 + npad, *i1 = i0 + npad, *rd, *ri;
     for (int e = threadIdx.x; e < npad; e += (int)blockDim.x) {
         const bool real = e < take;
-        d0[e] = real ? wkey[(int64_t)b * k + e] : 0xffffffffu;        // padding: last, unique (a flat index is below 2^31)
-        i0[e] = real ? widx[(int64_t)b * k + e] : 0x80000000u + (uint32_t)e;
+        d0[e] = real ? wkey[(int64_t)b * k + e] : kPadKey<uint32_t>;  // padding: last, unique (a flat index is below 2^31)
+        i0[e] = real ? widx[(int64_t)b * k + e] : kPadIndex + (uint32_t)e;
     }
     __syncthreads();
     sort_lds<EPT>(d0, i0, d1, i1, npad, &rd, &ri);
@@ -307,16 +264,6 @@ __global__ __launch_bounds__(kPeakSortThreads) void k_peak_sort(const BITS *__re
 // ---------------------------------------------------------------- circle_nms
 constexpr int kCircleMax = 4096;
 constexpr int kCircleThreads = 1024;
-
-// lane r's value in every lane (r wave-uniform)
-__device__ __forceinline__ float lane_value(float v, int r) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), r)); }
-__device__ __forceinline__ double lane_value(double v, int r)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, r);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), r);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 
 // det3d's test, every operation one rounding in T (the build does not contract); a NaN d2 is no hit
 template <class T> __device__ __forceinline__ bool circle_hit(T xi, T yi, T xj, T yj, T t)
@@ -353,11 +300,7 @@ __global__ __launch_bounds__(kCircleThreads) void k_circle_nms(const T *__restri
     // ---- the order: KeyBits composites with the LOCAL index (ties: ascending position, i.e. ascending row for a stable perm)
     U *d0 = reinterpret_cast<U *>(circle_lds), *d1 = d0 + npad, *rd;
     uint32_t *i0 = reinterpret_cast<uint32_t *>(d1 + npad), *i1 = i0 + npad, *ri;
-    for (int e = threadIdx.x; e < npad; e += (int)blockDim.x) {
-        d0[e] = e < n ? KeyBits<T>::desc(scores[perm ? perm[seg0 + e] : seg0 + e]) : ~(U)0;      // padding: last, unique
-        i0[e] = e < n ? (uint32_t)e : 0x80000000u + (uint32_t)e;
-    }
-    __syncthreads();
+    fill_desc_keys(d0, i0, npad, n, [&](int e) { return scores[perm ? perm[seg0 + e] : seg0 + e]; });
     sort_lds<EPT>(d0, i0, d1, i1, npad, &rd, &ri);
     // ---- the rows of this thread's ranks; the coordinates by rank go where the sort was
     const int nchunks = (n + kWave - 1) / kWave;
@@ -394,7 +337,7 @@ __global__ __launch_bounds__(kCircleThreads) void k_circle_nms(const T *__restri
 #pragma unroll 4
                 for (int r = 0; r < kWave - 1; r++) {
                     if ((s >> r) & 1ull) continue;                     // (wave-uniform: a suppressed row suppresses nothing)
-                    const T xr = lane_value(x[u], r), yr = lane_value(y[u], r);
+                    const T xr = wave_readlane(x[u], r), yr = wave_readlane(y[u], r);
                     s |= __ballot(lane > r && circle_hit(xr, yr, x[u], y[u], thr));
                 }
                 sup[u] = (s >> lane) & 1ull;
@@ -491,13 +434,6 @@ __global__ __launch_bounds__(kDrawThreads) void k_gaussian_heatmap(const int32_t
     }
 }
 
-static int pow2_at_least(int64_t n)
-{
-    int p = kWave;
-    while (p < n) p <<= 1;
-    return p;
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------- entries
@@ -555,14 +491,14 @@ extern "C" int d3d_heatmap_peaks(const void *heat, int64_t b, int64_t c, int64_t
                 D3D_LAUNCH("k_peak_pick", k_peak_pick, dim3((unsigned)b), dim3(1024), 0, st, a.state, a.hist, level, (int)k, counts);
             }
             D3D_LAUNCH("k_peak_count", (k_peak_count<T, KS>), grid, dim3(kPeakThreads), 0, st, (const T *)heat, d, a.state, a.bsum);
-            D3D_LAUNCH("k_peak_scan", k_peak_scan, dim3((unsigned)b), dim3(1024), 0, st, a.bsum, tiles);
+            D3D_LAUNCH("k_scan_tile_sums", k_scan_tile_sums<kSumsNone>, dim3((unsigned)b), dim3(1024), 0, st, a.bsum, tiles, (int64_t *)nullptr);
             D3D_LAUNCH("k_peak_emit", (k_peak_emit<T, KS>), grid, dim3(kPeakThreads), 0, st, (const T *)heat, d, a.state, a.bsum, (int)k, a.wkey,
                        a.widx);
             return D3D_OK;
         });
     });
     if (rc != D3D_OK) return rc;
-    const int npad = pow2_at_least(k);
+    const int npad = sort_lds_pad(k);
     const size_t lds = (size_t)npad * 16;
     return dispatch(dtype == D3D_F32, [&](auto wide) -> int {
         typedef typename std::conditional<decltype(wide)::value, uint32_t, uint16_t>::type BITS;
@@ -590,7 +526,7 @@ extern "C" int d3d_circle_nms(const void *centers, int32_t stride, const void *s
     if (max_segment > kCircleMax || segments > 0x7fffffffll || n > 0x7fffffffll) return D3D_ERR_UNSUPPORTED;
     if (n == 0 || segments == 0 || max_segment == 0) return D3D_OK;
     if (!centers || !scores || !seg_offsets || !keep) return D3D_ERR_BAD_ARG;
-    const int npad = pow2_at_least(max_segment);
+    const int npad = sort_lds_pad(max_segment);
     return dispatch_dtype<D3D_F32, D3D_F64>(dtype, [&](auto p) -> int {
         typedef typename decltype(p)::T T;
         return dispatch(npad > kCircleThreads, [&](auto big) -> int {

@@ -140,13 +140,21 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v)
     v += d3d_dpp_u32<0x143, 0xc>(v);
     return v;
 }
+// lane `lane`'s value in every lane (`lane` wave-uniform); 64-bit values travel as two halves
+__device__ __forceinline__ uint32_t wave_readlane(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
+__device__ __forceinline__ uint64_t wave_readlane(uint64_t v, int lane)
+{
+    return ((uint64_t)wave_readlane((uint32_t)(v >> 32), lane) << 32) | wave_readlane((uint32_t)v, lane);
+}
+__device__ __forceinline__ float wave_readlane(float v, int lane) { return __uint_as_float(wave_readlane(__float_as_uint(v), lane)); }
+__device__ __forceinline__ double wave_readlane(double v, int lane)
+{
+    return __longlong_as_double((long long)wave_readlane((uint64_t)__double_as_longlong(v), lane));
+}
 // sum over the wavefront, the same in every lane (wave-uniform: lane 63 of the scan)
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 {
-    const unsigned long long incl = wave_incl_scan_u64(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)incl, kWave - 1);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(incl >> 32), kWave - 1);
-    return ((unsigned long long)hi << 32) | lo;
+    return wave_readlane((uint64_t)wave_incl_scan_u64(v), kWave - 1);
 }
 
 // Reductions over the wavefront on the same DPP steps; the result is valid in LANE 63 only.  A lane without a source adds
@@ -251,6 +259,17 @@ __device__ __forceinline__ unsigned long long lookback_exclusive(unsigned long l
     if (lane == 0) __hip_atomic_store(&status[tile], kLbIncl | ((total + excl) & kLbMask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return excl;
 }
+// the whole workgroup calls it: the first wavefront looks back, the others get the result through *word (LDS); one barrier
+__device__ __forceinline__ unsigned long long lookback_exclusive_block(unsigned long long *status, unsigned int tile, unsigned long long total,
+                                                                       unsigned long long *word)
+{
+    if (threadIdx.x < kWave) {
+        const unsigned long long e = lookback_exclusive(status, tile, total);
+        if (threadIdx.x == 0) *word = e;
+    }
+    __syncthreads();
+    return *word;
+}
 
 // exclusive scan over the block; *total = block sum.  smem: BLOCK/64 u64 entries.
 template <int BLOCK>
@@ -273,48 +292,66 @@ __device__ __forceinline__ unsigned long long block_excl_scan_u64(unsigned long 
     return woff + incl - v;
 }
 
-// ---------------------------------------------------------------- generic 3-kernel scan
-// F provides:  u64 value(int64 i)   (count pass; may record side data)
-//              u64 value2(int64 i)  (apply pass; must return the same value)
-//              void apply(int64 i, u64 v, u64 excl)
-// Values are "packed pairs": two u32 sums in one u64 (hi, lo) -- both stay < 2^32.
-template <class F>
-__global__ __launch_bounds__(kScanBlock) void k_scan_count(F f, int64_t n, unsigned long long *bsum)
+// ---------------------------------------------------------------- tile scans
+// A tile is BLOCK x ITEMS consecutive items, one workgroup each.  Wavefront w owns 64 * ITEMS consecutive items and row k of it
+// is 64 consecutive items, one per lane: every access to the items is coalesced (consecutive items per THREAD would stride the
+// lanes by ITEMS).  tile_item: the index of this thread's row-0 item of tile `tile`; its item k is + k * kWave.
+template <int BLOCK, int ITEMS>
+__device__ __forceinline__ int64_t tile_item(int64_t tile)
 {
-    __shared__ unsigned long long smem[kScanBlock / kWave];
-    // item layout of a tile: wavefront w owns [w * 64 * kScanItems, ...), row k of it = 64 consecutive items, one per
-    // lane -> every access of f is coalesced (consecutive items per THREAD would stride the lanes by kScanItems)
-    const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)(threadIdx.x >> 6) * (kWave * kScanItems) + (threadIdx.x & (kWave - 1));
-    unsigned long long s = 0;
-#pragma unroll
-    for (int k = 0; k < kScanItems; k++) {
-        int64_t i = base + (int64_t)k * kWave;
-        if (i < n) s += f.value(i);
-    }
-    // block reduce via wave shuffles
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) s += __shfl_down(s, d, kWave);
-    if ((threadIdx.x & (kWave - 1)) == 0) smem[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-#pragma unroll
-        for (int k = 0; k < kScanBlock / kWave; k++) t += smem[k];
-        bsum[blockIdx.x] = t;
-    }
+    return tile * (BLOCK * ITEMS) + (int64_t)(threadIdx.x >> 6) * (kWave * ITEMS) + (threadIdx.x & (kWave - 1));
 }
 
-// single block: exclusive scan of bsum[nb] in place; writes clamped totals to counts.
-// counts[idx_hi] = min(total_hi, cap_hi) (if idx_hi >= 0); counts[idx_lo] = total_lo (if idx_lo >= 0)
-// Optional early read-back (see d3d_voxelize_3d_dense_notify): host[0..4) = first_counts, host[5..9) = counts, then the flag
-// host[4] = 1 -- the sizes of the compaction's outputs reach the host while k_scan_apply is still writing them.
-static __global__ __launch_bounds__(1024) void k_scan_bsum(unsigned long long *bsum, int64_t nb, int64_t *counts, int idx_hi,
-                                                     int idx_lo, unsigned long long cap_hi, int64_t *host = nullptr,
-                                                     const int64_t *first_counts = nullptr, int adopt_voxels = 0)
+// Exclusive scan of the tile's items in the order of their indices: ex[k] = the sum of the tile's items before item k of this
+// thread, *total = the sum of the tile (in every thread).  A DPP scan per row, a carry over the rows, the wavefront totals
+// through smem (BLOCK / 64 words) and ONE barrier; the caller owns the reuse of smem (a second call needs a barrier in
+// between, or other words).
+template <int BLOCK, int ITEMS>
+__device__ __forceinline__ void tile_excl_scan_u64(const unsigned long long (&v)[ITEMS], unsigned long long (&ex)[ITEMS],
+                                                   unsigned long long *smem, unsigned long long *total)
 {
-    __shared__ unsigned long long smem[1024 / kWave];
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
     unsigned long long carry = 0;
-    // 4 consecutive block sums per thread and step (a 136 MB bitmap has 16.6 k of them: 5 steps instead of 17)
+#pragma unroll
+    for (int k = 0; k < ITEMS; k++) {
+        const unsigned long long incl = wave_incl_scan_u64(v[k]);
+        ex[k] = carry + incl - v[k];
+        carry += wave_readlane((uint64_t)incl, kWave - 1);      // row total
+    }
+    if (lane == 0) smem[w] = carry;                              // wavefront total
+    __syncthreads();
+    unsigned long long woff = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < BLOCK / kWave; k++) {
+        const unsigned long long x = smem[k];
+        if (k < w) woff += x;
+        tot += x;
+    }
+#pragma unroll
+    for (int k = 0; k < ITEMS; k++) ex[k] += woff;
+    *total = tot;
+}
+
+// the sum of s over the workgroup, valid in THREAD 0 only; smem: BLOCK / 64 words, one barrier
+template <int BLOCK>
+__device__ __forceinline__ unsigned long long tile_sum_u64(unsigned long long s, unsigned long long *smem)
+{
+    s = wave_sum_u64(s);
+    if ((threadIdx.x & (kWave - 1)) == 0) smem[threadIdx.x >> 6] = s;
+    __syncthreads();
+    unsigned long long t = 0;
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < BLOCK / kWave; k++) t += smem[k];
+    }
+    return t;
+}
+
+// a workgroup of 1024: exclusive scan of the nb tile sums bsum[] in place; returns their total (in every thread).  smem: 16
+// words.  4 consecutive sums per thread and step (a 136 MB bitmap has 16.6 k of them: 5 steps instead of 17)
+__device__ __forceinline__ unsigned long long scan_tile_sums(unsigned long long *bsum, int64_t nb, unsigned long long *smem)
+{
+    unsigned long long carry = 0;
     for (int64_t c0 = 0; c0 < nb; c0 += 4096) {
         const int64_t i = c0 + (int64_t)threadIdx.x * 4;
         unsigned long long v[4], mine = 0, tot;
@@ -328,6 +365,56 @@ static __global__ __launch_bounds__(1024) void k_scan_bsum(unsigned long long *b
         }
         carry += tot;
     }
+    return carry;
+}
+
+// workgroup g: scan_tile_sums over row g of bsum[.][nb].  The row's total goes to totals[2 g], totals[2 g + 1] as the two
+// packed 32-bit fields (kSumsPacked), to totals[g] as one 64-bit value (kSumsWhole), or nowhere (kSumsNone).
+enum { kSumsNone = 0, kSumsPacked = 1, kSumsWhole = 2 };
+template <int TOTAL>
+__global__ __launch_bounds__(1024) void k_scan_tile_sums(unsigned long long *__restrict__ bsum, int64_t nb, int64_t *__restrict__ totals)
+{
+    __shared__ unsigned long long smem[1024 / kWave];
+    const unsigned long long t = scan_tile_sums(bsum + (int64_t)blockIdx.x * nb, nb, smem);
+    if (threadIdx.x != 0) return;
+    if (TOTAL == kSumsPacked) {
+        totals[2 * blockIdx.x] = (int64_t)(t >> 32);
+        totals[2 * blockIdx.x + 1] = (int64_t)(t & 0xffffffffull);
+    } else if (TOTAL == kSumsWhole) {
+        totals[blockIdx.x] = (int64_t)t;
+    }
+}
+
+// ---------------------------------------------------------------- generic 3-kernel scan
+// F provides:  u64 value(int64 i)   (count pass; may record side data)
+//              u64 value2(int64 i)  (apply pass; must return the same value)
+//              void apply(int64 i, u64 v, u64 excl)
+// Values are "packed pairs": two u32 sums in one u64 (hi, lo) -- both stay < 2^32.
+template <class F>
+__global__ __launch_bounds__(kScanBlock) void k_scan_count(F f, int64_t n, unsigned long long *bsum)
+{
+    __shared__ unsigned long long smem[kScanBlock / kWave];
+    const int64_t base = tile_item<kScanBlock, kScanItems>(blockIdx.x);
+    unsigned long long s = 0;
+#pragma unroll
+    for (int k = 0; k < kScanItems; k++) {
+        int64_t i = base + (int64_t)k * kWave;
+        if (i < n) s += f.value(i);
+    }
+    s = tile_sum_u64<kScanBlock>(s, smem);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = s;
+}
+
+// single block: exclusive scan of bsum[nb] in place; writes clamped totals to counts.
+// counts[idx_hi] = min(total_hi, cap_hi) (if idx_hi >= 0); counts[idx_lo] = total_lo (if idx_lo >= 0)
+// Optional early read-back (see d3d_voxelize_3d_dense_notify): host[0..4) = first_counts, host[5..9) = counts, then the flag
+// host[4] = 1 -- the sizes of the compaction's outputs reach the host while k_scan_apply is still writing them.
+static __global__ __launch_bounds__(1024) void k_scan_bsum(unsigned long long *bsum, int64_t nb, int64_t *counts, int idx_hi,
+                                                     int idx_lo, unsigned long long cap_hi, int64_t *host = nullptr,
+                                                     const int64_t *first_counts = nullptr, int adopt_voxels = 0)
+{
+    __shared__ unsigned long long smem[1024 / kWave];
+    const unsigned long long carry = scan_tile_sums(bsum, nb, smem);
     if (threadIdx.x == 0) {
         unsigned long long hi = carry >> 32, lo = carry & 0xffffffffull;
         if (idx_hi >= 0) counts[idx_hi] = (int64_t)(hi < cap_hi ? hi : cap_hi);
@@ -352,27 +439,19 @@ template <class F>
 __global__ __launch_bounds__(kScanBlock) void k_scan_apply(F f, int64_t n, const unsigned long long *bsum_excl)
 {
     __shared__ unsigned long long smem[kScanBlock / kWave];
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
-    const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)w * (kWave * kScanItems) + lane;   // see k_scan_count
-    unsigned long long v[kScanItems], ex[kScanItems], carry = 0;
+    const int64_t base = tile_item<kScanBlock, kScanItems>(blockIdx.x);
+    unsigned long long v[kScanItems], ex[kScanItems], total;
 #pragma unroll
     for (int k = 0; k < kScanItems; k++) {
         int64_t i = base + (int64_t)k * kWave;
         v[k] = i < n ? f.value2(i) : 0ull;
-        const unsigned long long incl = wave_incl_scan_u64(v[k]);
-        ex[k] = carry + incl - v[k];
-        carry += __shfl(incl, kWave - 1, kWave);        // row total
     }
-    if (lane == 0) smem[w] = carry;                      // wavefront total
-    __syncthreads();
-    unsigned long long woff = bsum_excl[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < kScanBlock / kWave; k++)
-        if (k < w) woff += smem[k];
+    tile_excl_scan_u64<kScanBlock, kScanItems>(v, ex, smem, &total);
+    const unsigned long long before = bsum_excl[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < kScanItems; k++) {
         int64_t i = base + (int64_t)k * kWave;
-        if (i < n) f.apply(i, v[k], woff + ex[k]);
+        if (i < n) f.apply(i, v[k], before + ex[k]);
     }
 }
 

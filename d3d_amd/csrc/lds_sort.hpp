@@ -49,6 +49,30 @@ __device__ __forceinline__ unsigned long long shfl_xor_u(unsigned long long v, i
     return ((unsigned long long)shfl_xor_u((uint32_t)(v >> 32), m) << 32) | shfl_xor_u((uint32_t)v, m);
 }
 
+// ---------------------------------------------------------------- the score order of a segment
+// the padded length sort_lds wants for n entries: the power of two that is at least n and at least 64
+static __host__ __device__ inline int sort_lds_pad(int64_t n)
+{
+    int p = kWave;
+    while (p < n) p <<= 1;
+    return p;
+}
+// padding entry e: the key above every real key (a real all-ones key is an index apart) and an index no real entry has --
+// padding sorts last and stays unique
+template <typename U> constexpr U kPadKey = ~(U)0;
+constexpr uint32_t kPadIndex = 0x80000000u;
+// (d0, i0)[0 .. npad) = the composites of local entries 0 .. n - 1, load(e) the score of entry e, then padding; whole
+// workgroup, ends with the barrier sort_lds needs in front
+template <typename U, class Load>
+__device__ __forceinline__ void fill_desc_keys(U *d0, uint32_t *i0, int npad, int n, Load load)
+{
+    for (int e = threadIdx.x; e < npad; e += (int)blockDim.x) {
+        d0[e] = e < n ? KeyBits<decltype(load(e))>::desc(load(e)) : kPadKey<U>;
+        i0[e] = e < n ? (uint32_t)e : kPadIndex + (uint32_t)e;
+    }
+    __syncthreads();
+}
+
 // ascending sort of npad composites (power of two, 64 .. cap; entries are unique -- padding included) held in (d0, i0);
 // (d1, i1) is the second buffer.  Returns through *rd, *ri the buffer that holds the result.  Whole workgroup; EPT = entries
 // per thread (npad <= EPT * blockDim.x): with 2, a thread's two sorting networks / binary searches are interleaved, so the

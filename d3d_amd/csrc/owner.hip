@@ -505,15 +505,9 @@ __global__ __launch_bounds__(kFinishThreads) void k_merge_finish(const int32_t *
     }
     u64 total;
     u64 ex = block_excl_scan_u64<kFinishThreads>(mine, &total, smem);
-    if (threadIdx.x < kWave) {
-        const u64 e = lookback_exclusive(status, tile, total);
-        if (threadIdx.x == 0) {
-            sexcl = e;
-            if (tile == ntiles - 1) counts[D3D_COUNT_VOXELS] = (int64_t)(e + total);
-        }
-    }
-    __syncthreads();
-    ex += sexcl;
+    const u64 before = lookback_exclusive_block(status, tile, total, &sexcl);
+    if (threadIdx.x == 0 && tile == ntiles - 1) counts[D3D_COUNT_VOXELS] = (int64_t)(before + total);
+    ex += before;
 #pragma unroll
     for (int k = 0; k < kFinishItems; k++) {
         const int64_t i = i0 + k;
@@ -899,34 +893,19 @@ __global__ __launch_bounds__(kFinishThreads) void k_rec_finish(const int32_t *__
     __shared__ u64 sexcl;
     if (*overflow) return;                        // a bucket did not fit: rinfo is incomplete, the caller repeats on the chain path
     const unsigned int tile = lookback_ticket(reinterpret_cast<unsigned int *>(status + ntiles), &sid);
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
-    // row k of a wavefront = 64 consecutive records, one per lane: coalesced reads, and consecutive leaders write consecutive rows
-    const int64_t base = (int64_t)tile * kFinishTile + (int64_t)w * (kWave * kFinishItems) + lane;
+    // (the tile layout: coalesced reads, and consecutive leaders write consecutive rows)
+    const int64_t base = tile_item<kFinishThreads, kFinishItems>(tile);
     uint32_t info[kFinishItems];
-    u64 ex[kFinishItems], carry = 0;
+    u64 v[kFinishItems], ex[kFinishItems], total;
 #pragma unroll
     for (int k = 0; k < kFinishItems; k++) {
         const int64_t i = base + (int64_t)k * kWave;
         info[k] = i < R ? rinfo[i] : 0u;
-        const u64 v = (i < R && (info[k] & kRecLeader)) ? 1ull : 0ull;
-        const u64 incl = wave_incl_scan_u64(v);
-        ex[k] = carry + incl - v;
-        carry += __shfl(incl, kWave - 1, kWave);
+        v[k] = (i < R && (info[k] & kRecLeader)) ? 1ull : 0ull;
     }
-    if (lane == 0) smem[w] = carry;
-    __syncthreads();
-    u64 woff = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < kFinishThreads / kWave; k++) { if (k < w) woff += smem[k]; total += smem[k]; }
-    if (threadIdx.x < kWave) {
-        const u64 e = lookback_exclusive(status, tile, total);
-        if (threadIdx.x == 0) {
-            sexcl = e;
-            if (tile == ntiles - 1) counts[D3D_COUNT_VOXELS] = (int64_t)(e + total);
-        }
-    }
-    __syncthreads();
-    woff += sexcl;
+    tile_excl_scan_u64<kFinishThreads, kFinishItems>(v, ex, smem, &total);
+    const u64 woff = lookback_exclusive_block(status, tile, total, &sexcl);
+    if (threadIdx.x == 0 && tile == ntiles - 1) counts[D3D_COUNT_VOXELS] = (int64_t)(woff + total);
     // c == 4: one record per leader -- its own, or the merged record k_rec_bucket left for a cell of several; the records of
     // all rows are loaded before the first is used
     const bool fast4 = f.c == 4;
@@ -1016,36 +995,20 @@ __global__ __launch_bounds__(kPrefixThreads) void k_first_prefix(const u64 *__re
     __shared__ u64 smem[kPrefixThreads / kWave];
     __shared__ u64 sexcl;
     const unsigned int tile = lookback_ticket(reinterpret_cast<unsigned int *>(status + ntiles), &sid);
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
-    // row k of a wavefront = 64 consecutive words, one per lane (coalesced)
-    const int64_t base = (int64_t)tile * kPrefixTile + (int64_t)w * (kWave * kPrefixItems) + lane;
-    u64 v[kPrefixItems], ex[kPrefixItems], carry = 0;
+    const int64_t base = tile_item<kPrefixThreads, kPrefixItems>(tile);
+    u64 v[kPrefixItems], ex[kPrefixItems], total;
 #pragma unroll
     for (int k = 0; k < kPrefixItems; k++) {
         const int64_t i = base + (int64_t)k * kWave;
         v[k] = i < nw ? (u64)__popcll(global[i]) : 0ull;
-        const u64 incl = wave_incl_scan_u64(v[k]);
-        ex[k] = carry + incl - v[k];
-        carry += __shfl(incl, kWave - 1, kWave);
     }
-    if (lane == 0) smem[w] = carry;
-    __syncthreads();
-    u64 woff = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < kPrefixThreads / kWave; k++) { if (k < w) woff += smem[k]; total += smem[k]; }
-    if (threadIdx.x < kWave) {
-        const u64 e = lookback_exclusive(status, tile, total);
-        if (threadIdx.x == 0) {
-            sexcl = e;
-            if (tile == ntiles - 1) {
-                counts_out[D3D_COUNT_VOXELS] = (int64_t)(e + total);
-                counts_out[D3D_COUNT_STATUS] = global[nw] ? D3D_VOXEL_STATUS_BIN_OVERFLOW : 0;   // some owner's merge (see k_first_mark)
-                counts_out[D3D_COUNT_POINTS] = 0; counts_out[D3D_COUNT_AUX] = 0;
-            }
-        }
+    tile_excl_scan_u64<kPrefixThreads, kPrefixItems>(v, ex, smem, &total);
+    const u64 woff = lookback_exclusive_block(status, tile, total, &sexcl);
+    if (threadIdx.x == 0 && tile == ntiles - 1) {
+        counts_out[D3D_COUNT_VOXELS] = (int64_t)(woff + total);
+        counts_out[D3D_COUNT_STATUS] = global[nw] ? D3D_VOXEL_STATUS_BIN_OVERFLOW : 0;   // some owner's merge (see k_first_mark)
+        counts_out[D3D_COUNT_POINTS] = 0; counts_out[D3D_COUNT_AUX] = 0;
     }
-    __syncthreads();
-    woff += sexcl;
 #pragma unroll
     for (int k = 0; k < kPrefixItems; k++) {
         const int64_t i = base + (int64_t)k * kWave;

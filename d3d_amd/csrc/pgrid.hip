@@ -81,7 +81,7 @@ __global__ __launch_bounds__(kPgThreads) void k_pg_bounds(const T *__restrict__ 
     const unsigned long long has = __ballot(ok);
     if (has == 0) return;                      // (wave-uniform)
     const int src = __ffsll((long long)has) - 1;
-    const int64_t s0 = (int64_t)ps_readlane((uint64_t)s, src);
+    const int64_t s0 = (int64_t)wave_readlane((uint64_t)s, src);
     if (__ballot(ok && s != s0) == 0) {        // one segment: reduce, then the lane `src` alone
 #pragma unroll
         for (int a = 0; a < 6; a++) {
@@ -204,7 +204,7 @@ __device__ __forceinline__ void pg_runs(int64_t nruns, const int64_t *__restrict
         while (vote) {                         // (wave-uniform)
             const int src = __ffsll((long long)vote) - 1;
             vote &= vote - 1;
-            pg_walk<T>(packed, order, ps_readlane(beg, src), ps_readlane(end, src), lane, cx, cy, cz, tile);
+            pg_walk<T>(packed, order, wave_readlane(beg, src), wave_readlane(end, src), lane, cx, cy, cz, tile);
         }
     }
 }
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(kPgThreads) void k_ball_query_grid(const T *__restr
         }
     }
     const int count = found < nsample ? found : nsample;
-    const int32_t pad = (pad_first && count > 0) ? (int32_t)ps_readlane(held, 0) : -1;
+    const int32_t pad = (pad_first && count > 0) ? (int32_t)wave_readlane(held, 0) : -1;
     if (lane < nsample) table[c * nsample + lane] = lane < count ? (int32_t)held : pad;
     if (lane == 0) counts[c] = count;
 }

@@ -16,17 +16,6 @@ template <typename T> __device__ __forceinline__ bool ps_finite3(T x, T y, T z)
     return fabs(x) < inf && fabs(y) < inf && fabs(z) < inf;         // false for NaN
 }
 
-__device__ __forceinline__ uint32_t ps_readlane(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
-__device__ __forceinline__ uint64_t ps_readlane(uint64_t v, int lane)
-{
-    return ((uint64_t)ps_readlane((uint32_t)(v >> 32), lane) << 32) | ps_readlane((uint32_t)v, lane);
-}
-__device__ __forceinline__ float ps_readlane(float v, int lane) { return __uint_as_float(ps_readlane(__float_as_uint(v), lane)); }
-__device__ __forceinline__ double ps_readlane(double v, int lane)
-{
-    return __longlong_as_double((long long)ps_readlane((uint64_t)__double_as_longlong(v), lane));
-}
-
 // the segment b of centre c: center_offsets[b] <= c < center_offsets[b + 1] (the last such b where segments are empty)
 __device__ __forceinline__ int64_t ps_segment_of(const int64_t *__restrict__ center_offsets, int64_t segments, int64_t c)
 {
@@ -74,9 +63,9 @@ __device__ __forceinline__ uint32_t knn_row(uint64_t k) { return (uint32_t)k; }
 __device__ __forceinline__ uint32_t knn_row(const KnnKey64 &k) { return k.row; }
 __device__ __forceinline__ float knn_dist(uint64_t k, float) { return __uint_as_float((uint32_t)(k >> 32)); }
 __device__ __forceinline__ double knn_dist(const KnnKey64 &k, double) { return __longlong_as_double((long long)k.d); }
-__device__ __forceinline__ uint32_t knn_readlane(uint32_t k, int lane) { return ps_readlane(k, lane); }
-__device__ __forceinline__ uint64_t knn_readlane(uint64_t k, int lane) { return ps_readlane(k, lane); }
-__device__ __forceinline__ KnnKey64 knn_readlane(const KnnKey64 &k, int lane) { return KnnKey64{ps_readlane(k.d, lane), ps_readlane(k.row, lane)}; }
+__device__ __forceinline__ uint32_t knn_readlane(uint32_t k, int lane) { return wave_readlane(k, lane); }
+__device__ __forceinline__ uint64_t knn_readlane(uint64_t k, int lane) { return wave_readlane(k, lane); }
+__device__ __forceinline__ KnnKey64 knn_readlane(const KnnKey64 &k, int lane) { return KnnKey64{wave_readlane(k.d, lane), wave_readlane(k.row, lane)}; }
 // lane l reads lane l - 1 over the whole wavefront (wave_shr:1); lane 0 reads 0 and is never asked
 __device__ __forceinline__ uint32_t knn_up(uint32_t k) { return d3d_dpp_u32<0x138, 0xf>(k); }
 __device__ __forceinline__ uint64_t knn_up(uint64_t k) { return d3d_dpp_u64<0x138, 0xf>(k); }

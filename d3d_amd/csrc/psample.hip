@@ -107,7 +107,8 @@ template <int CTRL, int ROW_MASK> __device__ __forceinline__ FpsKey64 key_dpp(co
 {
     return FpsKey64{d3d_dpp_u64<CTRL, ROW_MASK>(k.d), d3d_dpp_u32<CTRL, ROW_MASK>(k.inv)};
 }
-__device__ __forceinline__ FpsKey64 ps_readlane(const FpsKey64 &k, int lane) { return FpsKey64{ps_readlane(k.d, lane), ps_readlane(k.inv, lane)}; }
+using ::wave_readlane;                              // (the overload for the key must not hide common.hpp's)
+__device__ __forceinline__ FpsKey64 wave_readlane(const FpsKey64 &k, int lane) { return FpsKey64{wave_readlane(k.d, lane), wave_readlane(k.inv, lane)}; }
 
 #define D3D_KEY_STEP(CTRL, MASK)                   \
     {                                              \
@@ -125,7 +126,7 @@ template <typename K> __device__ __forceinline__ K key_wave_max(K k)
 {
     k = key_row_max(k);
     D3D_KEY_STEP(0x142, 0xa) D3D_KEY_STEP(0x143, 0xc)
-    return ps_readlane(k, kWave - 1);
+    return wave_readlane(k, kWave - 1);
 }
 #undef D3D_KEY_STEP
 
@@ -174,9 +175,9 @@ __device__ __forceinline__ void fps_elect(const FpsBest<T> &b, int64_t s, int64_
     }
     ps_lds_barrier();
     const FpsSlot<T> mine = buf[lane & (kFpsWaves - 1)];
-    const K win = ps_readlane(key_row_max(mine.key), kWave - 1);
+    const K win = wave_readlane(key_row_max(mine.key), kWave - 1);
     const int src = __builtin_amdgcn_readfirstlane(__ffsll((long long)__ballot(key_eq(mine.key, win))) - 1);
-    cx = ps_readlane(mine.x, src), cy = ps_readlane(mine.y, src), cz = ps_readlane(mine.z, src);
+    cx = wave_readlane(mine.x, src), cy = wave_readlane(mine.y, src), cz = wave_readlane(mine.z, src);
     if (threadIdx.x == 0) {
         const bool none = key_none(win);                                       // every row of the segment is excluded
         idx_out[s] = row0 + (none ? 0 : (int64_t)key_row(win));
@@ -190,7 +191,7 @@ template <typename T, int LO, int HI>
 __device__ __forceinline__ void fps_pick(const T *x, const T *y, const T *z, int j, int l, T &ox, T &oy, T &oz)
 {
     if constexpr (HI - LO == 1) {
-        ox = ps_readlane(x[LO], l), oy = ps_readlane(y[LO], l), oz = ps_readlane(z[LO], l);
+        ox = wave_readlane(x[LO], l), oy = wave_readlane(y[LO], l), oz = wave_readlane(z[LO], l);
     } else {
         constexpr int MID = (LO + HI) / 2;
         if (j < MID) fps_pick<T, LO, MID>(x, y, z, j, l, ox, oy, oz);

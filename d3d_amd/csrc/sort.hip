@@ -569,11 +569,10 @@ __global__ __launch_bounds__(kSsSortThreads) void k_ss_bucket(const U *__restric
         }
         return;
     }
-    int npad = kWave;
-    while ((uint32_t)npad < m) npad <<= 1;
+    const int npad = sort_lds_pad(m);
     for (int e = threadIdx.x; e < npad; e += blockDim.x) {
-        d0[e] = (uint32_t)e < m ? dk[base + e] : ~(U)0;      // padding sorts behind every real entry (indices are < 2^31)
-        i0[e] = (uint32_t)e < m ? di[base + e] : 0x80000000u + (uint32_t)e;      // ... and is unique too
+        d0[e] = (uint32_t)e < m ? dk[base + e] : kPadKey<U>;      // padding sorts behind every real entry (indices are < 2^31)
+        i0[e] = (uint32_t)e < m ? di[base + e] : kPadIndex + (uint32_t)e;      // ... and is unique too
     }
     __syncthreads();
     U *d;
@@ -591,13 +590,8 @@ __global__ __launch_bounds__(kSsSortThreads) void k_sort_small(const K *__restri
     typedef typename KeyBits<K>::U U;
     __shared__ U d0[kSsBucketCap], d1[kSsBucketCap];
     __shared__ uint32_t i0[kSsBucketCap], i1[kSsBucketCap];
-    int npad = kWave;
-    while ((uint32_t)npad < n) npad <<= 1;
-    for (int e = threadIdx.x; e < npad; e += blockDim.x) {
-        d0[e] = (uint32_t)e < n ? KeyBits<K>::desc(keys[e]) : ~(U)0;     // padding sorts behind every real entry
-        i0[e] = (uint32_t)e < n ? (uint32_t)e : 0x80000000u + (uint32_t)e;
-    }
-    __syncthreads();
+    const int npad = sort_lds_pad(n);
+    fill_desc_keys(d0, i0, npad, (int)n, [&](int e) { return keys[e]; });
     U *d;
     uint32_t *ii;
     if (npad <= kSsSortThreads) sort_lds<1>(d0, i0, d1, i1, npad, &d, &ii);

@@ -157,6 +157,40 @@ def test_rig_in_one_call_equals_single_calls_bit_for_bit(ncam):
     cr.check_projection(cr.expected(model), gpu_full_form(ts, cloud, frames[-1]), cr.near_points(model), frames[-1])
 
 
+def test_two_cameras_over_more_than_4096_tiles():
+    """4098 tile sums per camera: the workgroup that scans a camera's sums takes a second step of 4096 with two live sums, and
+    camera 1's workgroup is not workgroup 0.  K, Kd, the compacted mask with its uv rows and dmask against the model."""
+    from d3d_amd import synth
+    n = 4096 * 1024 + 1025
+    cloud = synth.lidar_like(n, 11)
+    assert cloud.dtype == np.float32
+    ts, frames = six_camera_rig()
+    frames = frames[:2]
+    got = ts.project_points_to_cameras(torch.from_numpy(cloud).cuda(), frames, remove_outlier=True, return_dmask=True)
+    assert len(got) == 2
+    counts = []
+    for frame, res in zip(frames, got):
+        model = model_of(ts, cloud, frame)
+        near = cr.near_points(model)
+        assert int(near.sum()) <= cr.MAX_NEAR
+        exp = cr.expected(model)
+        uv, mask, dmask = to_np(res)
+        assert uv.shape == (len(mask), 2) and uv.dtype == np.float64 and mask.dtype == np.int64 and dmask.dtype == np.int64
+        for key, g_idx in (("mask", mask), ("dmask", dmask)):
+            assert g_idx.size == 0 or (g_idx[0] >= 0 and g_idx[-1] < n and np.all(np.diff(g_idx) > 0)), "%s: %s is not ascending" % (frame, key)
+            e, g = np.zeros(n, bool), np.zeros(n, bool)
+            e[exp[key]] = True
+            g[g_idx] = True
+            bad = np.nonzero((e != g) & ~near)[0]
+            assert bad.size == 0, "%s: %s differs at points %s" % (frame, key, bad[:10])
+            if not near.any():
+                assert np.array_equal(exp[key], g_idx), "%s: %s" % (frame, key)       # K / Kd and every index
+        kept = ~near[mask] & model["mask"][mask]
+        assert np.abs(uv[kept] - exp["uv_all"][mask[kept]]).max() <= cr.UV_ATOL, frame     # row j = the j-th point in view
+        counts.append((len(mask), len(dmask)))
+    assert counts[0] != counts[1] and all(k > 4096 * 1024 // 8 for c in counts for k in c)     # (live sums in both steps)
+
+
 def test_non_default_stream():
     from d3d_amd import synth
     cloud = torch.from_numpy(synth.lidar_like(200_000, 4)).cuda()

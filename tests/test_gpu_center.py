@@ -101,6 +101,55 @@ def test_peaks_thresholds(shape):
     assert int(heatmap_peaks(tenth.cuda(), 4, 1, threshold=0.1).counts[0]) == 0
 
 
+def tile_edge_scene(shape, last_in, k):
+    """One sample: a background of -1, `above` lone peaks with distinct values above 2 and ties of 1.0 on lone cells on both sides of
+    every multiple of 256 flat cells (a wavefront's share of a workgroup's tile of 1024) and on the last cells of the map.  The
+    k-th rank falls among the ties: `last_in` -- there are exactly as many ties as ranks left, the map's last cell takes the last
+    one; else one tie more, and the last cell is the one left out.  Which cells are lone peaks is for the model to say."""
+    c, h, w = shape
+    n = c * h * w
+    taken = []
+
+    def lone(e):
+        p, y, x = e // (h * w), e % (h * w) // w, e % w
+        return all(q // (h * w) != p or abs(q % (h * w) // w - y) > 1 or abs(q % w - x) > 1 for q in taken)
+
+    wanted = [n - 1, n - 3, n - 5] + [b + d for b in (256, 512, 768, 1024) for d in (-5, -3, -1, 1, 3)] + list(range(2, 40, 2))
+    for e in wanted:
+        if 0 <= e < n and e not in taken and lone(e):
+            taken.append(e)
+    ties = sorted(taken)
+    above = k - len(ties) + (0 if last_in else 1)
+    heat = np.full(n, -1.0, np.float32)
+    heat[ties] = 1.0
+    for e in np.random.default_rng(n).permutation(n):
+        if len(taken) == len(ties) + above:
+            break
+        if lone(int(e)):
+            taken.append(int(e))
+            heat[e] = 2.0 + (len(taken) - len(ties)) / 64.0            # (exact in fp16 and bf16 steps of 1 / 64 below 4)
+    assert len(taken) == len(ties) + above and above > 0
+    return heat.reshape(shape), ties
+
+
+@pytest.mark.parametrize("dtype", ("f32", "f16"))
+@pytest.mark.parametrize("shape", ((1, 1, 1, 1023), (2, 1, 32, 32), (1, 1, 25, 41)), ids=str)
+def test_peaks_ties_across_the_tile_edge(shape, dtype):
+    """c h w of 1023, 1024 and 1025 cells: the map ends one short of a tile of 1024, on it and one cell into the next.  Which ties of
+    the k-th value win is a matter of the lowest flat index, i.e. of the prefix over the rows, wavefronts and tiles before a cell."""
+    k, n = 65, int(np.prod(shape[1:]))
+    for first_in in (True, False):
+        built = [tile_edge_scene(shape[1:], first_in == (b % 2 == 0), k) for b in range(shape[0])]
+        heat = torch.from_numpy(np.stack([m for m, _ in built])).to(TORCH[dtype])
+        flat, counts = ref.heatmap_peaks_model(heat.float().numpy(), k, 3)
+        for b, (_, ties) in enumerate(built):                                  # the scene is what it is meant to be
+            last_in = first_in == (b % 2 == 0)
+            won = set(flat[b].tolist())
+            assert counts[b] == k and ties[-1] == n - 1 and (n - 1 in won) == last_in and set(ties[:-1]) <= won
+            assert any(e < 256 for e in ties) and any(768 <= e < 1024 for e in ties) and (n <= 1024 or ties[-1] == 1024)
+        check_peaks(heatmap_peaks(heat.cuda(), k, 3), heat, flat, counts, k)
+
+
 def test_peaks_inputs_and_determinism():
     shape = cases.PEAK_SHAPES[3]
     heat = scene(shape, "plateaus")

@@ -181,6 +181,40 @@ def test_raw_entries_capacity_and_repeat():
     assert not bool(offsets[1].any())
 
 
+@pytest.mark.parametrize("n", (1, 255, 256, 257, 1023, 1024, 1025))
+def test_rows_around_the_scan_tile(n):
+    """n rows around a wavefront's 256 and a workgroup's 1024 of the offsets scan against three columns, hits in the first and in
+    the last row: the raw entries on poisoned buffers, offsets, offsets[n] and the pairs against the matrix's"""
+    from d3d_amd.box import box2d_iou
+    lib = _lib.load()
+    m = 3
+    b2 = np.array([[10.0 * j, 0.0, 2.0, 2.0, 0.3] for j in range(m)])
+    i = np.arange(n)
+    b1 = np.stack([1000.0 + 3.0 * i, np.full(n, 500.0), np.full(n, 2.0), np.full(n, 1.5), 0.1 * (i % 7)], 1)      # far from every column
+    one = (i % 5 == 0) | (i == n - 1)                               # these rows lie on column i % 3 ...
+    b1[one, 0], b1[one, 1] = 10.0 * (i[one] % m) + 0.3, 0.2
+    wide = i % 11 == 0                                              # ... and these across up to all three
+    b1[wide, 0], b1[wide, 2] = 10.0, 30.0
+    b1, b2 = T(b1), T(b2)
+    dense = box2d_iou(b1, b2, method="rbox", precise=True)
+    assert bool((dense[0] > 0).any()) and bool((dense[n - 1] > 0).any())
+    ws = torch.empty(lib.d3d_iou_sparse_workspace_bytes(n, m), dtype=torch.uint8, device="cuda")
+    inputs = (_lib.ptr(b1), n, _lib.ptr(b2), m, 5, 2, _lib.F64, 0.0)
+    tail = (_lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+    offsets = torch.full((n + 1,), -7, dtype=torch.int64, device="cuda")
+    assert lib.d3d_iou_sparse_count(*inputs, _lib.ptr(offsets), *tail) == _lib.OK
+    mp, mv, mo = matrix_model(dense, 0.0)
+    assert torch.equal(offsets, mo)
+    k, extra = int(offsets[n]), 5
+    assert k == len(mp) and k > n // 5
+    pairs = torch.full((k + extra, 2), -1, dtype=torch.int64, device="cuda")
+    values = torch.full((k + extra,), -3.0, dtype=torch.float64, device="cuda")
+    assert lib.d3d_iou_sparse_emit(*inputs, _lib.ptr(offsets), k + extra, _lib.ptr(pairs), _lib.ptr(values), *tail) == _lib.OK
+    torch.cuda.synchronize()
+    assert bool((pairs[k:] == -1).all()) and bool((values[k:] == -3.0).all())
+    assert_is_model((pairs[:k], values[:k], offsets), dense, 0.0, n)
+
+
 def test_4000_by_3000_at_config_3_density():
     """the only non-tiny shape: 250 workgroups of 16 rows, three LDS chunks of 1024 columns (the last one partial)"""
     from d3d_amd.box import box2d_iou, box2d_iou_sparse
