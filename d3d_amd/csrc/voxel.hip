@@ -80,10 +80,9 @@ struct DenseKey {
     }
     float lo[3], size[3];
     int shape[3];
-    __device__ __forceinline__ bool make(const float *p, u64 &key, uint32_t &status) const
+    // the point's cell, or false for a point outside the grid (c is then not a cell)
+    __device__ __forceinline__ bool cell(const float *p, int *c) const
     {
-        (void)status;
-        int c[3];
 #pragma unroll
         for (int d = 0; d < 3; d++) {
             float q = (p[d] - lo[d]) / size[d];
@@ -93,7 +92,18 @@ struct DenseKey {
             if (idx < 0 || idx >= shape[d]) return false;
             c[d] = idx;
         }
-        key = ((u64)c[0] * (unsigned)shape[1] + (unsigned)c[1]) * (unsigned)shape[2] + (unsigned)c[2];
+        return true;
+    }
+    __device__ __forceinline__ u64 linear(const int *c) const
+    {
+        return ((u64)c[0] * (unsigned)shape[1] + (unsigned)c[1]) * (unsigned)shape[2] + (unsigned)c[2];
+    }
+    __device__ __forceinline__ bool make(const float *p, u64 &key, uint32_t &status) const
+    {
+        (void)status;
+        int c[3];
+        if (!cell(p, c)) return false;
+        key = linear(c);
         return true;
     }
     __device__ __forceinline__ void decode(u64 key, long long *c) const
@@ -2629,8 +2639,10 @@ __global__ __launch_bounds__(kMetaLbThreads) void k_meta_first_lb(Key kf, int64_
 // A wavefront owns 64 consecutive point indices; the nv of them that are a voxel's first point are nv CONSECUTIVE voxel ids
 // vid0 .. vid0 + nv - 1 (first-seen numbering, voxelize.cpp:119), i.e. one contiguous stretch of every output:
 //   1. the record positions and the point indices of those first points are compacted across the lanes (ds_permute); lane
-//      l < nv gathers voxel vid0 + l's record -- the one random access per voxel;
-//   2. ALL kept rows of the wavefront's voxels (sum of min(count, P): ~63 for a LiDAR frame) are fetched in one flat,
+//      l < nv gathers voxel vid0 + l's record -- the one random access per voxel -- or, without a record (fewer than 255
+//      points), its first row for the cell, whose three coordinates stay in registers until step 5 (no key is folded and
+//      divided apart again);
+//   2. ALL kept rows of the wavefront's voxels (sum of min(count, P): ~60 for a LiDAR frame) are fetched in one flat,
 //      lane-parallel pass into a row buffer in LDS: row t belongs to voxel j (binary search over the voxels' row offsets) at
 //      rank k; its point index is the voxel's first point (k = 0: ascending indices inside one 1 KiB window of the point
 //      tensor, nothing was staged for it) or entry k of the voxel's ranked list.  Two dependent loads for the whole
@@ -2642,6 +2654,45 @@ __global__ __launch_bounds__(kMetaLbThreads) void k_meta_first_lb(Key kf, int64_
 //   5. coords / npoints / pmask / aggregates: one lane per voxel, coalesced over the stretch.
 // A wavefront whose rows exceed the buffer (kEmitCap) takes its voxels in batches of consecutive ids.
 constexpr int kEmitCap = 256;                     // rows per wavefront in LDS (4 KiB); max_points <= kEmitCap on this path
+
+// One voxel's rows in point order into a0 .. a3 (sequential fp32: voxelize.cpp:137-164).  MODE: 0 sum, 1 max, 2 min
+template <int MODE>
+__device__ __forceinline__ void reduce_rows(const float __attribute__((ext_vector_type(4))) *rw, uint32_t kept, float &a0, float &a1,
+                                            float &a2, float &a3)
+{
+#pragma unroll 2                                             // (a deeper unroll holds eight rows in registers and costs two wavefronts per SIMD)
+    for (uint32_t k = 0; k < kept; k++) {
+        const float __attribute__((ext_vector_type(4))) x = rw[k];
+        if (MODE == 0) { a0 += x.x; a1 += x.y; a2 += x.z; a3 += x.w; }
+        else if (MODE == 1) {                                // std::max(acc, x) = acc < x ? x : acc
+            a0 = a0 < x.x ? x.x : a0; a1 = a1 < x.y ? x.y : a1; a2 = a2 < x.z ? x.z : a2; a3 = a3 < x.w ? x.w : a3;
+        } else {
+            a0 = x.x < a0 ? x.x : a0; a1 = x.y < a1 ? x.y : a1; a2 = x.z < a2 ? x.z : a2; a3 = x.w < a3 ? x.w : a3;
+        }
+    }
+}
+// the reduction type is the launch's: one dispatch per wavefront, a loop without branches behind it
+__device__ __forceinline__ void reduce_rows(int reduction, const float __attribute__((ext_vector_type(4))) *rw, uint32_t kept, float &a0,
+                                            float &a1, float &a2, float &a3)
+{
+    if (reduction == D3D_REDUCE_MEAN || reduction == kReduceSum) reduce_rows<0>(rw, kept, a0, a1, a2, a3);
+    else if (reduction == D3D_REDUCE_MAX) reduce_rows<1>(rw, kept, a0, a1, a2, a3);
+    else reduce_rows<2>(rw, kept, a0, a1, a2, a3);
+}
+
+// 16 bytes of a voxel's voxel_pmask row, slots k0 .. k0 + 15: byte k is 1 below `kept`.  A word holds clamp(kept - k, 0, 4)
+// ones from its low byte up: 0x01010101 shifted up by that many bytes, the part that crosses into the high word.
+__device__ __forceinline__ uint32_t __attribute__((ext_vector_type(4))) pmask_piece(uint32_t k0, uint32_t kept)
+{
+    uint32_t __attribute__((ext_vector_type(4))) w4;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        int m = (int)kept - (int)(k0 + 4u * q);
+        m = m < 0 ? 0 : (m > 4 ? 4 : m);
+        w4[q] = (uint32_t)((0x01010101ull << (8 * m)) >> 32);
+    }
+    return w4;
+}
 
 
 // RESIDENT (d3d_voxelize_3d_dense_resident): voxels[capacity, P, 4] is a buffer the caller keeps from frame to frame, with
@@ -2674,23 +2725,20 @@ __global__ __launch_bounds__(256) void k_emit(Key kf, int64_t npad, const uint32
     uint32_t *sh_loff = loff_all[RESIDENT ? w : 0];
     D3D_PHASE_DECL;
     const uint32_t tile = (uint32_t)(i / kFlagTile), ntile = (uint32_t)(npad / kFlagTile);
-    uint32_t before = 0, all = 0;
-    for (uint32_t t = lane; t < ntile; t += kWave) {
-        const uint32_t x = bsumF[t];
-        all += x;
-        if (t < tile) before += x;
-    }
-    {
-        const u64 both = wave_sum_u64(((u64)all << 32) | before);       // (each below 2^32: the halves do not carry)
-        before = (uint32_t)both;
-        all = (uint32_t)(both >> 32);
-    }
-    if (i == 0) {
-        counts[D3D_COUNT_VOXELS] = (int64_t)(all < max_voxels ? all : max_voxels);
-        counts[D3D_COUNT_AUX] = x.aux_value;
-        // sharded voxelizer: the status bits travel with the key list (row `status_row`, negative = not a cell)
-        if (x.keys_out && x.status_row >= 0) x.keys_out[x.status_row] = -1 - counts[D3D_COUNT_STATUS];
-        if (host_counts) notify_host(counts, host_counts);
+    uint32_t before = 0;
+    for (uint32_t t = lane; t < tile; t += kWave) before += bsumF[t];
+    before = wave_readlane(wave_incl_scan_u32(before), kWave - 1);
+    if (blockIdx.x == 0 && w == 0) {                        // the frame's voxel count: the one wavefront that publishes it adds it up
+        uint32_t all = 0;
+        for (uint32_t t = lane; t < ntile; t += kWave) all += bsumF[t];
+        all = wave_readlane(wave_incl_scan_u32(all), kWave - 1);
+        if (lane == 0) {
+            counts[D3D_COUNT_VOXELS] = (int64_t)(all < max_voxels ? all : max_voxels);
+            counts[D3D_COUNT_AUX] = x.aux_value;
+            // sharded voxelizer: the status bits travel with the key list (row `status_row`, negative = not a cell)
+            if (x.keys_out && x.status_row >= 0) x.keys_out[x.status_row] = -1 - counts[D3D_COUNT_STATUS];
+            if (host_counts) notify_host(counts, host_counts);
+        }
     }
     const uint32_t e = firstmap[i];
     const unsigned long long bal = __ballot(e != kInf);
@@ -2709,18 +2757,16 @@ __global__ __launch_bounds__(256) void k_emit(Key kf, int64_t npad, const uint32
     const uint32_t il = (uint32_t)__builtin_amdgcn_ds_permute((int)dst, (int)(uint32_t)i);
     const bool mine = (uint32_t)lane < nv;
     uint4 rec = make_uint4(0u, 0u, 0u, 0u);
-    if (mine) {
-        // packed entries (round 5): count and segment travel in the entry, the record only for 255 points and more
-        const bool has_rec = x.fm_packed ? (el >> kFmShift) == kFmRecord : el != kSingleVoxel;
-        if (has_rec) rec = vrec[x.fm_packed ? (el & kFmMask) : el];   // the one random access per such voxel
-        else {                                              // no record: the voxel's cell from its first point itself
-            const float4 p0 = points4[il];                  // (ascending indices inside the wavefront's 1 KiB window)
-            const float v3[3] = {p0.x, p0.y, p0.z};
-            u64 key = 0;
-            uint32_t st = 0;
-            (void)kf.make(v3, key, st);                     // the same arithmetic on the same floats as k_bin_count: the same cell
-            rec = make_uint4((uint32_t)key, (uint32_t)(key >> 32), x.fm_packed ? (el & kFmMask) : 0u, x.fm_packed ? (el >> kFmShift) : 1u);
-        }
+    // packed entries (round 5): count and segment travel in the entry, the record only for 255 points and more
+    const bool has_rec = mine && (x.fm_packed ? (el >> kFmShift) == kFmRecord : el != kSingleVoxel);
+    const unsigned long long recmask = __ballot(has_rec);   // (none in most wavefronts)
+    int cell[3] = {0, 0, 0};                                // a voxel without a record: its cell, kept for step 5
+    if (has_rec) rec = vrec[x.fm_packed ? (el & kFmMask) : el];       // the one random access per such voxel
+    else if (mine) {                                        // no record: the voxel's cell from its first point itself
+        const float4 p0 = points4[il];                      // (ascending indices inside the wavefront's 1 KiB window)
+        const float v3[3] = {p0.x, p0.y, p0.z};
+        (void)kf.cell(v3, cell);                            // the same arithmetic on the same floats as k_bin_count: the same cell
+        rec = make_uint4(0u, 0u, x.fm_packed ? (el & kFmMask) : 0u, x.fm_packed ? (el >> kFmShift) : 1u);
     }
     // (round 5) With packed entries the rows a voxel keeps are known NOW, before its record / first row / ranked rows have
     // arrived: the 128-byte lines of the stretch that hold no row at all -- three of four at config 2 -- are stored while
@@ -2805,18 +2851,7 @@ __global__ __launch_bounds__(256) void k_emit(Key kf, int64_t npad, const uint32
         D3D_PHASE(2, 2);                                    // rows gathered
         wave_lds_fence();
         // 3. reductions in point order, one lane per voxel
-        if (AGG4 && (uint32_t)lane >= ja && (uint32_t)lane < jb && cnt <= P) {
-            const vec4 *rw = rowbuf + (off - oa);
-            for (uint32_t k = 0; k < kept; k++) {
-                const vec4 x = rw[k];
-                if (is_sum) { a0 += x.x; a1 += x.y; a2 += x.z; a3 += x.w; }
-                else if (reduction == D3D_REDUCE_MAX) {      // std::max(acc, x) = acc < x ? x : acc
-                    a0 = a0 < x.x ? x.x : a0; a1 = a1 < x.y ? x.y : a1; a2 = a2 < x.z ? x.z : a2; a3 = a3 < x.w ? x.w : a3;
-                } else {
-                    a0 = x.x < a0 ? x.x : a0; a1 = x.y < a1 ? x.y : a1; a2 = x.z < a2 ? x.z : a2; a3 = x.w < a3 ? x.w : a3;
-                }
-            }
-        }
+        if (AGG4) reduce_rows(reduction, rowbuf + (off - oa), (uint32_t)lane >= ja && (uint32_t)lane < jb && cnt <= P ? kept : 0u, a0, a1, a2, a3);
         D3D_PHASE(2, 3);                                    // reductions
         // 4. the stretch of the batch's voxels
         if (RESIDENT) {
@@ -2863,13 +2898,15 @@ __global__ __launch_bounds__(256) void k_emit(Key kf, int64_t npad, const uint32
     {
         // coords[nv][3] i64: through LDS (the row buffer is free now), then 8-byte words 64 at a time
         long long *cbuf = reinterpret_cast<long long *>(rowbuf);       // 64 * 3 * 8 B = 1.5 KiB
+        long long cc[3] = {cell[0], cell[1], cell[2]};
+        if (recmask) {                                      // wave-uniform: a record holds the cell as its key
+            if (has_rec) kf.decode(((u64)rec.y << 32) | rec.x, cc);
+        }
         if (mine) {
-            long long cc[3];
-            kf.decode(((u64)rec.y << 32) | rec.x, cc);
             cbuf[lane * 3 + 0] = cc[0]; cbuf[lane * 3 + 1] = cc[1]; cbuf[lane * 3 + 2] = cc[2];
             __builtin_nontemporal_store((int32_t)cnt, &npoints[v]);
             // reduce contract (sharded voxelizer): linear cell key, global index of the first point, segment base
-            if (x.keys_out) x.keys_out[v] = (int64_t)(((u64)rec.y << 32) | rec.x);
+            if (x.keys_out) x.keys_out[v] = (int64_t)(has_rec ? ((u64)rec.y << 32) | rec.x : kf.linear(cell));
             if (x.first_out) x.first_out[v] = x.index_offset + (int64_t)il;
             if (x.voff) x.voff[v] = base;
         }
@@ -2883,16 +2920,8 @@ __global__ __launch_bounds__(256) void k_emit(Key kf, int64_t npad, const uint32
             typedef uint32_t uvec4 __attribute__((ext_vector_type(4)));
             uvec4 *pdst = reinterpret_cast<uvec4 *>(pmask + (int64_t)vid0 * P);
             for (uint32_t t = lane; t < total; t += kWave) {
-                const uint32_t j = t / per, k0 = (t - j * per) << 4, kj = sh_kept[j];
-                uvec4 w4;
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    uint32_t b = 0;
-#pragma unroll
-                    for (int x = 0; x < 4; x++) b |= ((k0 + q * 4 + x) < kj ? 1u : 0u) << (8 * x);
-                    w4[q] = b;
-                }
-                __builtin_nontemporal_store(w4, &pdst[t]);
+                const uint32_t j = pshift >= 4 ? t >> (pshift - 4) : t / per, k0 = (t - j * per) << 4;
+                __builtin_nontemporal_store(pmask_piece(k0, sh_kept[j]), &pdst[t]);
             }
         }
     }
@@ -2994,11 +3023,8 @@ __global__ __launch_bounds__(WG) void k_emit_split(Key kf, int64_t npad, const u
         long long *cbuf = WG == 512 ? zbuf_all[w & 3] : reinterpret_cast<long long *>(rowbuf);       // 64 * 3 * 8 B = 1.5 KiB
         if (mine && !isrec) {
             const float v3[3] = {p0.x, p0.y, p0.z};
-            u64 key = 0;
-            uint32_t st = 0;
-            (void)kf.make(v3, key, st);
-            long long cc[3];
-            kf.decode(key, cc);
+            int cc[3] = {0, 0, 0};
+            (void)kf.cell(v3, cc);
             cbuf[lane * 3 + 0] = cc[0]; cbuf[lane * 3 + 1] = cc[1]; cbuf[lane * 3 + 2] = cc[2];
             __builtin_nontemporal_store((int32_t)c8, &npoints[v]);
         }
@@ -3010,17 +3036,9 @@ __global__ __launch_bounds__(WG) void k_emit_split(Key kf, int64_t npad, const u
             const uint32_t per = P >> 4, total = nv * per;
             uvec4 *pdst = reinterpret_cast<uvec4 *>(pmask + (int64_t)vid0 * P);
             for (uint32_t t = lane; t < total; t += kWave) {
-                const uint32_t j = t / per, k0 = (t - j * per) << 4, kj = sh_kept[j];
+                const uint32_t j = pshift >= 4 ? t >> (pshift - 4) : t / per, k0 = (t - j * per) << 4;
                 if ((recmask >> j) & 1ull) continue;
-                uvec4 w4;
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    uint32_t b = 0;
-#pragma unroll
-                    for (int x = 0; x < 4; x++) b |= ((k0 + q * 4 + x) < kj ? 1u : 0u) << (8 * x);
-                    w4[q] = b;
-                }
-                __builtin_nontemporal_store(w4, &pdst[t]);
+                __builtin_nontemporal_store(pmask_piece(k0, sh_kept[j]), &pdst[t]);
             }
         }
         // rows [lim, P) of the voxels past the range filled under the index launches
@@ -3081,18 +3099,8 @@ __global__ __launch_bounds__(WG) void k_emit_split(Key kf, int64_t npad, const u
             }
         }
         wave_lds_fence();
-        if (AGG4 && (uint32_t)lane >= ja && (uint32_t)lane < jb && cnt <= P) {     // reductions in point order, one lane per voxel
-            const vec4 *rw = rowbuf + (off - oa);
-            for (uint32_t k = 0; k < kept; k++) {
-                const vec4 x = rw[k];
-                if (is_sum) { a0 += x.x; a1 += x.y; a2 += x.z; a3 += x.w; }
-                else if (reduction == D3D_REDUCE_MAX) {      // std::max(acc, x) = acc < x ? x : acc
-                    a0 = a0 < x.x ? x.x : a0; a1 = a1 < x.y ? x.y : a1; a2 = a2 < x.z ? x.z : a2; a3 = a3 < x.w ? x.w : a3;
-                } else {
-                    a0 = x.x < a0 ? x.x : a0; a1 = x.y < a1 ? x.y : a1; a2 = x.z < a2 ? x.z : a2; a3 = x.w < a3 ? x.w : a3;
-                }
-            }
-        }
+        // reductions in point order, one lane per voxel
+        if (AGG4) reduce_rows(reduction, rowbuf + (off - oa), (uint32_t)lane >= ja && (uint32_t)lane < jb && cnt <= P ? kept : 0u, a0, a1, a2, a3);
         // rows [0, lim) of the batch's voxels, flat: eight lanes per 128-byte line
         const uint32_t l0 = (uint32_t)__shfl((int)loff, (int)ja, kWave);
         const uint32_t l1 = (uint32_t)__shfl((int)lincl, (int)jb - 1, kWave);
